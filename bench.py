@@ -16,6 +16,12 @@ By default the steps run one after the other on one pipeline (handle + HIP strea
 `roofline` (HIP events on the launch stream) are the kernels' own and agree with rocprofv3 of the same command.
 `--streams N` (mono) runs consecutive steps on N pipelines round-robin; a kernel's duration then includes the time it shares the
 chip with its neighbours' kernels.  Weak scaling: every rank owns its own batch; no collective on the data path.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (metric, value, ms_per_step, config).  `--full` adds
+what takes runs of its own: the per-kernel calibration pass and the roofline built on it (the timed steps then also time the
+dominant kernel with HIP events), the collective's own time (N > 1), the single-thread CPU baseline and the PCIe-inclusive
+host_io figure.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32; a fixed sample of
+at most 64 frames), so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -170,6 +176,52 @@ def host_io_rate(L, frames, W, H, NF, cap, local_rank):
             "link_GBs": round(nh / th * (W * H + cap * 60 + 4) / 1e9, 2)}
 
 
+DUMP_BUDGET_BYTES = 60 << 20    # all .npy files of one --dump-outputs together (64 MB cap)
+
+
+def dump_outputs(out_dir, b, B, cap, stereo, merged):
+    """what the last timed step handed its caller, as float32 .npy files: per-frame keypoint / stereo-match counts for the whole
+    batch, and for a fixed seeded sample of at most 64 frames the keypoint records (x, y, size, angle, response, octave, class_id),
+    descriptor bytes and match results, [frame][cap] with the rows past the frame's count set to 0"""
+    os.makedirs(out_dir, exist_ok=True)
+    per_frame = cap * 4 * ((7 + 32) * 2 + 2 if stereo else 7 + 32 + 3)
+    S = max(1, min(B, 64, DUMP_BUDGET_BYTES // per_frame))
+    sample = np.sort(np.random.default_rng(0).choice(B, size=S, replace=False))
+    if merged:
+        kl, dl, nl = b["kpsM"][:B], b["descM"][:B], b["countsM"][:B]
+        kr, dr, nr = b["kpsM"][B:], b["descM"][B:], b["countsM"][B:]
+    else:
+        kl, dl, nl = b["kps"][1:], b["desc"][1:], b["counts"][1:]
+        if stereo:
+            kr, dr, nr = b["kpsR"], b["descR"], b["countsR"]
+    idx = torch.from_numpy(sample).to(kl.device)
+    rows = lambda t: t.index_select(0, idx).cpu().numpy()
+    live = lambda n: np.arange(cap)[None, :] < n[sample][:, None]       # [S][cap]: rows below the frame's count
+
+    def kps(t, n):
+        r = rows(t).view(_capi.KP_DTYPE).reshape(S, cap)
+        return np.where(live(n)[..., None], np.stack([r[f].astype(np.float32) for f in _capi.KP_DTYPE.names], -1), 0)
+
+    def desc(t, n):
+        return np.where(live(n)[..., None], rows(t).reshape(S, cap, 32).astype(np.float32), 0)
+
+    def per_kp(t, n):
+        return np.where(live(n), rows(t).astype(np.float32), 0)
+
+    nl = nl.cpu().numpy()
+    arrays = {"sample_frames": sample.astype(np.float32), "counts": nl.astype(np.float32)}
+    if stereo:
+        nr = nr.cpu().numpy()
+        arrays.update(counts_right=nr.astype(np.float32), stereo_matches=b["nmatch"].cpu().numpy().astype(np.float32),
+                      keypoints=kps(kl, nl), descriptors=desc(dl, nl), keypoints_right=kps(kr, nr), descriptors_right=desc(dr, nr),
+                      u_right=per_kp(b["uright"], nl), depth=per_kp(b["depth"], nl))
+    else:
+        arrays.update(keypoints=kps(kl, nl), descriptors=desc(dl, nl), match_best_idx=per_kp(b["midx"], nl),
+                      match_best_dist=per_kp(b["mbest"], nl), match_second_dist=per_kp(b["msecond"], nl))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -197,10 +249,17 @@ def main():
     ap.add_argument("--gather", default="gather", choices=("gather", "all_gather"),
                     help="collective for the per-frame keypoint records: to rank 0 (default) or to every rank")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-io", action="store_true", help="skip the PCIe-inclusive secondary figure (host_io)")
-    ap.add_argument("--stages", action="store_true", help="also print a per-kernel table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-kernel calibration + roofline, the collective's own time, "
+                         "the CPU baseline and host_io (off: only the timed steps and the result line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-io", action="store_true", help="with --full: skip the PCIe-inclusive secondary figure (host_io)")
+    ap.add_argument("--stages", action="store_true", help="with --full: also print a per-kernel table to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, a fixed sample of frames)")
     args = ap.parse_args()
+    if args.stages and not args.full:
+        ap.error("--stages needs --full (the per-kernel table comes from the calibration pass)")
 
     if args.fork_level > 0:
         os.environ["ORBX_FORK_LEVEL"] = str(args.fork_level)   # read by the library when a handle is configured
@@ -346,27 +405,28 @@ def main():
         raise SystemExit(3)
     handles = exs + ([exR] if exR is not None else [])
 
-    # calibration pass: which kernel dominates?  (all kernels timed with HIP events on the launch stream)
-    for e in handles:
-        e.profile_enable(0x1ff)
-    torch.cuda.synchronize(dev)
-    tc = time.perf_counter()
-    for _ in range(2 * NS):
-        step()
-    if gatherer is not None:
-        gatherer.wait_all()
-    torch.cuda.synchronize(dev)
-    calib_ms = (time.perf_counter() - tc) / (2 * NS) * 1e3
-    prof = {}
-    for e in handles:
-        for kname, (ms, n) in e.profile_read(reset=True).items():
-            a = prof.get(kname, (0.0, 0))
-            prof[kname] = (a[0] + ms, a[1] + n)
-    prof = {kname: (v[0] / NS, v[1] // NS) for kname, v in prof.items()}   # per 2 steps, like the single-pipeline table
-    dominant = max((k for k in prof if k != "misc"), key=lambda k: prof[k][0])
-    kid = _capi.K_NAMES.index(dominant)
-    for e in handles:
-        e.profile_enable(1 << kid)
+    if args.full:
+        # calibration pass: which kernel dominates?  (all kernels timed with HIP events on the launch stream)
+        for e in handles:
+            e.profile_enable(0x1ff)
+        torch.cuda.synchronize(dev)
+        tc = time.perf_counter()
+        for _ in range(2 * NS):
+            step()
+        if gatherer is not None:
+            gatherer.wait_all()
+        torch.cuda.synchronize(dev)
+        calib_ms = (time.perf_counter() - tc) / (2 * NS) * 1e3
+        prof = {}
+        for e in handles:
+            for kname, (ms, n) in e.profile_read(reset=True).items():
+                a = prof.get(kname, (0.0, 0))
+                prof[kname] = (a[0] + ms, a[1] + n)
+        prof = {kname: (v[0] / NS, v[1] // NS) for kname, v in prof.items()}   # per 2 steps, like the single-pipeline table
+        dominant = max((k for k in prof if k != "misc"), key=lambda k: prof[k][0])
+        kid = _capi.K_NAMES.index(dominant)
+        for e in handles:
+            e.profile_enable(1 << kid)
 
     if world > 1:
         dist.barrier()
@@ -389,11 +449,13 @@ def main():
         dist.all_gather(per_rank_dt, own)
     dt = float(tmax.item())
     per_rank_ms = [round(float(t.item()) / args.steps * 1e3, 4) for t in per_rank_dt]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bufs[(state["i"] - 1) % NS], B, cap, stereo, merged)
     # the exchange alone (events around the synchronous collective on the buffers of the last step), MAX over ranks: what a
     # step would cost if nothing but the gather of its records ran -- with the per-rank times above it attributes a
     # sub-linear scaling curve to the collective, to rank 0's ingress, or to one slow device
     gather_ms = None
-    if gatherer is not None:
+    if gatherer is not None and args.full:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         gatherer.collective_only()
         torch.cuda.synchronize(dev)
@@ -407,46 +469,15 @@ def main():
         dist.all_reduce(g, op=dist.ReduceOp.MAX)
         gather_ms = round(float(g.item()), 4)
     dom_ms, dom_launches = 0.0, 0
-    for e in handles:
-        ms_, n_ = e.profile_read(reset=True)[dominant]
-        dom_ms += ms_; dom_launches += n_
-        e.profile_enable(0)
+    if args.full:
+        for e in handles:
+            ms_, n_ = e.profile_read(reset=True)[dominant]
+            dom_ms += ms_; dom_launches += n_
+            e.profile_enable(0)
 
     if rank == 0:
         fps = world * B * args.steps / dt                      # mono: frames/s; stereo: stereo frames (left + right image)/s
         imgs_per_unit = 2 if stereo else 1
-        model, fused = algorithmic_bytes(ex, W, H, n_kp, stereo)
-        launches_per_step = dom_launches / max(args.steps, 1)
-        # bytes one launch of the dominant kernel processes (both eyes' launches counted as launches)
-        bytes_per_launch = model[dominant] * B * imgs_per_unit / max(launches_per_step, 1e-9)
-        avg_launch_s = dom_ms * 1e-3 / max(dom_launches, 1)
-        achieved = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
-        total_model = sum(model.values()) * imgs_per_unit
-        total_fused = sum(fused.values()) * imgs_per_unit
-        traffic = committed_counters("traffic", args.config, B, W, H, NF)
-        sq = committed_counters("sq", args.config, B, W, H, NF)
-        # per-port busy fractions of the dominant kernel over its LIVE launch duration, at the clock the chip held during that
-        # kernel (GRBM_GUI_ACTIVE / 8 / duration of the counter pass).  The ports issue independently (a vector, a scalar and an
-        # LDS instruction of different waves can leave a SIMD / CU in the same cycle), so the fractions do not add:
-        #   valu = SQ_INSTS_VALU x issue cycles per instruction of the kernel's rate-class mix (static, tools/valu_mix.py:
-        #          2 full-rate, 3 shifts, 4 half-rate classes) / (1024 SIMDs x cycles)
-        #   salu = SQ_INSTS_SALU / (256 CUs x cycles)      (one scalar instruction per cycle per CU)
-        #   lds  = SQ_LDS_IDX_ACTIVE / (256 CUs x cycles)  (LDS-array cycles, bank conflicts included)
-        ports = None
-        if sq is not None and dominant in sq["kernels"] and avg_launch_s > 0:
-            ks = sq["kernels"][dominant]
-            clk = ks.get("clock_ghz")
-            cyc = avg_launch_s * (clk if clk else SCLK_PEAK_HZ / 1e9) * 1e9
-            cpv = ks.get("valu_mix_static", {}).get("cycles_per_valu")
-            ports = {"clock_ghz": clk, "clock_source": "GRBM_GUI_ACTIVE/8/duration (PMC pass)" if clk else "peak clock assumed",
-                     "valu_frac": round(ks["SQ_INSTS_VALU"] * cpv / (N_SIMD * cyc), 4) if cpv else None,
-                     "valu_cycles_per_inst_static": cpv,
-                     "valu_frac_if_all_full_rate": round(ks["SQ_INSTS_VALU"] * 2 / (N_SIMD * cyc), 4),
-                     "salu_frac": round(ks["SQ_INSTS_SALU"] / (N_SIMD / 4 * cyc), 4),
-                     "lds_frac": round(ks["SQ_LDS_IDX_ACTIVE"] / (N_SIMD / 4 * cyc), 4) if "SQ_LDS_IDX_ACTIVE" in ks else None,
-                     "lds_bank_conflict_share": round(ks["SQ_LDS_BANK_CONFLICT"] / ks["SQ_LDS_IDX_ACTIVE"], 4) if ks.get("SQ_LDS_IDX_ACTIVE") else None,
-                     "valu_lane_inst_per_pixel": round(ks["SQ_INSTS_VALU"] * 64 / (model[dominant] * B * imgs_per_unit / max(launches_per_step, 1e-9)), 2)
-                                                 if dominant == "k_fast_rows" else None}
         metric = {"tum": "frames/sec ORB extract+match (1000 kp, 640x480)"}.get(
             args.config if (W, H, NF) == (640, 480, 1000) else "", f"frames/sec ORB extract+match ({NF} kp, {W}x{H}{', stereo' if stereo else ''})")
         kind = (f"synthetic {W}x{H} stereo stream (stereo frame = left + right image, both extracted), nFeatures={NF}, 8 levels, "
@@ -463,54 +494,90 @@ def main():
             "config": {"workload": kind + (f", fork level {os.environ['ORBX_FORK_LEVEL']}" if int(os.environ.get("ORBX_FORK_LEVEL", "0")) > 0 else ""), "name": args.config, "frames_per_gpu_per_step": B, "mean_keypoints": round(n_kp, 1),
                        "images_per_s": round(fps * imgs_per_unit, 1),
                        "parallelism": f"frames sharded x{world}, RCCL {args.gather} of keypoint records per step" if world > 1 else "single GPU"},
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": int(traffic["kernels"][dominant]["hbm_bytes_per_launch"]) if traffic and dominant in traffic["kernels"] else None,
-                         "ports": ports,
-                         "algorithmic_bytes_per_launch": int(bytes_per_launch),
-                         "avg_launch_us": round(avg_launch_s * 1e6, 2),
-                         # SURVEY 8(d) model (unfused pipeline: includes 2P for a blurred image that is never written here) ...
-                         "end_to_end_GBs": round(total_model * fps / world / 1e9, 2),
-                         "end_to_end_frac": round(total_model * fps / world / 1e9 / HBM_PEAK_GBS, 5),
-                         # ... and the bytes the fused kernels really have to move
-                         "end_to_end_fused_GBs": round(total_fused * fps / world / 1e9, 2),
-                         "end_to_end_fused_frac": round(total_fused * fps / world / 1e9 / HBM_PEAK_GBS, 5)},
-            # HIP events of the CALIBRATION pass (every kernel slot timed, 2 steps per pipeline), which runs slower than the timed
-            # region (one slot timed): its own wall time per step is printed beside the sum so that the two can be compared
-            "kernel_ms_per_step": {k: round(v[0] / 2, 4) for k, v in prof.items()},
-            "kernel_ms_sum": round(sum(v[0] / 2 for v in prof.values()), 4),
-            "calibration_ms_per_step": round(calib_ms, 4),
-            # with several pipelines, or the forked launch sequence, per-kernel durations include time shared with other kernels
-            "kernel_ms_overlapped": NS > 1 or int(os.environ.get("ORBX_FORK_LEVEL", "0")) > 0 or (stereo and args.stereo_streams == 2),
         }
         if world > 1:
             out.update({"per_rank_status": per_rank_status, "per_rank_keypoints": per_rank_keypoints,
-                        "per_rank_ms_per_step": per_rank_ms, "gather_ms_per_step": gather_ms,
-                        "gather_bytes_per_rank_per_step": int(B * sharding.record_bytes(cap))})
-        if not stereo and prof["k_match"][0] > 0 and os.environ.get("ORBX_MATCH_KERNEL") != "valu":
-            # the one GEMM-shaped kernel of the path: brute-force Hamming on the matrix pipe (dist = |q| + |t| - 2 q.t), by default
-            # with FP4 operands (v_mfma_scale_f32_32x32x64_f8f6f4, dense peak 10 Pop/s), with ORBX_MATCH_KERNEL=i8 as
-            # v_mfma_i32_32x32x32_i8 (5 Pop/s); 2 operations per (query bit, train bit) pair.
-            # Duration: HIP events of the calibration pass (every kernel alone on its stream).
-            m_us = prof["k_match"][0] / 2 * 1e3          # per step: one launch (plus the merge kernel for small batches)
-            m_ops = 2.0 * B * n_kp * n_kp * 256
-            m_i8 = os.environ.get("ORBX_MATCH_KERNEL") == "i8"
-            m_peak = 5000.0 if m_i8 else 10000.0
-            out["roofline_mfma"] = {"bound": "mfma", "kernel": "k_match", "operands": "int8" if m_i8 else "fp4 (e2m1)",
-                                    "achieved": round(m_ops / (m_us * 1e-6) / 1e12, 1),
-                                    "peak": m_peak, "unit": "TOP/s", "frac": round(m_ops / (m_us * 1e-6) / 1e12 / m_peak, 4),
-                                    "avg_launch_us": round(m_us, 2)}
-        if not args.no_cpu_baseline and world == 1:   # reported at N=1 only (the other ranks would idle through it)
-            cfps, nsample, pinned, cflags = cpu_baseline(frames, right, NF, stereo, mb, mbf)
-            out["cpu_baseline"] = {"value": round(cfps, 2), "unit": "frames/s", "cores": 1, "kind": "port", "flags": cflags,
-                                   "sample": f"{nsample} {'stereo frames' if stereo else 'frames'} of the same synthetic stream, "
-                                             f"single-thread CPU oracle (extract{' x2 + ComputeStereoMatches' if stereo else ' + brute-force match'}), "
-                                             f"{'pinned to one core' if pinned else 'not pinned'}, host has {os.cpu_count()} cores"}
-        if not stereo and not args.no_host_io and world == 1:
-            out["host_io"] = host_io_rate(L, frames, W, H, NF, cap, local_rank)
-        if args.stages:
-            for k, v in prof.items():
-                print(f"  {k:14s} {v[0] / 2:9.4f} ms/step  ({v[1] // 2} launches/step)", file=sys.stderr)
+                        "per_rank_ms_per_step": per_rank_ms})
+        if args.full:
+            model, fused = algorithmic_bytes(ex, W, H, n_kp, stereo)
+            launches_per_step = dom_launches / max(args.steps, 1)
+            # bytes one launch of the dominant kernel processes (both eyes' launches counted as launches)
+            bytes_per_launch = model[dominant] * B * imgs_per_unit / max(launches_per_step, 1e-9)
+            avg_launch_s = dom_ms * 1e-3 / max(dom_launches, 1)
+            achieved = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
+            total_model = sum(model.values()) * imgs_per_unit
+            total_fused = sum(fused.values()) * imgs_per_unit
+            traffic = committed_counters("traffic", args.config, B, W, H, NF)
+            sq = committed_counters("sq", args.config, B, W, H, NF)
+            # per-port busy fractions of the dominant kernel over its LIVE launch duration, at the clock the chip held during that
+            # kernel (GRBM_GUI_ACTIVE / 8 / duration of the counter pass).  The ports issue independently (a vector, a scalar and an
+            # LDS instruction of different waves can leave a SIMD / CU in the same cycle), so the fractions do not add:
+            #   valu = SQ_INSTS_VALU x issue cycles per instruction of the kernel's rate-class mix (static, tools/valu_mix.py:
+            #          2 full-rate, 3 shifts, 4 half-rate classes) / (1024 SIMDs x cycles)
+            #   salu = SQ_INSTS_SALU / (256 CUs x cycles)      (one scalar instruction per cycle per CU)
+            #   lds  = SQ_LDS_IDX_ACTIVE / (256 CUs x cycles)  (LDS-array cycles, bank conflicts included)
+            ports = None
+            if sq is not None and dominant in sq["kernels"] and avg_launch_s > 0:
+                ks = sq["kernels"][dominant]
+                clk = ks.get("clock_ghz")
+                cyc = avg_launch_s * (clk if clk else SCLK_PEAK_HZ / 1e9) * 1e9
+                cpv = ks.get("valu_mix_static", {}).get("cycles_per_valu")
+                ports = {"clock_ghz": clk, "clock_source": "GRBM_GUI_ACTIVE/8/duration (PMC pass)" if clk else "peak clock assumed",
+                         "valu_frac": round(ks["SQ_INSTS_VALU"] * cpv / (N_SIMD * cyc), 4) if cpv else None,
+                         "valu_cycles_per_inst_static": cpv,
+                         "valu_frac_if_all_full_rate": round(ks["SQ_INSTS_VALU"] * 2 / (N_SIMD * cyc), 4),
+                         "salu_frac": round(ks["SQ_INSTS_SALU"] / (N_SIMD / 4 * cyc), 4),
+                         "lds_frac": round(ks["SQ_LDS_IDX_ACTIVE"] / (N_SIMD / 4 * cyc), 4) if "SQ_LDS_IDX_ACTIVE" in ks else None,
+                         "lds_bank_conflict_share": round(ks["SQ_LDS_BANK_CONFLICT"] / ks["SQ_LDS_IDX_ACTIVE"], 4) if ks.get("SQ_LDS_IDX_ACTIVE") else None,
+                         "valu_lane_inst_per_pixel": round(ks["SQ_INSTS_VALU"] * 64 / (model[dominant] * B * imgs_per_unit / max(launches_per_step, 1e-9)), 2)
+                                                     if dominant == "k_fast_rows" else None}
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                             "traffic": int(traffic["kernels"][dominant]["hbm_bytes_per_launch"]) if traffic and dominant in traffic["kernels"] else None,
+                             "ports": ports,
+                             "algorithmic_bytes_per_launch": int(bytes_per_launch),
+                             "avg_launch_us": round(avg_launch_s * 1e6, 2),
+                             # SURVEY 8(d) model (unfused pipeline: includes 2P for a blurred image that is never written here) ...
+                             "end_to_end_GBs": round(total_model * fps / world / 1e9, 2),
+                             "end_to_end_frac": round(total_model * fps / world / 1e9 / HBM_PEAK_GBS, 5),
+                             # ... and the bytes the fused kernels really have to move
+                             "end_to_end_fused_GBs": round(total_fused * fps / world / 1e9, 2),
+                             "end_to_end_fused_frac": round(total_fused * fps / world / 1e9 / HBM_PEAK_GBS, 5)},
+                # HIP events of the CALIBRATION pass (every kernel slot timed, 2 steps per pipeline), which runs slower than the timed
+                # region (one slot timed): its own wall time per step is printed beside the sum so that the two can be compared
+                "kernel_ms_per_step": {k: round(v[0] / 2, 4) for k, v in prof.items()},
+                "kernel_ms_sum": round(sum(v[0] / 2 for v in prof.values()), 4),
+                "calibration_ms_per_step": round(calib_ms, 4),
+                # with several pipelines, or the forked launch sequence, per-kernel durations include time shared with other kernels
+                "kernel_ms_overlapped": NS > 1 or int(os.environ.get("ORBX_FORK_LEVEL", "0")) > 0 or (stereo and args.stereo_streams == 2),
+            })
+            if world > 1:
+                out.update({"gather_ms_per_step": gather_ms, "gather_bytes_per_rank_per_step": int(B * sharding.record_bytes(cap))})
+            if not stereo and prof["k_match"][0] > 0 and os.environ.get("ORBX_MATCH_KERNEL") != "valu":
+                # the one GEMM-shaped kernel of the path: brute-force Hamming on the matrix pipe (dist = |q| + |t| - 2 q.t), by default
+                # with FP4 operands (v_mfma_scale_f32_32x32x64_f8f6f4, dense peak 10 Pop/s), with ORBX_MATCH_KERNEL=i8 as
+                # v_mfma_i32_32x32x32_i8 (5 Pop/s); 2 operations per (query bit, train bit) pair.
+                # Duration: HIP events of the calibration pass (every kernel alone on its stream).
+                m_us = prof["k_match"][0] / 2 * 1e3          # per step: one launch (plus the merge kernel for small batches)
+                m_ops = 2.0 * B * n_kp * n_kp * 256
+                m_i8 = os.environ.get("ORBX_MATCH_KERNEL") == "i8"
+                m_peak = 5000.0 if m_i8 else 10000.0
+                out["roofline_mfma"] = {"bound": "mfma", "kernel": "k_match", "operands": "int8" if m_i8 else "fp4 (e2m1)",
+                                        "achieved": round(m_ops / (m_us * 1e-6) / 1e12, 1),
+                                        "peak": m_peak, "unit": "TOP/s", "frac": round(m_ops / (m_us * 1e-6) / 1e12 / m_peak, 4),
+                                        "avg_launch_us": round(m_us, 2)}
+            if not args.no_cpu_baseline and world == 1:   # reported at N=1 only (the other ranks would idle through it)
+                cfps, nsample, pinned, cflags = cpu_baseline(frames, right, NF, stereo, mb, mbf)
+                out["cpu_baseline"] = {"value": round(cfps, 2), "unit": "frames/s", "cores": 1, "kind": "port", "flags": cflags,
+                                       "sample": f"{nsample} {'stereo frames' if stereo else 'frames'} of the same synthetic stream, "
+                                                 f"single-thread CPU oracle (extract{' x2 + ComputeStereoMatches' if stereo else ' + brute-force match'}), "
+                                                 f"{'pinned to one core' if pinned else 'not pinned'}, host has {os.cpu_count()} cores"}
+            if not stereo and not args.no_host_io and world == 1:
+                out["host_io"] = host_io_rate(L, frames, W, H, NF, cap, local_rank)
+            if args.stages:
+                for k, v in prof.items():
+                    print(f"  {k:14s} {v[0] / 2:9.4f} ms/step  ({v[1] // 2} launches/step)", file=sys.stderr)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

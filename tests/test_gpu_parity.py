@@ -423,7 +423,7 @@ def test_bench_line_contract():
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1
@@ -444,7 +444,7 @@ def test_bench_line_contract_stereo(mode):
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "euroc_stereo", "--stereo-batch", mode, "--steps", "2",
-                        "--warmup", "1", "--batch", "4", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1
@@ -453,6 +453,43 @@ def test_bench_line_contract_stereo(mode):
     assert j["config"]["images_per_s"] == pytest.approx(2 * j["value"], rel=1e-3)
     assert ("one extractor batch of 8 images" in j["config"]["workload"]) == (mode == "merged")
     assert j["roofline"]["kernel"] in ("k_fast_rows", "k_describe", "k_pyr_resize", "k_match", "k_quadtree", "k_pyr_l0")
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain bench run (no --full) prints the headline fields only, and --dump-outputs writes what its last step computed:
+    float32 arrays whose keypoints, descriptors and matches are the oracle's for the same seeded frames"""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(line) == 1
+    j = json.loads(line[0])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["dtype"] == "u8" and j["higher_is_better"] is True
+    assert j["value"] == pytest.approx(8 / (j["ms_per_step"] / 1e3), rel=1e-2)
+    assert not {"roofline", "roofline_mfma", "kernel_ms_per_step", "cpu_baseline", "host_io"} & set(j)
+    files = sorted(os.listdir(tmp_path))
+    assert files == sorted(n + ".npy" for n in ("sample_frames", "counts", "keypoints", "descriptors", "match_best_idx",
+                                                "match_best_dist", "match_second_dist"))
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    a = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["sample_frames"], np.arange(8))
+    frames = synth.stream(640, 480, 8, stream_id=100)
+    orc = oracle.OracleExtractor(1000, 1.2, 8, 20, 7)
+    prev = None
+    for f in range(8):
+        n, k, d = orc.extract(frames[f])
+        assert a["counts"][f] == n
+        assert np.array_equal(a["keypoints"][f, :n], np.stack([k[c].astype(np.float32) for c in k.dtype.names], -1)), f
+        assert np.array_equal(a["descriptors"][f, :n], d.astype(np.float32)), f
+        assert not a["keypoints"][f, n:].any() and not a["descriptors"][f, n:].any()
+        if prev is not None:
+            bi, bd, sd = oracle.match_bruteforce(d, prev)
+            assert np.array_equal(a["match_best_idx"][f, :n], bi) and np.array_equal(a["match_best_dist"][f, :n], bd), f
+            assert np.array_equal(a["match_second_dist"][f, :n], sd), f
+        prev = d
 
 
 @pytest.mark.parametrize("fmt,nch,rgb", [(_capi.FMT_RGB8, 3, True), (_capi.FMT_BGR8, 3, False), (_capi.FMT_RGBA8, 4, True),

@@ -111,7 +111,7 @@ def test_bench_two_rank_line_carries_per_rank_fields():
     env = dict(os.environ, ORBX_BENCH_SHARE_GPU0="1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--batch", "8",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1, p.stdout[-2000:]

@@ -1,6 +1,6 @@
 for spec in "$@"; do
   label=${spec%%:*}; rest=${spec#*:}; cfg=${rest%%:*}; envs=${rest#*:}
-  env $envs timeout -k 10 300 python bench.py --config $cfg --no-cpu-baseline --no-host-io --steps 12 --warmup 3 2>/dev/null | python -c "
+  env $envs timeout -k 10 300 python bench.py --full --config $cfg --no-cpu-baseline --no-host-io --steps 12 --warmup 3 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

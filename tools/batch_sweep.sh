@@ -1,6 +1,6 @@
 #!/bin/bash
 # frames/s against the batch size per configuration: bash tools/batch_sweep.sh
-run() { python bench.py --config $1 --batch $2 --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | python -c "
+run() { python bench.py --full --config $1 --batch $2 --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -8,7 +8,7 @@ import numpy as np
 from orb_slam2_detailed_comments_amd import ORBextractor, Frame, synth
 
 def bench(args):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + args, capture_output=True, text=True)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + args, capture_output=True, text=True)
     j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     return j["value"], j["ms_per_step"], j["roofline"]["kernel"], j["roofline"]["end_to_end_frac"]
 

@@ -4,7 +4,7 @@
 test -f tools/bin/liborbx_knobs.so || bash tools/build_variant.sh knobs -DORBX_TIMING_KNOBS
 export ORBX_LIB=$PWD/tools/bin/liborbx_knobs.so
 for s in 1 2 3 0; do
-  ORBX_DESC_STOP=$s python bench.py --no-cpu-baseline --streams 1 --steps 8 --warmup 2 2>/dev/null | python -c "
+  ORBX_DESC_STOP=$s python bench.py --full --no-cpu-baseline --streams 1 --steps 8 --warmup 2 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -2,7 +2,7 @@
 # tools/env_sweep.sh KERNEL VAR value...
 k=$1; var=$2; shift; shift
 for v in "$@"; do
-  env $var=$v python bench.py --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | python -c "
+  env $var=$v python bench.py --full --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

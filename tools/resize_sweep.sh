@@ -1,6 +1,6 @@
 #!/bin/bash
 for v in "$@"; do
-  ORBX_RESIZE_IMPL=$v python bench.py --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | python -c "
+  ORBX_RESIZE_IMPL=$v python bench.py --full --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

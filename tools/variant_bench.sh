@@ -1,6 +1,6 @@
 #!/bin/bash
 # default bench with variant libraries (tools/build_variant.sh NAME -D...): bash tools/variant_bench.sh NAME...
-run() { ORBX_LIB=$1 python bench.py --no-cpu-baseline --steps 10 2>/dev/null | python -c "
+run() { ORBX_LIB=$1 python bench.py --full --no-cpu-baseline --steps 10 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):
