@@ -45,6 +45,12 @@ struct orbx_handle {
     hipEvent_t ev_stereo = nullptr;   // orders the batched stereo match with the OTHER eye's stream (two extractors, two streams)
     int fork_level = 0;       // first level whose resize + FAST run on the side stream (0 = no fork)
     int fork_group = 0;       // first FAST group of that level
+    // sub-batch pipeline of run_chunk (ORBX_PIPELINE=0|S, ORBX_PIPELINE_HEAD=0|1, ORBX_FAST_ROOM=0|1 for A/B runs)
+    int pipeline = 2;         // sub-batches of a batch of >= ORBX_PIPE_MIN_FRAMES frames (<= 1: the serial sequence)
+    bool pipe_head = true;    // the first sub-batch is half the size of the others (its pyramid is the one nothing hides): the
+                              // even split is 0.3 % faster on the default line but 1.8 % slower on the merged EuRoC stereo batch
+    bool fast_room = false;   // k_fast_rows capped at ORBX_FAST_PIPE_WAVES waves per CU while the pipeline runs (measured slower)
+    hipEvent_t ev_pipe[ORBX_PIPE_MAX] = {};   // pyramid of sub-batch k done (side stream) -> its FAST launch (main stream)
     // geometry-dependent device state
     uint8_t *d_pyr = nullptr, *d_blur = nullptr;
     OrbxCell *d_cells = nullptr;
@@ -285,6 +291,12 @@ static orbx_status configure(orbx_handle *h, int width, int height) {
             ++h->fork_group;
         if (h->fork_group == 0 || h->fork_group >= (int)hg.fast_groups.size()) h->fork_level = 0;
     }
+    // The sub-batch pipeline (run_chunk) and the fork exclude each other, both use the side stream: an explicit
+    // ORBX_FORK_LEVEL > 0 (an A/B knob) selects the fork and the serial sub-batch sequence.
+    if (const char *e = getenv("ORBX_PIPELINE")) h->pipeline = std::min(std::max(atoi(e), 0), ORBX_PIPE_MAX);
+    if (const char *e = getenv("ORBX_PIPELINE_HEAD")) h->pipe_head = atoi(e) != 0;
+    if (const char *e = getenv("ORBX_FAST_ROOM")) h->fast_room = atoi(e) != 0;
+    if (h->fork_level > 0) h->pipeline = 0;
     auto setup = [&]() -> hipError_t {
         hipError_t e;
 #define ORBX_TRY(expr) do { e = (expr); if (e != hipSuccess) return e; } while (0)
@@ -363,6 +375,7 @@ extern "C" orbx_status orbx_create(const orbx_params *params, orbx_handle **out)
         if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_fork, evflags);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_join, evflags);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_stereo, evflags);
+        for (int k = 0; k < ORBX_PIPE_MAX && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&h->ev_pipe[k], evflags);
     }
     if (e != hipSuccess) { orbx_destroy(h); return fail(ORBX_HIP_ERROR, hipGetErrorString(e)); }
     h->stream = h->own_stream;
@@ -392,6 +405,7 @@ extern "C" void orbx_destroy(orbx_handle *h) {
         if (h->ev_fork) hipEventDestroy(h->ev_fork);
         if (h->ev_join) hipEventDestroy(h->ev_join);
         if (h->ev_stereo) hipEventDestroy(h->ev_stereo);
+        for (auto ev : h->ev_pipe) if (ev) hipEventDestroy(ev);
         if (h->own_stream) hipStreamDestroy(h->own_stream);
     }
     delete h;
@@ -478,26 +492,96 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
     // (A two-stream level pipeline -- FAST of level l on a low-priority stream while the main stream resizes level
     // l+1 -- was measured and rejected: 81 k frames/s against 116 k for this single in-order sequence; the cross-stream
     // event waits and the 8 small FAST launches cost more than the overlap recovers.)
-    { ProfScope ps(h, ORBX_K_PYR_L0);
-      if (h->d_rect) {   // cv::remap of the EuRoC rectification fused into level 0
-          orbx_launch_pyr_l0_remap(s, g, B, d_imgs, W, H, stride, frame_stride, h->d_pyr, h->d_rect, d_status, h->d_cand_count);
-      } else if (h->input_format == ORBX_FMT_GRAY8) {
-          orbx_launch_pyr_l0(s, g, B, d_imgs, W, H, stride, frame_stride, h->d_pyr, d_status, h->d_cand_count);
-      } else {   // cvtColor of Tracking::GrabImage* fused into level 0
-          const int nch = (h->input_format == ORBX_FMT_RGB8 || h->input_format == ORBX_FMT_BGR8) ? 3 : 4;
-          const bool rgb = h->input_format == ORBX_FMT_RGB8 || h->input_format == ORBX_FMT_RGBA8;
-          orbx_launch_pyr_l0_color(s, g, B, d_imgs, W, H, stride, frame_stride, h->d_pyr, nch, rgb ? 0 : 2, rgb ? 2 : 0, d_status, h->d_cand_count);
-      } }
+    //
+    // Frames [f0, f0 + b) of the batch: every kernel takes its frame from the grid and indexes each per-frame buffer (input,
+    // pyramid, status, candidate lists and counters, quadtree output, keypoints, descriptors) from a base pointer, so a
+    // sub-batch is the same launch on offset base pointers.
+    const int ngroups = (int)h->geom.fast_groups.size();
+    auto pyramid = [&](hipStream_t st, int f0, int b, int l_end) {
+        const uint8_t *im = d_imgs + (int64_t)f0 * frame_stride;
+        uint8_t *pyr = h->d_pyr + (size_t)f0 * h->geom.pyr_bytes;
+        int32_t *stp = d_status + f0;
+        int *cc = h->d_cand_count + (size_t)f0 * NL;
+        { ProfScope ps(h, ORBX_K_PYR_L0, st);
+          if (h->d_rect) {   // cv::remap of the EuRoC rectification fused into level 0
+              orbx_launch_pyr_l0_remap(st, g, b, im, W, H, stride, frame_stride, pyr, h->d_rect, stp, cc);
+          } else if (h->input_format == ORBX_FMT_GRAY8) {
+              orbx_launch_pyr_l0(st, g, b, im, W, H, stride, frame_stride, pyr, stp, cc);
+          } else {   // cvtColor of Tracking::GrabImage* fused into level 0
+              const int nch = (h->input_format == ORBX_FMT_RGB8 || h->input_format == ORBX_FMT_BGR8) ? 3 : 4;
+              const bool rgb = h->input_format == ORBX_FMT_RGB8 || h->input_format == ORBX_FMT_RGBA8;
+              orbx_launch_pyr_l0_color(st, g, b, im, W, H, stride, frame_stride, pyr, nch, rgb ? 0 : 2, rgb ? 2 : 0, stp, cc);
+          } }
+        for (int l = 1; l < l_end; ++l) {
+            ProfScope ps(h, ORBX_K_PYR_RESIZE, st);
+            orbx_launch_pyr_resize(st, g, b, l, h->d_taps, pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy);
+        }
+    };
+    auto fast = [&](hipStream_t st, int f0, int b, int g0, int ng, int lds_floor) {
+        ProfScope ps(h, ORBX_K_FAST, st);
+        orbx_launch_fast_rows(st, g, b, h->d_cells, h->d_groups + g0, ng, h->d_pyr + (size_t)f0 * h->geom.pyr_bytes,
+                              h->d_dense + (size_t)f0 * g.cand_total, h->d_cand_count + (size_t)f0 * NL, d_status + f0, h->max_ch,
+                              h->fast_lcap, h->fast_stop, lds_floor);
+    };
+    auto finish = [&](int f0, int b) {
+        { ProfScope ps(h, ORBX_K_QUADTREE);
+          orbx_launch_quadtree(s, g, b, h->d_dense + (size_t)f0 * g.cand_total, h->d_cand_count + (size_t)f0 * NL,
+                               h->d_lvl_kp + (size_t)f0 * g.kp_total, h->d_lvl_count + (size_t)f0 * NL, d_status + f0,
+                               h->d_knode + (size_t)f0 * g.cand_total, h->ncap, (long long)b * NL >= 1024 ? h->lds_keys : h->lds_keys_few, 0, NL); }
+        // orientation (IC_Angle) is computed inside k_describe from the same LDS patch the descriptor uses
+        { ProfScope ps(h, ORBX_K_DESC);
+          orbx_launch_describe(s, g, b, h->d_pyr + (size_t)f0 * h->geom.pyr_bytes, h->d_lvl_kp + (size_t)f0 * g.kp_total,
+                               h->d_lvl_count + (size_t)f0 * NL, h->d_lvl_angle + (size_t)f0 * g.kp_total, d_kps + (int64_t)f0 * cap,
+                               d_desc + (int64_t)f0 * cap * 32, d_counts + f0, d_status + f0, cap); }
+    };
+    h->blur_valid = false;  // the Gaussian is fused into k_describe; the full blurred image is only built on request
+    // Sub-batch pipeline (large batches): the pyramids of the S sub-batches are queued on the high-priority side stream, FAST ->
+    // quadtree -> descriptors of sub-batch k on the main stream once the pyramid of k is done.  The pyramid is bound by load
+    // latency (its waves leave most of a CU's vector port idle), FAST and the descriptors by vector issue: pyramid k+1 takes
+    // the wave slots the main stream's kernels free while they work on sub-batch k (73-87 % of the pyramid's time overlaps
+    // them, but the kernels slow each other: about 2 % per step, profiles/r04_pipeline.md).  The first sub-batch is the
+    // small one by default: its pyramid is the only one nothing hides.  The calibration pass that profiles every kernel
+    // (more than one bit of the profiling mask) runs the serial sequence below, so that each kernel's time is its own; a
+    // single-kernel profile keeps the pipeline and times each of the S launches of that kernel from its stream, which includes
+    // the time it shares the CUs with the other stream's kernels.
+    const int S = h->pipeline > 1 && B >= ORBX_PIPE_MIN_FRAMES && __builtin_popcount(h->prof_mask) <= 1 ? h->pipeline : 1;
+    if (S > 1) {
+        int off[ORBX_PIPE_MAX + 1];
+        const int units = h->pipe_head ? 2 * S - 1 : S;
+        off[0] = 0;
+        for (int k = 0; k + 1 < S; ++k) {   // multiples of 8 frames (k_describe deals frames over the 8 XCDs); the last takes the rest
+            const int share = (int)((long long)B * (h->pipe_head && k > 0 ? 2 : 1) / units);
+            off[k + 1] = off[k] + std::max(8, share & ~7);
+        }
+        off[S] = B;
+        hipStream_t s2 = h->side_stream;
+        // the side stream starts behind everything queued on the main stream so far (the frames' upload, the previous batch's
+        // readers of the pyramid and of the outputs); every sub-batch's FAST launch waits for its pyramid, and the last of those
+        // waits joins the side stream.  Any error exit waits for the side stream: its work reads and writes the handle's buffers.
+        if (hipEventRecord(h->ev_fork, s) != hipSuccess || hipStreamWaitEvent(s2, h->ev_fork, 0) != hipSuccess)
+            { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, "pipeline fork event"); }
+        for (int k = 0; k < S; ++k) {
+            pyramid(s2, off[k], off[k + 1] - off[k], NL);
+            if (hipEventRecord(h->ev_pipe[k], s2) != hipSuccess)
+                { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, "pipeline event"); }
+        }
+        const int floor = h->fast_room ? ORBX_LDS_PER_CU / ORBX_FAST_PIPE_WAVES : 0;
+        for (int k = 0; k < S; ++k) {
+            if (hipStreamWaitEvent(s, h->ev_pipe[k], 0) != hipSuccess)
+                { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, "pipeline event wait"); }
+            fast(s, off[k], off[k + 1] - off[k], 0, ngroups, floor);
+            finish(off[k], off[k + 1] - off[k]);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, std::string("kernel launch: ") + hipGetErrorString(e)); }
+        h->last_batch = B;
+        return ORBX_OK;
+    }
     // Large batches fork after level fork_level - 1: the remaining (small) levels are resized on the high-priority side stream
     // -- seven dependent launches of which the last four have few waves and are pure latency -- followed by their FAST
     // groups, while the main stream runs the issue-bound FAST kernel of the large levels; joined before the quadtree.
-    const int ngroups = (int)h->geom.fast_groups.size();
     const bool fork = h->fork_level > 0 && (long long)B * ngroups >= 16384;
-    const int l_main_end = fork ? h->fork_level : NL;
-    for (int l = 1; l < l_main_end; ++l) {
-        ProfScope ps(h, ORBX_K_PYR_RESIZE);
-        orbx_launch_pyr_resize(s, g, B, l, h->d_taps, h->d_pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy);
-    }
+    pyramid(s, 0, B, fork ? h->fork_level : NL);
     if (fork) {
         hipStream_t s2 = h->side_stream;
         if (hipEventRecord(h->ev_fork, s) != hipSuccess || hipStreamWaitEvent(s2, h->ev_fork, 0) != hipSuccess)
@@ -506,31 +590,17 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
             ProfScope ps(h, ORBX_K_PYR_RESIZE, s2);
             orbx_launch_pyr_resize(s2, g, B, l, h->d_taps, h->d_pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy);
         }
-        { ProfScope ps(h, ORBX_K_FAST, s2);
-          orbx_launch_fast_rows(s2, g, B, h->d_cells, h->d_groups + h->fork_group, ngroups - h->fork_group, h->d_pyr, h->d_dense,
-                                h->d_cand_count, d_status, h->max_ch, h->fast_lcap, h->fast_stop); }
+        fast(s2, 0, B, h->fork_group, ngroups - h->fork_group, 0);
         // (The quadtree of the small levels was tried on the side stream behind its FAST groups: it needs CU residency the
         // FAST kernel of the large levels does not give up -- 201 us for 1024 workgroups that take 57 us alone -- and delays the
         // join.  It runs after the join.)
-        { ProfScope ps(h, ORBX_K_FAST);
-          orbx_launch_fast_rows(s, g, B, h->d_cells, h->d_groups, h->fork_group, h->d_pyr, h->d_dense,
-                                h->d_cand_count, d_status, h->max_ch, h->fast_lcap, h->fast_stop); }
+        fast(s, 0, B, 0, h->fork_group, 0);
         if (hipEventRecord(h->ev_join, s2) != hipSuccess || hipStreamWaitEvent(s, h->ev_join, 0) != hipSuccess)
             { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, "join event"); }   // the side stream's work reads the handle's buffers: never leave it unjoined
     } else {
-        ProfScope ps(h, ORBX_K_FAST);
-        orbx_launch_fast_rows(s, g, B, h->d_cells, h->d_groups, ngroups, h->d_pyr, h->d_dense,
-                              h->d_cand_count, d_status, h->max_ch, h->fast_lcap, h->fast_stop);
+        fast(s, 0, B, 0, ngroups, 0);
     }
-    { ProfScope ps(h, ORBX_K_QUADTREE);
-      orbx_launch_quadtree(s, g, B, h->d_dense, h->d_cand_count, h->d_lvl_kp,
-                           h->d_lvl_count, d_status, h->d_knode,
-                           h->ncap, (long long)B * NL >= 1024 ? h->lds_keys : h->lds_keys_few, 0, NL); }
-    // orientation (IC_Angle) is computed inside k_describe from the same LDS patch the descriptor uses
-    h->blur_valid = false;  // the Gaussian is fused into k_describe; the full blurred image is only built on request
-    { ProfScope ps(h, ORBX_K_DESC);
-      orbx_launch_describe(s, g, B, h->d_pyr, h->d_lvl_kp, h->d_lvl_count, h->d_lvl_angle, d_kps, d_desc, d_counts,
-                           d_status, cap); }
+    finish(0, B);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ORBX_HIP_ERROR, std::string("kernel launch: ") + hipGetErrorString(e));
     h->last_batch = B;

@@ -2924,7 +2924,7 @@ void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, con
 }
 void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell *cells, const OrbxFastGroup *groups,
                            int ngroups, const uint8_t *pyr, uint2 *cand, int *cand_cursor, int *status, int max_ch, int lcap,
-                           int dbg_stop) {
+                           int dbg_stop, int lds_floor) {
     if (ngroups <= 0) return;
     lcap = (max(lcap, 64) + 1) & ~1;
     // LDS per wave decides how many waves a CU holds: the corner list of a group is sized for its usual load, FR_CCAP entries (the
@@ -2934,7 +2934,10 @@ void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell 
     // against 256 entries = 7 680 bytes, because fewer groups take the rescan; 640 entries = 8 448 bytes = 19 waves: 1.39-1.41 ms).
     const int ccap = min(lcap, FR_CCAP);
     const size_t map_bytes = ((size_t)max_ch * FR_TP + 15) & ~(size_t)15;
-    const size_t smem = 2 * map_bytes + (size_t)2 * lcap + 256 + (size_t)2 * ccap;
+    // lds_floor (the sub-batch pipeline): the request is raised to cap the waves a CU holds, leaving registers for the pyramid
+    // kernels of the other stream; the kernel uses no more than it did
+    const size_t need = 2 * map_bytes + (size_t)2 * lcap + 256 + (size_t)2 * ccap;
+    const size_t smem = lds_floor > 0 && (size_t)lds_floor > need ? (size_t)lds_floor : need;
     // groups per wave: FR_GPW when the launch has waves to spare (the second group's tile is prefetched while the first
     // is processed); one per wave for small batches, where the serial length of a wave is what the caller waits for
     const int gpw = (long long)B * ngroups >= 16384 ? FR_GPW : 1;
