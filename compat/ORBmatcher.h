@@ -188,6 +188,54 @@ public:
         return n;
     }
 
+    // ---- the candidate loops around the two calls above as ONE call each: Tracking::Relocalization
+    // (src/Tracking.cc:2283-2300) and LoopClosing::ComputeSim3 (src/LoopClosing.cc:440-466).  Entry k of the result and of
+    // vvpMapPointMatches is what SearchByBoW(vpKFs[k], ...) gives.  The caller drops isBad() candidates first, as both loops do.
+    std::vector<int> SearchByBoWBatch(const std::vector<KeyFrame *> &vpKFs, Frame &F, std::vector<std::vector<MapPoint *> > &vvpMapPointMatches) {
+        const int K = (int)vpKFs.size();
+        std::vector<std::vector<MapPoint *> > vpKF((size_t)K);
+        std::vector<KeyFrameArrays> a;
+        a.reserve((size_t)K);
+        for (int k = 0; k < K; ++k) { vpKF[k] = vpKFs[k]->GetMapPointMatches(); a.push_back(KeyFrameArrays(vpKFs[k], vpKF[k], true)); }
+        FeatVec ff(F.mFeatVec);
+        const orbx_featvec_view fv = ff.View();
+        std::vector<orbx_keyframe_view> v((size_t)K);
+        std::vector<const orbx_keyframe_view *> vp((size_t)K);
+        std::vector<std::vector<int32_t> > matched((size_t)K, std::vector<int32_t>(std::max(F.N, 1), -1));
+        std::vector<int32_t *> mp((size_t)K);
+        std::vector<int> n((size_t)K, 0);
+        for (int k = 0; k < K; ++k) { v[k] = a[k].View(); vp[k] = &v[k]; mp[k] = matched[k].data(); }
+        Check(orbx_search_by_bow_keyframe_frame_batch(Handle(), K, vp.data(), Keys(F.mvKeys), F.mDescriptors.ptr<uint8_t>(), F.N, &fv,
+                                                      mfNNratio, mbCheckOrientation ? 1 : 0, mp.data(), n.data()));
+        vvpMapPointMatches.assign((size_t)K, std::vector<MapPoint *>(F.N, static_cast<MapPoint *>(NULL)));
+        for (int k = 0; k < K; ++k)
+            for (int i = 0; i < F.N; ++i)
+                if (matched[k][i] >= 0) vvpMapPointMatches[k][i] = vpKF[k][matched[k][i]];
+        return n;
+    }
+    std::vector<int> SearchByBoWBatch(KeyFrame *pKF1, const std::vector<KeyFrame *> &vpKFs2, std::vector<std::vector<MapPoint *> > &vvpMatches12) {
+        const int K = (int)vpKFs2.size();
+        const std::vector<MapPoint *> vp1 = pKF1->GetMapPointMatches();
+        std::vector<std::vector<MapPoint *> > vp2((size_t)K);
+        KeyFrameArrays a1(pKF1, vp1, true);
+        std::vector<KeyFrameArrays> a2;
+        a2.reserve((size_t)K);
+        for (int k = 0; k < K; ++k) { vp2[k] = vpKFs2[k]->GetMapPointMatches(); a2.push_back(KeyFrameArrays(vpKFs2[k], vp2[k], true)); }
+        const orbx_keyframe_view v1 = a1.View();
+        std::vector<orbx_keyframe_view> v((size_t)K);
+        std::vector<const orbx_keyframe_view *> vp((size_t)K);
+        std::vector<std::vector<int32_t> > m12((size_t)K, std::vector<int32_t>(std::max((int)vp1.size(), 1), -1));
+        std::vector<int32_t *> mp((size_t)K);
+        std::vector<int> n((size_t)K, 0);
+        for (int k = 0; k < K; ++k) { v[k] = a2[k].View(); vp[k] = &v[k]; mp[k] = m12[k].data(); }
+        Check(orbx_search_by_bow_keyframes_batch(Handle(), &v1, K, vp.data(), mfNNratio, mbCheckOrientation ? 1 : 0, mp.data(), n.data()));
+        vvpMatches12.assign((size_t)K, std::vector<MapPoint *>(vp1.size(), static_cast<MapPoint *>(NULL)));
+        for (int k = 0; k < K; ++k)
+            for (size_t i = 0; i < vp1.size(); ++i)
+                if (m12[k][i] >= 0) vvpMatches12[k][i] = vp2[k][m12[k][i]];
+        return n;
+    }
+
     // ---- include/ORBmatcher.h:156 -- src/ORBmatcher.cc:570-712, caller Tracking::MonocularInitialization (src/Tracking.cc:950-962)
     int SearchForInitialization(Frame &F1, Frame &F2, std::vector<cv::Point2f> &vbPrevMatched, std::vector<int> &vnMatches12,
                                 int windowSize = 10) {

@@ -256,6 +256,21 @@ orbx_status orbx_search_by_bow_keyframe_frame(orbx_handle *h, const orbx_keyfram
  * LoopClosing::ComputeSim3).  matches12[i1] = index of the KF2 feature whose MapPoint is vpMatches12[i1], -1 = NULL. */
 orbx_status orbx_search_by_bow_keyframes(orbx_handle *h, const orbx_keyframe_view *kf1, const orbx_keyframe_view *kf2,
                                          float nnratio, int check_orientation, int32_t *matches12, int *nmatches);
+/* Batched forms of the two calls above for the loops that run them once per candidate keyframe.  The iterations of those
+ * loops are independent (each writes only its own vvpMapPointMatches[i]), and with every feature index held at most once
+ * per feature vector the reference's selection is order-dependent only inside one vocabulary node: the selection runs on
+ * the device, one wave per (problem, common node), the rotation check one workgroup per problem.  One upload, one
+ * download.  Views of more than 65535 features return ORBX_UNSUPPORTED (16-bit positions inside a node). */
+/* Tracking::Relocalization (src/Tracking.cc:2283-2300): SearchByBoW(kfs[k], F) for k < nproblems.  matched_kf[k] (nf entries)
+ * and nmatches[k] are exactly what orbx_search_by_bow_keyframe_frame returns for (kfs[k], F).  Every feature vector must
+ * hold each feature index at most once (true of DBoW2::transform); otherwise ORBX_BAD_ARGUMENT. */
+orbx_status orbx_search_by_bow_keyframe_frame_batch(orbx_handle *h, int nproblems, const orbx_keyframe_view *const *kfs,
+        const orbx_keypoint *f_keys, const uint8_t *f_desc, int nf, const orbx_featvec_view *f_feat_vec,
+        float nnratio, int check_orientation, int32_t *const *matched_kf, int *nmatches);
+/* LoopClosing::ComputeSim3 (src/LoopClosing.cc:440-466): SearchByBoW(kf1, kf2[k]); matches12[k] (kf1->n entries) and
+ * nmatches[k] exactly as orbx_search_by_bow_keyframes(kf1, kf2[k]).  Same feature-vector rule. */
+orbx_status orbx_search_by_bow_keyframes_batch(orbx_handle *h, const orbx_keyframe_view *kf1, int nproblems,
+        const orbx_keyframe_view *const *kf2, float nnratio, int check_orientation, int32_t *const *matches12, int *nmatches);
 /* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (:879-1087, CheckDistEpipolarLine
  * :206-233; caller LocalMapping::CreateNewMapPoints).  F12: row-major 3x3; (ex, ey): epipole of KF1's centre in KF2
  * (:892-898, computed by the caller from its pose matrices).  vMatchedPairs = (i1, matches12[i1]) for ascending i1 with

@@ -90,7 +90,7 @@ SYMBOLS = [
     "orbx_grid_create", "orbx_grid_destroy", "orbx_grid_query", "orbx_three_maxima",
     "orbx_search_for_initialization", "orbx_stereo_match", "orbx_search_by_projection_frame",
     "orbx_search_by_projection_mappoints", "orbx_set_input_format", "orbx_search_by_bow_keyframe_frame",
-    "orbx_search_by_bow_keyframes", "orbx_search_for_triangulation", "orbx_triangulation_batch_create", "orbx_triangulation_batch_select", "orbx_triangulation_batch_destroy", "orbx_fuse", "orbx_fuse_sim3", "orbx_fuse_batch", "orbx_fuse_sim3_batch",
+    "orbx_search_by_bow_keyframes", "orbx_search_by_bow_keyframe_frame_batch", "orbx_search_by_bow_keyframes_batch", "orbx_search_for_triangulation", "orbx_triangulation_batch_create", "orbx_triangulation_batch_select", "orbx_triangulation_batch_destroy", "orbx_fuse", "orbx_fuse_sim3", "orbx_fuse_batch", "orbx_fuse_sim3_batch",
     "orbx_search_by_projection_sim3", "orbx_search_by_sim3", "orbx_search_by_projection_keyframe",
     "orbx_stereo_match_batch_device", "orbx_host_alloc", "orbx_host_free", "orbx_set_rectification", "orbx_undistort_keypoints_device",
     "orbx_grid_build_device", "orbx_gated_candidates",
@@ -166,6 +166,10 @@ def lib():
     L.orbx_search_by_bow_keyframes.restype = i32
     L.orbx_search_by_bow_keyframes.argtypes = [vp, C.POINTER(KeyFrameView), C.POINTER(KeyFrameView), f32, i32, vp,
                                                C.POINTER(i32)]
+    L.orbx_search_by_bow_keyframe_frame_batch.restype = i32   # arrays of pointers to the views / output arrays
+    L.orbx_search_by_bow_keyframe_frame_batch.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(FeatVecView), f32, i32, vp, vp]
+    L.orbx_search_by_bow_keyframes_batch.restype = i32
+    L.orbx_search_by_bow_keyframes_batch.argtypes = [vp, C.POINTER(KeyFrameView), i32, vp, f32, i32, vp, vp]
     L.orbx_search_for_triangulation.restype = i32
     L.orbx_search_for_triangulation.argtypes = [vp, C.POINTER(KeyFrameView), C.POINTER(KeyFrameView), vp, f32, f32, i32,
                                                 i32, vp, C.POINTER(i32)]

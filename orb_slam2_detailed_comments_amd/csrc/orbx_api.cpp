@@ -1141,6 +1141,66 @@ orbx_status orbx_block_distances(orbx_handle *h, const uint8_t *d1, int n1, cons
     return ORBX_OK;
 }
 
+// Batched SearchByBoW: one upload (every set's descriptors, angles, MapPoint flags and feature-vector indices, the work list,
+// the outputs preset to -1), k_bow_select + k_bow_rot, one download of the outputs and counts, one synchronisation.
+orbx_status orbx_bow_select_batch(orbx_handle *h, bool kk, const OrbxBowSet *sets, int nsets, const std::vector<DBowItem> &items,
+                                  int max_ncol, float nnratio, int check_orientation, int32_t *const *outs, int *nmatches) {
+    if (!h || h->host_only) return fail(h ? ORBX_NO_DEVICE : ORBX_BAD_ARGUMENT, "no device handle");
+    const int K = nsets - 1, nout = sets[0].n;
+    size_t nfeat = 0, nidx = 0;
+    for (int s = 0; s < nsets; ++s) {
+        nfeat += (size_t)sets[s].n;
+        nidx += sets[s].fv->n_nodes > 0 ? (size_t)sets[s].fv->begin[sets[s].fv->n_nodes] : 0;
+    }
+    if (nfeat > 0xffffffffull / 32 || nidx > 0xffffffffull || (size_t)K * nout > 0xffffffffull)
+        return fail(ORBX_UNSUPPORTED, "batch too large for 32-bit offsets");
+    HIPCHK(hipSetDevice(h->dev));
+    // counts | outputs (the download) | descriptors | angles | MapPoint flags | indices | work items | candidate bases
+    const size_t o_cnt = 0, o_out = pad256((size_t)K * 4), o_desc = o_out + pad256((size_t)K * nout * 4),
+                 o_ang = o_desc + pad256(nfeat * 32), o_hmp = o_ang + pad256(nfeat * 4), o_idx = o_hmp + pad256(nfeat),
+                 o_it = o_idx + pad256(nidx * 4), o_cb = o_it + pad256(items.size() * sizeof(DBowItem)),
+                 in_bytes = o_cb + pad256((size_t)K * 4), down_bytes = o_out + (size_t)K * nout * 4;
+    orbx_status st = scratch_reserve(h, in_bytes + 256);
+    if (st == ORBX_OK) st = pin_reserve(h, in_bytes);
+    if (st != ORBX_OK) return st;
+    uint8_t *pin = h->pin;
+    memset(pin + o_cnt, 0, (size_t)K * 4);
+    memset(pin + o_out, 0xff, (size_t)K * nout * 4);
+    size_t fb = 0, ib = 0;
+    for (int s = 0; s < nsets; ++s) {
+        const OrbxBowSet &S = sets[s];
+        if (s > 0) ((uint32_t *)(pin + o_cb))[s - 1] = (uint32_t)fb;
+        if (S.n > 0) {
+            memcpy(pin + o_desc + fb * 32, S.desc, (size_t)S.n * 32);
+            float *ang = (float *)(pin + o_ang) + fb;
+            for (int i = 0; i < S.n; ++i) ang[i] = S.keys[i].angle;
+            if (S.hmp) memcpy(pin + o_hmp + fb, S.hmp, (size_t)S.n);
+            else memset(pin + o_hmp + fb, 0, (size_t)S.n);
+        }
+        const size_t ni = S.fv->n_nodes > 0 ? (size_t)S.fv->begin[S.fv->n_nodes] : 0;
+        if (ni) memcpy(pin + o_idx + ib * 4, S.fv->index, ni * 4);
+        fb += (size_t)S.n; ib += ni;
+    }
+    if (!items.empty()) memcpy(pin + o_it, items.data(), items.size() * sizeof(DBowItem));
+    uint8_t *d = scratch_take<uint8_t>(h, in_bytes);
+    hipStream_t s = h->stream;
+    HIPCHK(hipMemcpyAsync(d, pin, in_bytes, hipMemcpyHostToDevice, s));
+    { ProfScope ps(h, ORBX_K_MATCH);
+      orbx_launch_bow_select(s, kk, (const DBowItem *)(d + o_it), (int)items.size(), (const uint32_t *)(d + o_idx), d + o_desc,
+                             d + o_hmp, nnratio, std::max(1, (max_ncol + 31) / 32), (int32_t *)(d + o_out));
+      orbx_launch_bow_rot(s, kk, K, nout, (const uint32_t *)(d + o_cb), (const float *)(d + o_ang), check_orientation ? 1 : 0,
+                          (int32_t *)(d + o_out), (int32_t *)(d + o_cnt)); }
+    HIPCHK(hipMemcpyAsync(pin, d, down_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
+    for (int k = 0; k < K; ++k) {
+        nmatches[k] = ((const int32_t *)(pin + o_cnt))[k];
+        if (nout > 0) memcpy(outs[k], pin + o_out + (size_t)k * nout * 4, (size_t)nout * 4);
+    }
+    return ORBX_OK;
+}
+
 // ---------------------------------------------------------------- matching
 extern "C" orbx_status orbx_match_bruteforce_device(orbx_handle *h, int npairs, const uint8_t *d_q, const int32_t *d_nq,
                                                     int64_t q_stride, const uint8_t *d_t, const int32_t *d_nt,

@@ -45,6 +45,10 @@ struct DGrid { float minx, miny, winv, hinv; };
 struct DGateQuery { float x, y, r; int min_level, max_level; int frame = 0; int desc = -1; };
 // one row of a BoW-guided distance block: descriptor q of set 1 against ncol features of set 2
 struct DDistRow { uint32_t q, col_begin, ncol, out_off; };
+// one work item of k_bow_select: a common vocabulary node of one batched SearchByBoW problem.  Rows are the feature indices
+// idx[rbeg .. rbeg + nrow) of one set, columns idx[cbeg .. cbeg + ncol) of the other; the indices are local to their set,
+// whose first feature is packed at rbase / cbase.  The problem's output array starts at obase.
+struct DBowItem { uint32_t rbeg, nrow, cbeg, ncol, rbase, cbase, obase, pad; };
 
 #define ORBX_WAVE 64
 

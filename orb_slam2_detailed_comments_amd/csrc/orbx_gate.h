@@ -31,3 +31,11 @@ orbx_status orbx_gate_lists(orbx_handle *h, const orbx_keypoint *tkeys, const ui
 orbx_status orbx_block_distances(orbx_handle *h, const uint8_t *d1, int n1, const uint8_t *d2, int n2,
                                  const std::vector<DDistRow> &rows, const std::vector<uint32_t> &col_idx, size_t total,
                                  std::vector<uint16_t> &out);
+// One set of a batched SearchByBoW call (orbx_search_by_bow_*_batch): keypoints (angles read), descriptors, MapPoint flags
+// (nullptr: none read) and feature vector.  sets[0] is the side every problem shares (F, or kf1), sets[1 + k] the candidate of
+// problem k.  Packing order = set order: the features of set s start at the sum of the n of the sets before it, and its
+// feature-vector indices at the sum of their index counts; DBowItem offsets refer to that packing.  Outputs are per problem,
+// `nout` entries each (nout = sets[0].n); outs[k] / nmatches[k] receive them.
+struct OrbxBowSet { const orbx_keypoint *keys; const uint8_t *desc; const uint8_t *hmp; int n; const orbx_featvec_view *fv; };
+orbx_status orbx_bow_select_batch(orbx_handle *h, bool kk, const OrbxBowSet *sets, int nsets, const std::vector<DBowItem> &items,
+                                  int max_ncol, float nnratio, int check_orientation, int32_t *const *outs, int *nmatches);

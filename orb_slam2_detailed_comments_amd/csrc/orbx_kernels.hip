@@ -2813,6 +2813,153 @@ __global__ __launch_bounds__(256) void k_block_dist(const uint8_t *__restrict__ 
     }
 }
 
+// Batched SearchByBoW (orbx_search_by_bow_*_batch): the selection of src/ORBmatcher.cc:300-350 (KF <-> F, rows = keyframe
+// features, columns = frame features) and :760-815 (KF <-> KF, rows = kf1 features, columns = kf2 features) for one common
+// vocabulary node per wave.  With every feature index at most once per feature vector, the "already matched" test reads and
+// writes only columns of this node pair, so work items are independent; inside one the rows run in the reference's order.
+// Per row the lanes take the node's columns; the wave reduces 32-bit keys dist << 16 | position: the smallest is (bestDist1,
+// bestIdx) with the first occurrence winning ties as the sequential `<` update does, the smallest other key bestDist2.  A
+// masked column or no column at all gives 256.  Columns already matched in this node pair: a bitmap in LDS (`words` words
+// per wave).  The first 64 columns stay in registers; wider nodes reload the rest per row.
+#define BOW_KEY_NONE ((256u << 16) | 0xffffu)
+template <bool KK>
+__global__ __launch_bounds__(256) void k_bow_select(const DBowItem *__restrict__ items, int nitems, const uint32_t *__restrict__ idx,
+                                                    const uint8_t *__restrict__ desc, const uint8_t *__restrict__ hmp, float nnratio,
+                                                    int words, int32_t *__restrict__ out) {
+    extern __shared__ uint32_t bow_taken[];
+    const int lane = threadIdx.x & 63;
+    const int it = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (it >= nitems) return;
+    uint32_t *taken = bow_taken + (threadIdx.x >> 6) * words;
+    const DBowItem I = items[it];
+    for (uint32_t w = lane; w < (I.ncol + 31) / 32; w += 64) taken[w] = 0;
+    uint32_t cidx0 = 0;
+    bool cok0 = false;
+    uint4 ca = make_uint4(0, 0, 0, 0), cb = ca;
+    if ((uint32_t)lane < I.ncol) {
+        cidx0 = idx[I.cbeg + lane];
+        cok0 = !KK || hmp[I.cbase + cidx0];
+        const uint4 *p = (const uint4 *)(desc + (size_t)(I.cbase + cidx0) * 32);
+        ca = p[0]; cb = p[1];
+    }
+    for (uint32_t r0 = 0; r0 < I.nrow; r0 += 64) {
+        // the next 64 rows: index, MapPoint flag and descriptor one per lane, broadcast row by row with readlane
+        uint32_t ridx = 0;
+        int rok = 0;
+        uint4 ra = make_uint4(0, 0, 0, 0), rb = ra;
+        if (r0 + lane < I.nrow) {
+            ridx = idx[I.rbeg + r0 + lane];
+            rok = hmp[I.rbase + ridx];
+            if (rok) { const uint4 *p = (const uint4 *)(desc + (size_t)(I.rbase + ridx) * 32); ra = p[0]; rb = p[1]; }
+        }
+        const uint32_t nr = min(64u, I.nrow - r0);
+        for (uint32_t rr = 0; rr < nr; ++rr) {
+            if (!__builtin_amdgcn_readlane(rok, rr)) continue;                       // no MapPoint in the row's keyframe
+            const uint4 qa = make_uint4(__builtin_amdgcn_readlane(ra.x, rr), __builtin_amdgcn_readlane(ra.y, rr),
+                                        __builtin_amdgcn_readlane(ra.z, rr), __builtin_amdgcn_readlane(ra.w, rr));
+            const uint4 qb = make_uint4(__builtin_amdgcn_readlane(rb.x, rr), __builtin_amdgcn_readlane(rb.y, rr),
+                                        __builtin_amdgcn_readlane(rb.z, rr), __builtin_amdgcn_readlane(rb.w, rr));
+            uint32_t b1 = BOW_KEY_NONE, b2 = BOW_KEY_NONE;
+            for (uint32_t c0 = 0; c0 < I.ncol; c0 += 64) {
+                const uint32_t c = c0 + lane;
+                uint32_t key = BOW_KEY_NONE;
+                if (c < I.ncol && !((taken[c >> 5] >> (c & 31)) & 1u)) {
+                    uint4 ta = ca, tb = cb;
+                    bool ok = cok0;
+                    if (c0 > 0) {
+                        const uint32_t ic = idx[I.cbeg + c];
+                        ok = !KK || hmp[I.cbase + ic];
+                        if (ok) { const uint4 *p = (const uint4 *)(desc + (size_t)(I.cbase + ic) * 32); ta = p[0]; tb = p[1]; }
+                    }
+                    if (ok) {
+                        const uint32_t d = __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) +
+                                           __popc(qb.x ^ tb.x) + __popc(qb.y ^ tb.y) + __popc(qb.z ^ tb.z) + __popc(qb.w ^ tb.w);
+                        key = (d << 16) | c;
+                    }
+                }
+                if (key < b1) { b2 = b1; b1 = key; }
+                else if (key < b2) b2 = key;
+            }
+            const uint32_t m1 = orbx_wave_min(b1);
+            const uint32_t m2 = orbx_wave_min(b1 == m1 ? b2 : b1);
+            const int d1 = (int)(m1 >> 16), d2 = (int)(m2 >> 16);
+            if ((KK ? d1 < 50 : d1 <= 50) && (float)d1 < nnratio * (float)d2) {   // TH_LOW: '<' in KF <-> KF (:809), '<=' (:339)
+                const uint32_t c = m1 & 0xffffu;
+                const uint32_t irow = (uint32_t)__builtin_amdgcn_readlane((int)ridx, rr);
+                const uint32_t icol = c < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)cidx0, c) : idx[I.cbeg + c];
+                if (lane == 0) {
+                    taken[c >> 5] |= 1u << (c & 31);
+                    if (KK) out[I.obase + irow] = (int32_t)icol;
+                    else out[I.obase + icol] = (int32_t)irow;
+                }
+            }
+        }
+    }
+}
+
+// bin of RotHist::push (orbx_policies.cpp, src/ORBmatcher.cc:340-351), -1 = the reference's `bin >= 0 && bin < HISTO` fails
+__device__ __forceinline__ int bow_rot_bin(float a1, float a2) {
+    float rot = a1 - a2;
+    if (rot < 0.0f) rot += 360.0f;
+    const float r = roundf(rot * (30 / 360.0f));
+    if (!(r >= 0.0f && r <= 30.0f)) return -1;
+    const int bin = (int)r;
+    return bin == 30 ? 0 : bin;
+}
+// Rotation check (ComputeThreeMaxima + the removal loop, :380-398) and the match count: one workgroup per problem.  It depends
+// on the set of matches in each bin only, so it runs after all of the problem's node pairs.  1024 threads: one pass over a
+// 1000-feature output (the kernel is a chain of dependent loads; a 256-thread version took 9 us).
+#define BOW_ROT_THREADS 1024
+template <bool KK>
+__global__ __launch_bounds__(BOW_ROT_THREADS) void k_bow_rot(int nout, const uint32_t *__restrict__ cand_base, const float *__restrict__ ang,
+                                                 int check, int32_t *__restrict__ out, int32_t *__restrict__ counts) {
+    __shared__ int hist[30];
+    __shared__ int keep[3];
+    __shared__ int total;
+    const int k = blockIdx.x, t = threadIdx.x;
+    int32_t *o = out + (size_t)k * nout;
+    const uint32_t base = cand_base[k];
+    if (t < 30) hist[t] = 0;
+    if (t == 0) total = 0;
+    __syncthreads();
+    if (check) {
+        for (int i = t; i < nout; i += BOW_ROT_THREADS) {
+            const int m = o[i];
+            if (m < 0) continue;
+            const int b = KK ? bow_rot_bin(ang[i], ang[base + m]) : bow_rot_bin(ang[base + m], ang[i]);
+            if (b >= 0) atomicAdd(&hist[b], 1);
+        }
+        __syncthreads();
+        if (t == 0) {   // orbx_three_maxima
+            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+            for (int i = 0; i < 30; ++i) {
+                const int s = hist[i];
+                if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
+                else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
+                else if (s > max3) { max3 = s; i3 = i; }
+            }
+            if (max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+            else if (max3 < 0.1f * (float)max1) { i3 = -1; }
+            keep[0] = i1; keep[1] = i2; keep[2] = i3;
+        }
+        __syncthreads();
+    }
+    int n = 0;
+    for (int i = t; i < nout; i += BOW_ROT_THREADS) {
+        const int m = o[i];
+        if (m < 0) continue;
+        if (check) {
+            const int b = KK ? bow_rot_bin(ang[i], ang[base + m]) : bow_rot_bin(ang[base + m], ang[i]);
+            if (b >= 0 && b != keep[0] && b != keep[1] && b != keep[2]) { o[i] = -1; continue; }
+        }
+        ++n;
+    }
+    const int s = orbx_wave_sum(n);
+    if ((t & 63) == 0) atomicAdd(&total, s);
+    __syncthreads();
+    if (t == 0) counts[k] = total;
+}
+
 __global__ void k_clear(int *a, int na, int *b, int nb, int *c, int nc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < na) a[i] = 0;
@@ -3038,6 +3185,19 @@ void orbx_launch_block_dist(hipStream_t s, const uint8_t *d1, const uint8_t *d2,
                             int nrows, uint16_t *out) {
     if (nrows <= 0) return;
     hipLaunchKernelGGL(k_block_dist, dim3((nrows + 3) / 4), dim3(256), 0, s, d1, d2, rows, col_idx, nrows, out);
+}
+void orbx_launch_bow_select(hipStream_t s, bool kk, const DBowItem *items, int nitems, const uint32_t *idx, const uint8_t *desc,
+                            const uint8_t *hmp, float nnratio, int words, int32_t *out) {
+    if (nitems <= 0) return;
+    const size_t smem = (size_t)4 * words * sizeof(uint32_t);
+    if (kk) hipLaunchKernelGGL(k_bow_select<true>, dim3((nitems + 3) / 4), dim3(256), smem, s, items, nitems, idx, desc, hmp, nnratio, words, out);
+    else hipLaunchKernelGGL(k_bow_select<false>, dim3((nitems + 3) / 4), dim3(256), smem, s, items, nitems, idx, desc, hmp, nnratio, words, out);
+}
+void orbx_launch_bow_rot(hipStream_t s, bool kk, int nproblems, int nout, const uint32_t *cand_base, const float *ang, int check,
+                         int32_t *out, int32_t *counts) {
+    if (nproblems <= 0) return;
+    if (kk) hipLaunchKernelGGL(k_bow_rot<true>, dim3(nproblems), dim3(BOW_ROT_THREADS), 0, s, nout, cand_base, ang, check, out, counts);
+    else hipLaunchKernelGGL(k_bow_rot<false>, dim3(nproblems), dim3(BOW_ROT_THREADS), 0, s, nout, cand_base, ang, check, out, counts);
 }
 size_t orbx_match_workspace_bytes(int npairs, int out_stride) { return (size_t)npairs * MT_SPLIT * out_stride * sizeof(uint2); }
 void orbx_launch_match(hipStream_t s, int npairs, int max_nq, const uint8_t *q, const int *nq, long long q_stride,

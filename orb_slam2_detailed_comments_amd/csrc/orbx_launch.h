@@ -39,6 +39,12 @@ void orbx_launch_gate(hipStream_t s, const DGrid &gp, const orbx_keypoint *kps, 
                       uint32_t *out_items, uint32_t cap, int fstride);
 void orbx_launch_block_dist(hipStream_t s, const uint8_t *d1, const uint8_t *d2, const DDistRow *rows, const uint32_t *col_idx,
                             int nrows, uint16_t *out);
+// batched SearchByBoW: selection, one wave per DBowItem (`words` = LDS bitmap words per wave, >= ceil(max ncol / 32)), then
+// the rotation check and the counts, one workgroup per problem (outputs nout entries apart)
+void orbx_launch_bow_select(hipStream_t s, bool kk, const DBowItem *items, int nitems, const uint32_t *idx, const uint8_t *desc,
+                            const uint8_t *hmp, float nnratio, int words, int32_t *out);
+void orbx_launch_bow_rot(hipStream_t s, bool kk, int nproblems, int nout, const uint32_t *cand_base, const float *ang, int check,
+                         int32_t *out, int32_t *counts);
 void orbx_launch_hamming_matrix(hipStream_t s, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *dist);
 
 void orbx_launch_stereo_batch(hipStream_t s, const OrbxStereoGeom &sg, int npairs, int cap, const orbx_keypoint *kL,

@@ -197,6 +197,103 @@ extern "C" orbx_status orbx_search_by_bow_keyframes(orbx_handle *h, const orbx_k
     return ORBX_OK;
 }
 
+// Batched SearchByBoW (the candidate loops of Tracking::Relocalization and LoopClosing::ComputeSim3).  Validation first, for
+// every view; then the work list -- one DBowItem per (problem, common node), from the same merge walk -- and one device call
+// (orbx_bow_select_batch) that selects on the device.
+namespace {
+// each feature index at most once (DBoW2::transform adds a feature to one node): the "already matched" test of the
+// selection then never crosses nodes, which is what lets the node pairs run in parallel
+bool featvec_unique(const orbx_featvec_view &fv, int nfeat) {
+    if (fv.n_nodes <= 0) return true;
+    std::vector<uint8_t> seen((size_t)std::max(nfeat, 1), 0);
+    for (int i = 0; i < fv.begin[fv.n_nodes]; ++i) {
+        if (seen[fv.index[i]]) return false;
+        seen[fv.index[i]] = 1;
+    }
+    return true;
+}
+bool bow_view_ok(const orbx_keyframe_view *kf) {
+    return kf && kf->n >= 0 && !(kf->n > 0 && (!kf->keys_un || !kf->desc || !kf->has_map_point)) &&
+           featvec_ok(kf->feat_vec, kf->n) && featvec_unique(kf->feat_vec, kf->n);
+}
+size_t fv_len(const orbx_featvec_view &fv) { return fv.n_nodes > 0 ? (size_t)fv.begin[fv.n_nodes] : 0; }
+
+// sets[0] = shared side, sets[1 + k] = candidate k.  KF <-> F: rows = the candidate keyframe, columns = F; KF <-> KF: rows =
+// kf1, columns = the candidate.  Outputs are preset (-1 / 0) by the caller.
+orbx_status bow_batch_run(orbx_handle *h, bool kk, const std::vector<OrbxBowSet> &sets, float nnratio, int check_orientation,
+                          int32_t *const *outs, int *nmatches) {
+    for (const OrbxBowSet &s : sets)
+        if (s.n > 65535) return orbx_fail(ORBX_UNSUPPORTED, "more than 65535 features in a view (16-bit positions inside a node)");
+    std::vector<DBowItem> items;
+    std::vector<uint32_t> fbase(sets.size()), ibase(sets.size());
+    uint32_t fb = 0, ib = 0;
+    for (size_t s = 0; s < sets.size(); ++s) { fbase[s] = fb; ibase[s] = ib; fb += (uint32_t)sets[s].n; ib += (uint32_t)fv_len(*sets[s].fv); }
+    const OrbxBowSet &S0 = sets[0];
+    int max_ncol = 0;
+    for (size_t s = 1; s < sets.size(); ++s) {
+        const OrbxBowSet &C = sets[s];
+        if (S0.n == 0 || C.n == 0) continue;
+        const size_t r = kk ? 0 : s, c = kk ? s : 0;
+        const orbx_featvec_view &fr = *sets[r].fv, &fc = *sets[c].fv;
+        walk_common_nodes(fr, fc, [&](int a, int b) {
+            const int nrow = fr.begin[a + 1] - fr.begin[a], ncol = fc.begin[b + 1] - fc.begin[b];
+            if (nrow <= 0 || ncol <= 0) return;
+            DBowItem it;
+            it.rbeg = ibase[r] + (uint32_t)fr.begin[a]; it.nrow = (uint32_t)nrow;
+            it.cbeg = ibase[c] + (uint32_t)fc.begin[b]; it.ncol = (uint32_t)ncol;
+            it.rbase = fbase[r]; it.cbase = fbase[c];
+            it.obase = (uint32_t)(s - 1) * (uint32_t)S0.n; it.pad = 0;
+            items.push_back(it);
+            max_ncol = std::max(max_ncol, ncol);
+        });
+    }
+    if (items.empty()) return ORBX_OK;   // no common node anywhere: no match, nothing to compute
+    return orbx_bow_select_batch(h, kk, sets.data(), (int)sets.size(), items, max_ncol, nnratio, check_orientation, outs, nmatches);
+}
+}  // namespace
+
+extern "C" orbx_status orbx_search_by_bow_keyframe_frame_batch(orbx_handle *h, int nproblems, const orbx_keyframe_view *const *kfs,
+                                                               const orbx_keypoint *f_keys, const uint8_t *f_desc, int nf,
+                                                               const orbx_featvec_view *f_fv, float nnratio, int check_orientation,
+                                                               int32_t *const *matched_kf, int *nmatches) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "null handle");
+    if (nproblems < 0 || (nproblems > 0 && (!kfs || !matched_kf || !nmatches)) || !f_fv || nf < 0 || (nf > 0 && (!f_keys || !f_desc)))
+        return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
+    if (!featvec_ok(*f_fv, nf) || !featvec_unique(*f_fv, nf)) return orbx_fail(ORBX_BAD_ARGUMENT, "malformed feature vector of F");
+    for (int k = 0; k < nproblems; ++k) {
+        if (!matched_kf[k]) return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
+        if (!bow_view_ok(kfs[k])) return orbx_fail(ORBX_BAD_ARGUMENT, "bad keyframe view / malformed feature vector");
+    }
+    std::vector<OrbxBowSet> sets((size_t)nproblems + 1);
+    sets[0] = OrbxBowSet{f_keys, f_desc, nullptr, nf, f_fv};
+    for (int k = 0; k < nproblems; ++k) {
+        sets[(size_t)k + 1] = OrbxBowSet{kfs[k]->keys_un, kfs[k]->desc, kfs[k]->has_map_point, kfs[k]->n, &kfs[k]->feat_vec};
+        nmatches[k] = 0;
+        for (int i = 0; i < nf; ++i) matched_kf[k][i] = -1;
+    }
+    return bow_batch_run(h, false, sets, nnratio, check_orientation, matched_kf, nmatches);
+}
+
+extern "C" orbx_status orbx_search_by_bow_keyframes_batch(orbx_handle *h, const orbx_keyframe_view *kf1, int nproblems,
+                                                          const orbx_keyframe_view *const *kf2, float nnratio, int check_orientation,
+                                                          int32_t *const *matches12, int *nmatches) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "null handle");
+    if (nproblems < 0 || (nproblems > 0 && (!kf2 || !matches12 || !nmatches)) || !kf1) return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
+    if (!bow_view_ok(kf1)) return orbx_fail(ORBX_BAD_ARGUMENT, "bad keyframe view / malformed feature vector of kf1");
+    for (int k = 0; k < nproblems; ++k) {
+        if (!matches12[k]) return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
+        if (!bow_view_ok(kf2[k])) return orbx_fail(ORBX_BAD_ARGUMENT, "bad keyframe view / malformed feature vector");
+    }
+    std::vector<OrbxBowSet> sets((size_t)nproblems + 1);
+    sets[0] = OrbxBowSet{kf1->keys_un, kf1->desc, kf1->has_map_point, kf1->n, &kf1->feat_vec};
+    for (int k = 0; k < nproblems; ++k) {
+        sets[(size_t)k + 1] = OrbxBowSet{kf2[k]->keys_un, kf2[k]->desc, kf2[k]->has_map_point, kf2[k]->n, &kf2[k]->feat_vec};
+        nmatches[k] = 0;
+        for (int i = 0; i < kf1->n; ++i) matches12[k][i] = -1;
+    }
+    return bow_batch_run(h, true, sets, nnratio, check_orientation, matches12, nmatches);
+}
+
 // ORBmatcher::CheckDistEpipolarLine (src/ORBmatcher.cc:206-233); the final comparison is in double (3.84 is a double)
 static bool check_dist_epipolar(const orbx_keypoint &kp1, const orbx_keypoint &kp2, const float *F12, float sigma2, bool fma_mode) {
     float a, b, c, num, den;

@@ -161,6 +161,40 @@ class ORBmatcher:
                                                    int(self.mbCheckOrientation), ptr(out), C.byref(n)))
         return n.value, out[:v1.n].copy()
 
+    def SearchByBoWBatch(self, kfs, f_keys, f_desc, f_feat_vec):
+        """the candidate loop of Tracking::Relocalization (src/Tracking.cc:2283-2300) as ONE call: SearchByBoW(kfs[k], F) for every
+        k, selected on the device.  Returns [(nmatches_k, matched_kf_k[F.N])], per problem exactly what SearchByBoW returns.
+        Every feature vector must hold each feature index at most once (DBoW2::transform does)."""
+        import ctypes as C
+        K = len(kfs)
+        keep = []
+        kvs = [self._kf_view(kf, keep) for kf in kfs]
+        fk, fd = np.ascontiguousarray(f_keys, _capi.KP_DTYPE), np.ascontiguousarray(f_desc, np.uint8)
+        fv = self._featvec(f_feat_vec, keep)
+        outs = [np.full(max(len(fk), 1), -1, np.int32) for _ in range(K)]
+        karr = (C.c_void_p * max(K, 1))(*[C.addressof(v) for v in kvs])
+        oarr = (C.c_void_p * max(K, 1))(*[o.ctypes.data for o in outs])
+        n = (C.c_int * max(K, 1))()
+        check(self._L.orbx_search_by_bow_keyframe_frame_batch(self._ex.handle, K, karr, ptr(fk), ptr(fd), len(fk), C.byref(fv),
+                                                              float(self.mfNNratio), int(self.mbCheckOrientation), oarr, n))
+        return [(int(n[k]), outs[k][:len(fk)].copy()) for k in range(K)]
+
+    def SearchByBoWKeyFramesBatch(self, kf1, kf2_list):
+        """the candidate loop of LoopClosing::ComputeSim3 (src/LoopClosing.cc:440-466) as ONE call: SearchByBoW(kf1, kf2_list[k]).
+        Returns [(nmatches_k, matches12_k[KF1.N])], per problem exactly what SearchByBoWKeyFrames returns."""
+        import ctypes as C
+        K = len(kf2_list)
+        keep = []
+        v1 = self._kf_view(kf1, keep)
+        v2 = [self._kf_view(k, keep) for k in kf2_list]
+        outs = [np.full(max(v1.n, 1), -1, np.int32) for _ in range(K)]
+        karr = (C.c_void_p * max(K, 1))(*[C.addressof(v) for v in v2])
+        oarr = (C.c_void_p * max(K, 1))(*[o.ctypes.data for o in outs])
+        n = (C.c_int * max(K, 1))()
+        check(self._L.orbx_search_by_bow_keyframes_batch(self._ex.handle, C.byref(v1), K, karr, float(self.mfNNratio),
+                                                         int(self.mbCheckOrientation), oarr, n))
+        return [(int(n[k]), outs[k][:v1.n].copy()) for k in range(K)]
+
     def SearchForTriangulation(self, kf1, kf2, F12, epipole, bOnlyStereo=False):
         """Returns (nmatches, matches12[KF1.N]); vMatchedPairs = [(i, m) for i, m in enumerate(matches12) if m >= 0]."""
         import ctypes as C

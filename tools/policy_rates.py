@@ -125,6 +125,42 @@ def main():
         lambda: m.SearchByBoW(kf1, k2, d2, kf2["feat_vec"]), lambda: oracle.search_by_bow_kf_frame(kf1, k2, d2, kf2["feat_vec"], 0.7, True))
     add("orbx_search_by_bow_keyframes", "ORBmatcher.cc:722-866",
         lambda: m.SearchByBoWKeyFrames(kf1, kf2), lambda: oracle.search_by_bow_kf_kf(kf1, kf2, 0.7, True))
+    # the candidate loops of Tracking::Relocalization / LoopClosing::ComputeSim3 as one batched call: K keyframes of 1000 features
+    # from distinct frames of the stream; synthetic vocabulary, make_featvec(bits=7): ~126 nodes, close to ORBvoc at levelsup=4.
+    # us PER PROBLEM (C ABI, views marshalled once) next to K single calls at the C ABI and the CPU oracle's loop over the K problems
+    ex16 = ORBextractor(1000, max_batch=16)
+    res16 = ex16.extract_batch(synth.stream(640, 480, 16, stream_id=42))
+    bkfs = [dict(keys_un=k, desc=d, has_map_point=(rng.uniform(size=len(k)) < 0.7).astype(np.uint8),
+                 feat_vec=make_featvec(d, bits=7, shuffle_rng=rng)) for k, d in res16]
+    bF = bkfs[0]
+    for K in (1, 5, 15):
+        keep = []
+        kvs = [m._kf_view(kf, keep) for kf in bkfs[1:1 + K]]
+        v0 = m._kf_view(bF, keep)
+        fv0 = m._featvec(bF["feat_vec"], keep)
+        fk0, fd0 = np.ascontiguousarray(bF["keys_un"], _capi.KP_DTYPE), np.ascontiguousarray(bF["desc"], np.uint8)
+        karr = (C.c_void_p * K)(*[C.addressof(v) for v in kvs])
+        outs = [np.full(len(fk0), -1, np.int32) for _ in range(K)]
+        oarr = (C.c_void_p * K)(*[o.ctypes.data for o in outs]); nn_ = (C.c_int * K)(); n1_ = C.c_int(0)
+        cases = (
+            ("orbx_search_by_bow_keyframe_frame_batch", "Tracking.cc:2283-2300 loop",
+             lambda: _capi.check(Lc.orbx_search_by_bow_keyframe_frame_batch(ex.handle, K, karr, _capi.ptr(fk0), _capi.ptr(fd0), len(fk0),
+                                                                            C.byref(fv0), 0.7, 1, oarr, nn_)),
+             lambda: [_capi.check(Lc.orbx_search_by_bow_keyframe_frame(ex.handle, C.byref(kvs[k]), _capi.ptr(fk0), _capi.ptr(fd0), len(fk0),
+                                                                       C.byref(fv0), 0.7, 1, _capi.ptr(outs[k]), C.byref(n1_))) for k in range(K)],
+             lambda: [oracle.search_by_bow_kf_frame(kf, bF["keys_un"], bF["desc"], bF["feat_vec"], 0.7, True) for kf in bkfs[1:1 + K]]),
+            ("orbx_search_by_bow_keyframes_batch", "LoopClosing.cc:440-466 loop",
+             lambda: _capi.check(Lc.orbx_search_by_bow_keyframes_batch(ex.handle, C.byref(v0), K, karr, 0.7, 1, oarr, nn_)),
+             lambda: [_capi.check(Lc.orbx_search_by_bow_keyframes(ex.handle, C.byref(v0), C.byref(kvs[k]), 0.7, 1, _capi.ptr(outs[k]),
+                                                                  C.byref(n1_))) for k in range(K)],
+             lambda: [oracle.search_by_bow_kf_kf(bF, kf, 0.7, True) for kf in bkfs[1:1 + K]]),
+        )
+        for name, ref, batch_fn, single_fn, orc in cases:
+            g, g1, c = bench(batch_fn, 30), bench(single_fn, 10), bench(orc, 5)
+            rows.append(dict(entry_point=f"{name} K={K}", reference=ref, gpu_us=round(g / K, 1), single_calls_us=round(g1 / K, 1),
+                             cpu_oracle_us=round(c / K, 1), ratio=round(c / g, 2), problems=K))
+            print(f"{name + f' K={K}':40s} {'us per problem (C ABI)':38s} GPU {g / K:9.1f} us   CPU oracle {c / K:10.1f} us   x{c / g:6.2f}   (K single calls at the C ABI: {g1 / K:.1f} us each)", flush=True)
+
     F12 = np.array([[0, 0, 2.0], [0, 0, -3.0], [-2.0, 3.0, 0]], np.float32)
     add("orbx_search_for_triangulation", "ORBmatcher.cc:879-1087",
         lambda: m.SearchForTriangulation(kf1, kf2, F12, (-1000.0, -700.0), False),
