@@ -1,6 +1,7 @@
 // compat/Frame_stereo.inl -- replacement BODIES for the two Frame members that sit on the hot path (reference src/Frame.cc).
 //
-// How to apply (maintainer, inside the ORB-SLAM2 tree; needs OpenCV, not compiled by this repository):
+// How to apply (maintainer, inside the ORB-SLAM2 tree; needs OpenCV -- this repository's tests run both bodies against working
+// stand-ins, tests/compat_runtime/, and the maintainer's build remains the final check):
 //   in src/Frame.cc, delete the bodies of Frame::ComputeStereoMatches (:880-1176) and, optionally, Frame::UndistortKeyPoints
 //   (:770-825), and put   #include "Frame_stereo.inl"   in their place, inside namespace ORB_SLAM2.  Nothing else in
 //   Frame.cc / Frame.h changes: ExtractORB (:468-481) already goes through compat/ORBextractor.h's operator().

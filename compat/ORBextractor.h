@@ -2,8 +2,9 @@
 //
 // Same namespace, class name, constructor, operator(), getters and the public mvImagePyramid member as
 // reference include/ORBextractor.h:82-185; every call forwards to the C ABI of liborbx.so (include/orbx.h).
-// Needs OpenCV headers (cv::Mat / cv::KeyPoint), which this build image does not have: the file is compiled
-// by the maintainer inside the ORB-SLAM2 tree, not by this repository's tests.
+// Needs OpenCV headers (cv::Mat / cv::KeyPoint).  This repository's tests build and run it against a working cv::Mat stand-in
+// (tests/compat_runtime/, tests/test_compat_runtime.py); the maintainer's build inside the ORB-SLAM2 tree
+// remains the final check.
 #ifndef ORBEXTRACTOR_H
 #define ORBEXTRACTOR_H
 #include <vector>

@@ -11,13 +11,15 @@
 // rotation histogram and every order-dependent skip rule run behind the C ABI, bit-identical to the CPU path
 // (tests/test_gpu_policies.py, test_bow_policies.py, test_projection_policies.py).
 //
-// Needs the ORB-SLAM2 tree (Frame.h, KeyFrame.h, MapPoint.h) and OpenCV: compiled by the maintainer,
-// not by this repository's tests -- this build image has no OpenCV.  Remove src/ORBmatcher.cc from the library's sources.
+// Needs the ORB-SLAM2 tree (Frame.h, KeyFrame.h, MapPoint.h) and OpenCV.  This repository's tests build and run it against working
+// stand-ins of those (tests/compat_runtime/, tests/test_compat_runtime.py); the maintainer's build inside an ORB-SLAM2 + OpenCV tree
+//  remains the final check.  Remove src/ORBmatcher.cc from the library's sources.
 #ifndef ORBMATCHER_H
 #define ORBMATCHER_H
 
 #include <climits>
 #include <cmath>
+#include <cstring>
 #include <set>
 #include <stdexcept>
 #include <utility>
@@ -383,27 +385,18 @@ public:
         orbx_projected_points pv = pts.View();
         int n = 0;
         Check(orbx_fuse(Handle(), &tv, &pv, th, best.data(), &n));
-        for (int i = 0; i < pts.n; ++i) {          // the map update of :1248-1275, in point order
-            if (best[i] < 0) continue;
-            MapPoint *p = vpMapPoints[i], *inKF = pKF->GetMapPoint(best[i]);
-            if (inKF) {
-                if (!inKF->isBad()) { if (inKF->Observations() > p->Observations()) p->Replace(inKF); else inKF->Replace(p); }
-            } else {
-                p->AddObservation(pKF, best[i]);
-                pKF->AddMapPoint(p, best[i]);
-            }
-        }
-        return n;
+        return FuseUpdate(pKF, tv, pts, vpMapPoints, best.data(), pts.desc, th);
     }
 
     // ---- the loop around the call above, as ONE device round trip: LocalMapping::SearchInNeighbors (src/LocalMapping.cc:750-768)
     //        for (pKFi : vpTargetKFs) matcher.Fuse(pKFi, vpMapPointMatches);      ->      matcher.FuseBatch(vpTargetKFs, vpMapPointMatches);
     // (10-20 neighbour keyframes + their second neighbours: every synchronous orbx_fuse call pays ~60 us of upload / launch /
-    // download before it has done any work; orbx_fuse_batch pays it once.)  Same map as the loop, step for step: the selection of
-    // a keyframe depends on earlier iterations only through (a) pMP->isBad() / IsInKeyFrame(pKF), tested again here at the moment
-    // the reference would test them (:1118-1121), and (b) the descriptor of a point that survived `pMPinKF->Replace(pMP)` --
-    // MapPoint::Replace ends in ComputeDistinctiveDescriptors() -- so points whose 32 bytes changed are re-submitted (alone,
-    // orbx_fuse) for the keyframes still to come.
+    // download before it has done any work; orbx_fuse_batch pays it once.)  Same map as the loop of Fuse calls, point by point:
+    // a point's answer depends on earlier points and keyframes only through its bad flag, whether it observes the keyframe, and
+    // its descriptor (the survivor of a MapPoint::Replace gets a new one from ComputeDistinctiveDescriptors()).  The first two are
+    // tested again at update time; points whose descriptor no longer equals the one the batch used are searched again with
+    // the current one, together (orbx_fuse) at the start of each keyframe and alone if it changes within the keyframe
+    // (FuseUpdate).
     int FuseBatch(const std::vector<KeyFrame *> &vpTargetKFs, const std::vector<MapPoint *> &vpMapPoints, const float th = 3.0) {
         const int K = (int)vpTargetKFs.size(), N = (int)vpMapPoints.size();
         if (K == 0 || N == 0) return 0;
@@ -437,49 +430,31 @@ public:
             tp[k] = &tv[k]; pp[k] = &pv[k]; bp[k] = best[k].data();
         }
         Check(orbx_fuse_batch(Handle(), K, tp.data(), pp.data(), th, bp.data(), nf.data()));
-        std::vector<uint8_t> dirty((size_t)N, 0);   // descriptor changed since the batch was computed
-        bool any_dirty = false;
         int total = 0;
+        std::vector<uint8_t> used;
         for (int k = 0; k < K; ++k) {
             KeyFrame *pKF = vpTargetKFs[k];
-            if (any_dirty) {   // (b): this keyframe's answers for the points whose descriptor changed, from their new descriptor
-                Points sub(N);
-                bool some = false;
-                for (int i = 0; i < N; ++i) {
-                    if (!dirty[i] || !pts[k].valid[i]) continue;
-                    sub.Set(i, pts[k].uv[2 * i], pts[k].uv[2 * i + 1], pts[k].ur[i], pts[k].level[i], vpMapPoints[i]->GetDescriptor(), 0.f);
-                    some = true;
-                }
-                if (some) {
-                    std::vector<int32_t> b2((size_t)N, -1);
-                    orbx_projected_points sv = sub.View();
-                    int n2 = 0;
-                    Check(orbx_fuse(Handle(), &tv[k], &sv, th, b2.data(), &n2));
-                    for (int i = 0; i < N; ++i) if (sub.valid[i]) best[k][i] = b2[i];
-                }
-            }
-            for (int i = 0; i < N; ++i) {              // the map update of :1248-1275, in point order
-                if (best[k][i] < 0) continue;
+            used = all_desc;            // the descriptor behind each answer best[k][i]
+            Points sub(N);
+            bool some = false;
+            for (int i = 0; i < N; ++i) {
+                if (!pts[k].valid[i]) continue;
                 MapPoint *p = vpMapPoints[i];
-                if (p->isBad() || p->IsInKeyFrame(pKF)) continue;   // (a): what an earlier keyframe's fusion did to this point
-                MapPoint *inKF = pKF->GetMapPoint(best[k][i]);
-                if (inKF) {
-                    if (!inKF->isBad()) {
-                        if (inKF->Observations() > p->Observations()) p->Replace(inKF);
-                        else {
-                            uint8_t before[32], after[32];
-                            CopyDescriptor(p->GetDescriptor(), before);
-                            inKF->Replace(p);
-                            CopyDescriptor(p->GetDescriptor(), after);
-                            for (int b = 0; b < 32; ++b) if (before[b] != after[b]) { dirty[i] = 1; any_dirty = true; break; }
-                        }
-                    }
-                } else {
-                    p->AddObservation(pKF, best[k][i]);
-                    pKF->AddMapPoint(p, best[k][i]);
-                }
-                ++total;
+                if (p->isBad() || p->IsInKeyFrame(pKF)) continue;
+                uint8_t *u = &used[(size_t)i * 32];
+                CopyDescriptor(p->GetDescriptor(), u);
+                if (std::memcmp(u, &all_desc[(size_t)i * 32], 32) == 0) continue;
+                sub.SetRaw(i, pts[k].uv[2 * i], pts[k].uv[2 * i + 1], pts[k].ur[i], pts[k].level[i], u);
+                some = true;
             }
+            if (some) {   // the points whose descriptor changed before this keyframe, searched again together
+                std::vector<int32_t> b2((size_t)N, -1);
+                orbx_projected_points sv = sub.View();
+                int n2 = 0;
+                Check(orbx_fuse(Handle(), &tv[k], &sv, th, b2.data(), &n2));
+                for (int i = 0; i < N; ++i) if (sub.valid[i]) best[k][i] = b2[i];
+            }
+            total += FuseUpdate(pKF, tv[k], pts[k], vpMapPoints, best[k].data(), used, th);
         }
         return total;
     }
@@ -603,11 +578,49 @@ protected:
             valid[i] = 1; uv[2 * i] = u; uv[2 * i + 1] = v; ur[i] = u_right; level[i] = lvl; angle[i] = ang;
             CopyDescriptor(d, &desc[(size_t)i * 32]);
         }
+        void SetRaw(int i, float u, float v, float u_right, int lvl, const uint8_t *d) {
+            valid[i] = 1; uv[2 * i] = u; uv[2 * i + 1] = v; ur[i] = u_right; level[i] = lvl; angle[i] = 0.f;
+            for (int k = 0; k < 32; ++k) desc[(size_t)i * 32 + k] = d[k];
+        }
         orbx_projected_points View() const {
             orbx_projected_points v = {n, valid.data(), uv.data(), ur.data(), level.data(), desc.data(), angle.data()};
             return v;
         }
     };
+    // The map update of Fuse (:1248-1275) for one keyframe, in point order, given best[i], the answer orbx_fuse computed for
+    // the projection pts[i] and the 32 bytes used[32 i ..].  The reference runs the whole loop body point by point, so every
+    // point sees the map the points before it left: one that has become bad or has come to observe pKF is skipped (:1118-1121),
+    // and one whose descriptor changed since (it survived a Replace, which ends in ComputeDistinctiveDescriptors()) is searched
+    // again, alone, with the descriptor it has now.  Returns the number of fusions, as nFused counts them.
+    static int FuseUpdate(KeyFrame *pKF, const orbx_target_view &tv, const Points &pts, const std::vector<MapPoint *> &vpMapPoints,
+                          const int32_t *best, const std::vector<uint8_t> &used, const float th) {
+        int nFused = 0;
+        for (int i = 0; i < pts.n; ++i) {
+            if (!pts.valid[i]) continue;
+            MapPoint *p = vpMapPoints[i];
+            if (p->isBad() || p->IsInKeyFrame(pKF)) continue;
+            int32_t bestIdx = best[i];
+            uint8_t now[32];
+            CopyDescriptor(p->GetDescriptor(), now);
+            if (std::memcmp(now, &used[(size_t)i * 32], 32) != 0) {
+                Points one(1);
+                one.SetRaw(0, pts.uv[2 * i], pts.uv[2 * i + 1], pts.ur[i], pts.level[i], now);
+                const orbx_projected_points ov = one.View();
+                int n1 = 0;
+                Check(orbx_fuse(Handle(), &tv, &ov, th, &bestIdx, &n1));
+            }
+            if (bestIdx < 0) continue;
+            MapPoint *inKF = pKF->GetMapPoint(bestIdx);
+            if (inKF) {
+                if (!inKF->isBad()) { if (inKF->Observations() > p->Observations()) p->Replace(inKF); else inKF->Replace(p); }
+            } else {
+                p->AddObservation(pKF, bestIdx);
+                pKF->AddMapPoint(p, bestIdx);
+            }
+            ++nFused;
+        }
+        return nFused;
+    }
     // Scw = s [R | t]: rotation, translation and camera centre with the scale divided out (:1292-1301, :424-433)
     static void SplitSim3(const cv::Mat &Scw, cv::Mat &Rcw, cv::Mat &tcw, cv::Mat &Ow) {
         const cv::Mat sR = Scw.rowRange(0, 3).colRange(0, 3);

@@ -1,0 +1,985 @@
+"""The compat/ drop-in shims (ORBmatcher.h, ORBextractor.h, Frame_stereo.inl) executed against the working stand-ins of
+tests/compat_runtime/ (a small cv::Mat and the MapPoint / KeyFrame / Frame map rules of ORB-SLAM2, restated), through the
+extern "C" entry points of tests/compat_runtime/harness.cpp, built here into a shared object linked against liborbx.so.
+
+CPU: the harness builds with -Wall -Werror; the cv::Mat stand-in equals numpy; the MapPoint model equals a Python model of the
+same rules.  None of these creates an orbx handle.
+GPU: (a) the shim's output equals the CPU oracle bit for bit where the shim does no float arithmetic before the call;
+(b) the same for the six methods that do pose algebra first, on scenes where that algebra is exact (axis-permutation
+rotations, power-of-two depths and Sim3 scales, dyadic intrinsics, point offsets that are Pythagorean quadruples, every point
+half a pyramid level away from a PredictScale boundary); (c) the batched forms equal the loops of single calls they replace,
+with the map changing between steps."""
+import ctypes as C
+import math
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle
+from test_bow_policies import make_featvec, perturbed_copy, random_kf
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RUNTIME = os.path.join(ROOT, "tests", "compat_runtime")
+LIBDIR = os.path.join(ROOT, "orb_slam2_detailed_comments_amd", "lib")
+KP = oracle.KP_DTYPE
+F32 = C.c_float
+W, H_, FX, CX, CY = 640, 480, 256.0, 320.0, 240.0
+K4 = np.array([FX, FX, CX, CY], np.float32)
+
+
+class HarnessError(RuntimeError):
+    pass
+
+
+def _build(out):
+    cmd = ["g++", "-std=c++14", "-Wall", "-Werror", "-O1", "-shared", "-fPIC", "-I" + RUNTIME, "-I" + os.path.join(ROOT, "compat"),
+           "-I" + os.path.join(ROOT, "include"), os.path.join(RUNTIME, "harness.cpp"), os.path.join(RUNTIME, "map_model.cpp"),
+           "-L" + LIBDIR, "-lorbx", "-Wl,-rpath," + LIBDIR, "-o", out]
+    return subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+
+
+class Harness:
+    def __init__(self, path):
+        self.L = C.CDLL(path)
+        self.L.h_error.restype = C.c_char_p
+
+    def __call__(self, name, *args):
+        conv = [a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray) else int(a) if isinstance(a, np.integer) else a for a in args]
+        if getattr(self.L, name)(*conv) != 0:
+            raise HarnessError(self.L.h_error().decode())
+
+
+@pytest.fixture(scope="module")
+def H(built_lib, tmp_path_factory):
+    assert shutil.which("g++")
+    out = str(tmp_path_factory.mktemp("compat_runtime") / "harness.so")
+    p = _build(out)
+    assert p.returncode == 0, p.stderr[-4000:]
+    return Harness(out)
+
+
+def i32(n=1):
+    return np.zeros(n, np.int32)
+
+
+def scale_tables(levels=8, f=1.2):
+    sf = np.ones(levels, np.float32)
+    for l in range(1, levels):
+        sf[l] = np.float32(sf[l - 1] * np.float32(f))
+    s2 = (sf * sf).astype(np.float32)
+    return sf, s2, (np.float32(1.0) / s2).astype(np.float32)
+
+
+class Scene:
+    """A fresh map in the harness; keyframes, frames and points are addressed by the index the harness returns."""
+
+    def __init__(self, H):
+        self.H = H
+        H("h_reset")
+        H("h_set_frame_bounds", F32(0), F32(W), F32(0), F32(H_))
+        self.kf_n = []
+        self.nmp = 0
+
+    def kf(self, keys, desc, u_right=None, Tcw=None, mbf=0.0, fv=None, K=K4):
+        n = len(keys)
+        ur = np.full(n, -1, np.float32) if u_right is None else np.ascontiguousarray(u_right, np.float32)
+        T = np.eye(4, dtype=np.float32) if Tcw is None else np.ascontiguousarray(Tcw, np.float32)
+        nodes, begin, index = oracle.orb_oracle._flat_featvec(fv or {})
+        out = i32()
+        self.H("h_add_keyframe", n, np.ascontiguousarray(keys, KP), np.ascontiguousarray(desc, np.uint8).reshape(-1, 32), ur, T,
+               np.ascontiguousarray(K, np.float32), F32(mbf), np.array([0, W, 0, H_], np.int32), 8, F32(1.2), len(nodes),
+               np.ascontiguousarray(nodes, np.uint32), np.ascontiguousarray(begin, np.int32), np.ascontiguousarray(index, np.uint32), out)
+        self.kf_n.append(n)
+        return int(out[0])
+
+    def frame(self, keys, desc, u_right=None, Tcw=None, mb=0.0, mbf=0.0, fv=None, keys_raw=None, K=K4):
+        n = len(keys)
+        ur = np.full(n, -1, np.float32) if u_right is None else np.ascontiguousarray(u_right, np.float32)
+        nodes, begin, index = oracle.orb_oracle._flat_featvec(fv or {})
+        out = i32()
+        k = np.ascontiguousarray(keys, KP)
+        self.H("h_add_frame", n, k if keys_raw is None else np.ascontiguousarray(keys_raw, KP), k,
+               np.ascontiguousarray(desc, np.uint8).reshape(-1, 32), ur, None if Tcw is None else np.ascontiguousarray(Tcw, np.float32),
+               np.ascontiguousarray(K, np.float32), F32(mb), F32(mbf), 8, F32(1.2), len(nodes), np.ascontiguousarray(nodes, np.uint32),
+               np.ascontiguousarray(begin, np.int32), np.ascontiguousarray(index, np.uint32), out)
+        return int(out[0])
+
+    def mp(self, desc, pos=(0.0, 0.0, 1.0), normal=(0.0, 0.0, 1.0), dmin=0.5, dmax=4.0):
+        out = i32()
+        self.H("h_add_mappoint", np.array(pos, np.float32), np.array(normal, np.float32), np.ascontiguousarray(desc, np.uint8),
+               F32(dmin), F32(dmax), out)
+        self.nmp += 1
+        return int(out[0])
+
+    def observe(self, mp, kf, idx):
+        self.H("h_observe", mp, kf, idx)
+
+    def slots(self, kf):
+        out = i32(max(self.kf_n[kf], 1))
+        self.H("h_kf_slots", kf, out)
+        return out[:self.kf_n[kf]].copy()
+
+    def state(self, mp):
+        bad, nobs, ne = i32(), i32(), i32()
+        d = np.zeros(32, np.uint8); ok, oi = i32(64), i32(64)
+        self.H("h_mp_state", mp, bad, nobs, d, ok, oi, 64, ne)
+        return bool(bad[0]), int(nobs[0]), d.tobytes(), tuple(zip(ok[:ne[0]].tolist(), oi[:ne[0]].tolist()))
+
+    def map_state(self):
+        return [self.slots(k).tolist() for k in range(len(self.kf_n))], [self.state(i) for i in range(self.nmp)]
+
+
+def flips(rng, d, nbits):
+    d = np.array(d, np.uint8).copy()
+    for b in rng.choice(256, nbits, replace=False):
+        d[b >> 3] ^= np.uint8(1 << (b & 7))
+    return d
+
+
+def hamming(a, b):
+    a, b = (np.frombuffer(x, np.uint8) if isinstance(x, bytes) else np.asarray(x, np.uint8) for x in (a, b))
+    return int(np.unpackbits(np.bitwise_xor(a, b)).sum())
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU
+
+def test_harness_compiles_without_warnings(built_lib, tmp_path):
+    p = _build(str(tmp_path / "h.so"))
+    assert p.returncode == 0 and "warning" not in p.stderr, p.stderr[-4000:]
+
+
+@pytest.mark.parametrize("seed,s", [(0, 0.5), (1, 4.0), (2, -0.25)])
+def test_mat_algebra_equals_numpy(H, seed, s):
+    rng = np.random.default_rng(seed)
+    A = (rng.integers(-64, 64, (4, 4)) / 8.0).astype(np.float32)      # dyadic: every result below is exact
+    B = (rng.integers(-64, 64, (4, 4)) / 16.0).astype(np.float32)
+    out, n = np.zeros(256), i32()
+    H("h_mat_suite", A, B, C.c_double(s), out, 256, n)
+    r = out[:n[0]]
+    a, b = A.astype(np.float64), B.astype(np.float64)
+    R, t = a[:3, :3], a[:3, 3]
+    want = np.concatenate([(a @ b).ravel(), (a + b).ravel(), (a - b).ravel(), (-a).ravel(), a.T.ravel(), (s * a).ravel(),
+                           (a * s).ravel(), (a / s).ravel(), R @ b[:3, 3] + t, -R.T @ t, b[1], [np.linalg.norm(a[:, 2])],
+                           [np.linalg.norm(a - b)], [a[3] @ b[0]], t, [1000.0, a[2, 1]], [16.0, 16.0, 1.0, 0.0]])
+    assert len(r) == len(want)
+    assert np.array_equal(r, want), np.nonzero(r != want)
+
+
+class PyPoint:
+    """Python model of the map rules restated in tests/compat_runtime/MapPoint.h"""
+
+    def __init__(self, desc):
+        self.desc, self.obs, self.nobs, self.bad = bytes(desc), {}, 0, False
+
+
+def py_add_obs(p, kf, idx, u_right):
+    if kf in p.obs:
+        return
+    p.obs[kf] = idx
+    p.nobs += 2 if u_right[kf][idx] >= 0 else 1
+
+
+def py_best_descriptor(rows):
+    n = len(rows)
+    D = np.array([[hamming(rows[i], rows[j]) for j in range(n)] for i in range(n)])
+    med = np.sort(D, axis=1)[:, (n - 1) // 2]
+    return bytes(rows[int(np.argmin(med))])                           # argmin: the first of equal medians
+
+
+def py_replace(pts, slots, descs, u_right, i, j):
+    p, q = pts[i], pts[j]
+    if i == j:
+        return
+    obs, p.obs, p.bad = dict(p.obs), {}, True
+    for kf in sorted(obs):
+        if kf not in q.obs:
+            slots[kf][obs[kf]] = j
+            py_add_obs(q, kf, obs[kf], u_right)
+        else:
+            slots[kf][obs[kf]] = -1
+    if not q.bad and q.obs:
+        q.desc = bytes(py_best_descriptor([descs[kf][q.obs[kf]] for kf in sorted(q.obs)]))
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_map_point_model_equals_python_model(H, seed):
+    """AddObservation / Observations (2 for a stereo observation), Replace's bookkeeping (slots, bad flag, observations, the
+    survivor's descriptor), SetBadFlag, GetMapPoints and IsInImage, against the Python model, over random operation lists"""
+    rng = np.random.default_rng(seed)
+    S = Scene(H)
+    nkf, nslot, npt = 6, 12, 10
+    base = rng.integers(0, 256, (4, 32), dtype=np.uint8)             # few distinct rows: equal distances and medians happen
+    descs, u_right = [], []
+    for k in range(nkf):
+        d = np.stack([flips(rng, base[rng.integers(0, 4)], int(rng.integers(0, 3))) for _ in range(nslot)])
+        ur = np.where(rng.uniform(size=nslot) < 0.4, rng.uniform(0, 600, nslot), -1).astype(np.float32)
+        S.kf(np.zeros(nslot, KP), d, ur)
+        descs.append([bytes(r) for r in d]); u_right.append(ur)
+    pts = []
+    for i in range(npt):
+        d = rng.integers(0, 256, 32, dtype=np.uint8)
+        S.mp(d); pts.append(PyPoint(d))
+    slots = [[-1] * nslot for _ in range(nkf)]
+    for step in range(40):
+        op = rng.integers(0, 10)
+        i, j, k, s = (int(rng.integers(0, npt)), int(rng.integers(0, npt)), int(rng.integers(0, nkf)), int(rng.integers(0, nslot)))
+        if op < 6:
+            if pts[i].bad or slots[k][s] >= 0 or k in pts[i].obs:
+                continue
+            S.observe(i, k, s)
+            slots[k][s] = i
+            py_add_obs(pts[i], k, s, u_right)
+        elif op < 9:
+            if pts[i].bad or pts[j].bad:
+                continue
+            H("h_replace", i, j)
+            py_replace(pts, slots, descs, u_right, i, j)
+        else:
+            if pts[i].bad:
+                continue
+            H("h_set_bad", i)
+            for kf, idx in pts[i].obs.items():
+                slots[kf][idx] = -1
+            pts[i].obs, pts[i].bad = {}, True
+        for kf in range(nkf):
+            assert S.slots(kf).tolist() == slots[kf], (step, kf)
+        for q in range(npt):
+            bad, nobs, d, obs = S.state(q)
+            assert (bad, nobs, d, obs) == (pts[q].bad, pts[q].nobs, pts[q].desc, tuple(sorted(pts[q].obs.items()))), (step, q)
+    for kf in range(nkf):
+        out, n = i32(nslot), i32()
+        H("h_kf_map_points", kf, out, nslot, n)
+        assert sorted(out[:n[0]].tolist()) == sorted({q for q in slots[kf] if q >= 0 and not pts[q].bad})
+    inside = i32()
+    for x, y, want in ((0, 0, 1), (639.9, 479.9, 1), (640, 10, 0), (10, 480, 0), (-0.1, 10, 0)):
+        H("h_kf_is_in_image", 0, F32(x), F32(y), inside)
+        assert inside[0] == want, (x, y)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_compute_distinctive_descriptors_equals_median_rule(H, seed):
+    rng = np.random.default_rng(seed)
+    S = Scene(H)
+    n = int(rng.integers(1, 9))
+    base = rng.integers(0, 256, (3, 32), dtype=np.uint8)
+    rows = [flips(rng, base[rng.integers(0, 3 if seed % 2 else 1)], int(rng.integers(0, 4))) for _ in range(n)]
+    if seed % 3 == 0:
+        rows = [base[0].copy() if i % 2 else base[1].copy() for i in range(n)]       # two camps: ties in the median
+    for r in rows:
+        S.kf(np.zeros(1, KP), r[None])
+    p = S.mp(np.zeros(32, np.uint8))
+    H("h_compute_descriptor", p)
+    assert S.state(p)[2] == bytes(32)                                 # no observations: the descriptor stays
+    for k in range(n):
+        S.observe(p, k, 0)
+    H("h_compute_descriptor", p)
+    assert S.state(p)[2] == bytes(py_best_descriptor(rows))
+
+
+def test_predict_scale_and_distance_invariance(H):
+    S = Scene(H)
+    S.kf(np.zeros(1, KP), np.zeros((1, 32), np.uint8))
+    f = S.frame(np.zeros(1, KP), np.zeros((1, 32), np.uint8))
+    p = S.mp(np.zeros(32, np.uint8), dmin=0.75, dmax=6.0)
+    lo, hi = np.zeros(1, np.float32), np.zeros(1, np.float32)
+    H("h_mp_invariance", p, lo, hi)
+    assert lo[0] == np.float32(0.8) * np.float32(0.75) and hi[0] == np.float32(1.2) * np.float32(6.0)
+    out = i32()
+    for dist in np.linspace(0.3, 9.0, 300).astype(np.float32):
+        x = math.log(6.0 / float(dist)) / math.log(1.2)
+        if abs(x - round(x)) < 1e-3:
+            continue                                                  # a level boundary: float rounding decides
+        want = min(max(math.ceil(x), 0), 7)
+        for tgt, is_frame in ((0, 0), (f, 1)):
+            H("h_predict_scale", p, F32(dist), tgt, is_frame, out)
+            assert out[0] == want, (dist, is_frame)
+
+
+def test_entry_points_report_exceptions(H):
+    S = Scene(H)
+    with pytest.raises(HarnessError, match="range|vector"):
+        H("h_kf_slots", 7, i32(1))                                  # no such keyframe
+    S.kf(np.zeros(2, KP), np.zeros((2, 32), np.uint8))
+    with pytest.raises(HarnessError):
+        H("h_observe", 0, 0, 0)                                      # no such point
+
+
+SHIM_METHODS = {"DescriptorDistance": 1, "SearchByProjection": 4, "SearchByBoW": 2, "SearchByBoWBatch": 2,
+                "SearchForInitialization": 1, "SearchForTriangulation": 1, "SearchBySim3": 1, "Fuse": 2, "FuseBatch": 1}
+
+
+def _entry_points():
+    """harness entry point -> the shim calls in its body"""
+    src = open(os.path.join(RUNTIME, "harness.cpp")).read()
+    out = {}
+    for m in re.finditer(r"\nint (h_\w+)\(", src):
+        end = src.find("\nint h_", m.end())
+        body = src[m.end(): end if end > 0 else len(src)]
+        out[m.group(1)] = body
+    return out
+
+
+def _gpu_test_bodies():
+    src = open(os.path.abspath(__file__)).read()
+    return [m.group(0) for m in re.finditer(r"@pytest\.mark\.gpu\n(?:@.*\n)*def \w+\(.*?(?=\n(?:@|def |class |# -)|\Z)", src, re.S)]
+
+
+def test_every_shim_method_is_called_by_a_gpu_test():
+    src = open(os.path.join(ROOT, "compat", "ORBmatcher.h")).read()
+    for name, count in SHIM_METHODS.items():            # the public methods, with their overloads
+        assert len(re.findall(r"\n    (?:int|std::vector<int>|static int) %s\(" % name, src)) == count, name
+    entries, gpu = _entry_points(), "\n".join(_gpu_test_bodies())
+    called = lambda pat: [e for e, body in entries.items() if re.search(pat, body) and re.search(r'"%s"' % e, gpu)]
+    pats = {"DescriptorDistance": r"ORBmatcher::DescriptorDistance\(", "SearchByProjection(F, points)": r"SearchByProjection\(\*FR\(f\), MPs",
+            "SearchByProjection(F, F)": r"SearchByProjection\(\*FR\(cur\)", "SearchByProjection(F, KF)": r"SearchByProjection\(\*FR\(f\), KF",
+            "SearchByProjection(KF, Scw)": r"SearchByProjection\(KF\(kf\), Floats", "SearchByBoW(KF, F)": r"SearchByBoW\(KF\(kf\), \*FR",
+            "SearchByBoW(KF, KF)": r"SearchByBoW\(KF\(kf1\), KF\(kf2\)", "SearchByBoWBatch(F)": r"SearchByBoWBatch\(v, \*FR",
+            "SearchByBoWBatch(KF)": r"SearchByBoWBatch\(KF\(kf1\), v", "SearchForInitialization": r"SearchForInitialization\(",
+            "SearchForTriangulation": r"SearchForTriangulation\(", "TriangulationBatch::Search": r"tb->Search\(",
+            "SearchBySim3": r"SearchBySim3\(", "Fuse": r"m\.Fuse\(KF\(kf\), MPs", "Fuse(Scw)": r"Fuse\(KF\(kf\), Floats",
+            "FuseBatch": r"FuseBatch\(", "ORBextractor::operator()": r"\(\*EX\(ex\)\)\(", "ComputeStereoMatches": r"ComputeStereoMatches\(\)",
+            "UndistortKeyPoints": r"UndistortKeyPoints\(\)"}
+    missing = [k for k, p in pats.items() if not called(p)]
+    assert not missing, missing
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU (a)
+
+@pytest.mark.gpu
+def test_gpu_extractor_equals_oracle(H):
+    from orb_slam2_detailed_comments_amd import synth
+    S = Scene(H)
+    for (w, h, nf), sid in (((640, 480, 1000), 21), ((320, 240, 300), 22)):
+        img = np.ascontiguousarray(synth.stream(w, h, 1, stream_id=sid)[0])
+        ex, n = i32(), i32()
+        H("h_extractor_new", nf, F32(1.2), 8, 20, 7, ex)
+        cap = nf + 64 * 8
+        k, d = np.zeros(cap, KP), np.zeros((cap, 32), np.uint8)
+        H("h_extract", int(ex[0]), img, w, h, k, d, cap, n)
+        orc = oracle.OracleExtractor(nf, 1.2, 8, 20, 7)
+        on, ok, od = orc.extract(img)
+        assert n[0] == on > 50
+        assert k[:on].tobytes() == ok.tobytes() and d[:on].tobytes() == od.tobytes()
+        pw, ph = i32(), i32()
+        for l in range(8):
+            H("h_pyramid", int(ex[0]), l, None, 0, pw, ph)
+            buf = np.zeros(pw[0] * ph[0], np.uint8)
+            H("h_pyramid", int(ex[0]), l, buf, len(buf), pw, ph)
+            assert np.array_equal(buf.reshape(ph[0], pw[0]), orc.level_image(l)), l
+        H("h_extract", int(ex[0]), np.zeros((h, w), np.uint8), w, h, k, d, cap, n)     # flat image: no keypoints, descriptors released
+        assert n[0] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h,nf,sid,mb,mbf", [(752, 480, 1200, 5, 0.11, 47.9), (1241, 376, 2000, 6, 0.537, 386.1448)])
+def test_gpu_compute_stereo_matches_equals_oracle(H, w, h, nf, sid, mb, mbf):
+    """EuRoC and KITTI geometries (Examples/Stereo/*.yaml baselines); then a left image without keypoints (N == 0)"""
+    from orb_slam2_detailed_comments_amd import synth
+    Scene(H)
+    L, R = synth.stereo_pair(w, h, stream_id=sid)
+    exs, res, orcs = [], [], []
+    for img in (L, R):
+        img = np.ascontiguousarray(img)
+        ex, n = i32(), i32()
+        H("h_extractor_new", nf, F32(1.2), 8, 20, 7, ex)
+        cap = nf + 64 * 8
+        k, d = np.zeros(cap, KP), np.zeros((cap, 32), np.uint8)
+        H("h_extract", int(ex[0]), img, w, h, k, d, cap, n)
+        exs.append(int(ex[0])); res.append((k[:n[0]].copy(), d[:n[0]].copy()))
+        o = oracle.OracleExtractor(nf, 1.2, 8, 20, 7); o.extract(img); orcs.append(o)
+    (kL, dL), (kR, dR) = res
+    uR, dep = np.zeros(len(kL), np.float32), np.zeros(len(kL), np.float32)
+    H("h_compute_stereo", exs[0], exs[1], len(kL), kL, dL, len(kR), kR, dR, F32(mb), F32(mbf), uR, dep)
+    t = orcs[0].tables()
+    on, ou, od = oracle.stereo_matches(kL, dL, kR, dR, t["scale"], t["inv_scale"], [orcs[0].level_image(l) for l in range(8)],
+                                       [orcs[1].level_image(l) for l in range(8)], mb, mbf)
+    assert np.array_equal(uR.view(np.uint32), ou.view(np.uint32)) and np.array_equal(dep.view(np.uint32), od.view(np.uint32))
+    assert on > 20
+    H("h_compute_stereo", exs[0], exs[1], 0, kL[:0], dL[:0], len(kR), kR, dR, F32(mb), F32(mbf), uR, dep)
+
+
+@pytest.mark.gpu
+def test_gpu_undistort_and_descriptor_distance_equal_oracle(H):
+    S = Scene(H)
+    ex = i32()
+    H("h_extractor_new", 500, F32(1.2), 8, 20, 7, ex)
+    rng = np.random.default_rng(5)
+    k = np.zeros(300, KP)
+    k["x"] = rng.uniform(0, 640, 300); k["y"] = rng.uniform(0, 480, 300); k["octave"] = rng.integers(0, 8, 300)
+    tum1 = ((517.306408, 516.469215, 318.643040, 255.313989), (0.262383, -0.953104, -0.005358, 0.002628, 1.163314))
+    for K, D in (tum1, (tum1[0], tum1[1][:4]), ((718.856, 718.856, 607.1928, 185.2157), (0.0, 0.0, 0.0, 0.0))):
+        out = np.zeros(len(k), KP)
+        H("h_undistort", int(ex[0]), len(k), k, np.array(K, np.float32), np.array(D, np.float32), len(D), out)
+        assert out.tobytes() == oracle.undistort_keypoints(k, K, D).tobytes()
+    H("h_undistort", int(ex[0]), 0, k[:0], np.array(tum1[0], np.float32), np.array(tum1[1], np.float32), 5, k[:0].copy())
+    d = rng.integers(0, 256, (64, 32), dtype=np.uint8)
+    out = i32()
+    for i in range(0, 64, 2):
+        a = np.stack([d[(i + 5) % 64], d[i]])
+        H("h_descriptor_distance", a, d[i + 1].copy(), out)
+        assert out[0] == oracle.descriptor_distance(d[i], d[i + 1])
+
+
+def _frame_with_points(S, rng, keys, desc, p_slot=0.25, p_bad=0.1):
+    """a frame whose features partly already carry map points (some bad, some observed once or twice)"""
+    n = len(keys)
+    f = S.frame(keys, desc)
+    holder = S.kf(np.zeros(n, KP), desc)
+    holder2 = S.kf(np.zeros(n, KP), desc)
+    slot_mp = np.full(n, -1, np.int32)
+    for i in np.nonzero(rng.uniform(size=n) < p_slot)[0]:
+        p = S.mp(desc[i])
+        r = rng.integers(0, 3)
+        if r >= 1: S.observe(p, holder, int(i))
+        if r >= 2: S.observe(p, holder2, int(i))
+        S.H("h_frame_set", f, int(i), p, 0)
+        slot_mp[i] = p
+    return f, slot_mp
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("th,ratio", [(1.0, 0.8), (3.0, 0.6)])
+def test_gpu_search_by_projection_map_points_equals_oracle(H, th, ratio):
+    from orb_slam2_detailed_comments_amd import synth
+    S = Scene(H)
+    ex, n = i32(), i32()
+    H("h_extractor_new", 1000, F32(1.2), 8, 20, 7, ex)
+    ks = []
+    for img in synth.stream(640, 480, 2, stream_id=6):
+        k, d = np.zeros(1512, KP), np.zeros((1512, 32), np.uint8)
+        H("h_extract", int(ex[0]), np.ascontiguousarray(img), 640, 480, k, d, 1512, n)
+        ks.append((k[:n[0]].copy(), d[:n[0]].copy()))
+    (k0, d0), (k1, d1) = ks
+    rng = np.random.default_rng(3)
+    f, slot_mp = _frame_with_points(S, rng, k1, d1)
+    nmp = len(k0)
+    proj = np.stack([k0["x"] + 3.0 + rng.normal(0, 1.0, nmp), k0["y"] + 2.0 + rng.normal(0, 1.0, nmp), k0["x"] - 17.0], 1).astype(np.float32)
+    in_view = rng.uniform(size=nmp) < 0.85
+    bad = rng.uniform(size=nmp) < 0.05
+    level = np.clip(k0["octave"] + rng.integers(-1, 2, nmp), 0, 7).astype(np.int32)
+    view_cos = rng.uniform(0.99, 1.0, nmp).astype(np.float32)
+    holder = S.kf(np.zeros(nmp, KP), d0)
+    ids = []
+    for i in range(nmp):
+        p = S.mp(d0[i])
+        if rng.uniform() < 0.5: S.observe(p, holder, i)
+        H("h_mp_track", p, int(in_view[i]), F32(proj[i, 0]), F32(proj[i, 1]), F32(proj[i, 2]), int(level[i]), F32(view_cos[i]))
+        if bad[i]: H("h_set_bad", p)
+        ids.append(p)
+    mp_obs = np.array([S.state(p)[1] for p in ids], np.int32)
+    frame_obs = np.array([S.state(p)[1] if p >= 0 else -1 for p in slot_mp], np.int32)
+    H("h_search_by_projection_mappoints", f, np.array(ids, np.int32), nmp, F32(th), F32(ratio), n)
+    on, oa = oracle.search_by_projection_mp(k1, d1, np.full(len(k1), -1, np.float32), frame_obs, (0, 640, 0, 480), scale_tables()[0],
+                                            (in_view & ~bad).astype(np.uint8), proj, level, view_cos, d0, mp_obs, th, ratio)
+    got = i32(len(k1))
+    H("h_frame_slots", f, got)
+    want = np.where(oa >= 0, np.array(ids, np.int32)[np.maximum(oa, 0)], slot_mp)
+    assert n[0] == on > 30 and np.array_equal(got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mono,th", [(True, 15.0), (False, 7.0)])
+def test_gpu_search_by_projection_frame_to_frame_equals_oracle(H, mono, th):
+    from orb_slam2_detailed_comments_amd import synth
+    S = Scene(H)
+    ex, n = i32(), i32()
+    H("h_extractor_new", 1000, F32(1.2), 8, 20, 7, ex)
+    ks = []
+    for img in synth.stream(640, 480, 2, stream_id=4):
+        k, d = np.zeros(1512, KP), np.zeros((1512, 32), np.uint8)
+        H("h_extract", int(ex[0]), np.ascontiguousarray(img), 640, 480, k, d, 1512, n)
+        ks.append((k[:n[0]].copy(), d[:n[0]].copy()))
+    (k0, d0), (k1, d1) = ks
+    fx = fy = 500.0; cx, cy = 339.0, 259.0; Z = 2.0; mb, mbf = 0.1, 40.0
+    rng = np.random.default_rng(0)
+    n0 = len(k0)
+    xw = np.stack([(k0["x"] - cx) / fx * Z, (k0["y"] - cy) / fy * Z, np.full(n0, Z)], 1).astype(np.float32)
+    Tlw = np.eye(4, dtype=np.float32)
+    Tcw = np.eye(4, dtype=np.float32); Tcw[0, 3], Tcw[1, 3] = -3.0 / fx * Z, -2.0 / fy * Z
+    ur = np.full(len(k1), -1, np.float32)
+    if not mono:
+        ur[::3] = (k1["x"][::3] - mbf / Z).astype(np.float32)
+    K = np.array([fx, fy, cx, cy], np.float32)
+    last = S.frame(k0, d0, Tcw=Tlw, mb=mb, mbf=mbf, K=K)
+    cur = S.frame(k1, d1, u_right=ur, Tcw=Tcw, mb=mb, mbf=mbf, K=K)
+    holder, holder2 = S.kf(np.zeros(n0, KP), d0), S.kf(np.zeros(n0, KP), d0)
+    has = np.zeros(n0, np.uint8); obs = np.zeros(n0, np.int32); mpd = np.zeros((n0, 32), np.uint8); ids = np.full(n0, -1, np.int32)
+    for i in range(n0):
+        if rng.uniform() < 0.2:
+            continue                                                  # no point
+        p = S.mp(flips(rng, d0[i], 4), pos=xw[i])
+        r = int(rng.integers(0, 3))
+        if r >= 1: S.observe(p, holder, i)
+        if r >= 2: S.observe(p, holder2, i)
+        outlier = rng.uniform() < 0.1
+        H("h_frame_set", last, i, p, int(outlier))
+        ids[i] = p
+        if not outlier:
+            has[i], obs[i], mpd[i] = 1, r, np.frombuffer(S.state(p)[2], np.uint8)
+    H("h_search_by_projection_frame", cur, last, F32(th), int(mono), 1, n)
+    on, om = oracle.search_by_projection_ff(k1, d1, ur, Tcw, (fx, fy, cx, cy), (0, 640, 0, 480), mb, mbf, scale_tables()[0], k0,
+                                            has, xw, mpd, obs, Tlw, th, mono)
+    got = i32(len(k1))
+    H("h_frame_slots", cur, got)
+    assert n[0] == on > 100 and np.array_equal(got, np.where(om >= 0, ids[np.maximum(om, 0)], -1))
+
+
+def _bow_keyframe(S, rng, kf, p_bad=0.1):
+    """kf (random_kf / perturbed_copy layout) into the harness with a MapPoint per has_map_point slot, some of them bad;
+    returns the keyframe, its slots and the has_map_point the policies see (bad = absent)"""
+    k = S.kf(kf["keys_un"], kf["desc"], kf["u_right"], fv=kf["feat_vec"])
+    for i in np.nonzero(kf["has_map_point"])[0]:
+        p = S.mp(kf["desc"][i])
+        S.observe(p, k, int(i))
+        if rng.uniform() < p_bad:
+            S.H("h_set_bad", p)                                      # erases its slot ...
+            if rng.uniform() < 0.5:
+                S.observe(S.mp(kf["desc"][i]), k, int(i))            # ... which another point may take
+    slots = S.slots(k)
+    return k, slots
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ratio,ori", [(0.7, True), (0.9, False)])
+def test_gpu_search_by_bow_and_batches(H, ratio, ori):
+    """both SearchByBoW overloads against the oracle, and both SearchByBoWBatch overloads against the loops of single calls
+    (candidates with no map points and an empty keyframe included)"""
+    rng = np.random.default_rng(31)
+    S = Scene(H)
+    base = random_kf(rng, 400)
+    kfs = [base] + [perturbed_copy(rng, base, nflip=int(rng.integers(4, 16))) for _ in range(4)]
+    kfs[3]["has_map_point"][:] = 0                                   # a candidate without map points
+    kfs.append(random_kf(rng, 0))
+    for kf in kfs:
+        kf["feat_vec"] = make_featvec(kf["desc"])
+    ids, slots = zip(*[_bow_keyframe(S, rng, kf) for kf in kfs])
+    fr = perturbed_copy(rng, base, nflip=10)
+    fv = make_featvec(fr["desc"])
+    f = S.frame(fr["keys_un"], fr["desc"], fv=fv)
+    N = len(fr["desc"])
+    n, out = i32(), i32(N)
+    for k in range(len(kfs)):
+        H("h_search_by_bow_frame", ids[k], f, F32(ratio), int(ori), out, n)
+        if k == 5:                                                   # the empty keyframe
+            assert n[0] == 0 and (out == -1).all()
+            continue
+        ov = dict(kfs[k], has_map_point=(slots[k] >= 0).astype(np.uint8))
+        on, om = oracle.search_by_bow_kf_frame(ov, fr["keys_un"], fr["desc"], fv, ratio, ori)
+        assert n[0] == on and np.array_equal(out, np.where(om >= 0, slots[k][np.maximum(om, 0)], -1)), k
+        if k == 0: assert on > 50
+        if k in (1, 2): assert on > 20
+        if k == 3: assert on == 0
+    N1 = len(kfs[0]["desc"])
+    for k in range(1, len(kfs)):
+        out1 = i32(N1)
+        H("h_search_by_bow_keyframes", ids[0], ids[k], F32(ratio), int(ori), out1, n)
+        if k == 5:
+            assert n[0] == 0 and (out1 == -1).all()
+            continue
+        o1 = dict(kfs[0], has_map_point=(slots[0] >= 0).astype(np.uint8)); o2 = dict(kfs[k], has_map_point=(slots[k] >= 0).astype(np.uint8))
+        on, om = oracle.search_by_bow_kf_kf(o1, o2, ratio, ori)
+        assert n[0] == on and np.array_equal(out1, np.where(om >= 0, slots[k][np.maximum(om, 0)], -1)), k
+        if k in (1, 2): assert on > 20
+    K = len(kfs)
+    cand = np.array(ids, np.int32)
+    res = []
+    for batch in (1, 0):
+        o, c = i32(K * N), i32(K)
+        H("h_search_by_bow_frame_batch", cand, K, f, F32(ratio), int(ori), batch, o, c)
+        o2, c2 = i32((K - 1) * N1), i32(K - 1)
+        H("h_search_by_bow_keyframes_batch", ids[0], cand[1:], K - 1, F32(ratio), int(ori), batch, o2, c2)
+        res.append((o, c, o2, c2))
+    for a, b in zip(*res):
+        assert np.array_equal(a, b)
+    assert res[0][1][0] > 50 and res[0][3][0] > 20
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("window,ratio,ori", [(100, 0.9, True), (30, 0.6, False)])
+def test_gpu_search_for_initialization_equals_oracle(H, window, ratio, ori):
+    from orb_slam2_detailed_comments_amd import synth
+    S = Scene(H)
+    ex, n = i32(), i32()
+    H("h_extractor_new", 2000, F32(1.2), 8, 20, 7, ex)
+    ks = []
+    for img in synth.stream(640, 480, 3, stream_id=0):
+        k, d = np.zeros(2600, KP), np.zeros((2600, 32), np.uint8)
+        H("h_extract", int(ex[0]), np.ascontiguousarray(img), 640, 480, k, d, 2600, n)
+        ks.append((k[:n[0]].copy(), d[:n[0]].copy()))
+    f1 = S.frame(*ks[0])
+    k1, d1 = ks[0]
+    prev = np.stack([k1["x"], k1["y"]], 1).astype(np.float32).copy()
+    oprev = prev.copy()
+    for t in (1, 2):                                                 # the second call starts from the updated vbPrevMatched
+        f2 = S.frame(*ks[t])
+        m12 = i32(len(k1))
+        H("h_search_for_initialization", f1, f2, prev, window, F32(ratio), int(ori), m12, n)
+        on, om, oprev = oracle.search_for_initialization(k1, d1, ks[t][0], ks[t][1], (0, 640, 0, 480), oprev, window, ratio, ori)
+        assert n[0] == on and np.array_equal(m12, om) and np.array_equal(prev.view(np.uint32), oprev.view(np.uint32))
+    assert n[0] > 50
+    f0 = S.frame(k1[:0], d1[:0])
+    H("h_search_for_initialization", f1, f0, prev, window, F32(ratio), int(ori), m12, n)
+    assert n[0] == 0 and (m12 == -1).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU (b)
+# Scenes in which the shims' float pose algebra is exact.  A point is placed by its camera coordinates xc = (a, b, c) * 2^e with
+# a^2 + b^2 + c^2 = d^2 (c a power of two larger than |a|, |b|): the projection (fx = 256) and the distance d * 2^e are exact;
+# mfMaxDistance = dist * 1.2^(L - 1/2), so PredictScale gives L with half a level to spare.
+
+QUADS = [(a, b, c, int(math.isqrt(a * a + b * b + c * c))) for c in (32, 64, 128) for a in range(0, c // 2) for b in range(0, c // 2)
+         if math.isqrt(a * a + b * b + c * c) ** 2 == a * a + b * b + c * c]
+PERMS = [np.eye(3, dtype=np.float32), np.eye(3, dtype=np.float32)[[1, 0, 2]], np.eye(3, dtype=np.float32)[[2, 0, 1]]]
+
+
+def exact_camera_point(rng):
+    a, b, c, d = QUADS[rng.integers(0, len(QUADS))]
+    a, b = (a, b) if rng.uniform() < 0.5 else (b, a)
+    e = 2.0 ** int(rng.integers(-5, -1))
+    xc = np.array([a * rng.choice([-1, 1]), b * rng.choice([-1, 1]), c], np.float64) * e
+    return xc, d * e
+
+
+def project(xc):
+    return np.float32(FX * (xc[0] / xc[2]) + CX), np.float32(FX * (xc[1] / xc[2]) + CY)
+
+
+def add_exact_point(S, rng, R, t, xc, dist, desc, level):
+    """a MapPoint with camera coordinates xc in the camera [R | t]: world position R^T (xc - t)"""
+    X = (R.astype(np.float64).T @ (xc - t.astype(np.float64)))
+    assert np.array_equal(X.astype(np.float32).astype(np.float64), X)
+    dmax = np.float32(dist * 1.2 ** (level - 0.5))
+    o = X - (-R.astype(np.float64).T @ t)
+    return S.mp(desc, pos=X, normal=(o / dist).astype(np.float32), dmin=dmax / np.float32(1.2 ** 7), dmax=dmax)
+
+
+def keys_near(rng, uv, levels, n_extra):
+    """a keypoint near each projection (octave = predicted level or one below) and distractors"""
+    n = len(uv) + n_extra
+    k = np.zeros(n, KP)
+    k["x"][:len(uv)] = uv[:, 0] + rng.integers(-4, 5, len(uv)) / 4.0
+    k["y"][:len(uv)] = uv[:, 1] + rng.integers(-4, 5, len(uv)) / 4.0
+    k["octave"][:len(uv)] = np.maximum(levels - rng.integers(0, 2, len(uv)), 0)
+    k["x"][len(uv):] = rng.uniform(10, W - 10, n_extra); k["y"][len(uv):] = rng.uniform(10, H_ - 10, n_extra)
+    k["octave"][len(uv):] = rng.integers(0, 8, n_extra)
+    k["angle"] = rng.uniform(0, 360, n)
+    perm = rng.permutation(n)
+    return k[perm], perm
+
+
+def target_dict(keys, desc, u_right=None):
+    sf, s2, is2 = scale_tables()
+    return dict(keys_un=keys, desc=desc, bounds=(0.0, float(W), 0.0, float(H_)), scale_factors=sf, inv_level_sigma2=is2,
+                level_sigma2=s2, u_right=np.full(len(keys), -1, np.float32) if u_right is None else u_right)
+
+
+def exact_scene(S, rng, R, t, npts, mbf=0.0, n_extra=60, p_key=0.8):
+    """npts points seen by the camera [R | t] and a keyframe (pose [R | t]) with keypoints near most of their projections"""
+    xcs, ds, levels, descs = [], [], [], []
+    for _ in range(npts):
+        xc, dist = exact_camera_point(rng)
+        xcs.append(xc); ds.append(dist); levels.append(int(rng.integers(1, 7))); descs.append(rng.integers(0, 256, 32, dtype=np.uint8))
+    uv = np.array([project(x) for x in xcs], np.float32)
+    levels = np.array(levels, np.int32)
+    seen = np.nonzero(rng.uniform(size=npts) < p_key)[0]
+    keys, perm = keys_near(rng, uv[seen], levels[seen], n_extra)
+    kdesc = np.zeros((len(keys), 32), np.uint8)
+    src = np.concatenate([seen, np.full(n_extra, -1)])[perm]
+    for j, i in enumerate(src):
+        kdesc[j] = flips(rng, descs[i], int(rng.integers(0, 30))) if i >= 0 else rng.integers(0, 256, 32, dtype=np.uint8)
+    ur = np.where(rng.uniform(size=len(keys)) < 0.4, keys["x"] - rng.integers(1, 40, len(keys)), -1).astype(np.float32)
+    Tcw = np.eye(4, dtype=np.float32); Tcw[:3, :3] = R; Tcw[:3, 3] = t
+    kf = S.kf(keys, kdesc, ur, Tcw=Tcw, mbf=mbf)
+    ids = [add_exact_point(S, rng, R, t, xcs[i], ds[i], descs[i], levels[i]) for i in range(npts)]
+    pts = dict(uv=uv, level=levels, desc=np.array(descs), u_right=(uv[:, 0] - np.float32(mbf) / np.array([x[2] for x in xcs], np.float32)).astype(np.float32),
+               angle=np.zeros(npts, np.float32))
+    return kf, np.array(ids, np.int32), pts, target_dict(keys, kdesc, ur)
+
+
+def pose(R, t):
+    T = np.eye(4, dtype=np.float32); T[:3, :3] = R; T[:3, 3] = t
+    return T
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_gpu_fuse_and_fuse_sim3_exact_scenes_equal_oracle(H, seed):
+    rng = np.random.default_rng(100 + seed)
+    R, t = PERMS[seed], np.array([0.25, -0.5, 0.125], np.float32) * (seed + 1)
+    for sim3 in (False, True):
+        S = Scene(H)
+        kf, ids, pts, tgt = exact_scene(S, rng, R, t, 300, mbf=0.0 if sim3 else 64.0)
+        n = len(ids)
+        bad = rng.uniform(size=n) < 0.05
+        for i in np.nonzero(bad)[0]: H("h_set_bad", int(ids[i]))
+        slots0 = S.slots(kf)
+        # some points already observed by the keyframe (skipped), some slots taken by other points
+        inkf = np.zeros(n, bool)
+        free = [j for j in range(len(slots0)) if slots0[j] < 0]
+        for i in np.nonzero((rng.uniform(size=n) < 0.05) & ~bad)[0]:
+            S.observe(int(ids[i]), kf, free.pop()); inkf[i] = True
+        others = [S.mp(rng.integers(0, 256, 32, dtype=np.uint8)) for _ in range(80)]
+        for p in others:
+            S.observe(p, kf, free.pop())
+        slots0 = S.slots(kf)
+        valid = (~bad & ~inkf).astype(np.uint8)
+        ov = dict(pts, valid=valid)
+        cnt = i32()
+        if sim3:
+            s = 2.0 ** (seed - 1)
+            rep = i32(n)
+            H("h_fuse_sim3", kf, pose(R * np.float32(s), t * np.float32(s)), ids, n, F32(4.0), rep, cnt)
+            on, ob = oracle.fuse_sim3(tgt, ov, 4.0)
+        else:
+            H("h_fuse", kf, ids, n, F32(3.0), cnt)
+            on, ob = oracle.fuse(tgt, ov, 3.0)
+        # the map update, point by point: a free slot takes the point; an occupied slot is reported (Fuse(Scw)) or, the
+        # occupant having more observations than the new point (which has none), keeps it
+        want_slots, want_rep = slots0.copy(), np.full(n, -1, np.int32)
+        for i in range(n):
+            if ob[i] < 0: continue
+            if want_slots[ob[i]] < 0: want_slots[ob[i]] = ids[i]
+            else: want_rep[i] = want_slots[ob[i]]
+        assert cnt[0] == on > 40 and (ob >= 0).sum() == on
+        assert np.array_equal(S.slots(kf), want_slots)
+        if sim3:
+            assert np.array_equal(rep, want_rep)
+        else:
+            assert all(S.state(int(ids[i]))[0] for i in np.nonzero(want_rep >= 0)[0])   # replaced by the occupant
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", [0, 1])
+def test_gpu_projection_sim3_and_keyframe_exact_scenes_equal_oracle(H, seed):
+    """SearchByProjection(KF, Scw, points, matched, th) and SearchByProjection(Frame, KF, found, th, ORBdist)"""
+    rng = np.random.default_rng(200 + seed)
+    R, t = PERMS[seed + 1], np.array([-0.5, 0.25, 0.0625], np.float32)
+    S = Scene(H)
+    kf, ids, pts, tgt = exact_scene(S, rng, R, t, 300)
+    n = len(ids)
+    bad = rng.uniform(size=n) < 0.05
+    for i in np.nonzero(bad)[0]: H("h_set_bad", int(ids[i]))
+    N = len(tgt["keys_un"])
+    matched = np.where(rng.uniform(size=N) < 0.1, ids[rng.integers(0, n, N)], -1).astype(np.int32)
+    found = set(matched[matched >= 0].tolist())
+    valid = np.array([not bad[i] and ids[i] not in found for i in range(n)], np.uint8)
+    s = 2.0 ** (seed + 1)
+    cnt = i32()
+    got = matched.copy()
+    H("h_search_by_projection_sim3", kf, pose(R * np.float32(s), t * np.float32(s)), ids, n, got, 10, cnt)
+    om = (matched >= 0).astype(np.uint8)
+    on, ob = oracle.search_by_projection_sim3(tgt, dict(pts, valid=valid), om, 10)
+    want = matched.copy()
+    for i in range(n):
+        if ob[i] >= 0: want[ob[i]] = ids[i]
+    assert cnt[0] == on > 40 and np.array_equal(got, want)
+    # relocalisation: the keyframe's own map points projected into a frame with the same camera as the scene's
+    S2 = Scene(H)
+    kf2, ids2, pts2, tgt2 = exact_scene(S2, rng, R, t, 300)
+    angles = rng.uniform(0, 360, len(ids2)).astype(np.float32)    # SearchByProjection(F, KF) reads pKF->mvKeysUn[i].angle
+    hk = np.zeros(len(ids2), KP); hk["angle"] = angles
+    holder = S2.kf(hk, pts2["desc"])                                 # the keyframe holding the points (slot i = point i)
+    bad2 = rng.uniform(size=len(ids2)) < 0.05
+    for i in range(len(ids2)):
+        if rng.uniform() < 0.1: continue                             # a NULL slot
+        S2.observe(int(ids2[i]), holder, i)
+    for i in np.nonzero(bad2)[0]: H("h_set_bad", int(ids2[i]))
+    hslots = S2.slots(holder)
+    foundset = ids2[rng.uniform(size=len(ids2)) < 0.1]
+    f = S2.frame(tgt2["keys_un"], tgt2["desc"], Tcw=pose(R, t))
+    has = (rng.uniform(size=len(tgt2["keys_un"])) < 0.15)
+    filler = S2.mp(np.zeros(32, np.uint8))
+    for j in np.nonzero(has)[0]: H("h_frame_set", f, int(j), filler, 0)
+    for ori in (True, False):
+        for j in range(len(has)): H("h_frame_set", f, int(j), filler if has[j] else -1, 0)
+        H("h_search_by_projection_keyframe", f, holder, foundset.astype(np.int32), len(foundset), F32(10.0), 100, int(ori), cnt)
+        valid2 = np.array([hslots[i] >= 0 and not bad2[i] and hslots[i] not in set(foundset.tolist()) for i in range(len(ids2))], np.uint8)
+        on, ob = oracle.search_by_projection_kf(tgt2, dict(pts2, valid=valid2, angle=angles), has.astype(np.uint8).copy(), 10.0, 100, ori)
+        fs = i32(len(has))
+        H("h_frame_slots", f, fs)
+        want = np.where(ob >= 0, hslots[np.maximum(ob, 0)], np.where(has, filler, -1))
+        assert cnt[0] == on > 15 and np.array_equal(fs, want), ori
+
+
+@pytest.mark.gpu
+def test_gpu_search_by_sim3_exact_scene_equals_oracle(H):
+    rng = np.random.default_rng(400)
+    S = Scene(H)
+    R1, t1 = PERMS[1], np.array([0.5, 0.25, -0.125], np.float32)
+    R2, t2 = PERMS[2], np.array([-0.25, 0.5, 0.25], np.float32)
+    s12, R12 = 2.0, PERMS[1]                                         # c1 = s12 R12 c2 (t12 = 0): both distances exact
+    npts = 200
+    c2s, d2s, lv = [], [], []
+    for _ in range(npts):
+        c2, d2 = exact_camera_point(rng)
+        c2s.append(c2); d2s.append(d2); lv.append(int(rng.integers(1, 6)))
+    c1s = [s12 * (R12.astype(np.float64) @ c) for c in c2s]
+    uv1 = np.array([project(c) for c in c1s], np.float32); uv2 = np.array([project(c) for c in c2s], np.float32)
+    lv = np.array(lv, np.int32)
+    descs = rng.integers(0, 256, (npts, 32), dtype=np.uint8)
+    k1, perm1 = keys_near(rng, uv1, lv, 40); k2, perm2 = keys_near(rng, uv2, lv, 40)
+    inv1, inv2 = np.argsort(perm1), np.argsort(perm2)                # slot of physical point i in kf1 / kf2
+    d1 = rng.integers(0, 256, (len(k1), 32), dtype=np.uint8); d2 = rng.integers(0, 256, (len(k2), 32), dtype=np.uint8)
+    d1[inv1[:npts]] = [flips(rng, d, 6) for d in descs]; d2[inv2[:npts]] = [flips(rng, d, 6) for d in descs]
+    kf1 = S.kf(k1, d1, Tcw=pose(R1, t1)); kf2 = S.kf(k2, d2, Tcw=pose(R2, t2))
+    # kf1's point i lies where the Sim3 puts c2 (projected into kf2), kf2's point i where it puts c1 (projected into kf1)
+    # (the distance argument is the one PredictScale sees: |c2| for kf1's points, |c1| = 2 |c2| for kf2's)
+    P1 = [add_exact_point(S, rng, R1, t1, c1s[i], d2s[i], flips(rng, descs[i], 4), lv[i]) for i in range(npts)]
+    P2 = [add_exact_point(S, rng, R2, t2, c2s[i], 2 * d2s[i], flips(rng, descs[i], 4), lv[i]) for i in range(npts)]
+    for i in range(npts):
+        if rng.uniform() < 0.9: S.observe(P1[i], kf1, int(inv1[i]))
+        if rng.uniform() < 0.9: S.observe(P2[i], kf2, int(inv2[i]))
+    for i in rng.choice(npts, 8, replace=False): H("h_set_bad", P2[i])
+    s1, s2 = S.slots(kf1), S.slots(kf2)
+    matches = np.where(rng.uniform(size=len(k1)) < 0.05, s2[rng.integers(0, len(k2), len(k1))], -1).astype(np.int32)
+    done1 = matches >= 0
+    done2 = np.zeros(len(k2), bool)
+    for p in matches[done1]:
+        st = S.state(int(p))
+        for kk, idx in st[3]:
+            if kk == kf2: done2[idx] = True
+    p12 = dict(valid=np.zeros(len(k1), np.uint8), uv=np.zeros((len(k1), 2), np.float32), level=np.zeros(len(k1), np.int32),
+               desc=np.zeros((len(k1), 32), np.uint8))
+    p21 = dict(valid=np.zeros(len(k2), np.uint8), uv=np.zeros((len(k2), 2), np.float32), level=np.zeros(len(k2), np.int32),
+               desc=np.zeros((len(k2), 32), np.uint8))
+    for i in range(npts):
+        for slots, done, P, p, uvo, j in ((s1, done1, P1, p12, uv2, inv1[i]), (s2, done2, P2, p21, uv1, inv2[i])):
+            if slots[j] != P[i] or done[j] or S.state(P[i])[0]: continue
+            p["valid"][j] = 1; p["uv"][j] = uvo[i]; p["level"][j] = lv[i]; p["desc"][j] = np.frombuffer(S.state(P[i])[2], np.uint8)
+    got, cnt = matches.copy(), i32()
+    H("h_search_by_sim3", kf1, kf2, got, F32(s12), np.ascontiguousarray(R12), np.zeros(3, np.float32), F32(7.5), cnt)
+    on, om = oracle.search_by_sim3(target_dict(k1, d1), target_dict(k2, d2), p12, p21, 7.5)
+    assert cnt[0] == on > 40 and np.array_equal(got, np.where(om >= 0, s2[np.maximum(om, 0)], matches))
+
+
+def _triangulation_scene(S, rng, nneigh):
+    """kf1 (pose [I | (-1, -2, 0)]) and neighbours of pose [swap-xy | (2, -1, 1/4)]: the epipole C2 = (4, 0, 1/4) is exact;
+    F12 maps a point to the horizontal line through it, along which perturbed_copy moves the features"""
+    base = random_kf(rng, 400, p_mp=0.3)
+    base["feat_vec"] = make_featvec(base["desc"])
+    T1 = pose(np.eye(3, dtype=np.float32), np.array([-1, -2, 0], np.float32))
+    T2 = pose(PERMS[1], np.array([2, -1, 0.25], np.float32))
+    kf1 = S.kf(base["keys_un"], base["desc"], base["u_right"], Tcw=T1, fv=base["feat_vec"])
+    for i in np.nonzero(base["has_map_point"])[0]: S.observe(S.mp(base["desc"][i]), kf1, int(i))
+    neigh = []
+    for _ in range(nneigh):
+        kf = perturbed_copy(rng, base, nflip=int(rng.integers(4, 12)))
+        kf["feat_vec"] = make_featvec(kf["desc"])
+        k = S.kf(kf["keys_un"], kf["desc"], kf["u_right"], Tcw=T2, fv=kf["feat_vec"])
+        for i in np.nonzero(kf["has_map_point"])[0]: S.observe(S.mp(kf["desc"][i]), k, int(i))
+        neigh.append((k, kf))
+    F12 = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], np.float32)
+    return base, kf1, neigh, F12, (FX * 4 * 4 + CX, CY)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("only_stereo,ori", [(False, True), (True, False)])
+def test_gpu_search_for_triangulation_exact_epipole_equals_oracle(H, only_stereo, ori):
+    rng = np.random.default_rng(500)
+    S = Scene(H)
+    base, kf1, neigh, F12, epi = _triangulation_scene(S, rng, 1)
+    k2, kf = neigh[0]
+    sf, s2, _ = scale_tables()
+    o1 = dict(base, has_map_point=(S.slots(kf1) >= 0).astype(np.uint8))
+    o2 = dict(kf, has_map_point=(S.slots(k2) >= 0).astype(np.uint8), scale_factors=sf, level_sigma2=s2)
+    pairs, cnt = i32(2 * 400), i32()
+    H("h_search_for_triangulation", kf1, k2, F12, int(only_stereo), int(ori), pairs, 400, cnt)
+    on, om = oracle.search_for_triangulation(o1, o2, F12, epi, only_stereo, ori)
+    want = [(i, int(om[i])) for i in range(len(om)) if om[i] >= 0]
+    assert cnt[0] == on == len(want) and [tuple(p) for p in pairs[:2 * cnt[0]].reshape(-1, 2).tolist()] == want
+    assert on > (2 if only_stereo else 50)
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU (c)
+
+@pytest.mark.gpu
+def test_gpu_triangulation_batch_equals_the_loop_with_new_map_points(H):
+    results = []
+    for batch in (0, 1):
+        rng = np.random.default_rng(600)
+        S = Scene(H)
+        base, kf1, neigh, F12, _ = _triangulation_scene(S, rng, 5)
+        K = len(neigh)
+        pairs, counts = i32(K * 2 * 400), i32(K)
+        H("h_triangulation_loop", kf1, np.array([k for k, _ in neigh], np.int32), K, np.tile(F12.ravel(), K), 0, 1, batch, 3,
+          pairs, 400, counts)
+        results.append((pairs.copy(), counts.copy(), S.map_state()[0]))
+    (p0, c0, m0), (p1, c1, m1) = results
+    assert np.array_equal(c0, c1) and np.array_equal(p0, p1) and m0 == m1
+    assert c0[0] > 50 and c0[-1] < c0[0]                             # later neighbours see kf1's new map points
+
+
+def _fuse_scene(S, rng):
+    """two target keyframes a, b (same camera), list members p_i and p_j with p_j in a's slot s:
+    at a, p_i matches slot s and, observed less, is replaced by p_j (p_i->Replace(p_j)); p_j takes p_i's observations and its
+    descriptor becomes B; at b, p_j then matches the B keypoint instead of the A keypoint.  Plus ordinary points, a repeated
+    pointer and NULL entries."""
+    A = rng.integers(0, 256, 32, dtype=np.uint8)
+    B = flips(rng, A, 30)
+    X = rng.integers(0, 256, 32, dtype=np.uint8)
+    R, t = np.eye(3, dtype=np.float32), np.zeros(3, np.float32)
+    xc, dist = np.array([4.0, 8.0, 64.0]) / 64, 72.0 / 64            # (4, 8, 64) has norm 72
+    u, v = project(xc)
+    nrm = 40
+    others = [exact_camera_point(rng) for _ in range(nrm)]
+    ouv = np.array([project(x) for x, _ in others], np.float32)
+    odesc = rng.integers(0, 256, (nrm, 32), dtype=np.uint8)
+
+    def kf_keys(extra):
+        k = np.zeros(len(extra) + nrm, KP)
+        for j, (x, y, o) in enumerate(extra):
+            k[j]["x"], k[j]["y"], k[j]["octave"] = x, y, o
+        k["x"][len(extra):] = ouv[:, 0] + 0.25; k["y"][len(extra):] = ouv[:, 1]; k["octave"][len(extra):] = 1
+        return k
+    # keyframe a: slot 0 = the keypoint p_j was seen at (descriptor A, stereo); b: slot 0 the A keypoint, slot 1 the B keypoint
+    ka = kf_keys([(u + 0.5, v, 1)]); da = np.vstack([A[None], [flips(rng, d, 3) for d in odesc]])
+    kb = kf_keys([(u + 0.5, v, 1), (u - 0.5, v + 0.25, 1)]); db = np.vstack([A[None], B[None], [flips(rng, d, 5) for d in odesc]])
+    ura = np.full(len(ka), -1, np.float32); ura[0] = u
+    a = S.kf(ka, da, ura); b = S.kf(kb, db)
+    c = S.kf(np.zeros(1, KP), X[None], np.zeros(1, np.float32))     # p_j's second, stereo observation
+    ds = [S.kf(np.zeros(1, KP), B[None]) for _ in range(3)]          # p_i's three mono observations
+    lvl = 1
+    pj = add_exact_point(S, rng, R, t, xc, dist, A, lvl)
+    S.observe(pj, a, 0); S.observe(pj, c, 0)                          # Observations() = 4
+    pi = add_exact_point(S, rng, R, t, xc, dist, B, lvl)
+    for d in ds: S.observe(pi, d, 0)                                   # Observations() = 3
+    ords = [add_exact_point(S, rng, R, t, others[q][0], others[q][1], odesc[q], 1) for q in range(nrm)]
+    for q in range(0, nrm, 4): S.observe(S.mp(odesc[q]), a, 1 + q)   # some of a's slots already hold (fewer-observed) points
+    lst = [pi, -1, pj] + ords[:10] + [ords[3], -1] + ords[10:]
+    return dict(a=a, b=b, pi=pi, pj=pj, A=A, B=B, list=np.array(lst, np.int32), kfs=np.array([a, b], np.int32))
+
+
+@pytest.mark.gpu
+def test_gpu_fuse_batch_equals_the_loop_of_fuse_calls(H):
+    """FuseBatch(K, list), for k: Fuse(kf_k, list) and for k: for i: Fuse(kf_k, {p_i}) leave the same map (slots, bad flags,
+    observations, descriptors) and return the same count; the scene contains the case where a list member survives a
+    Replace at keyframe a with a new descriptor that changes its match at keyframe b"""
+    states = []
+    for mode in (2, 0, 1):
+        rng = np.random.default_rng(700)
+        S = Scene(H)
+        sc = _fuse_scene(S, rng)
+        cnt = i32()
+        H("h_fuse_loop", sc["kfs"], 2, sc["list"], len(sc["list"]), F32(3.0), mode, cnt)
+        slots, mps = S.map_state()
+        states.append((int(cnt[0]), slots, mps))
+        if mode == 2:                                                # the advisor's case did happen, in the reference order
+            bad_i, _, _, _ = S.state(sc["pi"])
+            _, _, dj, obs_j = S.state(sc["pj"])
+            assert bad_i and dj == sc["B"].tobytes() != sc["A"].tobytes()
+            assert (sc["b"], 1) in obs_j, obs_j                      # p_j went to b's B keypoint (slot 1), not to the
+            assert S.slots(sc["b"])[0] == -1                         # A keypoint (slot 0) its old descriptor matches exactly
+    ref = states[0]
+    assert ref[0] > 20
+    errors = []
+    for name, st in zip(("FuseBatch", "for k: Fuse(kf_k, list)"), states[1:]):
+        if st[1] != ref[1]: errors.append(f"{name}: keyframe slots differ from the point-by-point loop")
+        if st[2] != ref[2]:
+            errors.append(f"{name}: map points differ from the point-by-point loop: " +
+                          str([q for q in range(len(ref[2])) if st[2][q] != ref[2][q]]))
+        if st[0] != ref[0]: errors.append(f"{name}: count {st[0]} != {ref[0]}")
+    assert not errors, errors

@@ -1,8 +1,8 @@
 """Typo guard for compat/ (pins nothing): the three drop-in shims -- compat/ORBextractor.h, compat/ORBmatcher.h, compat/
-Frame_stereo.inl, 600 lines of C++ that need OpenCV and the ORB-SLAM2 headers and therefore meet no compiler in this image --
-are parsed and type-checked with `g++ -std=c++14 -Wall -fsyntax-only` against tests/compat_stubs/, which declares exactly the
-cv:: / ORB_SLAM2:: members they touch (tests/compat_stubs/README.md).  It protects the shims from the next edit; the real check
-is the maintainer's build inside an ORB-SLAM2 + OpenCV tree."""
+Frame_stereo.inl, 600 lines of C++ that need OpenCV and the ORB-SLAM2 headers -- are parsed and type-checked with `g++ -std=c++14 -Wall -fsyntax-only` against tests/compat_stubs/, which declares exactly the
+cv:: / ORB_SLAM2:: members they touch (tests/compat_stubs/README.md).  It protects the shims from the next edit.  The shims are
+executed against working stand-ins by tests/test_compat_runtime.py; the final check is still the maintainer's build inside an
+ORB-SLAM2 + OpenCV tree."""
 import os
 import shutil
 import subprocess
