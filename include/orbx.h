@@ -394,6 +394,44 @@ orbx_status orbx_undistort_keypoints_device(orbx_handle *h, int nframes, const o
                                             orbx_keypoint *d_kps_un);
 orbx_status orbx_undistort_keypoints(orbx_handle *h, const orbx_keypoint *kps, int n, const float *camera4, const float *dist,
                                      int ndist, orbx_keypoint *kps_un);
+/* ---- RGB-D Frame (reference src/Frame.cc:237-321): Frame::ComputeStereoFromRGBD (src/Frame.cc:1179-1226) after the depth
+ * conversion of Tracking::GrabImageRGBD (src/Tracking.cc:327-332).  depth_scale = Tracking's mDepthMapFactor (1 / DepthMapFactor
+ * of the settings file, 1 if |DepthMapFactor| < 1e-5).  Depth frames are W x H, `stride` bytes per row (>= W * element size,
+ * a multiple of it), `frame_stride` bytes apart:
+ *   ORBX_DEPTH_U16: convertTo(CV_32F, scale) makes a continuous float image, pixel = (float)raw * scale;
+ *   ORBX_DEPTH_F32: with fabs(scale - 1.0f) > 1e-5 converted in place (the caller's stride is kept, bytes between rows stay
+ *                   unscaled), otherwise read as they are.
+ * Per keypoint: u = (int)kps[i].x, v = (int)kps[i].y (the DISTORTED keypoint, padded-image coordinates in this fork); the
+ * sample is byte o = v * pitch + 4 * u of that float image (pitch = 4 * W for u16, `stride` for f32; a u beyond the row wraps
+ * into the next row, as in the reference).  F7: o + 4 > (H - 1) * pitch + 4 * W lies past the image's
+ * memory and gives no depth, and so do negative, non-finite or too-large coordinates.  d > 0: depth[i] = d,
+ * u_right[i] = kps_un[i].x - mbf / d (IEEE single division); otherwise both -1. */
+enum { ORBX_DEPTH_U16 = 0, ORBX_DEPTH_F32 = 1 };
+/* Device buffers as orbx_extract_batch_device filled them (records `cap` apart, d_counts per frame), fused with
+ * orbx_undistort_keypoints_device: one launch computes mvKeysUn (camera4 / dist / ndist as there; written to d_kps_un unless it
+ * is NULL, byte-identical to orbx_undistort_keypoints_device), mvuRight and mvDepth ([nframes][cap], rows beyond a frame's
+ * count untouched).  Asynchronous on the handle's stream. */
+orbx_status orbx_rgbd_depth_device(orbx_handle *h, int nframes, const orbx_keypoint *d_kps, const int32_t *d_counts, int cap,
+                                   const float *camera4, const float *dist, int ndist, const void *d_depth, int depth_format,
+                                   int width, int height, int stride, int64_t frame_stride, float depth_scale, float mbf,
+                                   orbx_keypoint *d_kps_un, float *d_u_right, float *d_depth_out);
+/* The body of Frame::ComputeStereoFromRGBD for one frame: host buffers, kps = mvKeys, kps_un = mvKeysUn (as the Frame holds
+ * them), depth = the frame's depth image; run on the device like orbx_undistort_keypoints. */
+orbx_status orbx_rgbd_depth(orbx_handle *h, const orbx_keypoint *kps, const orbx_keypoint *kps_un, int n, const void *depth,
+                            int depth_format, int width, int height, int stride, float depth_scale, float mbf, float *u_right,
+                            float *depth_out);
+/* The RGB-D Frame constructor for nframes host frames: extraction exactly as orbx_extract_batch (input format of
+ * orbx_set_input_format, same chunks), then per frame kps_un / u_right / depth as orbx_rgbd_depth_device; depth frames have
+ * the image's width and height.  Outputs [nframes][cap].  Depth reaches the device in one of two ways, with identical results:
+ * uploaded chunk by chunk on the copy stream, or -- when `depth` is page-locked and device-mapped (orbx_host_alloc,
+ * hipHostMalloc, hipHostRegister with the mapped flag) -- read in place by the kernel, one sample per keypoint.  The environment
+ * variable ORBX_RGBD_DEPTH=upload|inplace (read per call) selects between them for mapped depth; the default is in DESIGN.md
+ * section 0.  Like the output buffers of orbx_extract_batch, mapped kps_un / u_right / depth are written in place. */
+orbx_status orbx_extract_rgbd_batch(orbx_handle *h, int nframes, const uint8_t *imgs, int width, int height, int stride,
+                                    int64_t frame_stride, const void *depth, int depth_format, int depth_stride,
+                                    int64_t depth_frame_stride, float depth_scale, const float *camera4, const float *dist,
+                                    int ndist, float mbf, orbx_keypoint *kps, orbx_keypoint *kps_un, uint8_t *desc,
+                                    int32_t *counts, float *u_right, float *depth_out, int cap);
 /* Frame::AssignFeaturesToGrid + PosInGrid (src/Frame.cc:432-460, 729-745) on the device, for the keypoint buffers
  * orbx_extract_batch_device / orbx_undistort_keypoints_device filled (records `cap` apart, cap <= 65535): per frame
  * d_cell_begin[64 * 48 + 1] offsets (bucket c = column * 48 + row, the reference's mGrid[column][row]) into d_items[cap], the

@@ -16,6 +16,7 @@ assert KP_DTYPE.itemsize == 28
 OK, EMPTY_IMAGE, BAD_ARGUMENT, BAD_ASPECT, CAPACITY, HIP_ERROR, NO_DEVICE, UNSUPPORTED = range(8)
 FP_GCC_FMA, FP_STRICT = 0, 1
 FMT_GRAY8, FMT_RGB8, FMT_BGR8, FMT_RGBA8, FMT_BGRA8 = range(5)
+DEPTH_U16, DEPTH_F32 = 0, 1
 K_NAMES = ("k_pyr_l0", "k_pyr_resize", "k_fast_rows", "k_quadtree", "k_orient", "k_blur", "k_describe",
            "k_match", "misc")
 K_COUNT = len(K_NAMES)
@@ -94,7 +95,8 @@ SYMBOLS = [
     "orbx_search_by_projection_sim3", "orbx_search_by_sim3", "orbx_search_by_projection_keyframe",
     "orbx_stereo_match_batch_device", "orbx_host_alloc", "orbx_host_free", "orbx_set_rectification", "orbx_undistort_keypoints_device",
     "orbx_grid_build_device", "orbx_gated_candidates",
-    "orbx_undistort_keypoints", "orbx_image_bounds", "orbx_vocabulary_create", "orbx_vocabulary_destroy", "orbx_bow_transform", "orbx_bow_transform_device", "orbx_bow_vectors",
+    "orbx_undistort_keypoints", "orbx_image_bounds", "orbx_rgbd_depth_device", "orbx_rgbd_depth", "orbx_extract_rgbd_batch",
+    "orbx_vocabulary_create", "orbx_vocabulary_destroy", "orbx_bow_transform", "orbx_bow_transform_device", "orbx_bow_vectors",
 ]
 
 _lib = None
@@ -206,6 +208,13 @@ def lib():
     L.orbx_undistort_keypoints.restype = i32; L.orbx_undistort_keypoints.argtypes = [vp, vp, i32, vp, vp, i32, vp]
     L.orbx_image_bounds.restype = i32; L.orbx_image_bounds.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     L.orbx_set_rectification.restype = i32; L.orbx_set_rectification.argtypes = [vp, vp, vp, i32, i32]
+    L.orbx_rgbd_depth_device.restype = i32
+    L.orbx_rgbd_depth_device.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i64, f32, f32, vp, vp, vp]
+    L.orbx_rgbd_depth.restype = i32
+    L.orbx_rgbd_depth.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, f32, vp, vp]
+    L.orbx_extract_rgbd_batch.restype = i32
+    L.orbx_extract_rgbd_batch.argtypes = [vp, i32, vp, i32, i32, i32, i64, vp, i32, i32, i64, f32, vp, vp, i32, f32,
+                                          vp, vp, vp, vp, vp, vp, i32]
     L.orbx_host_alloc.restype = vp; L.orbx_host_alloc.argtypes = [C.c_size_t]
     L.orbx_host_free.restype = None; L.orbx_host_free.argtypes = [vp]
     _lib = L

@@ -12,11 +12,17 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <cmath>
 #include "orbx_internal.h"
 #include "orbx_launch.h"
 #include "orbx_gate.h"
 
 static thread_local std::string g_last_error;
+// orbx_extract_rgbd_batch with page-locked, device-mapped depth: read it in place (true) or upload it (false) by default;
+// ORBX_RGBD_DEPTH=upload|inplace overrides per call.  Measured at 640x480, chunks of 64: 46.8 k / 49.2 k frames/s per 256 /
+// 1024-frame call in place against 33.4 k / 34.7 k uploaded (profiles/rgbd_rates.log)
+#define ORBX_RGBD_INPLACE_DEFAULT true
+
 static orbx_status fail(orbx_status s, const std::string &msg) {
     g_last_error = msg;
     return s;
@@ -73,6 +79,9 @@ struct orbx_handle {
     int *pin_stat = nullptr; size_t pin_stat_ints = 0;   // page-locked landing place of the per-frame counts | status words of a call (grow-only)
     hipStream_t s_in = nullptr;   // the ONE copy stream of the pipelined host-buffer call (uploads and downloads in turn)
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
+    // staging of orbx_extract_rgbd_batch (grow-only): the depth frames of a chunk; kps_un | u_right | depth of a chunk (one block)
+    uint8_t *st_dep[2] = {nullptr, nullptr}; size_t dep_bytes = 0;
+    uint8_t *st_rg[2] = {nullptr, nullptr}; size_t rg_bytes = 0;
     int last_batch = 0;
     int mk_w = 0, mk_h = 0, mk_total = 0;   // orbx_max_keypoints cache
     void *d_match_ws = nullptr; size_t match_ws_bytes = 0;   // partial (best, second) keys of k_match
@@ -396,6 +405,7 @@ extern "C" void orbx_destroy(orbx_handle *h) {
         if (h->pin_stat) hipHostFree(h->pin_stat);
         for (int s = 0; s < 2; ++s) {
             hipFree(h->st_in[s]); hipFree(h->st_kps[s]);   // st_desc / st_cnt live inside the st_kps allocation
+            hipFree(h->st_dep[s]); hipFree(h->st_rg[s]);
             if (h->ev_in[s]) hipEventDestroy(h->ev_in[s]);
             if (h->ev_done[s]) hipEventDestroy(h->ev_done[s]);
             if (h->ev_out[s]) hipEventDestroy(h->ev_out[s]);
@@ -675,9 +685,35 @@ extern "C" void *orbx_host_alloc(size_t bytes) {
 }
 extern "C" void orbx_host_free(void *p) { if (p) hipHostFree(p); }
 
-extern "C" orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uint8_t *imgs, int width, int height,
-                                          int stride, int64_t frame_stride, orbx_keypoint *kps, uint8_t *desc,
-                                          int32_t *counts, int cap) {
+// The RGB-D part of orbx_extract_rgbd_batch (NULL for orbx_extract_batch): k_rgbd runs behind every chunk's kernels on the
+// chunk's keypoints, reading the chunk's depth from staging or, mapped, from the caller's memory.
+struct RgbdHost {
+    const uint8_t *depth; int format, stride; int64_t frame_stride; float scale, mbf; int scale_f32;
+    double K4[4], k14[14]; int identity;
+    orbx_keypoint *kps_un; float *u_right, *depth_out;
+};
+static int depth_elem(int format) { return format == ORBX_DEPTH_U16 ? 2 : 4; }
+// bytes of one depth frame the kernel may read: (H - 1) rows and the W samples of the last one
+static int64_t depth_span(int format, int width, int height, int stride) {
+    return (int64_t)(height - 1) * stride + (int64_t)width * depth_elem(format);
+}
+static orbx_status ensure_rgbd_staging(orbx_handle *h, size_t dep_bytes, size_t rg_bytes) {
+    if (dep_bytes <= h->dep_bytes && rg_bytes <= h->rg_bytes) return ORBX_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t db = std::max(dep_bytes, h->dep_bytes), rb = std::max(rg_bytes, h->rg_bytes);
+    for (int s = 0; s < 2; ++s) { hipFree(h->st_dep[s]); hipFree(h->st_rg[s]); h->st_dep[s] = nullptr; h->st_rg[s] = nullptr; }
+    h->dep_bytes = 0; h->rg_bytes = 0;
+    for (int s = 0; s < 2; ++s) {
+        if (db) HIPCHK(hipMalloc(&h->st_dep[s], db));
+        HIPCHK(hipMalloc(&h->st_rg[s], rb));
+    }
+    h->dep_bytes = db; h->rg_bytes = rb;
+    return ORBX_OK;
+}
+
+static orbx_status extract_host(orbx_handle *h, int nframes, const uint8_t *imgs, int width, int height, int stride,
+                                int64_t frame_stride, orbx_keypoint *kps, uint8_t *desc, int32_t *counts, int cap,
+                                const RgbdHost *rg) {
     if (!h) return fail(ORBX_BAD_ARGUMENT, "null handle");
     if (!imgs || width <= 0 || height <= 0 || nframes <= 0) return fail(ORBX_EMPTY_IMAGE, "empty image");
     if (!kps || !desc || !counts || cap <= 0 || stride < width * orbx_fmt_channels(h->input_format)) return fail(ORBX_BAD_ARGUMENT, "bad output buffers / stride");
@@ -696,12 +732,27 @@ extern "C" orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uin
     // synchronous), one slot per chunk so that nothing is reused before the call's single final wait
     if ((size_t)2 * nchunks * chunk > h->pin_stat_ints) {
         HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->s_in) HIPCHK(hipStreamSynchronize(h->s_in));
         if (h->pin_stat) { hipHostFree(h->pin_stat); h->pin_stat = nullptr; h->pin_stat_ints = 0; }
         HIPCHK(hipHostMalloc((void **)&h->pin_stat, (size_t)2 * nchunks * chunk * sizeof(int), hipHostMallocDefault));
         h->pin_stat_ints = (size_t)2 * nchunks * chunk;
     }
     int *hstat = h->pin_stat;
     orbx_status worst = ORBX_OK;
+    // RGB-D depth: read in place over the link when the caller's depth is page-locked and device-mapped (about one 64-byte
+    // sample per keypoint instead of the whole frame) unless ORBX_RGBD_DEPTH=upload; staged chunk by chunk otherwise, dfb bytes
+    // per frame in staging
+    const uint8_t *d_inplace = nullptr;
+    const int64_t dspan = rg ? depth_span(rg->format, width, height, rg->stride) : 0, dfb = rg ? (int64_t)rg->stride * height : 0;
+    if (rg) {
+        const char *e = getenv("ORBX_RGBD_DEPTH");
+        const bool want_inplace = e ? strcmp(e, "inplace") == 0 : ORBX_RGBD_INPLACE_DEFAULT;
+        void *pd = nullptr;
+        if (want_inplace && hipHostGetDevicePointer(&pd, (void *)rg->depth, 0) == hipSuccess && pd) d_inplace = (const uint8_t *)pd;
+        else (void)hipGetLastError();
+        st = ensure_rgbd_staging(h, d_inplace ? 0 : (size_t)chunk * dfb, (size_t)chunk * cap * (sizeof(orbx_keypoint) + 2 * sizeof(float)));
+        if (st != ORBX_OK) return st;
+    }
     // a single chunk needs no second stream: copies and kernels in order on the handle's stream (the latency path)
     const bool piped = nchunks > 1;
     // Pipelined calls use ONE copy stream for both directions: upload(c+1) and download(c-1) take turns on it while chunk c
@@ -726,6 +777,19 @@ extern "C" orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uin
                 if (e != hipSuccess) return e;
             }
         }
+        if (rg && !d_inplace) {   // the chunk's depth frames, dfb bytes apart in staging: only the span the kernel may read
+            if (rg->frame_stride == dfb) {
+                const hipError_t e = hipMemcpyAsync(h->st_dep[s], rg->depth + (int64_t)f0 * dfb, (size_t)((B - 1) * dfb + dspan),
+                                                    hipMemcpyHostToDevice, sin);
+                if (e != hipSuccess) return e;
+            } else {
+                for (int i = 0; i < B; ++i) {
+                    const hipError_t e = hipMemcpyAsync(h->st_dep[s] + (int64_t)i * dfb, rg->depth + (int64_t)(f0 + i) * rg->frame_stride,
+                                                        (size_t)dspan, hipMemcpyHostToDevice, sin);
+                    if (e != hipSuccess) return e;
+                }
+            }
+        }
         return piped ? hipEventRecord(h->ev_in[s], sin) : hipSuccess;
     };
     // Page-locked, device-mapped output buffers (orbx_host_alloc, hipHostMalloc, hipHostRegister with the mapped flag) are
@@ -743,12 +807,29 @@ extern "C" orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uin
             (void)hipGetLastError();   // pageable (or unmapped) buffers: results are staged in device memory and copied
         }
     }
+    // RGB-D outputs: written in place when all three are mapped (as kps / desc above), staged otherwise
+    orbx_keypoint *zun = nullptr; float *zur = nullptr, *zdp = nullptr;
+    if (rg) {
+        void *pu = nullptr, *pr = nullptr, *pd = nullptr;
+        if (hipHostGetDevicePointer(&pu, rg->kps_un, 0) == hipSuccess && hipHostGetDevicePointer(&pr, rg->u_right, 0) == hipSuccess &&
+            hipHostGetDevicePointer(&pd, rg->depth_out, 0) == hipSuccess && pu && pr && pd) {
+            zun = (orbx_keypoint *)pu; zur = (float *)pr; zdp = (float *)pd;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
     // download of chunk c: queued behind the chunk's kernels; its event frees the output set for chunk c+2's kernels
     auto download_enqueue = [&](int c) -> hipError_t {
         const int s = c & 1, f0 = c * chunk, B = std::min(chunk, nframes - f0);
         hipError_t e = piped ? hipStreamWaitEvent(sout, h->ev_done[s], 0) : hipSuccess;
         if (e == hipSuccess && !zk) e = hipMemcpyAsync(kps + (int64_t)f0 * cap, h->st_kps[s], (size_t)B * cap * sizeof(orbx_keypoint), hipMemcpyDeviceToHost, sout);
         if (e == hipSuccess && !zk) e = hipMemcpyAsync(desc + (int64_t)f0 * cap * 32, h->st_desc[s], (size_t)B * cap * 32, hipMemcpyDeviceToHost, sout);
+        if (rg && !zun) {
+            const size_t nk = (size_t)chunk * cap;
+            if (e == hipSuccess) e = hipMemcpyAsync(rg->kps_un + (int64_t)f0 * cap, h->st_rg[s], (size_t)B * cap * sizeof(orbx_keypoint), hipMemcpyDeviceToHost, sout);
+            if (e == hipSuccess) e = hipMemcpyAsync(rg->u_right + (int64_t)f0 * cap, h->st_rg[s] + nk * sizeof(orbx_keypoint), (size_t)B * cap * sizeof(float), hipMemcpyDeviceToHost, sout);
+            if (e == hipSuccess) e = hipMemcpyAsync(rg->depth_out + (int64_t)f0 * cap, h->st_rg[s] + nk * (sizeof(orbx_keypoint) + sizeof(float)), (size_t)B * cap * sizeof(float), hipMemcpyDeviceToHost, sout);
+        }
         // counts | status are one device block (st_cnt[s][0 .. 2 chunk)): ONE small copy (every copy costs ~15 us of link
         // turn-around whatever its size); the counts go on to the caller's array from the landing buffer
         if (e == hipSuccess) e = hipMemcpyAsync(hstat + (size_t)c * 2 * chunk, h->st_cnt[s], (size_t)2 * chunk * sizeof(int), hipMemcpyDeviceToHost, sout);
@@ -764,27 +845,37 @@ extern "C" orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uin
             }
         }
     };
+    // Every error exit from here on waits for both streams first: kernels and copies may still be writing the caller's
+    // buffers (zero-copy outputs) or reading them (in-place depth), and the caller may free them once the call returns.
+#define DRAINCHK(expr)                                                                                              \
+    do {                                                                                                            \
+        hipError_t _e = (expr);                                                                                     \
+        if (_e != hipSuccess) {                                                                                     \
+            hipStreamSynchronize(h->stream); hipStreamSynchronize(sin);                                             \
+            return fail(ORBX_HIP_ERROR, std::string(#expr) + ": " + hipGetErrorString(_e));                         \
+        }                                                                                                           \
+    } while (0)
     // Latency path (one chunk that fills its staging block exactly, a few MB at most -- the drop-in call of Tracking.cc): the
     // frames go through page-locked staging (one true DMA instead of a runtime-staged pageable copy) and the results come
     // back with ONE copy of the whole output block instead of four.
     const size_t out_bytes = (size_t)chunk * cap * (sizeof(orbx_keypoint) + 32) + (size_t)2 * chunk * sizeof(int);
     const size_t in_bytes_q = (size_t)nframes * fbytes;
     const bool stage_in = in_bytes_q <= ((size_t)1 << 20);   // beyond ~1 MB the host-side memcpy costs more than the runtime's own staging
-    const bool quick = !piped && nframes == h->stage_chunk && cap == h->out_cap && out_bytes <= ((size_t)4 << 20) &&
+    const bool quick = !rg && !piped && nframes == h->stage_chunk && cap == h->out_cap && out_bytes <= ((size_t)4 << 20) &&
                        pin_reserve(h, (stage_in ? in_bytes_q : 0) + out_bytes) == ORBX_OK;
     if (quick) {
         uint8_t *pin_in = h->pin, *pin_out = h->pin + (stage_in ? in_bytes_q : 0);
         if (stage_in) {
             for (int i = 0; i < nframes; ++i) memcpy(pin_in + (size_t)i * fbytes, imgs + (int64_t)i * frame_stride, fbytes);
-            HIPCHK(hipMemcpyAsync(h->st_in[0], pin_in, in_bytes_q, hipMemcpyHostToDevice, h->stream));
+            DRAINCHK(hipMemcpyAsync(h->st_in[0], pin_in, in_bytes_q, hipMemcpyHostToDevice, h->stream));
         } else {
-            HIPCHK(upload(0));
+            DRAINCHK(upload(0));
         }
         st = run_chunk(h, nframes, h->st_in[0], width, height, stride, (int64_t)fbytes, h->st_kps[0], h->st_desc[0], h->st_cnt[0],
                        h->st_cnt[0] + chunk, cap);
         if (st != ORBX_OK) { hipStreamSynchronize(h->stream); return st; }
-        HIPCHK(hipMemcpyAsync(pin_out, h->st_kps[0], out_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        DRAINCHK(hipMemcpyAsync(pin_out, h->st_kps[0], out_bytes, hipMemcpyDeviceToHost, h->stream));
+        DRAINCHK(hipStreamSynchronize(h->stream));
         const size_t kb = (size_t)nframes * cap * sizeof(orbx_keypoint), db = (size_t)nframes * cap * 32;
         const int *cnt = (const int *)(pin_out + kb + db);
         // only the meaningful part of every frame's records leaves the staging buffer
@@ -798,30 +889,153 @@ extern "C" orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uin
         if (worst != ORBX_OK) return fail(worst, "a frame exceeded the keypoint / candidate capacity");
         return ORBX_OK;
     }
-    HIPCHK(upload(0));
+    DRAINCHK(upload(0));
     for (int c = 0; c < nchunks; ++c) {
         const int s = c & 1, f0 = c * chunk, B = std::min(chunk, nframes - f0);
-        if (piped) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_in[s], 0));             // the chunk's frames have arrived
-        st = run_chunk(h, B, h->st_in[s], width, height, stride, (int64_t)fbytes, zk ? zk + (int64_t)f0 * cap : h->st_kps[s],
-                       zk ? zd + (int64_t)f0 * cap * 32 : h->st_desc[s], h->st_cnt[s], h->st_cnt[s] + chunk, cap);
+        if (piped) DRAINCHK(hipStreamWaitEvent(h->stream, h->ev_in[s], 0));             // the chunk's frames have arrived
+        orbx_keypoint *ck = zk ? zk + (int64_t)f0 * cap : h->st_kps[s];
+        st = run_chunk(h, B, h->st_in[s], width, height, stride, (int64_t)fbytes, ck, zk ? zd + (int64_t)f0 * cap * 32 : h->st_desc[s],
+                       h->st_cnt[s], h->st_cnt[s] + chunk, cap);
         if (st != ORBX_OK) { hipStreamSynchronize(h->stream); hipStreamSynchronize(sin); return st; }
-        if (piped) HIPCHK(hipEventRecord(h->ev_done[s], h->stream));
+        if (rg) {   // Frame::ComputeStereoFromRGBD behind the chunk's kernels, on the records they just wrote
+            const size_t nk = (size_t)chunk * cap;
+            OrbxRgbdArgs a;
+            a.depth = d_inplace ? d_inplace + (int64_t)f0 * rg->frame_stride : h->st_dep[s];
+            a.frame_stride = d_inplace ? rg->frame_stride : dfb; a.stride = rg->stride;
+            a.format = rg->format; a.width = width; a.height = height; a.scale_f32 = rg->scale_f32; a.scale = rg->scale; a.mbf = rg->mbf;
+            { ProfScope ps(h, ORBX_K_MISC);
+              orbx_launch_rgbd(h->stream, B, cap, cap, rg->K4, rg->k14, rg->identity, a, ck, nullptr, h->st_cnt[s],
+                               zun ? zun + (int64_t)f0 * cap : (orbx_keypoint *)h->st_rg[s],
+                               zun ? zur + (int64_t)f0 * cap : (float *)(h->st_rg[s] + nk * sizeof(orbx_keypoint)),
+                               zun ? zdp + (int64_t)f0 * cap : (float *)(h->st_rg[s] + nk * (sizeof(orbx_keypoint) + sizeof(float)))); }
+            DRAINCHK(hipGetLastError());
+        }
+        if (piped) DRAINCHK(hipEventRecord(h->ev_done[s], h->stream));
         // copy stream: results of chunk c-1 first (its kernels are done or nearly so), then the frames of chunk c+1 (its input
         // set was read by chunk c-1: the download in front of it already waited for that chunk)
-        if (c >= 1) HIPCHK(download_enqueue(c - 1));
-        if (c + 1 < nchunks) HIPCHK(upload(c + 1));
+        if (c >= 1) DRAINCHK(download_enqueue(c - 1));
+        if (c + 1 < nchunks) DRAINCHK(upload(c + 1));
         // the calling thread stays one chunk ahead of the device, not more: it waits here until chunk c-1's results have left
         // their output set, which chunk c+1's kernels (enqueued next) write.  (Letting it run ahead of the whole call with
         // stream-side waits instead was measured: 82 k against 111 k frames/s at chunks of 32, 84 k against 95 k at 16 chunks
         // of 64 -- many queued cross-stream waits cost more than the wake-ups they save.)
-        if (piped && c >= 1) HIPCHK(hipEventSynchronize(h->ev_out[(c - 1) & 1]));
+        if (piped && c >= 1) DRAINCHK(hipEventSynchronize(h->ev_out[(c - 1) & 1]));
     }
-    HIPCHK(download_enqueue(nchunks - 1));
-    HIPCHK(hipStreamSynchronize(sout));
-    if (piped) HIPCHK(hipStreamSynchronize(h->stream));
+    DRAINCHK(download_enqueue(nchunks - 1));
+    DRAINCHK(hipStreamSynchronize(sout));
+    if (piped) DRAINCHK(hipStreamSynchronize(h->stream));
+#undef DRAINCHK
     collect();
     if (worst != ORBX_OK) return fail(worst, "a frame exceeded the keypoint / candidate capacity");
     return ORBX_OK;
+}
+
+extern "C" orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uint8_t *imgs, int width, int height,
+                                          int stride, int64_t frame_stride, orbx_keypoint *kps, uint8_t *desc,
+                                          int32_t *counts, int cap) {
+    return extract_host(h, nframes, imgs, width, height, stride, frame_stride, kps, desc, counts, cap, nullptr);
+}
+
+// ---------------------------------------------------------------- RGB-D Frame: Frame::ComputeStereoFromRGBD (k_rgbd)
+static void undistort_args(const float *camera4, const float *dist, int ndist, double *K4, double *k14, int *identity);
+// argument rules shared by the three RGB-D entry points (checked before any device work)
+static orbx_status rgbd_check(int nframes, const void *depth, int format, int width, int height, int stride, int64_t frame_stride) {
+    if (format != ORBX_DEPTH_U16 && format != ORBX_DEPTH_F32) return fail(ORBX_BAD_ARGUMENT, "unknown depth format");
+    const int el = depth_elem(format);
+    if (!depth || width <= 0 || height <= 0) return fail(ORBX_BAD_ARGUMENT, "empty depth image");
+    if ((int64_t)stride < (int64_t)width * el || stride % el != 0) return fail(ORBX_BAD_ARGUMENT, "depth stride below W * element size or not a multiple of it");
+    if ((uintptr_t)depth % el != 0) return fail(ORBX_BAD_ARGUMENT, "depth pointer not aligned to its element size");
+    if (nframes > 1 && (frame_stride % el != 0 || frame_stride < depth_span(format, width, height, stride)))
+        return fail(ORBX_BAD_ARGUMENT, "depth frame stride overlaps the frames or is not a multiple of the element size");
+    return ORBX_OK;
+}
+// mDepthMapFactor != 1 (|f - 1| > 1e-5, src/Tracking.cc:327): f32 input is converted in place; u16 input always is
+static int rgbd_scale_f32(int format, float scale) { return format == ORBX_DEPTH_F32 && (double)fabsf(scale - 1.0f) > 1e-5; }
+
+extern "C" orbx_status orbx_rgbd_depth_device(orbx_handle *h, int nframes, const orbx_keypoint *d_kps, const int32_t *d_counts, int cap,
+                                              const float *camera4, const float *dist, int ndist, const void *d_depth, int depth_format,
+                                              int width, int height, int stride, int64_t frame_stride, float depth_scale, float mbf,
+                                              orbx_keypoint *d_kps_un, float *d_u_right, float *d_depth_out) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "null handle");
+    if (nframes <= 0 || cap <= 0 || !d_kps || !d_counts || !d_u_right || !d_depth_out || !camera4 || ndist < 0 || ndist > 14 ||
+        (ndist > 0 && !dist))
+        return fail(ORBX_BAD_ARGUMENT, "bad argument");
+    orbx_status st = rgbd_check(nframes, d_depth, depth_format, width, height, stride, frame_stride);
+    if (st != ORBX_OK) return st;
+    if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
+    HIPCHK(hipSetDevice(h->dev));
+    double K4[4], k14[14]; int identity;
+    undistort_args(camera4, dist, ndist, K4, k14, &identity);
+    OrbxRgbdArgs a;
+    a.depth = (const uint8_t *)d_depth; a.frame_stride = frame_stride; a.stride = stride; a.format = depth_format;
+    a.width = width; a.height = height; a.scale_f32 = rgbd_scale_f32(depth_format, depth_scale); a.scale = depth_scale; a.mbf = mbf;
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_rgbd(h->stream, nframes, cap, cap, K4, k14, identity, a, d_kps, nullptr, d_counts, d_kps_un, d_u_right, d_depth_out); }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
+    return ORBX_OK;
+}
+
+static orbx_status scratch_reserve(orbx_handle *h, size_t bytes);
+template <typename T> static T *scratch_take(orbx_handle *h, size_t count);
+extern "C" orbx_status orbx_rgbd_depth(orbx_handle *h, const orbx_keypoint *kps, const orbx_keypoint *kps_un, int n, const void *depth,
+                                       int depth_format, int width, int height, int stride, float depth_scale, float mbf,
+                                       float *u_right, float *depth_out) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "null handle");
+    if (n < 0 || (n > 0 && (!kps || !kps_un || !u_right || !depth_out))) return fail(ORBX_BAD_ARGUMENT, "bad argument");
+    orbx_status st = rgbd_check(1, depth, depth_format, width, height, stride, 0);
+    if (st != ORBX_OK) return st;
+    if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
+    if (n == 0) return ORBX_OK;
+    HIPCHK(hipSetDevice(h->dev));
+    const size_t span = (size_t)depth_span(depth_format, width, height, stride);
+    const size_t kb = (size_t)n * sizeof(orbx_keypoint), fb = (size_t)n * sizeof(float);
+    st = scratch_reserve(h, 2 * ((kb + 255) & ~(size_t)255) + ((2 * fb + 255) & ~(size_t)255) + ((span + 255) & ~(size_t)255) + 256);
+    if (st != ORBX_OK) return st;
+    orbx_keypoint *dk = scratch_take<orbx_keypoint>(h, n), *dku = scratch_take<orbx_keypoint>(h, n);
+    float *dout = scratch_take<float>(h, 2 * (size_t)n);
+    uint8_t *dd = scratch_take<uint8_t>(h, span);
+    const double K4[4] = {1, 1, 0, 0}, k14[14] = {0};
+    OrbxRgbdArgs a;
+    a.depth = dd; a.frame_stride = 0; a.stride = stride; a.format = depth_format; a.width = width; a.height = height;
+    a.scale_f32 = rgbd_scale_f32(depth_format, depth_scale); a.scale = depth_scale; a.mbf = mbf;
+#define SYNCCHK(expr)                                                                                                       \
+    do {                                                                                                                    \
+        hipError_t _e = (expr);                                                                                             \
+        if (_e != hipSuccess) { hipStreamSynchronize(h->stream); return fail(ORBX_HIP_ERROR, std::string(#expr) + ": " + hipGetErrorString(_e)); } \
+    } while (0)
+    SYNCCHK(hipMemcpyAsync(dk, kps, kb, hipMemcpyHostToDevice, h->stream));
+    SYNCCHK(hipMemcpyAsync(dku, kps_un, kb, hipMemcpyHostToDevice, h->stream));
+    SYNCCHK(hipMemcpyAsync(dd, depth, span, hipMemcpyHostToDevice, h->stream));
+    orbx_launch_rgbd(h->stream, 1, n, n, K4, k14, 1, a, dk, dku, nullptr, nullptr, dout, dout + n);
+    SYNCCHK(hipGetLastError());
+    SYNCCHK(hipMemcpyAsync(u_right, dout, fb, hipMemcpyDeviceToHost, h->stream));
+    SYNCCHK(hipMemcpyAsync(depth_out, dout + n, fb, hipMemcpyDeviceToHost, h->stream));
+    SYNCCHK(hipStreamSynchronize(h->stream));
+#undef SYNCCHK
+    return ORBX_OK;
+}
+
+extern "C" orbx_status orbx_extract_rgbd_batch(orbx_handle *h, int nframes, const uint8_t *imgs, int width, int height, int stride,
+                                               int64_t frame_stride, const void *depth, int depth_format, int depth_stride,
+                                               int64_t depth_frame_stride, float depth_scale, const float *camera4, const float *dist,
+                                               int ndist, float mbf, orbx_keypoint *kps, orbx_keypoint *kps_un, uint8_t *desc,
+                                               int32_t *counts, float *u_right, float *depth_out, int cap) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "null handle");
+    if (nframes <= 0 || !imgs || width <= 0 || height <= 0) return fail(ORBX_EMPTY_IMAGE, "empty image");
+    if (!kps || !kps_un || !desc || !counts || !u_right || !depth_out || cap <= 0 || !camera4 || ndist < 0 || ndist > 14 ||
+        (ndist > 0 && !dist))
+        return fail(ORBX_BAD_ARGUMENT, "bad argument");
+    orbx_status st = rgbd_check(nframes, depth, depth_format, width, height, depth_stride, depth_frame_stride);
+    if (st != ORBX_OK) return st;
+    if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
+    RgbdHost rg;
+    rg.depth = (const uint8_t *)depth; rg.format = depth_format; rg.stride = depth_stride;
+    rg.frame_stride = nframes > 1 ? depth_frame_stride : depth_span(depth_format, width, height, depth_stride);
+    rg.scale = depth_scale; rg.mbf = mbf; rg.scale_f32 = rgbd_scale_f32(depth_format, depth_scale);
+    undistort_args(camera4, dist, ndist, rg.K4, rg.k14, &rg.identity);
+    rg.kps_un = kps_un; rg.u_right = u_right; rg.depth_out = depth_out;
+    return extract_host(h, nframes, imgs, width, height, stride, frame_stride, kps, desc, counts, cap, &rg);
 }
 
 extern "C" orbx_status orbx_extract(orbx_handle *h, const uint8_t *img, int width, int height, int stride,

@@ -2627,12 +2627,8 @@ __global__ __launch_bounds__(256) void k_bow_transform(DVoc voc, const uint8_t *
 // oracle/orb_oracle_match.c).  One thread per keypoint, the other 20 bytes of the record are copied.
 // ------------------------------------------------------------------------------------------------
 struct DUndist { double fx, fy, cx, cy, k[14]; int identity; };
-__global__ __launch_bounds__(256) void k_undistort(DUndist u, const orbx_keypoint *__restrict__ kps, const int *__restrict__ counts,
-                                                   int fixed_n, int cap, orbx_keypoint *__restrict__ out) {
-    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    const int n = counts ? min(counts[f], cap) : fixed_n;
-    if (i >= n) return;
-    orbx_keypoint kp = kps[(long long)f * cap + i];
+// the per-keypoint body of K10, shared with k_rgbd (K10b): both write the same undistorted record
+__device__ __forceinline__ void undistort_kp(const DUndist &u, orbx_keypoint &kp) {
     if (!u.identity) {
         const double ifx = 1. / u.fx, ify = 1. / u.fy;
         double x = (double)kp.x, y = (double)kp.y;
@@ -2651,7 +2647,78 @@ __global__ __launch_bounds__(256) void k_undistort(DUndist u, const orbx_keypoin
         kp.x = (float)(xx * ww);
         kp.y = (float)(yy * ww);
     }
+}
+__global__ __launch_bounds__(256) void k_undistort(DUndist u, const orbx_keypoint *__restrict__ kps, const int *__restrict__ counts,
+                                                   int fixed_n, int cap, orbx_keypoint *__restrict__ out) {
+    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n = counts ? min(counts[f], cap) : fixed_n;
+    if (i >= n) return;
+    orbx_keypoint kp = kps[(long long)f * cap + i];
+    undistort_kp(u, kp);
     out[(long long)f * cap + i] = kp;
+}
+
+// ------------------------------------------------------------------------------------------------
+// K10b: the RGB-D Frame (reference src/Frame.cc:237-321): Frame::ComputeStereoFromRGBD (:1179-1226) fused with K10.  One
+// thread per keypoint: mvKeysUn (the record k_undistort writes, or read from `kun_in` when the caller has it already), then
+// the depth sample at the DISTORTED keypoint, u = (int)kp.x, v = (int)kp.y, read where the reference reads it: byte
+// o = v * pitch + 4 * u of the float image Tracking::GrabImageRGBD made (src/Tracking.cc:327-332; pitch = 4 * W for u16 input,
+// which convertTo turned into a continuous float image, the caller's stride for f32 input).  A u beyond the row wraps into the
+// next row, as in the reference (the coordinates are padded-image coordinates).  F7: a sample with o + 4 > limit =
+// (H - 1) * pitch + 4 * W lies past the image's memory (undefined behaviour in the reference) and gives no depth; so do
+// negative, non-finite and too-large coordinates, rejected before the integer conversion.  d > 0: mvDepth = d, mvuRight =
+// xU - mbf / d (IEEE single division, no contraction: the build has -ffp-contract=off); otherwise both stay -1.
+// ------------------------------------------------------------------------------------------------
+struct DRgbd {
+    const uint8_t *depth;       // frame 0 of the depth input
+    long long frame_stride;     // bytes between frames
+    long long stride;           // bytes per row of the input (u16 or f32)
+    long long pitch;            // bytes per row of the float image the reference reads
+    long long limit;            // (H - 1) * pitch + 4 * W
+    int W, u16, scale_rows;     // scale_rows: f32 input converted in place (only the W floats of each row are scaled)
+    float scale, mbf;
+};
+__global__ __launch_bounds__(256) void k_rgbd(DUndist u, DRgbd r, const orbx_keypoint *__restrict__ kps,
+                                              const orbx_keypoint *__restrict__ kun_in, const int *__restrict__ counts, int fixed_n,
+                                              int cap, orbx_keypoint *__restrict__ kun_out, float *__restrict__ u_right,
+                                              float *__restrict__ depth) {
+    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n = counts ? min(counts[f], cap) : fixed_n;
+    if (i >= n) return;
+    const long long at = (long long)f * cap + i;
+    const orbx_keypoint kp = kps[at];
+    float xu;
+    if (kun_in) {
+        xu = kun_in[at].x;
+    } else {
+        orbx_keypoint ku = kp;
+        undistort_kp(u, ku);
+        if (kun_out) kun_out[at] = ku;
+        xu = ku.x;
+    }
+    float ur = -1.0f, dd = -1.0f;
+    // NaN fails both comparisons; 2^31 keeps the conversion defined
+    if (kp.x >= 0.0f && kp.y >= 0.0f && kp.x < 2147483648.0f && kp.y < 2147483648.0f) {
+        const long long uu = (int)kp.x, vv = (int)kp.y;
+        const long long o = vv * r.pitch + 4 * uu;
+        if (o + 4 <= r.limit) {
+            const uint8_t *img = r.depth + (long long)f * r.frame_stride;
+            float d;
+            if (r.u16) {   // cvtScale_ (OpenCV 3.2): one float multiply, then + 0.0f
+                const long long p = o >> 2, row = p / r.W, col = p - row * r.W;
+                d = (float)*(const uint16_t *)(img + row * r.stride + 2 * col) * r.scale + 0.0f;
+            } else {
+                d = *(const float *)(img + o);
+                if (r.scale_rows && o % r.pitch < 4LL * r.W) d = d * r.scale + 0.0f;   // the gap between rows stays unscaled
+            }
+            if (d > 0.0f) {
+                dd = d;
+                ur = xu - r.mbf / d;
+            }
+        }
+    }
+    u_right[at] = ur;
+    depth[at] = dd;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3099,6 +3166,23 @@ void orbx_launch_undistort(hipStream_t s, int B, int max_n, int cap, const doubl
     for (int i = 0; i < 14; ++i) u.k[i] = k14[i];
     u.identity = identity;
     hipLaunchKernelGGL(k_undistort, dim3((max_n + 255) / 256, B), dim3(256), 0, s, u, kps, counts, max_n, cap, out);
+}
+void orbx_launch_rgbd(hipStream_t s, int B, int max_n, int cap, const double *K4, const double *k14, int identity,
+                      const OrbxRgbdArgs &a, const orbx_keypoint *kps, const orbx_keypoint *kun_in, const int *counts,
+                      orbx_keypoint *kun_out, float *u_right, float *depth) {
+    if (B <= 0 || max_n <= 0) return;
+    DUndist u;
+    u.fx = K4[0]; u.fy = K4[1]; u.cx = K4[2]; u.cy = K4[3];
+    for (int i = 0; i < 14; ++i) u.k[i] = k14[i];
+    u.identity = identity;
+    DRgbd r;
+    r.depth = a.depth; r.frame_stride = a.frame_stride; r.stride = a.stride; r.W = a.width;
+    r.u16 = a.format == ORBX_DEPTH_U16;
+    r.pitch = r.u16 ? 4LL * a.width : a.stride;
+    r.limit = (long long)(a.height - 1) * r.pitch + 4LL * a.width;
+    r.scale_rows = a.scale_f32; r.scale = a.scale; r.mbf = a.mbf;
+    hipLaunchKernelGGL(k_rgbd, dim3((max_n + 255) / 256, B), dim3(256), 0, s, u, r, kps, kun_in, counts, max_n, cap, kun_out,
+                       u_right, depth);
 }
 void orbx_launch_bow_transform(hipStream_t s, int B, int max_n, const int *child_begin, const uint32_t *child_ids,
                                const uint8_t *node_desc, int n_nodes, int L, const uint8_t *desc, const int *counts,

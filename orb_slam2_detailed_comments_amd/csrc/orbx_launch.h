@@ -19,6 +19,16 @@ void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell 
                            int dbg_stop, int lds_floor = 0);
 void orbx_launch_undistort(hipStream_t s, int B, int max_n, int cap, const double *K4, const double *k14, int identity,
                            const orbx_keypoint *kps, const int *counts, orbx_keypoint *out);
+// depth input of k_rgbd (Frame::ComputeStereoFromRGBD): `depth` = frame 0, frames `frame_stride` bytes apart, rows `stride`
+// bytes apart; scale_f32 = f32 input that Tracking::GrabImageRGBD converts in place (|scale - 1| > 1e-5)
+struct OrbxRgbdArgs {
+    const uint8_t *depth; long long frame_stride, stride;
+    int format, width, height, scale_f32;
+    float scale, mbf;
+};
+void orbx_launch_rgbd(hipStream_t s, int B, int max_n, int cap, const double *K4, const double *k14, int identity,
+                      const OrbxRgbdArgs &a, const orbx_keypoint *kps, const orbx_keypoint *kun_in, const int *counts,
+                      orbx_keypoint *kun_out, float *u_right, float *depth);
 void orbx_launch_bow_transform(hipStream_t s, int B, int max_n, const int *child_begin, const uint32_t *child_ids,
                                const uint8_t *node_desc, int n_nodes, int L, const uint8_t *desc, const int *counts,
                                long long frame_stride, int levelsup, uint32_t *out_leaf, uint32_t *out_nid, int out_stride);

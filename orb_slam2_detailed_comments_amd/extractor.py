@@ -114,6 +114,41 @@ class ORBextractor:
                                          ptr(desc), ptr(counts), cap))
         return [(kps[i, :counts[i]].copy(), desc[i, :counts[i]].copy()) for i in range(b)]
 
+    def extract_rgbd_batch(self, images, depths, K, dist, mbf, depth_scale, out=None):
+        """The RGB-D Frame constructor (src/Frame.cc:237-321) for a batch: images [B,H,W] (gray) or [B,H,W,C] (the format set
+        with set_input_format), depths [B,H,W] uint16 or float32 (page-locked depth, e.g. a _capi.PinnedArray, may be read in
+        place), K = (fx, fy, cx, cy), dist = mDistCoef, depth_scale = mDepthMapFactor.  Returns a list of
+        (keypoints, keypoints_un, descriptors, u_right, depth) per frame; `out` = (kps, kps_un, desc, counts, u_right, depth)
+        preallocated [B, cap] arrays (e.g. page-locked) to write into instead."""
+        imgs = np.ascontiguousarray(images)
+        dep = np.asarray(depths)   # not copied: page-locked depth must keep its address
+        assert imgs.dtype == np.uint8 and imgs.ndim in (3, 4)
+        assert dep.ndim == 3 and dep.dtype in (np.uint16, np.float32) and dep.strides[2] == dep.itemsize
+        b, h, w = imgs.shape[:3]
+        assert dep.shape == (b, h, w), "one depth frame of the image's size per image"
+        k4 = np.ascontiguousarray(K, np.float32); d = np.ascontiguousarray(dist, np.float32)
+        cap = self.max_keypoints(w, h)
+        if out is None:
+            out = (np.zeros((b, cap), KP_DTYPE), np.zeros((b, cap), KP_DTYPE), np.zeros((b, cap, 32), np.uint8),
+                   np.zeros(b, np.int32), np.zeros((b, cap), np.float32), np.zeros((b, cap), np.float32))
+        kps, kun, desc, counts, ur, dp = out
+        assert kps.shape[1] == cap and kun.shape[1] == cap and desc.shape[1] == cap and ur.shape[1] == cap and dp.shape[1] == cap
+        fmt = _capi.DEPTH_U16 if dep.dtype == np.uint16 else _capi.DEPTH_F32
+        check(self._L.orbx_extract_rgbd_batch(self._h, b, ptr(imgs), w, h, imgs.strides[1], imgs.strides[0], ptr(dep), fmt,
+                                              dep.strides[1], dep.strides[0], float(depth_scale), ptr(k4), ptr(d), len(d),
+                                              float(mbf), ptr(kps), ptr(kun), ptr(desc), ptr(counts), ptr(ur), ptr(dp), cap))
+        return [(kps[i, :counts[i]].copy(), kun[i, :counts[i]].copy(), desc[i, :counts[i]].copy(), ur[i, :counts[i]].copy(),
+                 dp[i, :counts[i]].copy()) for i in range(b)]
+
+    def rgbd_depth_device(self, nframes, d_kps, d_counts, cap, K, dist, d_depth, depth_format, width, height, stride,
+                          frame_stride, depth_scale, mbf, d_kps_un, d_u_right, d_depth_out):
+        """device-pointer entry (orbx_rgbd_depth_device) on the buffers extract_batch_device filled; d_kps_un may be None.
+        Asynchronous on the handle's stream."""
+        k4 = np.ascontiguousarray(K, np.float32); d = np.ascontiguousarray(dist, np.float32)
+        check(self._L.orbx_rgbd_depth_device(self._h, nframes, ptr(d_kps), ptr(d_counts), cap, ptr(k4), ptr(d), len(d),
+                                             ptr(d_depth), depth_format, width, height, stride, frame_stride, float(depth_scale),
+                                             float(mbf), ptr(d_kps_un), ptr(d_u_right), ptr(d_depth_out)))
+
     def set_rectification(self, map_x=None, map_y=None):
         """cv::remap(., M1, M2, INTER_LINEAR) of the EuRoC driver fused into level 0 (float32 maps of the image size);
         None, None switches it off"""

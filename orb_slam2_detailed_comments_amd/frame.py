@@ -10,6 +10,23 @@ from ._capi import KP_DTYPE, check, ptr, lib
 FRAME_GRID_ROWS, FRAME_GRID_COLS = 48, 64  # include/Frame.h:54,59
 
 
+def depth_map_factor(yaml_value):
+    """Tracking's mDepthMapFactor from the settings file's DepthMapFactor (src/Tracking.cc:201-211): 1 if |f| < 1e-5,
+    otherwise 1.0f / f in single precision (TUM: 5000 -> 1/5000.f)"""
+    f = np.float32(yaml_value)
+    if float(abs(f)) < 1e-5:   # fabs(float) compared in double
+        return np.float32(1.0)
+    return np.float32(np.float32(1.0) / f)
+
+
+def _depth_args(depth):
+    """(format, width, height, row stride in bytes) of a u16 / f32 depth image (rows may be strided, elements contiguous)"""
+    d = np.asarray(depth)
+    assert d.ndim == 2 and d.dtype in (np.uint16, np.float32) and d.strides[1] == d.itemsize, \
+        "depth: H x W uint16 (raw sensor units) or float32, contiguous rows"
+    return (_capi.DEPTH_U16 if d.dtype == np.uint16 else _capi.DEPTH_F32), d.shape[1], d.shape[0], d.strides[0]
+
+
 class Frame:
     def __init__(self, keys, descriptors, width, height, bounds=None):
         """keys: KP_DTYPE array (mvKeys == mvKeysUn: no distortion), descriptors [N,32] uint8,
@@ -58,6 +75,18 @@ class Frame:
                                       ptr(right.mDescriptors), right.N, mb, mbf, ptr(self.mvuRight), ptr(self.mvDepth),
                                       C.byref(n)))
         return n.value
+
+    def ComputeStereoFromRGBD(self, extractor, imDepth, mbf, depth_scale=1.0):
+        """Frame::ComputeStereoFromRGBD (src/Frame.cc:1179-1226) after Tracking::GrabImageRGBD's conversion (src/Tracking.cc:327-332):
+        imDepth = the raw depth image (uint16 or float32, H x W), depth_scale = mDepthMapFactor (depth_map_factor()).  Samples at
+        the distorted keypoint; F7 samples past the image get no depth.  Sets and returns (mvuRight, mvDepth)."""
+        fmt, w, h, stride = _depth_args(imDepth)
+        self.mvuRight = np.full(self.N, -1.0, np.float32)
+        self.mvDepth = np.full(self.N, -1.0, np.float32)
+        kun = np.ascontiguousarray(self.mvKeysUn, KP_DTYPE)
+        check(lib().orbx_rgbd_depth(extractor.handle, ptr(self.mvKeys), ptr(kun), self.N, ptr(np.asarray(imDepth)), fmt, w, h,
+                                    stride, float(depth_scale), float(mbf), ptr(self.mvuRight), ptr(self.mvDepth)))
+        return self.mvuRight, self.mvDepth
 
     def _free(self):
         if getattr(self, "_grid", None):

@@ -5,6 +5,8 @@ image and cannot be fetched, so every test and bench input comes from here.
 stream(...)  : the same scene translated by (3t mod 17, 2t mod 11) px with gain 1 +- 0.02.
 stereo_pair(): right image = left scene re-rendered with a per-rectangle disparity U[4,60] px
                (rectified by construction).
+depth_stream(): RGB-D depth frames to go with stream(): smooth metric depth in TUM's units (x5000, uint16) with
+               Kinect-like holes of 0, or float32 metres with NaN holes.
 """
 from __future__ import annotations
 import numpy as np
@@ -88,6 +90,41 @@ def stream(width, height, nframes, stream_id=0):
 def stereo_pair(width, height, stream_id=0, t=0):
     sc = Scene(width, height, stream_id)
     return sc.frame(t, right=False), sc.frame(t, right=True)
+
+
+def depth_stream(width, height, nframes, stream_id=0, fmt="u16", hole_frac=0.08):
+    """[nframes, H, W] depth: a tilted plane 0.8 .. 4 m with smooth bumps, moving like stream(); holes (zero for u16 as a
+    Kinect leaves them, NaN for float32) cover about hole_frac of each frame in blobs, plus single dropped pixels."""
+    assert fmt in ("u16", "f32")
+    rng = np.random.Generator(np.random.PCG64(_SEED_BASE + 0xD000 + stream_id))
+    m = 64
+    H, W = height + 2 * m, width + 2 * m
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    base = 0.8 + 2.4 * (yy / H) + 0.8 * (xx / W)
+    base += _value_noise(rng, H, W, 48, 0.35) + _value_noise(rng, H, W, 16, 0.05)
+    base = np.clip(base, 0.5, 6.0).astype(np.float32)
+    out = []
+    for t in range(nframes):
+        dx, dy = (3 * t) % 17, (2 * t) % 11
+        d = base[m + dy:m + dy + height, m + dx:m + dx + width].copy()
+        fr = np.random.Generator(np.random.PCG64(_SEED_BASE + 0xD100 + 7919 * stream_id + t))
+        hole = np.zeros((height, width), bool)
+        target = hole_frac * width * height
+        while hole.sum() < 0.8 * target:
+            cy, cx = fr.uniform(0, height), fr.uniform(0, width)
+            ry, rx = fr.uniform(2, 0.06 * height + 3), fr.uniform(2, 0.06 * width + 3)
+            y0, y1 = int(max(0, cy - ry)), int(min(height, cy + ry + 1))
+            x0, x1 = int(max(0, cx - rx)), int(min(width, cx + rx + 1))
+            hole[y0:y1, x0:x1] = True
+        hole |= fr.uniform(size=(height, width)) < 0.2 * hole_frac
+        if fmt == "u16":
+            v = np.rint(d * 5000.0).astype(np.uint16)
+            v[hole] = 0
+        else:
+            v = d.astype(np.float32)
+            v[hole] = np.nan
+        out.append(v)
+    return np.stack(out)
 
 
 def degenerate(kind, width, height):

@@ -201,6 +201,13 @@ def main():
         lambda: FL.ComputeStereoMatches(FR, exL, exR, 0.537, 386.1448),
         lambda: oracle.stereo_matches(kL, dL, kR, dR, tabs["scale"], tabs["inv_scale"], pl, pr, 0.537, 386.1448))
     add("orbx_match_bruteforce", "DescriptorDistance x 1000 x 1000", lambda: m.match_bruteforce(d2, d1), lambda: oracle.match_bruteforce(d2, d1))
+    # ---- Frame::ComputeStereoFromRGBD as the compat body calls it: CV_32F depth (GrabImageRGBD converted it), scale 1.  CPU side:
+    # the same body in vectorised numpy (tests/rgbd_model.py) -- the oracle has no RGB-D step
+    import rgbd_model
+    depf = synth.depth_stream(640, 480, 1, stream_id=41, fmt="f32")[0]
+    Fd = Frame(k2, d2, 640, 480)
+    add("orbx_rgbd_depth", "Frame.cc:1179-1226 (640x480 f32 depth)", lambda: Fd.ComputeStereoFromRGBD(ex, depf, 40.0, 1.0),
+        lambda: rgbd_model.rgbd_depth_vectorized(k2["x"], k2["y"], k2["x"], depf, 1.0, 40.0))
     if "--json" in sys.argv:
         json.dump(dict(host_cores=os.cpu_count(), note="host buffers in/out, synchronous; CPU = single-thread oracle (-O2 scalar C)", rows=rows),
                   open(sys.argv[sys.argv.index("--json") + 1], "w"), indent=1)
