@@ -382,6 +382,64 @@ orbx_status orbx_bow_vectors(const orbx_vocabulary *voc, const uint32_t *word_id
                              const uint32_t *node_id, int n, uint32_t *bow_word, double *bow_value, int *n_bow,
                              uint32_t *fv_node, int32_t *fv_begin, uint32_t *fv_index, int *n_fv_nodes);
 
+/* ---- Keyframe database (reference src/KeyFrameDatabase.cc, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp): the link between
+ * orbx_bow_vectors and the batched SearchByBoW calls.  The database keeps the BowVectors of its entries (on the device for a
+ * device handle) and the per-entry state the reference keeps in the KeyFrames: mnRelocQuery / mnRelocWords / mRelocScore and
+ * mnLoopQuery / mnLoopWords / mLoopScore.  That state persists across queries exactly as in the reference; DESIGN.md section 2
+ * F8 states what a read of a score no query has written yields.  A database needs nothing from the vocabulary but its scoring
+ * type (orbx_vocabulary_scoring), so it also works with a host-only handle, where every call runs the reference's
+ * inverted-file walk on the host; ORBX_KFDB=host (read per call) selects that path on a device handle too.  KL scoring needs
+ * libm's log and exists on the host path only (ORBX_UNSUPPORTED otherwise).  All buffers are host buffers; BowVectors are
+ * passed as orbx_bow_vectors writes them (words ascending).  One database serves one thread at a time. */
+typedef struct orbx_kfdb orbx_kfdb;
+int orbx_vocabulary_scoring(const orbx_vocabulary *voc);   /* the view's scoring field; -1 for NULL */
+/* TemplatedVocabulary::score(a, b) for all six scoring types, on the host.  The handle supplies fp_mode: `score += vi * wi`
+ * of L2 / dot product (and the products of KL) is one fused multiply-add under ORBX_FP_GCC_FMA. */
+orbx_status orbx_bow_score(const orbx_handle *h, int scoring, const uint32_t *a_word, const double *a_value, int na,
+                           const uint32_t *b_word, const double *b_value, int nb, double *score);
+orbx_status orbx_kfdb_create(orbx_handle *h, int scoring, orbx_kfdb **out);   /* the handle must outlive the database */
+void orbx_kfdb_destroy(orbx_kfdb *db);
+orbx_status orbx_kfdb_clear(orbx_kfdb *db);
+int orbx_kfdb_size(const orbx_kfdb *db);
+/* KeyFrameDatabase::add / erase (:56-88).  id = KeyFrame::mnId, unique: a duplicate add or an unknown erase is
+ * ORBX_BAD_ARGUMENT.  An entry starts with the state of a new KeyFrame (marks and counts 0, scores unwritten); erase keeps the
+ * order of the other entries.  New vectors reach the device pool with the next query (one copy for all of them). */
+orbx_status orbx_kfdb_add(orbx_kfdb *db, int64_t id, const uint32_t *bow_word, const double *bow_value, int n);
+orbx_status orbx_kfdb_erase(orbx_kfdb *db, int64_t id);
+/* mpVocabulary->score(query, entry) for the named entries, one launch: the minScore loop of LoopClosing::DetectLoop
+ * (src/LoopClosing.cc:143-157).  Touches no state. */
+orbx_status orbx_kfdb_score_entries(orbx_kfdb *db, const uint32_t *q_word, const double *q_value, int nq, const int64_t *ids,
+                                    int n, double *scores);
+/* Steps 1-3 of DetectRelocalizationCandidates (:274-343) for nqueries frames, as if run one after the other in that order:
+ * query q has id query_ids[q] (Frame::mnId) and the BowVector q_word / q_value[q_begin[q] .. q_begin[q + 1]).  Per query:
+ * n_matches[q] = length of lScoreAndMatch, min_common_words[q] = minCommonWords (0 when no entry shares a word); the list
+ * itself is read with orbx_kfdb_query_matches.  One launch set and one device round trip per call while nqueries x entries
+ * stays below 8 M pairs (whole queries per set beyond that); downloads are bounded by the number of sharers. */
+orbx_status orbx_kfdb_query_reloc(orbx_kfdb *db, int nqueries, const int64_t *query_ids, const int32_t *q_begin,
+                                  const uint32_t *q_word, const double *q_value, int32_t *n_matches, int32_t *min_common_words);
+/* Steps 1-3 of DetectLoopCandidates (:114-185): connected_ids = pKF->GetConnectedKeyFrames() (ids outside the database are
+ * ignored), lScoreAndMatch keeps si >= min_score. */
+orbx_status orbx_kfdb_query_loop(orbx_kfdb *db, int64_t query_id, const uint32_t *q_word, const double *q_value, int nq,
+                                 const int64_t *connected_ids, int nconnected, float min_score, int32_t *n_matches,
+                                 int32_t *min_common_words);
+/* lScoreAndMatch of query `query` of the last query call, in list order; valid until the next add / erase / clear / query */
+orbx_status orbx_kfdb_query_matches(orbx_kfdb *db, int query, int64_t *ids, float *scores, int cap, int *n);
+/* the entries whose marks / counts / scores that query changed (a drop-in class writes exactly these back to its KeyFrames) */
+orbx_status orbx_kfdb_query_touched(orbx_kfdb *db, int query, int64_t *ids, int cap, int *n);
+/* Steps 4-5 (:187-263, :345-411) for query `query` of the last query call.  neigh_ids[neigh_begin[i] .. neigh_begin[i + 1]) =
+ * GetBestCovisibilityKeyFrames(10) of lScoreAndMatch[i], evaluated by the caller at this moment, as the reference does (ids
+ * outside the database carry no mark and are skipped).  It is a second call because the covisibility graph is the caller's
+ * state -- the same split as orbx_triangulation_batch_create / _select.  It sees marks, counts and scores as of that query,
+ * not as of the end of the batch, so it is called for query 0, 1, ... in order, each at most once, before any other call on the
+ * database (ORBX_BAD_ARGUMENT otherwise; queries it is not called for still leave their state behind).  candidates: cap >=
+ * n_matches[query].  *n_unscored_reads = reads of a score that no query had written (F8: each read as 0.0f). */
+orbx_status orbx_kfdb_select_groups(orbx_kfdb *db, int query, const int32_t *neigh_begin, const int64_t *neigh_ids,
+                                    int64_t *candidates, int cap, int *n, int *n_unscored_reads);
+/* mn{Reloc,Loop}Query, mn{Reloc,Loop}Words, m{Reloc,Loop}Score of an entry (loop_form = 0 / 1); *score_valid = 0 while no
+ * query has written the score (*score is 0.0f then).  Ends the batch of the last query call like add / erase do. */
+orbx_status orbx_kfdb_state(orbx_kfdb *db, int64_t id, int loop_form, int64_t *mark, int32_t *words, float *score,
+                            int *score_valid);
+
 /* ---- Frame glue: Frame::UndistortKeyPoints / ComputeImageBounds (src/Frame.cc:770-865) =
  * cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK) on the keypoint coordinates.  camera4 = fx, fy, cx, cy of mK;
  * dist = mDistCoef (k1, k2, p1, p2[, k3], at most 14); dist[0] == 0 copies the keypoints unchanged (:772-776).  OpenCV 3.2

@@ -8,3 +8,4 @@ from .extractor import ORBextractor  # noqa: F401
 from .matcher import ORBmatcher  # noqa: F401
 from .frame import Frame, depth_map_factor  # noqa: F401
 from .vocabulary import ORBVocabulary  # noqa: F401
+from .keyframe_db import KeyFrameDatabase, bow_score  # noqa: F401

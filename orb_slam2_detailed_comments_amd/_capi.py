@@ -97,6 +97,9 @@ SYMBOLS = [
     "orbx_grid_build_device", "orbx_gated_candidates",
     "orbx_undistort_keypoints", "orbx_image_bounds", "orbx_rgbd_depth_device", "orbx_rgbd_depth", "orbx_extract_rgbd_batch",
     "orbx_vocabulary_create", "orbx_vocabulary_destroy", "orbx_bow_transform", "orbx_bow_transform_device", "orbx_bow_vectors",
+    "orbx_vocabulary_scoring", "orbx_bow_score", "orbx_kfdb_create", "orbx_kfdb_destroy", "orbx_kfdb_clear", "orbx_kfdb_size",
+    "orbx_kfdb_add", "orbx_kfdb_erase", "orbx_kfdb_score_entries", "orbx_kfdb_query_reloc", "orbx_kfdb_query_loop",
+    "orbx_kfdb_query_matches", "orbx_kfdb_query_touched", "orbx_kfdb_select_groups", "orbx_kfdb_state",
 ]
 
 _lib = None
@@ -215,6 +218,23 @@ def lib():
     L.orbx_extract_rgbd_batch.restype = i32
     L.orbx_extract_rgbd_batch.argtypes = [vp, i32, vp, i32, i32, i32, i64, vp, i32, i32, i64, f32, vp, vp, i32, f32,
                                           vp, vp, vp, vp, vp, vp, i32]
+    L.orbx_vocabulary_scoring.restype = i32; L.orbx_vocabulary_scoring.argtypes = [vp]
+    L.orbx_bow_score.restype = i32; L.orbx_bow_score.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, C.POINTER(C.c_double)]
+    L.orbx_kfdb_create.restype = i32; L.orbx_kfdb_create.argtypes = [vp, i32, C.POINTER(vp)]
+    L.orbx_kfdb_destroy.restype = None; L.orbx_kfdb_destroy.argtypes = [vp]
+    L.orbx_kfdb_clear.restype = i32; L.orbx_kfdb_clear.argtypes = [vp]
+    L.orbx_kfdb_size.restype = i32; L.orbx_kfdb_size.argtypes = [vp]
+    L.orbx_kfdb_add.restype = i32; L.orbx_kfdb_add.argtypes = [vp, i64, vp, vp, i32]
+    L.orbx_kfdb_erase.restype = i32; L.orbx_kfdb_erase.argtypes = [vp, i64]
+    L.orbx_kfdb_score_entries.restype = i32; L.orbx_kfdb_score_entries.argtypes = [vp, vp, vp, i32, vp, i32, vp]
+    L.orbx_kfdb_query_reloc.restype = i32; L.orbx_kfdb_query_reloc.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_kfdb_query_loop.restype = i32; L.orbx_kfdb_query_loop.argtypes = [vp, i64, vp, vp, i32, vp, i32, f32, vp, vp]
+    L.orbx_kfdb_query_matches.restype = i32; L.orbx_kfdb_query_matches.argtypes = [vp, i32, vp, vp, i32, C.POINTER(i32)]
+    L.orbx_kfdb_query_touched.restype = i32; L.orbx_kfdb_query_touched.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
+    L.orbx_kfdb_select_groups.restype = i32
+    L.orbx_kfdb_select_groups.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.orbx_kfdb_state.restype = i32
+    L.orbx_kfdb_state.argtypes = [vp, i64, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(f32), C.POINTER(i32)]
     L.orbx_host_alloc.restype = vp; L.orbx_host_alloc.argtypes = [C.c_size_t]
     L.orbx_host_free.restype = None; L.orbx_host_free.argtypes = [vp]
     _lib = L

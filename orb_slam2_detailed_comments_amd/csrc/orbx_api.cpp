@@ -105,6 +105,8 @@ struct orbx_handle {
 // shared with orbx_policies.cpp
 orbx_status orbx_fail(orbx_status s, const std::string &msg) { return fail(s, msg); }
 int orbx_handle_fp_mode(const orbx_handle *h) { return h->p.fp_mode; }
+bool orbx_handle_host_only(const orbx_handle *h) { return h->host_only; }   // orbx_kfdb.cpp
+int orbx_handle_device(const orbx_handle *h) { return h->dev; }
 
 static const char *k_names[ORBX_K_COUNT] = {"k_pyr_l0", "k_pyr_resize", "k_fast_rows", "k_quadtree", "k_orient",
                                             "k_blur",   "k_describe",   "k_match",      "misc"};
@@ -1994,6 +1996,8 @@ struct orbx_vocabulary {
     uint32_t *d_child_ids = nullptr;
     uint8_t *d_desc = nullptr;
 };
+
+extern "C" int orbx_vocabulary_scoring(const orbx_vocabulary *v) { return v ? v->scoring : -1; }
 
 extern "C" void orbx_vocabulary_destroy(orbx_vocabulary *v) {
     if (!v) return;

@@ -129,3 +129,10 @@ __device__ __forceinline__ float orbx_fast_atan2(float y, float x) {
     return a;
 }
 
+
+// Keyframe database (orbx_kfdb.cpp; KeyFrameDatabase::Detect*Candidates steps 1-3).  One record per (query, entry) pair that
+// shares at least one word, appended by k_kfdb_common in no particular order; k_kfdb_score fills score / ORBX_KF_SCORED.
+struct DKfRec { uint32_t q, slot, count, minword, flags; float score; };
+#define ORBX_KF_CONNECTED 1u   // entry is in the loop query's spConnectedKeyFrames: never marked, never listed
+#define ORBX_KF_SCORED 2u
+#define ORBX_KFDB_LDS_WORDS 4096   // query words staged in LDS (16 KB); longer queries are searched in global memory

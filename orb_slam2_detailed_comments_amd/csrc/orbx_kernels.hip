@@ -3035,6 +3035,197 @@ __global__ void k_clear(int *a, int na, int *b, int nb, int *c, int nc) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// K14: keyframe database (orbx_kfdb.cpp): steps 1-3 of KeyFrameDatabase::DetectRelocalizationCandidates / DetectLoopCandidates
+// (reference src/KeyFrameDatabase.cc:114-411) and DBoW2's scoring functions (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp).
+// An entry is a slot (offset, length) into the pooled BowVectors: words ascending, values next to them.
+// ------------------------------------------------------------------------------------------------
+#define KF_BATCH 32   // records a wave collects in LDS before it appends them
+// index of `w` in the ascending array `a[0..n)`, -1 if absent
+template <class P> __device__ __forceinline__ int kf_find(P a, int n, uint32_t w) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < w) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && a[lo] == w ? lo : -1;
+}
+// One wave per (query, entry): lanes stride over the entry's words and test membership in the query's; ballot / popcount
+// gives mn*Words, the wave minimum the smallest common word (the entry's position key in lKFsSharingWords).  Integer only.
+template <class P> __device__ __forceinline__ void kf_common_entries(P qw, int nq, uint32_t q, const uint2 *__restrict__ slots,
+                                                                     int nslots, const uint32_t *__restrict__ pool_w,
+                                                                     const uint8_t *__restrict__ connected, int *__restrict__ qmax,
+                                                                     uint32_t *__restrict__ cursor, DKfRec *__restrict__ rec,
+                                                                     uint32_t cap, DKfRec *s_rec) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // Records are collected per wave and appended KF_BATCH at a time, the maximum is kept per wave: one atomic on the shared
+    // cursor per sharer serialised the whole grid on one address (measured: 4.6 ms of a 4.8 ms launch).
+    int nbuf = 0, wmax = 0;
+    auto flush = [&]() {
+        orbx_wave_sync();
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(cursor, (uint32_t)nbuf);
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        for (int k = lane; k < nbuf; k += 64)
+            if (base + k < cap) rec[base + k] = s_rec[k];
+        orbx_wave_sync();
+        nbuf = 0;
+    };
+    for (int e = blockIdx.x * 4 + wave; e < nslots; e += gridDim.x * 4) {
+        const uint2 s = slots[e];
+        int cnt = 0;
+        uint32_t minw = 0xffffffffu;
+        // Four words per lane and round: the loads are issued together and the four searches advance in lockstep (the trip
+        // count depends on nq alone), so four independent chains hide the latency of one.
+        for (uint32_t i0 = 0; i0 < s.y; i0 += 256) {
+            uint32_t w[4], base[4];
+            bool in[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t i = i0 + 64 * k + lane;
+                in[k] = i < s.y;
+                w[k] = in[k] ? pool_w[s.x + i] : 0u;
+                base[k] = 0;
+            }
+            // if w is in qw[0..nq) its index stays inside [base, base + len)
+            for (int len = nq; len > 1;) {
+                const int half = len >> 1;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (qw[base[k] + half - 1] < w[k]) base[k] += half;
+                len -= half;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool f = in[k] && qw[base[k]] == w[k];
+                if (f) minw = min(minw, w[k]);
+                cnt += __popcll(orbx_ballot(f));
+            }
+        }
+        if (cnt == 0) continue;                      // wave-uniform
+        minw = orbx_wave_min(minw);
+        const uint32_t conn = connected && connected[e] ? ORBX_KF_CONNECTED : 0u;
+        if (!conn) wmax = max(wmax, cnt);            // maxCommonWords runs over lKFsSharingWords only
+        if (lane == 0) {
+            DKfRec R;
+            R.q = q; R.slot = (uint32_t)e; R.count = (uint32_t)cnt; R.minword = minw; R.flags = conn; R.score = 0.0f;
+            s_rec[nbuf] = R;
+        }
+        if (++nbuf == KF_BATCH) flush();
+    }
+    if (nbuf) flush();
+    if (wmax && lane == 0) atomicMax(&qmax[q], wmax);
+}
+// grid (entry groups, queries).  The query's sorted word ids are staged in LDS when they fit (the usual BowVector has at most
+// one word per feature); a longer query is searched where it lies: it is read by every wave of the grid row, so it stays in
+// L2, and the search is the same code -- a rare case is not worth a second LDS budget that would halve the occupancy of the
+// common one.
+__global__ __launch_bounds__(256) void k_kfdb_common(const uint2 *__restrict__ slots, int nslots, const uint32_t *__restrict__ pool_w,
+                                                     const uint32_t *__restrict__ qw_all, const int *__restrict__ q_begin, int q0,
+                                                     const uint8_t *__restrict__ connected, int *__restrict__ qmax,
+                                                     uint32_t *__restrict__ cursor, DKfRec *__restrict__ rec, uint32_t cap) {
+    __shared__ uint32_t s_q[ORBX_KFDB_LDS_WORDS];
+    __shared__ DKfRec s_rec[4][KF_BATCH];
+    DKfRec *my_rec = s_rec[threadIdx.x >> 6];
+    const int q = q0 + blockIdx.y;
+    const int qb = q_begin[q], nq = q_begin[q + 1] - qb;
+    if (nq <= 0) return;
+    if (nq <= ORBX_KFDB_LDS_WORDS) {
+        for (int i = threadIdx.x; i < nq; i += 256) s_q[i] = qw_all[qb + i];
+        __syncthreads();
+        kf_common_entries((const uint32_t *)s_q, nq, (uint32_t)q, slots, nslots, pool_w, connected, qmax, cursor, rec, cap, my_rec);
+    } else {
+        kf_common_entries(qw_all + qb, nq, (uint32_t)q, slots, nslots, pool_w, connected, qmax, cursor, rec, cap, my_rec);
+    }
+}
+// TemplatedVocabulary::score(v1 = query, v2 = entry) by one wave.  The lanes find the common words and compute the per-word
+// terms in parallel; the terms are compacted IN WORD ORDER into LDS and lane 0 adds them one after the other in double, as the
+// reference's merge walk does (floating-point addition is not associative: no tree, no reassociation).  L2 / dot product
+// under ORBX_FP_GCC_FMA keep both factors so that lane 0 performs the fused multiply-add GCC contracts `score += vi * wi` into.
+// The result is valid on lane 0.  KL (needs libm's log) is not computed here.
+__device__ __forceinline__ double kf_score_wave(const uint32_t *__restrict__ qw, const double *__restrict__ qv, int nq,
+                                                const uint32_t *__restrict__ ew, const double *__restrict__ ev, int ne,
+                                                int scoring, bool fma_mode, double *s_a, double *s_b) {
+    const int lane = threadIdx.x & 63;
+    const bool fused = fma_mode && (scoring == 1 || scoring == 5);
+    double acc = 0.0;
+    for (int i0 = 0; i0 < ne; i0 += 64) {
+        const int i = i0 + lane;
+        bool f = false;
+        double a = 0.0, b = 0.0;
+        if (i < ne) {
+            const int j = kf_find(qw, nq, ew[i]);
+            if (j >= 0) {
+                const double vi = qv[j], wi = ev[i];
+                f = true;
+                if (scoring == 0) a = fabs(vi - wi) - fabs(vi) - fabs(wi);
+                else if (scoring == 2) { if (vi + wi != 0.0) a = vi * wi / (vi + wi); else f = false; }
+                else if (scoring == 4) a = sqrt(vi * wi);
+                else if (fused) { a = vi; b = wi; }
+                else a = vi * wi;
+            }
+        }
+        const unsigned long long bal = orbx_ballot(f);
+        if (f) {
+            const int r = orbx_wave_rank(bal);
+            s_a[r] = a;
+            if (fused) s_b[r] = b;
+        }
+        orbx_wave_sync();
+        if (lane == 0) {
+            const int n = __popcll(bal);
+            if (fused) for (int k = 0; k < n; ++k) acc = __builtin_fma(s_a[k], s_b[k], acc);
+            else for (int k = 0; k < n; ++k) acc = acc + s_a[k];
+        }
+        orbx_wave_sync();
+    }
+    if (scoring == 0) return -acc / 2.0;
+    if (scoring == 1) return acc >= 1 ? 1.0 : 1.0 - sqrt(1.0 - acc);
+    if (scoring == 2) return 2. * acc;
+    return acc;
+}
+// step 3: one wave per record whose entry is listed and has more than minCommonWords = maxCommonWords * 0.8f common words
+__global__ __launch_bounds__(256) void k_kfdb_score(DKfRec *__restrict__ rec, const uint32_t *__restrict__ cursor, uint32_t cap,
+                                                    const int *__restrict__ qmax, const uint2 *__restrict__ slots,
+                                                    const uint32_t *__restrict__ pool_w, const double *__restrict__ pool_v,
+                                                    const uint32_t *__restrict__ qw_all, const double *__restrict__ qv_all,
+                                                    const int *__restrict__ q_begin, int scoring, int fma_mode) {
+    __shared__ double s_terms[4][2][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t n = min(*cursor, cap);
+    for (uint32_t r = blockIdx.x * 4 + wave; r < n; r += gridDim.x * 4) {
+        const DKfRec R = rec[r];
+        if (R.flags & ORBX_KF_CONNECTED) continue;
+        const int min_common = (int)((float)qmax[R.q] * 0.8f);
+        if ((int)R.count <= min_common) continue;
+        const uint2 s = slots[R.slot];
+        const int qb = q_begin[R.q];
+        const double sc = kf_score_wave(qw_all + qb, qv_all + qb, q_begin[R.q + 1] - qb, pool_w + s.x, pool_v + s.x, (int)s.y,
+                                        scoring, fma_mode != 0, s_terms[wave][0], s_terms[wave][1]);
+        if (lane == 0) {
+            rec[r].score = (float)sc;               // `float si = mpVoc->score(...)`: the double narrowed once
+            rec[r].flags = R.flags | ORBX_KF_SCORED;
+        }
+    }
+}
+// plain score calls against named entries (the minScore loop of LoopClosing::DetectLoop): one wave per entry, one query
+__global__ __launch_bounds__(256) void k_kfdb_score_slots(const uint32_t *__restrict__ slot_list, int n, const uint2 *__restrict__ slots,
+                                                          const uint32_t *__restrict__ pool_w, const double *__restrict__ pool_v,
+                                                          const uint32_t *__restrict__ qw, const double *__restrict__ qv, int nq,
+                                                          int scoring, int fma_mode, double *__restrict__ out) {
+    __shared__ double s_terms[4][2][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int k = blockIdx.x * 4 + wave; k < n; k += gridDim.x * 4) {
+        const uint2 s = slots[slot_list[k]];
+        const double sc = kf_score_wave(qw, qv, nq, pool_w + s.x, pool_v + s.x, (int)s.y, scoring, fma_mode != 0,
+                                        s_terms[wave][0], s_terms[wave][1]);
+        if (lane == 0) out[k] = sc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // launch wrappers (called from orbx_api.cpp)
 // ------------------------------------------------------------------------------------------------
 #include "orbx_launch.h"
@@ -3353,4 +3544,33 @@ void orbx_launch_stereo(hipStream_t s, const OrbxStereoGeom &sg, const orbx_keyp
     hipLaunchKernelGGL(k_stereo, dim3((nL + ST_KPB - 1) / ST_KPB), dim3(256), 0, s, sg, kL, dL, nL, kR, dR, nR, pyrL, pyrR, uRight,
                        depth, sad, table ? row_begin : nullptr, table ? row_items : nullptr);
 }
-
+void orbx_launch_kfdb_common(hipStream_t s, const uint2 *slots, int nslots, const uint32_t *pool_w, const uint32_t *qw_all,
+                             const int *q_begin, int q0, int nq, const uint8_t *connected, int *qmax, uint32_t *cursor,
+                             DKfRec *rec, uint32_t cap) {
+    if (nslots <= 0 || nq <= 0) return;
+    // every workgroup stages its query once: enough entries per workgroup to pay for that, enough workgroups to fill the device
+    // and few enough waves that each appends its records in batches (64 entries per wave once the device is full)
+    const int fill = (2048 + nq - 1) / nq, most = (nslots + 3) / 4;
+    int gx = (nslots + 255) / 256;
+    if (gx < (fill < most ? fill : most)) gx = fill < most ? fill : most;
+    hipLaunchKernelGGL(k_kfdb_common, dim3(gx, nq), dim3(256), 0, s, slots, nslots, pool_w, qw_all, q_begin, q0, connected, qmax,
+                       cursor, rec, cap);
+}
+void orbx_launch_kfdb_score(hipStream_t s, DKfRec *rec, const uint32_t *cursor, uint32_t cap, const int *qmax, const uint2 *slots,
+                            const uint32_t *pool_w, const double *pool_v, const uint32_t *qw_all, const double *qv_all,
+                            const int *q_begin, int scoring, int fma_mode) {
+    if (cap == 0) return;
+    unsigned g = (cap + 3) / 4;
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(k_kfdb_score, dim3(g), dim3(256), 0, s, rec, cursor, cap, qmax, slots, pool_w, pool_v, qw_all, qv_all,
+                       q_begin, scoring, fma_mode);
+}
+void orbx_launch_kfdb_score_slots(hipStream_t s, const uint32_t *slot_list, int n, const uint2 *slots, const uint32_t *pool_w,
+                                  const double *pool_v, const uint32_t *qw, const double *qv, int nq, int scoring, int fma_mode,
+                                  double *out) {
+    if (n <= 0) return;
+    int g = (n + 3) / 4;
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(k_kfdb_score_slots, dim3(g), dim3(256), 0, s, slot_list, n, slots, pool_w, pool_v, qw, qv, nq, scoring,
+                       fma_mode, out);
+}

@@ -65,3 +65,14 @@ int orbx_stereo_items_per_pair(const OrbxStereoGeom &sg, int cap);
 void orbx_launch_stereo(hipStream_t s, const OrbxStereoGeom &sg, const orbx_keypoint *kL, const uint8_t *dL, int nL,
                         const orbx_keypoint *kR, const uint8_t *dR, int nR, const uint8_t *pyrL, const uint8_t *pyrR,
                         float *uRight, float *depth, int *sad, int *row_begin, uint2 *row_items);
+// keyframe database (orbx_kfdb.cpp): common words of queries [q0, q0 + nq) with every slot (records appended at *cursor, the
+// maximum over unconnected sharers in qmax[q]), then the scores of the records above the word threshold
+void orbx_launch_kfdb_common(hipStream_t s, const uint2 *slots, int nslots, const uint32_t *pool_w, const uint32_t *qw_all,
+                             const int *q_begin, int q0, int nq, const uint8_t *connected, int *qmax, uint32_t *cursor,
+                             DKfRec *rec, uint32_t cap);
+void orbx_launch_kfdb_score(hipStream_t s, DKfRec *rec, const uint32_t *cursor, uint32_t cap, const int *qmax, const uint2 *slots,
+                            const uint32_t *pool_w, const double *pool_v, const uint32_t *qw_all, const double *qv_all,
+                            const int *q_begin, int scoring, int fma_mode);
+void orbx_launch_kfdb_score_slots(hipStream_t s, const uint32_t *slot_list, int n, const uint2 *slots, const uint32_t *pool_w,
+                                  const double *pool_v, const uint32_t *qw, const double *qv, int nq, int scoring, int fma_mode,
+                                  double *out);
