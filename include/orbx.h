@@ -365,7 +365,9 @@ typedef struct orbx_vocabulary_view {   /* m_nodes flattened; node 0 is the root
     const uint32_t *word_id;         /* Node::word_id (meaningful for leaves) */
 } orbx_vocabulary_view;
 typedef struct orbx_vocabulary orbx_vocabulary;
-/* copies the tree to the handle's device; the vocabulary can then be used with any handle on that device */
+/* copies the tree to the handle's device; the vocabulary can then be used with any handle on that device.  It keeps the
+ * handle's fp_mode for orbx_bow_vectors.  A host-only handle (device = -2) gets the host tables alone: orbx_bow_vectors and
+ * orbx_vocabulary_scoring work, the transform calls refuse it. */
 orbx_status orbx_vocabulary_create(orbx_handle *h, const orbx_vocabulary_view *view, orbx_vocabulary **out);
 void orbx_vocabulary_destroy(orbx_vocabulary *voc);
 /* per descriptor: transform(feature, word_id, weight, &nid, levelsup).  Host buffers. */
@@ -377,7 +379,9 @@ orbx_status orbx_bow_transform_device(orbx_handle *h, const orbx_vocabulary *voc
                                       const int32_t *d_counts, int64_t desc_frame_stride, int max_n, int levelsup,
                                       uint32_t *d_leaf_node, uint32_t *d_node_id, int out_stride);
 /* the BowVector and FeatureVector transform() builds from the per-descriptor results, flattened in map order (bow_word
- * ascending with bow_value; fv_node ascending, fv_begin[n_fv_nodes + 1], fv_index = an orbx_featvec_view).  Capacities: n. */
+ * ascending with bow_value; fv_node ascending, fv_begin[n_fv_nodes + 1], fv_index = an orbx_featvec_view).  Capacities: n.
+ * The L2 normalisation (scoring L2_NORM) sums `norm += v * v` fused under ORBX_FP_GCC_FMA, as g++ -O3 -mfma compiles
+ * BowVector::normalize, and unfused under ORBX_FP_STRICT. */
 orbx_status orbx_bow_vectors(const orbx_vocabulary *voc, const uint32_t *word_id, const double *weight,
                              const uint32_t *node_id, int n, uint32_t *bow_word, double *bow_value, int *n_bow,
                              uint32_t *fv_node, int32_t *fv_begin, uint32_t *fv_index, int *n_fv_nodes);

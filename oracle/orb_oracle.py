@@ -117,7 +117,7 @@ def lib():
         L.orc_bow_transform.restype = None
         L.orc_bow_transform.argtypes = [ci, ci] + [vp_] * 6 + [ci, ci] + [vp_] * 3
         L.orc_bow_vectors.restype = ci
-        L.orc_bow_vectors.argtypes = [ci, ci, vp_, vp_, vp_, ci, vp_, vp_, vp_, vp_, vp_, vp_, vp_]
+        L.orc_bow_vectors.argtypes = [ci, ci, ci, vp_, vp_, vp_, ci, vp_, vp_, vp_, vp_, vp_, vp_, vp_]
         L.orc_undistort_points.restype = None
         L.orc_undistort_points.argtypes = [vp_, ci, cf, cf, cf, cf, vp_, ci, vp_]
         L.orc_undistort_keypoints.restype = None
@@ -437,9 +437,10 @@ def search_by_projection_kf(cur, pts, cur_has_mp, th, orb_dist, check_ori=True):
     return n, out[:len(k)].copy()
 
 
-def bow_transform(voc, desc, levelsup=4):
+def bow_transform(voc, desc, levelsup=4, fp_mode=FP_GCC_FMA):
     """voc: dict n_nodes, L, child_begin, child_ids, desc, weight, word_id (+ weighting, scoring).  Per-descriptor results
-    and the flattened BowVector / FeatureVector: (word_id, weight, node_id, (bow_word, bow_value), (fv_node, fv_begin, fv_index))"""
+    and the flattened BowVector / FeatureVector: (word_id, weight, node_id, (bow_word, bow_value), (fv_node, fv_begin, fv_index)).
+    fp_mode decides whether the L2 normalisation (scoring = L2_NORM) sums its squares fused."""
     d = np.ascontiguousarray(desc, np.uint8); n = len(d)
     cb = np.ascontiguousarray(voc["child_begin"], np.int32); ci_ = np.ascontiguousarray(voc["child_ids"], np.uint32)
     nd = np.ascontiguousarray(voc["desc"], np.uint8); nw = np.ascontiguousarray(voc["weight"], np.float64)
@@ -450,7 +451,7 @@ def bow_transform(voc, desc, levelsup=4):
     bw = np.zeros(max(n, 1), np.uint32); bv = np.zeros(max(n, 1), np.float64)
     fn = np.zeros(max(n, 1), np.uint32); fb = np.zeros(n + 2, np.int32); fi = np.zeros(max(n, 1), np.uint32)
     nb, nn = C.c_int(0), C.c_int(0)
-    lib().orc_bow_vectors(int(voc.get("weighting", 0)), int(voc.get("scoring", 0)), _p(wid), _p(w), _p(nid), n, _p(bw), _p(bv),
+    lib().orc_bow_vectors(int(voc.get("weighting", 0)), int(voc.get("scoring", 0)), int(fp_mode), _p(wid), _p(w), _p(nid), n, _p(bw), _p(bv),
                           C.byref(nb), _p(fn), _p(fb), _p(fi), C.byref(nn))
     return (wid[:n].copy(), w[:n].copy(), nid[:n].copy(), (bw[:nb.value].copy(), bv[:nb.value].copy()),
             (fn[:nn.value].copy(), fb[:nn.value + 1].copy(), fi[:fb[nn.value]].copy()))

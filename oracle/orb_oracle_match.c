@@ -859,8 +859,10 @@ void orc_bow_transform(int n_nodes, int L, const int *child_begin, const uint32_
     }
 }
 
-/* literal std::map emulation with sorted arrays + insertion, in feature order */
-int orc_bow_vectors(int weighting, int scoring, const uint32_t *word_id, const double *weight, const uint32_t *node_id,
+/* literal std::map emulation with sorted arrays + insertion, in feature order.  fp_mode: BowVector::normalize(L2) sums
+ * `norm += v * v`, which g++ -O3 -mfma contracts to fma(v, v, norm) (checked against that build of the reference by
+ * tests/test_ref_dbow2.py); STRICT rounds the product and the sum separately.  The L1 sum has no product. */
+int orc_bow_vectors(int weighting, int scoring, int fp_mode, const uint32_t *word_id, const double *weight, const uint32_t *node_id,
                     int n, uint32_t *bow_word, double *bow_value, int *n_bow, uint32_t *fv_node, int *fv_begin,
                     uint32_t *fv_index, int *n_fv_nodes) {
     int nb = 0, nn = 0;
@@ -893,6 +895,7 @@ int orc_bow_vectors(int weighting, int scoring, const uint32_t *word_id, const d
     if (norm) {
         double s = 0.0;
         if (norm == 1) for (int i = 0; i < nb; ++i) s += fabs(bow_value[i]);
+        else if (fp_mode == ORC_FP_GCC_FMA) { for (int i = 0; i < nb; ++i) s = fma(bow_value[i], bow_value[i], s); s = sqrt(s); }
         else { for (int i = 0; i < nb; ++i) s += bow_value[i] * bow_value[i]; s = sqrt(s); }
         if (s > 0.0) for (int i = 0; i < nb; ++i) bow_value[i] /= s;
     }

@@ -1989,6 +1989,8 @@ extern "C" orbx_status orbx_search_by_projection_mappoints(orbx_handle *h, const
 struct orbx_vocabulary {
     int dev = 0;
     int n_nodes = 0, k = 0, L = 0, weighting = 0, scoring = 0;
+    int fp_mode = ORBX_FP_GCC_FMA;   // of the creating handle: which sums orbx_bow_vectors contracts
+    bool host_only = false;          // tables only (orbx_bow_vectors); no device copy, no transform
     std::vector<int32_t> child_begin;
     std::vector<uint32_t> child_ids, word_id;
     std::vector<double> weight;
@@ -2001,13 +2003,15 @@ extern "C" int orbx_vocabulary_scoring(const orbx_vocabulary *v) { return v ? v-
 
 extern "C" void orbx_vocabulary_destroy(orbx_vocabulary *v) {
     if (!v) return;
-    hipSetDevice(v->dev);
-    hipFree(v->d_child_begin); hipFree(v->d_child_ids); hipFree(v->d_desc);
+    if (!v->host_only) {
+        hipSetDevice(v->dev);
+        hipFree(v->d_child_begin); hipFree(v->d_child_ids); hipFree(v->d_desc);
+    }
     delete v;
 }
 
 extern "C" orbx_status orbx_vocabulary_create(orbx_handle *h, const orbx_vocabulary_view *view, orbx_vocabulary **out) {
-    if (!h || h->host_only) return fail(h ? ORBX_NO_DEVICE : ORBX_BAD_ARGUMENT, "no device handle");
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "no handle");
     if (!view || !out || view->n_nodes < 1 || !view->child_begin || !view->desc || !view->weight || !view->word_id ||
         view->L < 0 || view->weighting < 0 || view->weighting > 3 || view->scoring < 0 || view->scoring > 5)
         return fail(ORBX_BAD_ARGUMENT, "bad vocabulary view");
@@ -2023,14 +2027,16 @@ extern "C" orbx_status orbx_vocabulary_create(orbx_handle *h, const orbx_vocabul
         }
         if (view->child_begin[i + 1] - view->child_begin[i] > 65535) return fail(ORBX_BAD_ARGUMENT, "too many children");
     }
-    HIPCHK(hipSetDevice(h->dev));
+    if (!h->host_only) HIPCHK(hipSetDevice(h->dev));
     orbx_vocabulary *v = new orbx_vocabulary();
+    v->fp_mode = h->p.fp_mode; v->host_only = h->host_only;
     v->dev = h->dev; v->n_nodes = n; v->k = view->k; v->L = view->L; v->weighting = view->weighting; v->scoring = view->scoring;
     const int nchild = view->child_begin[n];
     v->child_begin.assign(view->child_begin, view->child_begin + n + 1);
     v->child_ids.assign(view->child_ids, view->child_ids + nchild);
     v->word_id.assign(view->word_id, view->word_id + n);
     v->weight.assign(view->weight, view->weight + n);
+    if (v->host_only) { *out = v; return ORBX_OK; }   // the host tables serve orbx_bow_vectors; the transform needs a device
     hipError_t e = hipMalloc(&v->d_child_begin, (size_t)(n + 1) * sizeof(int));
     if (e == hipSuccess) e = hipMalloc(&v->d_child_ids, std::max<size_t>(1, nchild) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&v->d_desc, (size_t)n * 32);
@@ -2051,7 +2057,7 @@ extern "C" orbx_status orbx_bow_transform_device(orbx_handle *h, const orbx_voca
     if (!h || h->host_only) return fail(h ? ORBX_NO_DEVICE : ORBX_BAD_ARGUMENT, "no device handle");
     if (!voc || nframes <= 0 || !d_desc || !d_counts || max_n <= 0 || !d_leaf_node || !d_node_id || out_stride < max_n)
         return fail(ORBX_BAD_ARGUMENT, "bad argument");
-    if (voc->dev != h->dev) return fail(ORBX_BAD_ARGUMENT, "vocabulary lives on another device");
+    if (voc->host_only || voc->dev != h->dev) return fail(ORBX_BAD_ARGUMENT, "vocabulary lives on another device");
     HIPCHK(hipSetDevice(h->dev));
     { ProfScope ps(h, ORBX_K_MISC);
       orbx_launch_bow_transform(h->stream, nframes, max_n, voc->d_child_begin, voc->d_child_ids, voc->d_desc, voc->n_nodes, voc->L,
@@ -2090,7 +2096,9 @@ extern "C" orbx_status orbx_bow_transform(orbx_handle *h, const orbx_vocabulary 
 
 // BowVector / FeatureVector exactly as TemplatedVocabulary::transform fills them (:1150-1216, BowVector.cpp:40-95):
 // addWeight / addIfNotExist in feature order, division by the vector size when the scoring does not normalise, L1 / L2
-// normalisation in ascending word order.  Outputs are the maps flattened in key order.
+// normalisation in ascending word order.  Outputs are the maps flattened in key order.  Under ORBX_FP_GCC_FMA (the fp_mode of
+// the handle that created the vocabulary) the L2 sum `norm += v * v` is contracted to fma(v, v, norm), as the reference
+// compiled with g++ -O3 -mfma does it (tests/test_ref_dbow2.py compares with that build); the L1 sum has no product.
 extern "C" orbx_status orbx_bow_vectors(const orbx_vocabulary *voc, const uint32_t *word_id, const double *weight,
                                         const uint32_t *node_id, int n, uint32_t *bow_word, double *bow_value, int *n_bow,
                                         uint32_t *fv_node, int32_t *fv_begin, uint32_t *fv_index, int *n_fv_nodes) {
@@ -2119,6 +2127,7 @@ extern "C" orbx_status orbx_bow_vectors(const orbx_vocabulary *voc, const uint32
     if (norm != 0) {
         double s = 0.0;
         if (norm == 1) for (int i = 0; i < nb; ++i) s += fabs(bow_value[i]);
+        else if (voc->fp_mode == ORBX_FP_GCC_FMA) { for (int i = 0; i < nb; ++i) s = fma(bow_value[i], bow_value[i], s); s = sqrt(s); }
         else { for (int i = 0; i < nb; ++i) s += bow_value[i] * bow_value[i]; s = sqrt(s); }
         if (s > 0.0) for (int i = 0; i < nb; ++i) bow_value[i] /= s;
     }

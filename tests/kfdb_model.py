@@ -6,9 +6,11 @@ The reference keeps the query marks, word counts and scores in the KeyFrames; so
 Python floats (IEEE double) narrowed to numpy float32 where the reference narrows them (`float si = mpVoc->score(...)`);
 accScore and every comparison of steps 4-5 are float32.  Results are compared as bit patterns.
 
-Parity with a real DBoW2 build is not pinned by a compiled oracle (as for the vocabulary transform): the model follows the
-source text, and the fused multiply-add of `score += vi * wi` under the default fp_mode is the SURVEY F4 assumption about a
-GCC -O3 -march=native build."""
+The model follows the source text; tests/test_ref_dbow2.py pins it to the source itself, compiled with g++ under two flag sets
+behind stand-ins for cv::Mat, KeyFrame and Frame (oracle/ref/): scores, candidates, list order and the per-keyframe fields
+equal the compiled code bit for bit, with `fma_mode=False` against -O3 -ffp-contract=off and `fma_mode=True` against -O3 -mfma.
+The fused multiply-add of `score += vi * wi` under the default fp_mode is therefore what GCC emits, not an
+assumption.  The stand-in KeyFrame starts the two scores at 0.0f, the value a never-written score reads as here."""
 import math
 from fractions import Fraction
 import numpy as np

@@ -4,10 +4,14 @@ TemplatedVocabulary<FORB>::transform(features, BowVector&, FeatureVector&, 4)
 so the vocabularies are synthetic: random k-ary trees in DBoW2's node numbering, regular and irregular (variable child
 counts, leaves above depth L, stopped words with weight 0), every weighting / scoring combination.
 CPU: the C oracle against a literal Python restatement with dict-based maps.  GPU: k_bow_transform + host vector builder
-against the oracle, bit-exact including the double-precision values."""
+against the oracle, bit-exact including the double-precision values.
+Oracle, restatement and library are themselves pinned to the reference's own TemplatedVocabulary / BowVector, compiled with g++
+under two flag sets behind a stand-in cv::Mat, by tests/test_ref_dbow2.py on these same CASES.  That comparison showed
+that BowVector::normalize(L2) sums its squares fused under -mfma: the L2 sum follows fp_mode in all three since."""
 import numpy as np
 import pytest
 import oracle
+from kfdb_model import fma
 
 
 def random_vocabulary(rng, k=10, L=3, irregular=False, weighting=0, scoring=0, stop=0.05):
@@ -39,8 +43,17 @@ def random_vocabulary(rng, k=10, L=3, irregular=False, weighting=0, scoring=0, s
                 desc=desc, weight=weight, word_id=word_id, weighting=weighting, scoring=scoring), children
 
 
-def py_transform(voc, children, feats, levelsup):
-    """literal restatement with Python dicts standing in for the std::maps"""
+def py_normalize(vals, norm, fma_mode=True):
+    """BowVector::normalize (BowVector.cpp:55-95) over the values in ascending word order; norm: 1 = L1, 2 = L2"""
+    s = 0.0
+    for v in vals: s = s + abs(v) if norm == 1 else fma(v, v, s) if fma_mode else s + v * v
+    if norm == 2: s = float(np.sqrt(np.float64(s)))
+    return [v / s for v in vals] if s > 0.0 else list(vals)
+
+
+def py_transform(voc, children, feats, levelsup, fma_mode=True):
+    """literal restatement with Python dicts standing in for the std::maps; fma_mode: the L2 sum `norm += v * v` rounded once
+    (g++ -O3 -mfma, fp_mode GCC_FMA) or twice (STRICT)"""
     def dist(a, b): return int(np.unpackbits(np.bitwise_xor(a, b)).sum())
     bow, fv = {}, {}
     per = []
@@ -66,10 +79,7 @@ def py_transform(voc, children, feats, levelsup):
     if voc["weighting"] in (0, 1) and keys and norm == 0:
         vals = [v / float(len(keys)) for v in vals]
     if norm:
-        s = 0.0
-        for v in vals: s += abs(v) if norm == 1 else v * v
-        if norm == 2: s = float(np.sqrt(np.float64(s)))
-        if s > 0.0: vals = [v / s for v in vals]
+        vals = py_normalize(vals, norm, fma_mode)
     return per, (keys, vals), {k: fv[k] for k in sorted(fv)}
 
 
@@ -83,11 +93,12 @@ def test_oracle_transform_equals_python_restatement(k, L, irr, weighting, scorin
     voc, children = random_vocabulary(rng, k, L, irr, weighting, scoring)
     feats = rng.integers(0, 256, (150, 32), dtype=np.uint8)
     feats[:20] = voc["desc"][rng.integers(1, voc["n_nodes"], 20)]          # exact hits and ties with node descriptors
-    wid, w, nid, (bw, bv), (fn, fb, fi) = oracle.bow_transform(voc, feats, levelsup)
-    per, (keys, vals), fv = py_transform(voc, children, feats, levelsup)
-    assert [(int(a), float(b), int(c)) for a, b, c in zip(wid, w, nid)] == per
-    assert bw.tolist() == keys and bv.tolist() == vals                        # doubles compared exactly
-    assert fn.tolist() == list(fv) and [fi[fb[i]:fb[i + 1]].tolist() for i in range(len(fn))] == list(fv.values())
+    for fp_mode in (oracle.FP_GCC_FMA, oracle.FP_STRICT):
+        wid, w, nid, (bw, bv), (fn, fb, fi) = oracle.bow_transform(voc, feats, levelsup, fp_mode)
+        per, (keys, vals), fv = py_transform(voc, children, feats, levelsup, fp_mode == oracle.FP_GCC_FMA)
+        assert [(int(a), float(b), int(c)) for a, b, c in zip(wid, w, nid)] == per
+        assert bw.tolist() == keys and bv.tolist() == vals                        # doubles compared exactly
+        assert fn.tolist() == list(fv) and [fi[fb[i]:fb[i + 1]].tolist() for i in range(len(fn))] == list(fv.values())
 
 
 @pytest.mark.gpu
@@ -103,7 +114,7 @@ def test_gpu_transform_equals_oracle(k, L, irr, weighting, scoring, levelsup):
         if n >= 16:
             feats[:8] = voc["desc"][rng.integers(1, voc["n_nodes"], 8)]
         wid, w, nid = V.transform_features(feats, levelsup)
-        owid, ow, onid, (obw, obv), (ofn, ofb, ofi) = oracle.bow_transform(voc, feats, levelsup)
+        owid, ow, onid, (obw, obv), (ofn, ofb, ofi) = oracle.bow_transform(voc, feats, levelsup, ex.params.fp_mode)
         assert np.array_equal(wid, owid) and np.array_equal(w.view(np.uint64), ow.view(np.uint64)) and np.array_equal(nid, onid)
         (bw, bv), (fn, fb, fi) = V.transform(feats, levelsup)
         assert np.array_equal(bw, obw) and np.array_equal(bv.view(np.uint64), obv.view(np.uint64))
@@ -134,7 +145,7 @@ def test_gpu_transform_on_extracted_descriptors_feeds_search_by_bow(tmp_path):
     fvs = []
     for d in (d1, d2):
         (bw, bv), fv = V.transform(d, 1)
-        obw, obv = oracle.bow_transform(voc, d, 1)[3]
+        obw, obv = oracle.bow_transform(voc, d, 1, ex.params.fp_mode)[3]
         assert np.array_equal(bw, obw) and np.array_equal(bv.view(np.uint64), obv.view(np.uint64))
         assert abs(bv.sum() - 1.0) < 1e-12                                          # L1-normalised
         fvs.append(fv)

@@ -3,7 +3,8 @@ reference's src/KeyFrameDatabase.cc:56-411 and Thirdparty/DBoW2/DBoW2/ScoringObj
 
 Every comparison is exact: candidate ids and order, lScoreAndMatch ids and order, score bit patterns, minCommonWords, the count
 of reads of never-written scores and the per-entry marks / word counts / scores after every call.
-Parity with a compiled DBoW2 is not pinned (kfdb_model.py says why).  CPU part: the model against hand-worked cases, and the
+The model itself, the host path and the device path are pinned to the compiled reference by tests/test_ref_dbow2.py, which
+replays HAND_CASES and the seeded sequences of this file on the reference's own KeyFrameDatabase.  CPU part: the model against hand-worked cases, and the
 library's host path (host-only handle) against the model.  GPU part: the device path (k_kfdb_common / k_kfdb_score), the
 host path on a device handle, batched against single calls, every device scoring type, the extremes, and one chain from
 descriptors.  The sequences come from tests/kfdb_driver.py, which asserts on the MODEL's output that they exercise stale
