@@ -505,6 +505,9 @@ protected:
         if (!t.h) {
             orbx_params p;
             orbx_default_params(&p);          // fp_mode GCC_FMA: the reference as its own CMake flags build it
+#ifdef ORBX_COMPAT_FP_MODE                     // a tree built with -ffp-contract=off: -DORBX_COMPAT_FP_MODE=ORBX_FP_STRICT
+            p.fp_mode = ORBX_COMPAT_FP_MODE;
+#endif
             Check(orbx_create(&p, &t.h));
         }
         return t.h;

@@ -1,6 +1,7 @@
 // tests/compat_runtime: a working stand-in for the small part of OpenCV 3.2's cv::Mat that compat/ runs on (see README.md in
 // this directory).  Only CV_8U and CV_32F single-channel matrices exist.  Storage is reference counted and rowRange / colRange /
 // row / col are views that share it and its row step, as in OpenCV; clone() and t() copy into a fresh continuous buffer.
+// oracle/ref/matcher/ compiles the reference's src/ORBmatcher.cc and src/MapPoint.cc against this same file.
 //
 // Arithmetic (CV_32F only; every result is a fresh matrix, and MatExpr is simply Mat):
 //   a + b, a - b, -a        element-wise in float
@@ -31,6 +32,14 @@ struct Point2f {
     Point2f() : x(0.f), y(0.f) {}
     Point2f(float x_, float y_) : x(x_), y(y_) {}
 };
+
+template <typename T> struct Point_ {
+    T x, y;
+    Point_() : x(0), y(0) {}
+    Point_(T x_, T y_) : x(x_), y(y_) {}
+};
+typedef Point_<int> Point2i;
+typedef Point2i Point;
 
 // the 28-byte POD of OpenCV 3.2 (pt, size, angle, response, octave, class_id); compat/ static_asserts the size
 struct KeyPoint {
@@ -70,11 +79,17 @@ public:
         for (int r = 0; r < rows; ++r) std::memcpy(m.ptr(r), ptr(r), (size_t)cols * elemSize());
         return m;
     }
-    // copies into dst's storage; dst is a header (usually _OutputArray::getMat() after create) of the same shape and type
-    void copyTo(Mat dst) const {
+    // copies into dst's storage; a temporary dst is a header (usually _OutputArray::getMat() after create) of the same shape
+    // and type; a named dst is (re)allocated first when its shape or type differs, as OpenCV's copyTo(OutputArray) does
+    void copyTo(Mat &&dst) const {
         CV_Assert(dst.rows == rows && dst.cols == cols && dst.type() == type_);
         for (int r = 0; r < rows; ++r) std::memcpy(dst.ptr(r), ptr(r), (size_t)cols * elemSize());
     }
+    void copyTo(Mat &dst) const {
+        dst.create(rows, cols, type_);
+        for (int r = 0; r < rows; ++r) std::memcpy(dst.ptr(r), ptr(r), (size_t)cols * elemSize());
+    }
+    static Mat zeros(int r, int c, int type) { return Mat(r, c, type); }   // create() zero-fills
     Mat t() const {
         Mat m(cols, rows, type_);
         const size_t es = elemSize();
