@@ -24,10 +24,14 @@
  * cv::fastAtan2 / cvRound lives in OpenCV (un-vendored system dependency, required
  * version 3.0+, README-tested 2.4.11 and 3.2; CMakeLists.txt:47-53, README.md:103),
  * which is absent from this image.  Those primitives are restated here from the published
- * OpenCV 3.2 algorithms (x86-64 SSE2 baseline build, no IPP).  The reference cannot be
- * built here (needs OpenCV headers+libs) => **parity unpinned** at the OpenCV boundary;
- * the only reference-held known answers (umax table, vmax/vmin, thresholds; see
- * tests/test_oracle_kat.py) are checked.
+ * OpenCV 3.2 algorithms (x86-64 SSE2 baseline build, no IPP) => **parity unpinned** for
+ * those six primitives.  Everything else of src/ORBextractor.cc is pinned: the file is
+ * compiled unmodified behind a cv:: stand-in that forwards exactly those six calls to the
+ * functions declared here (oracle/ref/extractor/), and this restatement equals it bit for
+ * bit, stage by stage, in both fp modes (tests/test_ref_extractor.py).  The matcher
+ * policies and DBoW2 are pinned the same way (oracle/ref/).  The sort tie-break of the
+ * quadtree is the reference's under an allocator whose addresses follow allocation order
+ * (DESIGN.md 2, F3).
  */
 #ifndef ORB_ORACLE_H
 #define ORB_ORACLE_H

@@ -9,6 +9,11 @@ MapPoint behind the stand-ins of matcher/ and the C ABI of matcher/harness.cpp (
     libref_matcher_strict.so, libref_matcher_fma.so     the same two flag sets for src/ORBmatcher.cc and src/MapPoint.cc; the
                                                           feature grid behind GetFeaturesInArea is the oracle's (orb_oracle_match.c,
                                                           compiled with the oracle's own flags and linked in)
+    libref_extractor_strict.so, libref_extractor_fma.so the same two flag sets for src/ORBextractor.cc behind the stand-ins of
+                                                          extractor/ and the C ABI of extractor/harness.cpp; the six OpenCV primitives
+                                                          forward to the oracle's (orb_oracle.c, compiled with the oracle's own flags
+                                                          and linked in); std::list nodes come from a monotonic arena (F3)
+    libref_extractor_strict_plain.so                    the strict flags with glibc malloc instead of the arena: one measurement
     BUILD_INFO.txt           compiler version, flags, source list
 
 The reference tree is read from $ORB_SLAM2_REFERENCE, by default the directory `reference` beside the repository.  Nothing of
@@ -28,6 +33,11 @@ SOURCES = ["Thirdparty/DBoW2/DBoW2/BowVector.cpp", "Thirdparty/DBoW2/DBoW2/Scori
 MATCHER = os.path.join(HERE, "matcher")
 MATCHER_SOURCES = ["src/ORBmatcher.cc", "src/MapPoint.cc", "Thirdparty/DBoW2/DBoW2/FeatureVector.cpp", "Thirdparty/DBoW2/DBoW2/BowVector.cpp"]
 MATCHER_STANDINS = ["Map.h", "KeyFrame.h", "Frame.h", "grid.h", "opencv2/core/core.hpp", "opencv2/features2d/features2d.hpp", "opencv/cv.h"]
+EXTRACTOR = os.path.join(HERE, "extractor")
+EXTRACTOR_SOURCES = ["src/ORBextractor.cc", "include/ORBextractor.h"]   # the first is #included by extractor/harness.cpp
+EXTRACTOR_STANDINS = ["opencv2/core/core.hpp", "opencv2/features2d/features2d.hpp", "opencv2/highgui/highgui.hpp",
+                      "opencv2/imgproc/imgproc.hpp", "opencv/cv.h"]
+EXTRACTOR_BUILDS = {"strict": ("strict", []), "fma": ("fma", []), "strict_plain": ("strict", ["-DREF_PLAIN_MALLOC"])}
 ORACLE_C = ["orb_oracle_match.c", "orb_oracle.c"]                      # the grid, and what it links against
 ORACLE_CFLAGS = ["-O2", "-fPIC", "-std=gnu99", "-ffp-contract=off", "-fno-fast-math", "-w"]   # oracle/Makefile's
 VARIANTS = {"strict": ["-O3", "-ffp-contract=off"], "fma": ["-O3", "-mfma"]}
@@ -39,7 +49,7 @@ def reference_dir():
 
 def reference_present():
     ref = reference_dir()
-    return all(os.path.isfile(os.path.join(ref, s)) for s in SOURCES + MATCHER_SOURCES)
+    return all(os.path.isfile(os.path.join(ref, s)) for s in SOURCES + MATCHER_SOURCES + EXTRACTOR_SOURCES)
 
 
 def lib_path(variant):
@@ -48,6 +58,14 @@ def lib_path(variant):
 
 def matcher_lib_path(variant):
     return os.path.join(OUT, "libref_matcher_%s.so" % variant)
+
+
+def extractor_lib_path(build):
+    return os.path.join(OUT, "libref_extractor_%s.so" % build)
+
+
+def extractor_built():
+    return all(os.path.isfile(extractor_lib_path(b)) for b in EXTRACTOR_BUILDS)
 
 
 def built():
@@ -87,6 +105,22 @@ def matcher_command(variant, out, extra=()):
     return ["sh", "-c", " && ".join(q(c) for c in cc + [link]) + "; rc=$?; rm -f " + q(objs) + "; exit $rc"]
 
 
+def extractor_command(build, out, extra=()):
+    """as matcher_command: the oracle's C files under the oracle's flags (the primitives must not change with the variant), then
+    extractor/harness.cpp, which #includes <src/ORBextractor.cc> from the reference, with the variant's flags"""
+    ref = reference_dir()
+    oracle = os.path.dirname(HERE)
+    variant, defs = EXTRACTOR_BUILDS[build]
+    objs = ["%s.%s.o" % (out, os.path.splitext(c)[0]) for c in ORACLE_C]
+    cc = [["gcc"] + ORACLE_CFLAGS + ["-c", os.path.join(oracle, c), "-o", o] for c, o in zip(ORACLE_C, objs)]
+    link = (["g++", "-std=c++11", "-w", "-shared", "-fPIC"] + VARIANTS[variant] + defs + list(extra) +
+            ["-I" + EXTRACTOR, "-I" + oracle, "-I" + ref, "-I" + os.path.join(ref, "include"),
+             os.path.join(EXTRACTOR, "harness.cpp")] + objs +
+            ["-Wl,--version-script=" + os.path.join(EXTRACTOR, "exports.map"), "-lm", "-o", out])
+    q = lambda c: " ".join("'%s'" % a for a in c)
+    return ["sh", "-c", " && ".join(q(c) for c in cc + [link]) + "; rc=$?; rm -f " + q(objs) + "; exit $rc"]
+
+
 def build(force=False):
     """Returns the seconds spent compiling (0.0 when everything is up to date)."""
     if not reference_present():
@@ -100,11 +134,14 @@ def build(force=False):
     mdeps = ([os.path.join(MATCHER, f) for f in MATCHER_STANDINS + ["harness.cpp"]] + [os.path.join(HERE, "build_ref.py")] +
              [os.path.join(ROOT, "tests", "compat_runtime", "opencv2", "core", "core.hpp")] +
              [os.path.join(oracle, f) for f in ORACLE_C + ["orb_oracle.h"]] + [os.path.join(reference_dir(), s) for s in MATCHER_SOURCES])
+    xdeps = ([os.path.join(EXTRACTOR, f) for f in EXTRACTOR_STANDINS + ["harness.cpp", "exports.map"]] + [os.path.join(HERE, "build_ref.py")] +
+             [os.path.join(oracle, f) for f in ORACLE_C + ["orb_oracle.h"]] + [os.path.join(reference_dir(), s) for s in EXTRACTOR_SOURCES])
     t0 = time.time()
     jobs = []
-    for path, cmd, dd in ((lib_path, command, deps), (matcher_lib_path, matcher_command, mdeps)):
+    for path, cmd, dd, names in ((lib_path, command, deps, VARIANTS), (matcher_lib_path, matcher_command, mdeps, VARIANTS),
+                                 (extractor_lib_path, extractor_command, xdeps, EXTRACTOR_BUILDS)):
         newest = max(os.path.getmtime(d) for d in dd)
-        for variant in VARIANTS:            # the four builds side by side
+        for variant in names:               # all builds side by side
             so = path(variant)
             if not force and os.path.isfile(so) and os.path.getmtime(so) >= newest:
                 continue
@@ -135,6 +172,11 @@ def build(force=False):
             f.write("matcher stand-ins: %s, tests/compat_runtime/opencv2/core/core.hpp (cv::Mat); C ABI: oracle/ref/matcher/harness.cpp\n"
                     % ", ".join("oracle/ref/matcher/" + m for m in MATCHER_STANDINS))
             f.write("matcher feature grid (ours, restated): %s, gcc %s\n" % (" ".join("oracle/" + c for c in ORACLE_C), " ".join(ORACLE_CFLAGS)))
+            for b, (variant, defs) in EXTRACTOR_BUILDS.items():
+                f.write("%s: g++ -std=c++11 -shared -fPIC %s ... -lm\n" % (os.path.basename(extractor_lib_path(b)), " ".join(VARIANTS[variant] + defs)))
+            f.write("extractor sources (unmodified, from the reference tree, #included by the harness): %s\n" % " ".join(EXTRACTOR_SOURCES))
+            f.write("extractor stand-ins: %s; C ABI: oracle/ref/extractor/harness.cpp\n" % ", ".join("oracle/ref/extractor/" + m for m in EXTRACTOR_STANDINS))
+            f.write("extractor OpenCV primitives (ours, restated): %s, gcc %s\n" % (" ".join("oracle/" + c for c in ORACLE_C), " ".join(ORACLE_CFLAGS)))
             f.write("build time: %.1f s\n" % dt)
     return dt
 

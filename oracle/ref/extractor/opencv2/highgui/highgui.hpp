@@ -1,0 +1,3 @@
+// oracle/ref/extractor: the reference includes this header for nothing the extractor uses; the stand-in declares all of its cv:: in one file
+#pragma once
+#include "../../opencv2/core/core.hpp"

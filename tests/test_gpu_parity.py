@@ -638,3 +638,64 @@ def test_forked_launch_sequence_is_bit_exact(monkeypatch):
             res = ex.extract_batch(frames)
             for f, w in want.items():
                 assert_frame_equal(res[f], w, f"fork level {lvl} rep {rep} frame {f}")
+
+
+# ---- against the records of the COMPILED REFERENCE (src/ORBextractor.cc built unmodified: tests/test_ref_extractor.py, records
+# ---- under tests/golden/ref_extractor_*).  Neither the reference tree nor oracle/_ref/ is read here.
+import ref_extractor as RX  # noqa: E402
+
+FP_OF = {"strict": _capi.FP_STRICT, "fma": _capi.FP_GCC_FMA}
+
+
+@pytest.fixture(scope="module")
+def ref_records():
+    return {v: RX.load_records(v) for v in RX.VARIANTS}
+
+
+@pytest.mark.parametrize("name", [c[0] for c in RX.CASES])
+def test_compiled_reference_records_every_stage(name, ref_records):
+    """liborbx in both fp modes against what the compiled reference returned: pyramid bytes, FAST candidates, keypoint order and
+    angle bits per level, final keypoints and descriptors"""
+    _, inp, p, kw = RX.CASE_BY_NAME[name]
+    img = RX.inputs()[inp]
+    for v in RX.VARIANTS:
+        ex = ORBextractor(*p, fp_mode=FP_OF[v], **kw)
+        res = ex(img)
+        RX.assert_matches_record(RX.gpu_stages(ex, res, 0, p[2]), ref_records[v][name], "%s/%s" % (name, v))
+        ex.close()
+
+
+def test_frames_on_which_the_fp_modes_differ(ref_records):
+    """Four frames (two of noise, two synthetic scenes) whose descriptors differ between the -mfma and the -ffp-contract=off
+    build of the reference, each alone and all in one batch between ordinary frames, under one FP_GCC_FMA and one FP_STRICT
+    handle.  Each mode has to reproduce its own record, and the records differ: a k_describe that ignored fp_mode, or fused
+    the other product, fails here."""
+    names = [c[0] for c in RX.MODE_CASES]
+    p, kw = RX.MODE_CASES[0][2], RX.MODE_CASES[0][3]
+    imgs = [RX.inputs()[RX.CASE_BY_NAME[n][1]] for n in names]
+    ordinary = RX.inputs()["golden/s160x120"]
+    batch = np.stack([ordinary] + imgs + [ordinary])
+    got = {}
+    for v in RX.VARIANTS:
+        ex = ORBextractor(*p, fp_mode=FP_OF[v], max_batch=len(batch), **kw)
+        for n, img in zip(names, imgs):
+            res = ex(img)
+            RX.assert_matches_record(RX.gpu_stages(ex, res, 0, p[2]), ref_records[v][n], "%s/%s alone" % (n, v))
+        plain = ex(ordinary)
+        res = ex.extract_batch(batch)
+        for f, n in enumerate(names, start=1):
+            RX.assert_matches_record(RX.gpu_stages(ex, res[f], f, p[2]), ref_records[v][n], "%s/%s in a batch" % (n, v))
+        for f in (0, len(batch) - 1):
+            assert res[f][0].tobytes() == plain[0].tobytes() and np.array_equal(res[f][1], plain[1]), "ordinary frame %d/%s" % (f, v)
+        got[v] = res
+        ex.close()
+    for f, n in enumerate(names, start=1):
+        rs, rf = ref_records["strict"][n], ref_records["fma"][n]
+        assert rs["desc"] != rf["desc"] and rs["kps"] == rf["kps"], n
+        rows = sorted(int(r) for r in rs["rows_differing_between_variants"])
+        assert rows and rows == sorted(int(r) for r in rf["rows_differing_between_variants"])
+        ds, df = got["strict"][f][1], got["fma"][f][1]
+        assert np.nonzero((ds != df).any(axis=1))[0].tolist() == rows, n
+        for r in rows:
+            assert ds[r].tolist() == rs["rows_differing_between_variants"][str(r)]["desc"], (n, r)
+            assert df[r].tolist() == rf["rows_differing_between_variants"][str(r)]["desc"], (n, r)
