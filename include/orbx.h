@@ -95,7 +95,22 @@ orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uint8_t *imgs,
                                int height, int stride, int64_t frame_stride, orbx_keypoint *kps,
                                uint8_t *desc, int32_t *counts, int cap);
 /* same, all pointers are DEVICE pointers; asynchronous on the handle's stream.  d_status[nframes]
- * receives a per-frame orbx_status (OK / CAPACITY).  No host synchronisation. */
+ * receives a per-frame orbx_status (OK / CAPACITY).  No host synchronisation.
+ *
+ * In-place level 0.  When ALL of these hold the kernels read level 0 IN PLACE from d_imgs and the padded copy of level 0 is
+ * not written during the call: this entry point; ORBX_FMT_GRAY8; no rectification maps; d_imgs, `stride` and `frame_stride`
+ * multiples of 4; at least 64 x 64 pixels and at least 2 levels; the level-1 tap table passed its footprint check (every usual
+ * scale factor); ORBX_RESIZE_IMPL=legacy and ORBX_FORK_LEVEL are not set; the handle's stereo match has not needed the late
+ * copy (below); and ORBX_LEVEL0_INPLACE=0 is not set.
+ * LIFETIME: in this mode d_imgs is read until the LAST kernel of the call has finished on the handle's stream, not only by
+ * its first kernel: it must stay valid and unchanged until then (orbx_synchronize, or an event on the handle's stream).  The
+ * Python wrapper holds a reference to the input of its last device call for this reason; C callers keep the buffer themselves.
+ * LATE COPY: the padded level 0 is written late, from d_imgs, by the calls that hand out or read the handle's level 0
+ * (orbx_pyramid_level_device / _copy, orbx_debug_blur_copy, orbx_stereo_match, orbx_stereo_match_batch_device): until
+ * then d_imgs of the LAST call must stay valid and unchanged as well.  A caller that cannot promise that sets ORBX_LEVEL0_INPLACE=0
+ * in the environment before the handle is configured (the copy is then written during the call, as for every other input).
+ * A handle whose stereo match needed the late copy writes it during the call from then on.  No load of the in-place
+ * kernels leaves [frame, frame + (height - 1) * stride + width) of its frame. */
 orbx_status orbx_extract_batch_device(orbx_handle *h, int nframes, const uint8_t *d_imgs, int width,
                                       int height, int stride, int64_t frame_stride,
                                       orbx_keypoint *d_kps, uint8_t *d_desc, int32_t *d_counts,
@@ -119,7 +134,8 @@ orbx_status orbx_set_rectification(orbx_handle *h, const float *map_x, const flo
  *      read by Frame::ComputeStereoMatches (src/Frame.cc:910,1040,1072,1079).  Valid until the next
  *      extract on this handle ("pyramid is overwritten every frame", include/ORBextractor.h:30-35). -- */
 orbx_status orbx_pyramid_level_info(orbx_handle *h, int level, int *width, int *height, int *pitch);
-/* device view of (frame, level): padded image, `pitch` bytes per row */
+/* device view of (frame, level): padded image, `pitch` bytes per row (after an in-place batch this queues the late
+ * level-0 copy on the handle's stream first, see orbx_extract_batch_device) */
 orbx_status orbx_pyramid_level_device(orbx_handle *h, int frame, int level, const uint8_t **d_ptr);
 /* copies the padded level into dst (dst_stride >= width) */
 orbx_status orbx_pyramid_level_copy(orbx_handle *h, int frame, int level, uint8_t *dst, int dst_stride);

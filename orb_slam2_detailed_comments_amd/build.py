@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liborbx.so")
 SOURCES = ["orbx_kernels.hip", "orbx_api.cpp", "orbx_geometry.cpp", "orbx_policies.cpp", "orbx_kfdb.cpp"]
-HEADERS = ["orbx_device.h", "orbx_internal.h", "orbx_launch.h", "orbx_sincos.h",
+HEADERS = ["orbx_device.h", "orbx_inplace.h", "orbx_internal.h", "orbx_launch.h", "orbx_sincos.h",
            os.path.join("..", "..", "include", "orbx.h"), os.path.join("..", "..", "include", "orbx_pattern_data.h")]
 
 

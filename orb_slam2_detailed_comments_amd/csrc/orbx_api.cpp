@@ -94,6 +94,13 @@ struct orbx_handle {
     uint2 *d_rect = nullptr; int rect_w = 0, rect_h = 0;   // pre-digested rectification maps (orbx_set_rectification)
     int input_format = ORBX_FMT_GRAY8;        // pixel format of the frames handed to the extract entry points
     bool blur_valid = false;                // d_blur holds the blurred pyramid of the last batch
+    // in-place level 0 (orbx_inplace.h): grey batches of orbx_extract_batch_device read level 0 from the caller's image and
+    // never write the slab's padded copy; whoever needs that copy afterwards calls ensure_level0() first
+    bool l0_inplace = true;                 // ORBX_LEVEL0_INPLACE=0 forces the eager k_pyr_l0 everywhere (A/B runs)
+    bool l0_eager_sticky = false;           // a stereo match needed the padded copy: this handle's later batches write it eagerly
+    bool l0_pending = false;                // the slab's level 0 of the last batch has not been written
+    OrbxRaw0 l0_src = {nullptr, 0, 0, 0, 0};   // ... and this is the input it would be written from (must stay valid and unchanged)
+    int *d_l0_scratch = nullptr;            // status / cursor words the late k_pyr_l0 may reset instead of the batch's own
     // profiling
     uint32_t prof_mask = 0;
     std::vector<ProfPair> pending;
@@ -197,6 +204,7 @@ static void free_geometry_buffers(orbx_handle *h) {
     hipFree(h->d_dense); h->d_dense = nullptr;
     hipFree(h->d_cand_count); hipFree(h->d_lvl_count); hipFree(h->d_status); hipFree(h->d_lvl_kp);
     hipFree(h->d_lvl_angle); hipFree(h->d_knode);
+    hipFree(h->d_l0_scratch); h->d_l0_scratch = nullptr; h->l0_pending = false;
     h->d_pyr = h->d_blur = nullptr; h->d_cells = nullptr; h->d_taps = nullptr;
     h->d_cand_count = h->d_lvl_count = h->d_status = nullptr; h->d_lvl_kp = nullptr; h->d_lvl_angle = nullptr;
     h->d_knode = nullptr;
@@ -305,6 +313,9 @@ static orbx_status configure(orbx_handle *h, int width, int height) {
     // The sub-batch pipeline (run_chunk) and the fork exclude each other, both use the side stream: an explicit
     // ORBX_FORK_LEVEL > 0 (an A/B knob) selects the fork and the serial sub-batch sequence.
     if (const char *e = getenv("ORBX_PIPELINE")) h->pipeline = std::min(std::max(atoi(e), 0), ORBX_PIPE_MAX);
+    h->l0_inplace = true;
+    if (const char *e = getenv("ORBX_LEVEL0_INPLACE")) h->l0_inplace = atoi(e) != 0;
+    h->l0_eager_sticky = false;   // a new geometry starts over
     if (const char *e = getenv("ORBX_PIPELINE_HEAD")) h->pipe_head = atoi(e) != 0;
     if (const char *e = getenv("ORBX_FAST_ROOM")) h->fast_room = atoi(e) != 0;
     if (h->fork_level > 0) h->pipeline = 0;
@@ -319,6 +330,7 @@ static orbx_status configure(orbx_handle *h, int width, int height) {
         ORBX_TRY(hipMalloc(&h->d_cand_count, (size_t)B * NL * sizeof(int)));
         ORBX_TRY(hipMalloc(&h->d_lvl_count, (size_t)B * NL * sizeof(int)));
         ORBX_TRY(hipMalloc(&h->d_status, (size_t)B * sizeof(int)));
+        ORBX_TRY(hipMalloc(&h->d_l0_scratch, (size_t)B * (NL + 1) * sizeof(int)));
         ORBX_TRY(hipMalloc(&h->d_lvl_kp, (size_t)B * hg.kp_total * sizeof(uint32_t)));
         ORBX_TRY(hipMalloc(&h->d_lvl_angle, (size_t)B * hg.kp_total * sizeof(float)));
         ORBX_TRY(hipMalloc(&h->d_groups, std::max<size_t>(1, hg.fast_groups.size()) * sizeof(OrbxFastGroup)));
@@ -493,8 +505,15 @@ extern "C" orbx_status orbx_set_input_format(orbx_handle *h, int pixel_format) {
 }
 static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W, int H, int stride,
                              int64_t frame_stride, orbx_keypoint *d_kps, uint8_t *d_desc, int32_t *d_counts,
-                             int32_t *d_status, int cap) {
+                             int32_t *d_status, int cap, bool device_entry = false) {
     const DGeom &g = h->dg;
+    // In-place level 0: only the device entry with grey, un-rectified, dword-aligned frames of at least ORBX_IP_MIN_W x
+    // ORBX_IP_MIN_H pixels whose level-1 raw tap table passed the narrow check (geom.l1_inplace covers the last two); the fork
+    // knob resizes level 1 on its own path.  Everything else runs k_pyr_l0 as before.
+    const bool inplace = device_entry && h->l0_inplace && !h->l0_eager_sticky && !h->d_rect && h->input_format == ORBX_FMT_GRAY8 &&
+                         h->geom.l1_inplace && !h->resize_legacy && h->fork_level == 0 && ((uintptr_t)d_imgs & 3) == 0 &&
+                         (stride & 3) == 0 && (frame_stride & 3) == 0 && frame_stride >= 0 && W == h->geom.width && H == h->geom.height;
+    h->l0_pending = false;
     hipStream_t s = h->stream;
     const int NL = g.nlevels;
     if (h->d_rect && (h->rect_w != W || h->rect_h != H))
@@ -514,6 +533,16 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
         uint8_t *pyr = h->d_pyr + (size_t)f0 * h->geom.pyr_bytes;
         int32_t *stp = d_status + f0;
         int *cc = h->d_cand_count + (size_t)f0 * NL;
+        if (inplace) {   // no level-0 launch: level 1 reads the image and takes over the status / cursor reset
+            { ProfScope ps(h, ORBX_K_PYR_RESIZE, st);
+              const OrbxRaw0 raw = {im, (long long)frame_stride, W, H, stride};
+              orbx_launch_pyr_resize_l1(st, g, b, h->d_taps + h->geom.l1_tap_begin, raw, pyr, h->geom.l1_tail_bx, stp, cc); }
+            for (int l = 2; l < l_end; ++l) {
+                ProfScope ps(h, ORBX_K_PYR_RESIZE, st);
+                orbx_launch_pyr_resize(st, g, b, l, h->d_taps, pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy);
+            }
+            return;
+        }
         { ProfScope ps(h, ORBX_K_PYR_L0, st);
           if (h->d_rect) {   // cv::remap of the EuRoC rectification fused into level 0
               orbx_launch_pyr_l0_remap(st, g, b, im, W, H, stride, frame_stride, pyr, h->d_rect, stp, cc);
@@ -531,9 +560,10 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
     };
     auto fast = [&](hipStream_t st, int f0, int b, int g0, int ng, int lds_floor) {
         ProfScope ps(h, ORBX_K_FAST, st);
+        const OrbxRaw0 raw = {d_imgs + (int64_t)f0 * frame_stride, (long long)frame_stride, W, H, stride};
         orbx_launch_fast_rows(st, g, b, h->d_cells, h->d_groups + g0, ng, h->d_pyr + (size_t)f0 * h->geom.pyr_bytes,
                               h->d_dense + (size_t)f0 * g.cand_total, h->d_cand_count + (size_t)f0 * NL, d_status + f0, h->max_ch,
-                              h->fast_lcap, h->fast_stop, lds_floor);
+                              h->fast_lcap, h->fast_stop, lds_floor, inplace ? &raw : nullptr);
     };
     auto finish = [&](int f0, int b) {
         { ProfScope ps(h, ORBX_K_QUADTREE);
@@ -542,11 +572,16 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
                                h->d_knode + (size_t)f0 * g.cand_total, h->ncap, (long long)b * NL >= 1024 ? h->lds_keys : h->lds_keys_few, 0, NL); }
         // orientation (IC_Angle) is computed inside k_describe from the same LDS patch the descriptor uses
         { ProfScope ps(h, ORBX_K_DESC);
+          const OrbxRaw0 raw = {d_imgs + (int64_t)f0 * frame_stride, (long long)frame_stride, W, H, stride};
           orbx_launch_describe(s, g, b, h->d_pyr + (size_t)f0 * h->geom.pyr_bytes, h->d_lvl_kp + (size_t)f0 * g.kp_total,
                                h->d_lvl_count + (size_t)f0 * NL, h->d_lvl_angle + (size_t)f0 * g.kp_total, d_kps + (int64_t)f0 * cap,
-                               d_desc + (int64_t)f0 * cap * 32, d_counts + f0, d_status + f0, cap); }
+                               d_desc + (int64_t)f0 * cap * 32, d_counts + f0, d_status + f0, cap, inplace ? &raw : nullptr); }
     };
     h->blur_valid = false;  // the Gaussian is fused into k_describe; the full blurred image is only built on request
+    if (inplace) {          // what ensure_level0() would build the slab's level 0 of this batch from
+        h->l0_src = OrbxRaw0{d_imgs, (long long)frame_stride, W, H, stride};
+        h->l0_pending = true;
+    }
     // Sub-batch pipeline (large batches): the pyramids of the S sub-batches are queued on the high-priority side stream, FAST ->
     // quadtree -> descriptors of sub-batch k on the main stream once the pyramid of k is done.  The pyramid is bound by load
     // latency (its waves leave most of a CU's vector port idle), FAST and the descriptors by vector issue: pyramid k+1 takes
@@ -633,7 +668,7 @@ extern "C" orbx_status orbx_extract_batch_device(orbx_handle *h, int nframes, co
         const int B = std::min(MB, nframes - f0);
         int32_t *stp = d_status ? d_status + f0 : h->d_status;
         st = run_chunk(h, B, d_imgs + (int64_t)f0 * frame_stride, width, height, stride, frame_stride,
-                       d_kps + (int64_t)f0 * cap, d_desc + (int64_t)f0 * cap * 32, d_counts + f0, stp, cap);
+                       d_kps + (int64_t)f0 * cap, d_desc + (int64_t)f0 * cap * 32, d_counts + f0, stp, cap, true);
         if (st != ORBX_OK) return st;
     }
     return ORBX_OK;
@@ -1064,9 +1099,26 @@ extern "C" orbx_status orbx_pyramid_level_info(orbx_handle *h, int level, int *w
     if (pitch) *pitch = h->geom.lv[level].pitch;
     return ORBX_OK;
 }
+// The slab's padded level 0 of the last batch, written late: an in-place batch (run_chunk) left it out.  Runs k_pyr_l0 on the
+// handle's stream from the recorded input, at most once per batch; its status / cursor resets go to scratch words.
+static orbx_status ensure_level0(orbx_handle *h) {
+    if (!h->l0_pending) return ORBX_OK;
+    HIPCHK(hipSetDevice(h->dev));
+    { ProfScope ps(h, ORBX_K_PYR_L0);
+      orbx_launch_pyr_l0(h->stream, h->dg, h->last_batch, h->l0_src.img, h->l0_src.W, h->l0_src.H, h->l0_src.stride,
+                         h->l0_src.frame_stride, h->d_pyr, h->d_l0_scratch, h->d_l0_scratch + h->p.max_batch); }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, std::string("late level 0: ") + hipGetErrorString(e));
+    h->l0_pending = false;
+    return ORBX_OK;
+}
 extern "C" orbx_status orbx_pyramid_level_device(orbx_handle *h, int frame, int level, const uint8_t **d_ptr) {
     orbx_status st = check_level(h, frame, level);
     if (st != ORBX_OK) return st;
+    if (level == 0) {   // the other levels were written by the batch itself
+        st = ensure_level0(h);
+        if (st != ORBX_OK) return st;
+    }
     *d_ptr = h->d_pyr + (size_t)frame * h->geom.pyr_bytes + h->geom.lv[level].off;
     return ORBX_OK;
 }
@@ -1076,6 +1128,10 @@ static orbx_status copy_level(orbx_handle *h, const uint8_t *slab, int frame, in
     const OrbxLevelGeom &L = h->geom.lv[level];
     if (!dst || dst_stride < L.pw) return fail(ORBX_BAD_ARGUMENT, "dst / dst_stride");
     HIPCHK(hipSetDevice(h->dev));
+    if (level == 0 && slab == h->d_pyr) {   // (the blurred slab's level 0 was built behind its own ensure_level0)
+        st = ensure_level0(h);
+        if (st != ORBX_OK) return st;
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy2D(dst, dst_stride, slab + (size_t)frame * h->geom.pyr_bytes + L.off, L.pitch, L.pw, L.ph,
                        hipMemcpyDeviceToHost));
@@ -1089,6 +1145,8 @@ extern "C" orbx_status orbx_debug_blur_copy(orbx_handle *h, int frame, int level
     if (st != ORBX_OK) return st;
     if (!h->blur_valid) {  // stand-alone k_blur over the resident pyramid (same arithmetic as the fused path)
         HIPCHK(hipSetDevice(h->dev));
+        st = ensure_level0(h);
+        if (st != ORBX_OK) return st;
         if (!h->d_blur) {      // the blurred slab only exists for inspection: allocated on first request
             HIPCHK(hipMalloc(&h->d_blur, (size_t)h->p.max_batch * h->geom.pyr_bytes + 256));
             HIPCHK(hipMemsetAsync(h->d_blur, 0, (size_t)h->p.max_batch * h->geom.pyr_bytes, h->stream));   // ordered with k_blur below
@@ -1697,6 +1755,11 @@ extern "C" orbx_status orbx_stereo_match(orbx_handle *hl, orbx_handle *hr, int f
     if (nmatches_out) *nmatches_out = 0;
     if (nl == 0) return ORBX_OK;
     HIPCHK(hipSetDevice(hl->dev));
+    for (orbx_handle *hh : {hl, hr}) {          // the match reads both padded level-0 images (then written eagerly: see run_chunk)
+        if (hh->l0_pending) hh->l0_eager_sticky = true;
+        st = ensure_level0(hh);
+        if (st != ORBX_OK) return st;
+    }
     HIPCHK(hipStreamSynchronize(hr->stream));   // the right pyramid is read from the left handle's stream
     OrbxStereoGeom sg;
     memset(&sg, 0, sizeof(sg));
@@ -1773,6 +1836,13 @@ extern "C" orbx_status orbx_stereo_match_batch_device(orbx_handle *hl, orbx_hand
         hl->p.nlevels != hr->p.nlevels || hl->p.scale_factor != hr->p.scale_factor)
         return fail(ORBX_BAD_ARGUMENT, "left and right extractor must share device, image size and pyramid parameters");
     HIPCHK(hipSetDevice(hl->dev));
+    // The match reads the padded level 0 of both eyes: an in-place batch writes it now, on its own handle's stream, and the
+    // handle goes back to the eager k_pyr_l0 for its later batches (a stereo pipeline would pay the late copy every time)
+    for (orbx_handle *hh : {hl, hr}) {
+        if (hh->l0_pending) hh->l0_eager_sticky = true;
+        st = ensure_level0(hh);
+        if (st != ORBX_OK) return st;
+    }
     // The reference extracts the two eyes on two threads (src/Frame.cc:158-168); here that is two handles on two streams.  The
     // match runs on the left stream: it waits for the right stream's work so far (an event, no host synchronisation) ...
     const bool two_streams = hr->stream != hl->stream;

@@ -8,6 +8,7 @@
 //
 // Built with -ffp-contract=off: every float expression below is a single IEEE operation per operator.
 #include "orbx_internal.h"
+#include "orbx_inplace.h"
 #include <cmath>
 #include <algorithm>
 
@@ -184,6 +185,35 @@ orbx_status orbx_build_geometry(const orbx_params &p, const OrbxTables &t, int w
                 if (hi + 2 - lo > 8) L.narrow_taps = false;
             }
         }
+    }
+    // level-1 taps in raw coordinates (in-place mode): padded source index s of level 0 holds raw pixel reflect101(s - 19)
+    if (p.nlevels >= 2 && width >= ORBX_IP_MIN_W && height >= ORBX_IP_MIN_H && width <= 0x7fff && height <= 0x7fff) {
+        const OrbxLevelGeom &L = g.lv[1];
+        const size_t nx = (size_t)L.pw, ny = (size_t)L.ph;
+        g.l1_tap_begin = (int)g.taps.size();
+        for (size_t i = 0; i < nx + ny; ++i) {
+            OrbxTap t = g.taps[(size_t)(i < nx ? L.tapx_begin : L.tapy_begin - (int)nx) + i];
+            const int n = i < nx ? width : height;
+            t.s0 = (int16_t)reflect101(t.s0 - ORBX_EDGE, n);
+            t.s1 = (int16_t)reflect101(t.s1 - ORBX_EDGE, n);
+            g.taps.push_back(t);
+        }
+        // narrow footprint over BOTH taps (the second is not "the next byte" inside the reflected border), per lane of every
+        // column strip -- the lanes beyond the level's width repeat its last column, as the kernel does
+        const int nbx = (L.pw + 255) / 256;
+        bool ok = L.narrow_taps;
+        g.l1_tail_bx = nbx;
+        for (int bx = 0; bx < nbx; ++bx)
+            for (int lane = 0; lane < 64; ++lane) {
+                int lo = 0x7fff, hi = 0;
+                for (int i = 0; i < 4; ++i) {
+                    const OrbxTap &t = g.taps[(size_t)g.l1_tap_begin + (size_t)std::min((bx * 64 + lane) * 4 + i, L.pw - 1)];
+                    lo = std::min<int>(lo, std::min(t.s0, t.s1)); hi = std::max<int>(hi, std::max(t.s0, t.s1));
+                }
+                if (hi - lo > 7) ok = false;
+                if (orbx_ip_rr_window_leaves_row(lo, width)) g.l1_tail_bx = std::min(g.l1_tail_bx, bx);
+            }
+        g.l1_inplace = ok;
     }
     // FAST wave groups: pair a cell with its right-hand neighbour when both interiors fit the 64 lanes of a wave plus the
     // ORBX_FAST_XCOLS columns k_fast_rows tests outside its row walk (two 33-column cells: 66)

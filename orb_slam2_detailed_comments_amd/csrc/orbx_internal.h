@@ -75,6 +75,12 @@ struct OrbxGeom {
     int kp_total = 0;          // per frame: sum of kp_cap
     int node_cap = 0;          // max over levels of quadtree node capacity
     int max_cand_cap = 0;
+    // in-place mode (orbx_inplace.h): level 1 resized straight from the caller's grey image.  A second tap table for level 1
+    // (lv[1].pw horizontal records, then lv[1].ph vertical ones, appended to `taps`) carries RAW source indices with level 0's
+    // reflect-101 border folded in.  l1_inplace: the table passed the narrow-footprint check of k_pyr_resize_rows_l1 and the
+    // image is large enough for the in-place paths of the three consumers; l1_tail_bx: first column strip of tail form.
+    int l1_tap_begin = 0, l1_tail_bx = 0;
+    bool l1_inplace = false;
 };
 
 struct OrbxTables {

@@ -7,6 +7,7 @@
 // Built with -ffp-contract=off: no implicit FMA anywhere; the only fused operations are the explicit
 // __builtin_fmaf calls of the descriptor taps (fp_mode GCC_FMA) and the fma() of the pinned sincos.
 #include "orbx_device.h"
+#include "orbx_inplace.h"
 #include "../../include/orbx_pattern_data.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -406,6 +407,126 @@ __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows(DGeom g, int le
 #undef RR_V
 }
 
+// Level 1 straight from the caller's grey image (in-place mode: no padded level-0 copy exists).  Same row walk, with
+//   * a tap table of its own (orbx_geometry.cpp): source indices in RAW coordinates, the reflection of level 0's border folded
+//     in, so the second tap of a column is no longer "the next byte": the byte selectors are built from both indices;
+//   * body strips reading the dword-aligned 12-byte window, tail strips (blockIdx.y >= tail_bx, wave-uniform: the strips with
+//     a lane whose window would leave its source row) reading 8 bytes at byte alignment from min(lo, W - 8);
+//   * the two side duties of k_pyr_l0 (it is the first launch of a batch on its stream now): status[f] and cand_cursor[f][*].
+// Address arithmetic: orbx_inplace.h.
+template <bool TAIL>
+__device__ __forceinline__ void rr_l1_body(const DLevel &L, const OrbxTap *__restrict__ taps, const uint8_t *__restrict__ src,
+                                           int W, int stride, uint8_t *__restrict__ dst, int X, int y_begin, int y_end) {
+    const bool on = X < L.pw;
+    const uint32_t ldst = (uint32_t)X;
+    uint32_t sel[4], wgt[4];
+    int lo = 0x7fff;
+    {
+        const uint2 *tq = (const uint2 *)taps;
+        uint2 t[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t[i] = tq[min(X + i, L.pw - 1)];   // .x = s0 | s1 << 16, .y = a0 | a1 << 16
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lo = min(lo, (int)min(t[i].x & 0xffffu, t[i].x >> 16));
+        const int org = TAIL ? orbx_ip_rr_tail_col(lo, W) : lo;       // raw column of byte 0 of the lane's 8-byte register pair
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t d0 = (t[i].x & 0xffffu) - (uint32_t)org, d1 = (t[i].x >> 16) - (uint32_t)org;   // 0..7 (checked on the host)
+            sel[i] = d0 | (0x0cu << 8) | (d1 << 16) | (0x0cu << 24);
+            wgt[i] = t[i].y;
+        }
+    }
+    const uint32_t sh = TAIL ? 0u : (uint32_t)(lo & 3);
+    const uint32_t lsrc = (uint32_t)(TAIL ? orbx_ip_rr_tail_col(lo, W) : orbx_ip_rr_body_col(lo));
+    const uint2 *ty = (const uint2 *)taps + L.pw;
+#define RR_LD(dstv, row)                                                                                                  \
+    {                                                                                                                     \
+        const uint8_t *p_ = src + orbx_ip_row_off((int)(row), stride, (int)lsrc);                                         \
+        if (TAIL) { const uint2 q_ = orbx_load8(p_); dstv.x = q_.x; dstv.y = q_.y; dstv.z = 0; }                          \
+        else dstv = *(const orbx_uint3_a *)p_;                                                                            \
+    }
+#define RR_H(dst, v)                                                                                                     \
+    {                                                                                                                   \
+        const uint32_t lo_ = __builtin_amdgcn_alignbyte((v).y, (v).x, sh), hi_ = __builtin_amdgcn_alignbyte((v).z, (v).y, sh); \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
+            dst[i] = orbx_udot2(__builtin_amdgcn_perm(hi_, lo_, sel[i]), wgt[i]) >> 4;                                  \
+    }
+#define RR_V(out, h0, h1, w0, w1)                                                                                       \
+    {                                                                                                                   \
+        out = 0;                                                                                                        \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
+            out |= (((__umul24(w0, h0[i]) >> 16) + (__umul24(w1, h1[i]) >> 16) + 2u) >> 2) << (8 * i);                  \
+    }
+    uint2 t[RR_R];
+    orbx_uint3_a u[RR_R], w[RR_R];
+    int pid = -1;
+    uint32_t hb[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+#pragma unroll
+    for (int r = 0; r < RR_R; ++r) {
+        t[r] = ty[min(y_begin + r, L.ph - 1)];
+        u[r].x = u[r].y = u[r].z = 0;
+        if (r == 0 || (int)(t[r].x & 0xffffu) != (int)(t[r - 1].x >> 16)) RR_LD(u[r], t[r].x & 0xffffu)
+        RR_LD(w[r], t[r].x >> 16)
+    }
+    for (int Y = y_begin; Y < y_end; Y += RR_R) {
+        uint2 ct[RR_R];
+        orbx_uint3_a cu[RR_R], cw[RR_R];
+#pragma unroll
+        for (int r = 0; r < RR_R; ++r) { ct[r] = t[r]; cu[r] = u[r]; cw[r] = w[r]; }
+        if (Y + RR_R < y_end) {
+            int last = (int)(ct[RR_R - 1].x >> 16);
+#pragma unroll
+            for (int r = 0; r < RR_R; ++r) {
+                t[r] = ty[min(Y + RR_R + r, L.ph - 1)];
+                const int s0 = (int)(t[r].x & 0xffffu), s1 = (int)(t[r].x >> 16);
+                if (s0 != last) RR_LD(u[r], s0)
+                RR_LD(w[r], s1)
+                last = s1;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RR_R; ++r) {
+            uint32_t (&h0)[4] = hb[r & 1], (&h1)[4] = hb[(r & 1) ^ 1];
+            const int s0 = (int)(ct[r].x & 0xffffu);
+            if (s0 != pid) RR_H(h0, cu[r])
+            RR_H(h1, cw[r])
+            uint32_t v;
+            RR_V(v, h0, h1, ct[r].y & 0xfffu, (ct[r].y >> 16) & 0xfffu)
+            pid = (int)(ct[r].x >> 16);
+            if (on && Y + r < y_end) *(uint32_t *)(dst + (uint32_t)((uint32_t)(Y + r) * (uint32_t)L.pitch + ldst)) = v;
+        }
+    }
+#undef RR_LD
+#undef RR_H
+#undef RR_V
+}
+__global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows_l1(DGeom g, const OrbxTap *__restrict__ taps, OrbxRaw0 raw,
+                                                            uint8_t *__restrict__ pyr, int rpw, int tail_bx,
+                                                            int *__restrict__ status, int *__restrict__ cand_cursor) {
+    const DLevel &L = g.lv[1];
+    const int lane = threadIdx.x;
+#if RR_FF
+    const int f = blockIdx.x, bx = blockIdx.y;
+    const int by = RR_REVERSE ? (int)gridDim.z - 1 - (int)blockIdx.z : (int)blockIdx.z;
+    const bool first = blockIdx.y == 0 && blockIdx.z == 0;
+#else
+    const int f = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
+    const bool first = blockIdx.x == 0 && blockIdx.y == 0;
+#endif
+    if (first && threadIdx.y == 0) {   // one block per frame, as k_pyr_l0 does in the eager mode
+        if (lane == 0) status[f] = 0;
+        if (lane < g.nlevels) cand_cursor[f * g.nlevels + lane] = 0;
+    }
+    const int X = (bx * 64 + lane) * 4;
+    const int y_begin = __builtin_amdgcn_readfirstlane((by * RR_WPB + threadIdx.y) * rpw);
+    if (y_begin >= L.ph) return;
+    const int y_end = min(y_begin + rpw, L.ph);
+    const uint8_t *src = raw.img + (long long)f * raw.frame_stride;
+    uint8_t *dst = pyr + (long long)f * g.pyr_bytes + L.off;
+    if (bx >= tail_bx) rr_l1_body<true>(L, taps, src, raw.W, raw.stride, dst, X, y_begin, y_end);
+    else rr_l1_body<false>(L, taps, src, raw.W, raw.stride, dst, X, y_begin, y_end);
+}
+
 // ------------------------------------------------------------------------------------------------
 // K2: FAST-9/16 + score + 3x3 strict NMS per cell, with the per-cell threshold retry
 // (reference src/ORBextractor.cc:1465-1548; cv::FAST semantics SURVEY App. B.1): helpers, then k_fast_rows.
@@ -723,7 +844,10 @@ __device__ __forceinline__ void fr_nms(const FrCtx &c, const FrCells &gc, const 
         // the score map is shared by the two cells: the neighbours across the seam belong to the other cell's cv::FAST call
         // (strictly greater than all eight <=> strictly greater than their maximum: one select per side, not one per neighbour)
         const bool seam_l = col == gc.iw0, seam_r = col == gc.iw0 - 1;
-        const int ml = seam_l ? 0 : max(max(l0, l1), l2), mr = seam_r ? 0 : max(max(r0, r1), r2);
+        // (two-input maxima, each intermediate in a register of its own: fused, they become the quarter-rate v_max3_u16)
+        int l01 = max(l0, l1), r01 = max(r0, r1);
+        asm("" : "+v"(l01), "+v"(r01));
+        const int ml = seam_l ? 0 : max(l01, l2), mr = seam_r ? 0 : max(r01, r2);
         const bool keep = (int)valid & (int)(sc > max(max(ml, mr), max(u, dn)));
         const unsigned long long m = orbx_ballot(keep), msec = orbx_ballot(keep && second);
         const unsigned long long mfirst = m & ~msec;
@@ -750,11 +874,35 @@ __device__ __forceinline__ void fr_nms(const FrCtx &c, const FrCells &gc, const 
     }
 }
 
-__global__ __launch_bounds__(64, FR_WPS) void k_fast_rows(DGeom g, const OrbxCell *__restrict__ cells,
-                                                          const OrbxFastGroup *__restrict__ groups,
-                                                          const uint8_t *__restrict__ pyr, uint2 *__restrict__ cand,
-                                                          int *__restrict__ cand_cursor, int *__restrict__ status, int rows,
-                                                          int lcap, int ngroups, int gpw, int dbg_stop, int ccap) {
+// a 12-byte piece shifted right by s bytes (zeros shifted in; s >= 12 leaves nothing): the in-place pieces that were loaded
+// from W - 12 because they would have left their source row (orbx_ip_fast_piece_col)
+__device__ __forceinline__ orbx_uint3_u orbx_shr96(orbx_uint3_u v, int s) {
+    uint32_t a = v.x, b = v.y, c = v.z;
+    if (s >= 8) { a = c; b = 0; c = 0; } else if (s >= 4) { a = b; b = c; c = 0; }
+    if (s >= 12) a = 0;
+    const uint32_t sh = (uint32_t)(s & 3);
+    orbx_uint3_u o;
+    o.x = __builtin_amdgcn_alignbyte(b, a, sh); o.y = __builtin_amdgcn_alignbyte(c, b, sh); o.z = __builtin_amdgcn_alignbyte(0u, c, sh);
+    return o;
+}
+// one in-place piece into its tile row: a row has 19 dwords, so the 7th piece is one dword, and none when the row is displaced by
+// one dword (dsh = 1, first cell column)
+__device__ __forceinline__ void fr_ip_store(uint32_t *d, const orbx_uint3_u &v, int dq, int dsh) {
+    if (dq < 6) { d[0] = v.x; d[1] = v.y; d[2] = v.z; }
+    else if (dsh == 0) d[0] = v.x;
+}
+// INPLACE: the level-0 groups read the caller's grey image (`raw`) instead of the slab's padded level 0, which is not written
+// in that mode: source rows through the reflection, the columns linearly; groups of the first / last cell column then mirror
+// their (at most 3) ring columns inside the LDS tile.  Address arithmetic: orbx_inplace.h.  Every other level, and every
+// instruction of the walk / ring test / NMS, is the same as in the slab form.
+// (Two kernels, k_fast_rows and k_fast_rows_ip, share this body, so that the slab form keeps its name and its staging code; fr_nms's
+// seam maxima changed for both: two kernels with the fused form would double the quarter-rate v_max3_u16 in the code object.)
+template <bool INPLACE>
+__device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__restrict__ cells,
+                                          const OrbxFastGroup *__restrict__ groups,
+                                          const uint8_t *__restrict__ pyr, uint2 *__restrict__ cand,
+                                          int *__restrict__ cand_cursor, int *__restrict__ status, int rows,
+                                          int lcap, int ngroups, int gpw, int dbg_stop, int ccap, const OrbxRaw0 &raw) {
     // dbg_stop (ORBX_FAST_STOP, phase-timing builds only, -DORBX_TIMING_KNOBS; results are wrong unless 0): 1 = after
     // staging, 2 = after the pre-test, 3 = after the ring test, 4 = before NMS.  The shipped library pins it to 0.
 #ifndef ORBX_TIMING_KNOBS
@@ -784,8 +932,30 @@ __global__ __launch_bounds__(64, FR_WPS) void k_fast_rows(DGeom g, const OrbxCel
     OrbxFastGroup grp_n = groups[g0];
     OrbxCell c0_n = cells[grp_n.cell0], c1_n = cells[grp_n.cell0 + grp_n.ncell - 1];
     const uint8_t *fbase = pyr + (long long)f * g.pyr_bytes;
+    const uint8_t *rbase = INPLACE ? raw.img + (long long)f * raw.frame_stride : nullptr;
 #define FR_PREFETCH()                                                                                                     \
-    {                                                                                                                     \
+    if (INPLACE && c0_n.level == 0) {                                                                                     \
+        int dsh_, shr_;                                                                                                   \
+        const int xb_ = orbx_ip_fast_xb(c0_n.x0, &dsh_);                                                                  \
+        const int col_ = orbx_ip_fast_piece_col(xb_, dq, raw.W, &shr_);                                                   \
+        const int ylast_ = (int)c0_n.y0 + (int)c0_n.ch - 1;                                                               \
+        if ((int)c0_n.y0 >= ORBX_EDGE && ylast_ - ORBX_EDGE < raw.H) {                                                    \
+            /* every cell row but the first and the last: no row is reflected, the offsets are the slab path's adds */    \
+            uint32_t vstride9 = (uint32_t)(9 * raw.stride);                                                               \
+            asm("" : "+v"(vstride9));                                                                                     \
+            const uint32_t olast = orbx_ip_row_off(ylast_ - ORBX_EDGE, raw.stride, col_);                                 \
+            uint32_t o = orbx_ip_row_off((int)c0_n.y0 - ORBX_EDGE + min(rq, 8), raw.stride, col_);                        \
+            _Pragma("unroll") for (int k = 0; k < 5; ++k) {                                                               \
+                tv[k] = *(const orbx_uint3_u *)(rbase + min(o, olast));                                                   \
+                o += vstride9;                                                                                            \
+            }                                                                                                             \
+        } else {                                                                                                          \
+            _Pragma("unroll") for (int k = 0; k < 5; ++k) {                                                               \
+                const int prow_ = min((int)c0_n.y0 + min(rq, 8) + 9 * k, ylast_);                                         \
+                tv[k] = *(const orbx_uint3_u *)(rbase + orbx_ip_row_off(orbx_ip_fast_row(prow_, raw.H), raw.stride, col_)); \
+            }                                                                                                             \
+        }                                                                                                                 \
+    } else {                                                                                                              \
         const DLevel &Ln = g.lv[c0_n.level];                                                                             \
         const uint8_t *srcn = fbase + Ln.off;                                                                             \
         uint32_t vpitch9 = (uint32_t)(9 * Ln.pitch);                                                                      \
@@ -806,7 +976,43 @@ __global__ __launch_bounds__(64, FR_WPS) void k_fast_rows(DGeom g, const OrbxCel
     const int niw = tw - 6;                                   // interior columns of the group (<= 64)
     const int iw0 = grp.ncell == 2 ? c0.cw - 6 : 64;
     // ---- stage the tile: prefetched registers -> LDS
-    {
+    const bool ip0 = INPLACE && c0.level == 0;   // wave-uniform
+    if (ip0) {
+        int dsh, shr;
+        const int xb = orbx_ip_fast_xb(c0.x0, &dsh);
+        const int col = orbx_ip_fast_piece_col(xb, dq, raw.W, &shr);
+        const bool clamped = xb + 84 > raw.W;    // some piece of this group was loaded from W - 12
+        uint32_t *trow = s_tile + rq * (FR_TP / 4) + 3 * dq + dsh;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            if (rq < 9 && 9 * k + rq < th_rows) {
+                uint32_t *d = trow + 9 * k * (FR_TP / 4);
+                fr_ip_store(d, clamped ? orbx_shr96(tv[k], shr) : tv[k], dq, dsh);
+            }
+        }
+        if (th_rows > 45) {
+            for (int r = 45 + rq; r < th_rows; r += 9) {
+                if (rq < 9) {
+                    orbx_uint3_u v = *(const orbx_uint3_u *)(rbase + orbx_ip_row_off(orbx_ip_fast_row((int)c0.y0 + r, raw.H), raw.stride, col));
+                    if (clamped) v = orbx_shr96(v, shr);
+                    fr_ip_store(s_tile + r * (FR_TP / 4) + 3 * dq + dsh, v, dq, dsh);
+                }
+            }
+        }
+        // ring columns: raw columns < 0 (first cell column) and >= W (last cell column) mirror columns of the tile itself
+        const int rs = (int)c0.x0 - ORBX_EDGE;
+        const int nl = rs < 0 ? -rs : 0, nr = max(rs + tw - raw.W, 0);
+        if (nl + nr > 0) {
+            orbx_wave_sync();
+            uint8_t *t8 = (uint8_t *)s_tile;
+            const int p0 = 4 * dsh - xb, pW = p0 + raw.W;   // LDS bytes of raw columns 0 and W
+            for (int r = lane; r < th_rows; r += 64) {
+                uint8_t *row = t8 + r * FR_TP;
+                for (int i = 1; i <= nl; ++i) row[p0 - i] = row[p0 + i];
+                for (int i = 0; i < nr; ++i) row[pW + i] = row[pW - 2 - i];
+            }
+        }
+    } else {
         const int xa = c0.x0 & ~3;
         uint32_t *trow = s_tile + rq * (FR_TP / 4) + 3 * dq;
 #pragma unroll
@@ -828,17 +1034,17 @@ __global__ __launch_bounds__(64, FR_WPS) void k_fast_rows(DGeom g, const OrbxCel
                 }
             }
         }
-        // score map cleared with 16-byte stores (the launcher rounds the row count to a multiple of 4, so the map is
-        // 16-byte aligned and a few bytes past the cell's last row still belong to it or to the not-yet-used list)
-        for (int i = lane; i < (th_rows * (FR_TP / 4) + 3) / 4; i += 64) ((uint4 *)s_score)[i] = make_uint4(0, 0, 0, 0);
     }
+    // score map cleared with 16-byte stores (the launcher rounds the row count to a multiple of 4, so the map is
+    // 16-byte aligned and a few bytes past the cell's last row still belong to it or to the not-yet-used list)
+    for (int i = lane; i < (th_rows * (FR_TP / 4) + 3) / 4; i += 64) ((uint4 *)s_score)[i] = make_uint4(0, 0, 0, 0);
     if (gi + 1 < ng) {
         grp_n = groups[g0 + gi + 1];
         c0_n = cells[grp_n.cell0]; c1_n = cells[grp_n.cell0 + grp_n.ncell - 1];
         FR_PREFETCH()
     }
     FrCtx cx;
-    cx.tile = (const uint8_t *)s_tile + (c0.x0 & 3);
+    cx.tile = (const uint8_t *)s_tile + (ip0 ? orbx_ip_fast_tile_off(c0.x0) : (c0.x0 & 3));
     cx.score = s_score;
     cx.list = s_list;
     cx.corn = s_corn;
@@ -1014,6 +1220,21 @@ __global__ __launch_bounds__(64, FR_WPS) void k_fast_rows(DGeom g, const OrbxCel
     orbx_wave_sync();   // the next group overwrites tile / score / lists
   }
 #undef FR_PREFETCH
+}
+__global__ __launch_bounds__(64, FR_WPS) void k_fast_rows(DGeom g, const OrbxCell *__restrict__ cells,
+                                                          const OrbxFastGroup *__restrict__ groups,
+                                                          const uint8_t *__restrict__ pyr, uint2 *__restrict__ cand,
+                                                          int *__restrict__ cand_cursor, int *__restrict__ status, int rows,
+                                                          int lcap, int ngroups, int gpw, int dbg_stop, int ccap) {
+    const OrbxRaw0 none = {nullptr, 0, 0, 0, 0};
+    fr_kernel<false>(g, cells, groups, pyr, cand, cand_cursor, status, rows, lcap, ngroups, gpw, dbg_stop, ccap, none);
+}
+__global__ __launch_bounds__(64, FR_WPS) void k_fast_rows_ip(DGeom g, const OrbxCell *__restrict__ cells,
+                                                             const OrbxFastGroup *__restrict__ groups,
+                                                             const uint8_t *__restrict__ pyr, uint2 *__restrict__ cand,
+                                                             int *__restrict__ cand_cursor, int *__restrict__ status, int rows,
+                                                             int lcap, int ngroups, int gpw, int dbg_stop, int ccap, OrbxRaw0 raw) {
+    fr_kernel<true>(g, cells, groups, pyr, cand, cand_cursor, status, rows, lcap, ngroups, gpw, dbg_stop, ccap, raw);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1510,13 +1731,18 @@ __device__ __forceinline__ uint32_t orbx_ds_tap(uint32_t adr) {
     I = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, d3), __builtin_bit_cast(u16x2, w3), I, false);
     return I;   // < 2^24.01
 }
-template <int FPM>
+// INPLACE: level-0 keypoints stage their patch from the caller's grey image (`raw`), which holds no border: interior
+// keypoints run the slab path's code on it; a patch that leaves the raw image (about 15 % of the level-0 keypoints: the 19-pixel
+// border of the padded level is gone) takes its rows through the reflection, loads one 48-byte window per row that is clamped
+// into the row, lays it into LDS displaced by whole dwords + the usual funnel shift, and then mirrors the ring columns from
+// the LDS row itself.  Address arithmetic: orbx_inplace.h.
+template <int FPM, bool INPLACE>
 __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const uint8_t *__restrict__ pyr,
                                                   const uint32_t *__restrict__ lvl_kp,
                                                   const int *__restrict__ lvl_count,
                                                   float *__restrict__ lvl_angle, orbx_keypoint *__restrict__ kps,
                                                   uint8_t *__restrict__ desc, int *__restrict__ counts,
-                                                  int *__restrict__ status, int cap, int dbg_stop, int nframes) {
+                                                  int *__restrict__ status, int cap, int dbg_stop, int nframes, OrbxRaw0 raw) {
     // dbg_stop (ORBX_DESC_STOP, phase-timing builds only, -DORBX_TIMING_KNOBS): 1 = after staging, 2 = after orientation,
     // 3 = after the row pass.  The shipped library pins it to 0.
 #ifndef ORBX_TIMING_KNOBS
@@ -1590,10 +1816,14 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
     const int4 pat = c_pattern_lane[lane];
     const DLevel &L = g.lv[level];
     const int x = (int)(pos & 0xfff) + (ORBX_EDGE - 3), y = (int)((pos >> 12) & 0xfff) + (ORBX_EDGE - 3);
-    const uint8_t *img = pyr + (long long)f * g.pyr_bytes + L.off;
-    const int px0 = x - DS_R, py0 = y - DS_R;
+    const bool ip0 = INPLACE && level == 0;   // wave-uniform
+    const uint8_t *img = ip0 ? raw.img + (long long)f * raw.frame_stride : pyr + (long long)f * g.pyr_bytes + L.off;
+    const int spitch = ip0 ? raw.stride : L.pitch;
+    // patch origin in the coordinates of the image the patch is staged from
+    const int px0 = x - DS_R - (ip0 ? ORBX_EDGE : 0), py0 = y - DS_R - (ip0 ? ORBX_EDGE : 0);
     const int xa = px0 & ~3;
-    const bool interior = px0 >= 0 && py0 >= 0 && xa + 48 <= L.pitch && x + DS_R < L.pw && y + DS_R < L.ph;
+    const bool interior = ip0 ? orbx_ip_desc_interior(px0, py0, raw.W, raw.H)
+                              : px0 >= 0 && py0 >= 0 && xa + 48 <= L.pitch && x + DS_R < L.pw && y + DS_R < L.ph;
     {
         // ---- stage the 43x43 patch (rows y-21.., columns x-21..): 12 ALIGNED dwords cover the 44 bytes of a patch
         // row; dword d of the LDS row = funnel shift of aligned dwords d, d+1.  A lane loads 3 aligned dwords (one
@@ -1603,10 +1833,10 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
         if (interior) {
             const int dq = lane & 3, rq = lane >> 2;
             const uint32_t shift = (uint32_t)(px0 & 3);
-            const uint8_t *p0 = img + (__mul24(py0, L.pitch) + xa + 12 * dq);   // 32-bit offsets: no 64-bit multiplies
+            const uint8_t *p0 = img + (__mul24(py0, spitch) + xa + 12 * dq);   // 32-bit offsets: no 64-bit multiplies
             orbx_uint3_u tv[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) tv[k] = *(const orbx_uint3_u *)(p0 + __mul24(min(16 * k + rq, DS_W - 1), L.pitch));
+            for (int k = 0; k < 3; ++k) tv[k] = *(const orbx_uint3_u *)(p0 + __mul24(min(16 * k + rq, DS_W - 1), spitch));
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const uint32_t nxt = orbx_lane_above(tv[k].x);
@@ -1618,13 +1848,60 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
                     if (dq < 3) d[2] = __builtin_amdgcn_alignbyte(nxt, tv[k].z, shift);   // dword 11 of a row does not exist
                 }
             }
+        } else if (ip0) {
+            // patch columns c <-> raw columns px0 + c; window byte i <-> raw column ws + i <-> patch column i + (ws - px0).
+            // LDS dword D of a row = window bytes [4 D + e, + 4) with e = px0 - ws (any sign): window dwords D + (e >> 2) and the
+            // next one, funnel-shifted by e & 3.  Lane dq holds window dwords 3 dq .. 3 dq + 2 and takes the 4th from the lane above.
+            const int dq = lane & 3, rq = lane >> 2;
+            const int ws = orbx_ip_desc_ws(px0, raw.W);
+            const int e = px0 - ws;
+            const uint32_t shift = (uint32_t)(e & 3);
+            const int dd = e >> 2;                                  // window dword of LDS dword 0 (floor)
+            orbx_uint3_u tv[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                tv[k] = *(const orbx_uint3_u *)(img + orbx_ip_row_off(orbx_ip_map(py0 + ORBX_EDGE + min(16 * k + rq, DS_W - 1), raw.H), raw.stride, ws + 12 * dq));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const uint32_t nxt = orbx_lane_above(tv[k].x);
+                const int r = 16 * k + rq;
+                if (r < DS_W) {
+                    uint32_t *d = patch + r * (DS_PP / 4);
+                    const int D = 3 * dq - dd;                      // LDS dword of this lane's first funnel
+                    // (the last window dword of a row has no successor: its funnel carries bytes of the next row's lane in
+                    // its top `shift` bytes, which are ring columns beyond W whenever that dword is stored)
+                    const uint32_t f0 = __builtin_amdgcn_alignbyte(tv[k].y, tv[k].x, shift), f1 = __builtin_amdgcn_alignbyte(tv[k].z, tv[k].y, shift),
+                                   f2 = __builtin_amdgcn_alignbyte(nxt, tv[k].z, shift);
+                    if (D >= 0 && D < DS_PP / 4) d[D] = f0;
+                    if (D + 1 >= 0 && D + 1 < DS_PP / 4) d[D + 1] = f1;
+                    if (D + 2 >= 0 && D + 2 < DS_PP / 4) d[D + 2] = f2;
+                    // the dword in front of window dword 0 (left edge: its top bytes are raw columns 0 ..)
+                    if (dq == 0 && D - 1 >= 0 && D - 1 < DS_PP / 4) d[D - 1] = __builtin_amdgcn_alignbyte(tv[k].x, 0u, shift);
+                }
+            }
+            // ring columns (raw column < 0 or >= W), one per step, lane = patch row: mirrored from the row's own real columns
+            // (source position 0..43 of the 44 staged bytes); the one position that can fall in front of the row
+            // (right edge, 37 <= c) is read from the image
+            const int c_end_l = px0 < 0 ? min(-px0, DS_W) : 0, c_beg_r = max(raw.W - px0, 0);
+            if (c_end_l > 0 || c_beg_r < DS_W) {
+                orbx_wave_sync();
+                uint8_t *pb = (uint8_t *)patch + min(lane, DS_W - 1) * DS_PP;
+                const uint8_t *grow = img + orbx_ip_row_off(orbx_ip_map(py0 + ORBX_EDGE + min(lane, DS_W - 1), raw.H), raw.stride, 0);
+                for (int c = 0; c < DS_W; ++c) {
+                    if (c >= c_end_l && c < c_beg_r) { c = c_beg_r - 1; continue; }
+                    const int j = orbx_ip_map(px0 + ORBX_EDGE + c, raw.W);   // wave-uniform
+                    const int sp = j - px0;
+                    const uint8_t v = (sp >= 0 && sp < DS_PP) ? pb[sp] : grow[j];
+                    if (lane < DS_W) pb[c] = v;
+                }
+            }
         } else {
             // image edge: reflect-101 of the padded level, byte by byte
             uint8_t *pb = (uint8_t *)patch;
             for (int i = lane; i < DS_W * DS_W; i += 64) {
                 const int r = i / DS_W, c = i - r * DS_W;
                 const int sy = orbx_reflect101(py0 + r, L.ph), sx = orbx_reflect101(px0 + c, L.pw);
-                pb[r * DS_PP + c] = img[(long long)sy * L.pitch + sx];
+                pb[r * DS_PP + c] = img[(long long)sy * L.pitch + sx];   // (never the in-place image: !ip0 here)
             }
         }
         orbx_wave_sync();
@@ -3327,9 +3604,21 @@ void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, con
     dim3 grid((L.pw + 255) / 256, (L.ph + 4 * RS_ROWS - 1) / (4 * RS_ROWS), B);
     hipLaunchKernelGGL(k_pyr_resize, grid, dim3(64, 4), 0, s, g, level, taps, pyr);
 }
+void orbx_launch_pyr_resize_l1(hipStream_t s, const DGeom &g, int B, const OrbxTap *taps_l1, const OrbxRaw0 &raw, uint8_t *pyr,
+                               int tail_bx, int *status, int *cand_cursor) {
+    const DLevel &L = g.lv[1];
+    int rpw = 16;   // as orbx_launch_pyr_resize
+    while (rpw > 2 && (long long)((L.pw + 255) / 256) * ((L.ph + rpw - 1) / rpw) * B < 4096) rpw >>= 1;
+#if RR_FF
+    dim3 grid(B, (L.pw + 255) / 256, (L.ph + RR_WPB * rpw - 1) / (RR_WPB * rpw));
+#else
+    dim3 grid((L.pw + 255) / 256, (L.ph + RR_WPB * rpw - 1) / (RR_WPB * rpw), B);
+#endif
+    hipLaunchKernelGGL(k_pyr_resize_rows_l1, grid, dim3(64, RR_WPB), 0, s, g, taps_l1, raw, pyr, rpw, tail_bx, status, cand_cursor);
+}
 void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell *cells, const OrbxFastGroup *groups,
                            int ngroups, const uint8_t *pyr, uint2 *cand, int *cand_cursor, int *status, int max_ch, int lcap,
-                           int dbg_stop, int lds_floor) {
+                           int dbg_stop, int lds_floor, const OrbxRaw0 *raw) {
     if (ngroups <= 0) return;
     lcap = (max(lcap, 64) + 1) & ~1;
     // LDS per wave decides how many waves a CU holds: the corner list of a group is sized for its usual load, FR_CCAP entries (the
@@ -3346,8 +3635,12 @@ void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell 
     // groups per wave: FR_GPW when the launch has waves to spare (the second group's tile is prefetched while the first
     // is processed); one per wave for small batches, where the serial length of a wave is what the caller waits for
     const int gpw = (long long)B * ngroups >= 16384 ? FR_GPW : 1;
-    hipLaunchKernelGGL(k_fast_rows, dim3(B, (ngroups + gpw - 1) / gpw), dim3(64), smem, s, g, cells, groups, pyr, cand,
-                       cand_cursor, status, max_ch, lcap, ngroups, gpw, dbg_stop, ccap);
+    if (raw)
+        hipLaunchKernelGGL(k_fast_rows_ip, dim3(B, (ngroups + gpw - 1) / gpw), dim3(64), smem, s, g, cells, groups, pyr, cand,
+                           cand_cursor, status, max_ch, lcap, ngroups, gpw, dbg_stop, ccap, *raw);
+    else
+        hipLaunchKernelGGL(k_fast_rows, dim3(B, (ngroups + gpw - 1) / gpw), dim3(64), smem, s, g, cells, groups, pyr, cand,
+                           cand_cursor, status, max_ch, lcap, ngroups, gpw, dbg_stop, ccap);
 }
 void orbx_launch_undistort(hipStream_t s, int B, int max_n, int cap, const double *K4, const double *k14, int identity,
                            const orbx_keypoint *kps, const int *counts, orbx_keypoint *out) {
@@ -3427,7 +3720,7 @@ void orbx_launch_blur(hipStream_t s, const DGeom &g, int B, const uint8_t *pyr, 
 }
 void orbx_launch_describe(hipStream_t s, const DGeom &g, int B, const uint8_t *pyr, const uint32_t *lvl_kp,
                           const int *lvl_count, float *lvl_angle, orbx_keypoint *kps, uint8_t *desc,
-                          int *counts, int *status, int cap) {
+                          int *counts, int *status, int cap, const OrbxRaw0 *raw) {
 #ifdef ORBX_TIMING_KNOBS
     static int dbg_stop = -1;
     if (dbg_stop < 0) { const char *e = getenv("ORBX_DESC_STOP"); dbg_stop = e ? atoi(e) : 0; }
@@ -3439,10 +3732,15 @@ void orbx_launch_describe(hipStream_t s, const DGeom &g, int B, const uint8_t *p
 #else
     const dim3 grid(B, (g.kp_total + DS_WPB - 1) / DS_WPB);
 #endif
-    if (g.fp_mode == ORBX_FP_GCC_FMA)
-        hipLaunchKernelGGL(k_describe<ORBX_FP_GCC_FMA>, grid, dim3(64 * DS_WPB), 0, s, g, pyr, lvl_kp, lvl_count, lvl_angle, kps, desc, counts, status, cap, dbg_stop, B);
+    const OrbxRaw0 none{nullptr, 0, 0, 0, 0};
+    if (raw && g.fp_mode == ORBX_FP_GCC_FMA)
+        hipLaunchKernelGGL((k_describe<ORBX_FP_GCC_FMA, true>), grid, dim3(64 * DS_WPB), 0, s, g, pyr, lvl_kp, lvl_count, lvl_angle, kps, desc, counts, status, cap, dbg_stop, B, *raw);
+    else if (raw)
+        hipLaunchKernelGGL((k_describe<ORBX_FP_STRICT, true>), grid, dim3(64 * DS_WPB), 0, s, g, pyr, lvl_kp, lvl_count, lvl_angle, kps, desc, counts, status, cap, dbg_stop, B, *raw);
+    else if (g.fp_mode == ORBX_FP_GCC_FMA)
+        hipLaunchKernelGGL((k_describe<ORBX_FP_GCC_FMA, false>), grid, dim3(64 * DS_WPB), 0, s, g, pyr, lvl_kp, lvl_count, lvl_angle, kps, desc, counts, status, cap, dbg_stop, B, none);
     else
-        hipLaunchKernelGGL(k_describe<ORBX_FP_STRICT>, grid, dim3(64 * DS_WPB), 0, s, g, pyr, lvl_kp, lvl_count, lvl_angle, kps, desc, counts, status, cap, dbg_stop, B);
+        hipLaunchKernelGGL((k_describe<ORBX_FP_STRICT, false>), grid, dim3(64 * DS_WPB), 0, s, g, pyr, lvl_kp, lvl_count, lvl_angle, kps, desc, counts, status, cap, dbg_stop, B, none);
 }
 void orbx_launch_grid_build(hipStream_t s, const DGrid &gp, int nframes, const orbx_keypoint *kps, const int *counts, int fixed_n,
                             int cap, int *cell_begin, uint16_t *items) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "orbx_device.h"
+#include "orbx_inplace.h"
 
 hipError_t orbx_upload_pattern();
 size_t orbx_quadtree_smem(int ncap, int lds_keys);
@@ -16,7 +17,11 @@ void orbx_launch_pyr_l0_remap(hipStream_t s, const DGeom &g, int B, const uint8_
 void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, const OrbxTap *taps, uint8_t *pyr, bool narrow);
 void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell *cells, const OrbxFastGroup *groups,
                            int ngroups, const uint8_t *pyr, uint2 *cand, int *cand_cursor, int *status, int max_ch, int lcap,
-                           int dbg_stop, int lds_floor = 0);
+                           int dbg_stop, int lds_floor = 0, const OrbxRaw0 *raw = nullptr);
+// in-place mode (orbx_inplace.h): level 1 from the caller's grey image `raw`; also resets status[f] and cand_cursor[f][*] as
+// k_pyr_l0 does.  taps_l1 = the level's raw-coordinate tap table (pw horizontal records, then ph vertical ones).
+void orbx_launch_pyr_resize_l1(hipStream_t s, const DGeom &g, int B, const OrbxTap *taps_l1, const OrbxRaw0 &raw, uint8_t *pyr,
+                               int tail_bx, int *status, int *cand_cursor);
 void orbx_launch_undistort(hipStream_t s, int B, int max_n, int cap, const double *K4, const double *k14, int identity,
                            const orbx_keypoint *kps, const int *counts, orbx_keypoint *out);
 // depth input of k_rgbd (Frame::ComputeStereoFromRGBD): `depth` = frame 0, frames `frame_stride` bytes apart, rows `stride`
@@ -37,7 +42,7 @@ void orbx_launch_quadtree(hipStream_t s, const DGeom &g, int B, const uint2 *den
 void orbx_launch_blur(hipStream_t s, const DGeom &g, int B, const uint8_t *pyr, uint8_t *blur);
 void orbx_launch_describe(hipStream_t s, const DGeom &g, int B, const uint8_t *pyr, const uint32_t *lvl_kp,
                           const int *lvl_count, float *lvl_angle, orbx_keypoint *kps, uint8_t *desc,
-                          int *counts, int *status, int cap);
+                          int *counts, int *status, int cap, const OrbxRaw0 *raw = nullptr);
 void orbx_launch_match(hipStream_t s, int npairs, int max_nq, const uint8_t *q, const int *nq, long long q_stride,
                        const uint8_t *t, const int *nt, long long t_stride, int *best_idx, int *best_dist,
                        int *second_dist, int out_stride, void *workspace, int kernel);

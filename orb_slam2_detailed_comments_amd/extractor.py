@@ -30,6 +30,7 @@ class ORBextractor:
         if getattr(self, "_h", None):
             self._L.orbx_destroy(self._h)
             self._h = None
+        self._dev_input = None
 
     __del__ = close
 
@@ -161,7 +162,11 @@ class ORBextractor:
 
     def extract_batch_device(self, d_imgs, nframes, width, height, stride, frame_stride, d_kps, d_desc, d_counts,
                              d_status, cap):
-        """device-pointer entry (torch tensors or raw addresses); asynchronous on the handle's stream"""
+        """device-pointer entry (torch tensors or raw addresses); asynchronous on the handle's stream.
+        The library reads grey input in place until the call's last kernel has run, and again when the padded level 0 is asked
+        for later (include/orbx.h, LIFETIME / LATE COPY): the extractor keeps a reference to `d_imgs` until its next device call
+        or close(), so a caller's temporary cannot be recycled under the kernels.  The CONTENT is still the caller's to keep."""
+        self._dev_input = d_imgs
         check(self._L.orbx_extract_batch_device(self._h, nframes, ptr(d_imgs), width, height, stride, frame_stride,
                                                 ptr(d_kps), ptr(d_desc), ptr(d_counts), ptr(d_status), cap))
 
