@@ -13,6 +13,13 @@
 #include <opencv2/features2d/features2d.hpp>
 #include "orbx.h"
 
+// What mvImagePyramid[level] is (include/orbx.h, orbx_params.pyramid_mode).  Default: the annotated fork, whose levels are the
+// padded images (src/ORBextractor.cc:2166).  A tree that is upstream ORB-SLAM2 in this respect (no such line) builds with
+// -DORBX_COMPAT_PYRAMID_MODE=ORBX_PYRAMID_UPSTREAM: un-padded levels, keypoints in image coordinates.
+#ifndef ORBX_COMPAT_PYRAMID_MODE
+#define ORBX_COMPAT_PYRAMID_MODE ORBX_PYRAMID_FORK_PADDED
+#endif
+
 namespace ORB_SLAM2 {
 
 class ORBextractor {
@@ -24,6 +31,7 @@ public:
         orbx_default_params(&p);
         p.nfeatures = nfeatures; p.scale_factor = scaleFactor; p.nlevels = nlevels;
         p.ini_th_fast = iniThFAST; p.min_th_fast = minThFAST;
+        p.pyramid_mode = ORBX_COMPAT_PYRAMID_MODE;
         if (orbx_create(&p, &h_) != ORBX_OK) throw std::runtime_error(orbx_last_error());
         nlevels_ = nlevels;
         mvScaleFactor.resize(nlevels); mvInvScaleFactor.resize(nlevels);
@@ -68,7 +76,8 @@ public:
         if (eager_pyramid_) FetchPyramid();
     }
 
-    // Fills mvImagePyramid with the padded levels of the last frame (fork semantics, src/ORBextractor.cc:2165-2166).  For a
+    // Fills mvImagePyramid with the levels of the last frame: the padded ones (fork semantics, src/ORBextractor.cc:2165-2166), or
+    // with ORBX_COMPAT_PYRAMID_MODE = ORBX_PYRAMID_UPSTREAM the un-padded ones (orbx_pyramid_level_info gives their size).  For a
     // caller that keeps the reference's own ComputeStereoMatches nothing needs doing (eager copy is the default); after
     // SetEagerPyramid(false) call it on both extractors before anything reads mvImagePyramid.
     void FetchPyramid() {

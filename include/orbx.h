@@ -25,7 +25,8 @@ extern "C" {
 /* Bit-compatible with cv::KeyPoint (28 bytes): what ORBextractor::operator() appends to
  * std::vector<cv::KeyPoint>& _keypoints (src/ORBextractor.cc:2016-2082). */
 typedef struct orbx_keypoint {
-    float x, y;       /* pt, in level-0 *padded-image* coordinates (fork semantics) */
+    float x, y;       /* pt.  ORBX_PYRAMID_FORK_PADDED: level-0 *padded-image* coordinates, 19 px off the camera model (fork
+                       * semantics).  ORBX_PYRAMID_UPSTREAM: un-padded image coordinates, as in upstream ORB-SLAM2 */
     float size;       /* (float)(int)(31 * scale[octave]) */
     float angle;      /* degrees [0,360) */
     float response;   /* FAST score */
@@ -44,7 +45,12 @@ typedef enum orbx_status {
     ORBX_UNSUPPORTED = 7
 } orbx_status;
 
-enum { ORBX_PYRAMID_FORK_PADDED = 0 };           /* src/ORBextractor.cc:2165-2166 */
+/* What mvImagePyramid[level] is.  FORK_PADDED: the padded buffer `temp` (the annotated fork's line src/ORBextractor.cc:2166,
+ * `mvImagePyramid[level] = temp;`).  UPSTREAM: ComputePyramid without that line, as in upstream ORB-SLAM2 -- the sw x sh view at
+ * (19, 19) inside `temp`: level l > 0 is resized from the un-padded level l - 1, the FAST region is [16, sw - 16) x [16, sh - 16),
+ * keypoints are in un-padded image coordinates, and SURVEY F6 / F7 do not arise.  A level with sw < 33 or sh < 33 has an empty
+ * FAST region there (the reference is undefined): ORBX_UNSUPPORTED, naming the level, before any launch. */
+enum { ORBX_PYRAMID_FORK_PADDED = 0, ORBX_PYRAMID_UPSTREAM = 1 };
 enum { ORBX_FP_GCC_FMA = 0, ORBX_FP_STRICT = 1 }; /* contraction of GET_VALUE, src/ORBextractor.cc:207-209 */
 
 /* The five values ORBextractor's constructor takes (include/ORBextractor.h:104; read from YAML at
@@ -55,7 +61,7 @@ typedef struct orbx_params {
     int32_t nlevels;
     int32_t ini_th_fast;
     int32_t min_th_fast;
-    int32_t pyramid_mode;        /* ORBX_PYRAMID_FORK_PADDED */
+    int32_t pyramid_mode;        /* ORBX_PYRAMID_FORK_PADDED (default) or ORBX_PYRAMID_UPSTREAM; per handle */
     int32_t fp_mode;             /* ORBX_FP_GCC_FMA (default parity contract) or ORBX_FP_STRICT */
     int32_t device;              /* HIP device ordinal; -1 = current device */
     int32_t max_batch;           /* frames in flight per call (>=1) */
@@ -100,7 +106,8 @@ orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uint8_t *imgs,
  * In-place level 0.  When ALL of these hold the kernels read level 0 IN PLACE from d_imgs and the padded copy of level 0 is
  * not written during the call: this entry point; ORBX_FMT_GRAY8; no rectification maps; d_imgs, `stride` and `frame_stride`
  * multiples of 4; at least 64 x 64 pixels and at least 2 levels; the level-1 tap table passed its footprint check (every usual
- * scale factor); ORBX_RESIZE_IMPL=legacy and ORBX_FORK_LEVEL are not set; the handle's stereo match has not needed the late
+ * scale factor); the handle's pyramid_mode is ORBX_PYRAMID_FORK_PADDED (upstream handles always write level 0 during the call);
+ * ORBX_RESIZE_IMPL=legacy and ORBX_FORK_LEVEL are not set; the handle's stereo match has not needed the late
  * copy (below); and ORBX_LEVEL0_INPLACE=0 is not set.
  * LIFETIME: in this mode d_imgs is read until the LAST kernel of the call has finished on the handle's stream, not only by
  * its first kernel: it must stay valid and unchanged until then (orbx_synchronize, or an event on the handle's stream).  The
@@ -133,11 +140,13 @@ orbx_status orbx_set_rectification(orbx_handle *h, const float *map_x, const flo
 /* ---- pyramid access: replaces the public member `mvImagePyramid` (include/ORBextractor.h:185),
  *      read by Frame::ComputeStereoMatches (src/Frame.cc:910,1040,1072,1079).  Valid until the next
  *      extract on this handle ("pyramid is overwritten every frame", include/ORBextractor.h:30-35). -- */
+/* width x height of mvImagePyramid[level]: the padded level (sw + 38) x (sh + 38) of a fork handle, the un-padded sw x sh view
+ * of an upstream handle (whose 19-pixel reflect-101 border still surrounds it in memory); `pitch` is the same for both */
 orbx_status orbx_pyramid_level_info(orbx_handle *h, int level, int *width, int *height, int *pitch);
-/* device view of (frame, level): padded image, `pitch` bytes per row (after an in-place batch this queues the late
+/* device view of (frame, level): that image, `pitch` bytes per row (after an in-place batch this queues the late
  * level-0 copy on the handle's stream first, see orbx_extract_batch_device) */
 orbx_status orbx_pyramid_level_device(orbx_handle *h, int frame, int level, const uint8_t **d_ptr);
-/* copies the padded level into dst (dst_stride >= width) */
+/* copies that image into dst (dst_stride >= width) */
 orbx_status orbx_pyramid_level_copy(orbx_handle *h, int frame, int level, uint8_t *dst, int dst_stride);
 
 /* ---- matching: ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:2073-2093) evaluated for every
@@ -179,7 +188,9 @@ orbx_status orbx_search_for_initialization(orbx_handle *h, const orbx_keypoint *
 /* Frame::ComputeStereoMatches (src/Frame.cc:880-1176).  hl / hr are the left / right extractors whose pyramids of
  * (frame_left, frame_right) are still resident (mvImagePyramid is read at :910,1040,1072,1079); keypoints and
  * descriptors are host buffers; u_right / depth = mvuRight / mvDepth.  The reference's unchecked row index (F6)
- * is clamped. */
+ * is clamped (on ORBX_PYRAMID_UPSTREAM handles every keypoint row lies inside the table and F6 does not arise).  Both
+ * handles must have the same pyramid_mode (ORBX_BAD_ARGUMENT otherwise), here and in the batched call; the behaviour of
+ * Frame.cc itself (:1067, the median cut) is the fork's in both modes. */
 orbx_status orbx_stereo_match(orbx_handle *hl, orbx_handle *hr, int frame_left, int frame_right,
                               const orbx_keypoint *kl, const uint8_t *dl, int nl, const orbx_keypoint *kr,
                               const uint8_t *dr, int nr, float mb, float mbf, float *u_right, float *depth,
@@ -479,7 +490,8 @@ orbx_status orbx_undistort_keypoints(orbx_handle *h, const orbx_keypoint *kps, i
  *   ORBX_DEPTH_U16: convertTo(CV_32F, scale) makes a continuous float image, pixel = (float)raw * scale;
  *   ORBX_DEPTH_F32: with fabs(scale - 1.0f) > 1e-5 converted in place (the caller's stride is kept, bytes between rows stay
  *                   unscaled), otherwise read as they are.
- * Per keypoint: u = (int)kps[i].x, v = (int)kps[i].y (the DISTORTED keypoint, padded-image coordinates in this fork); the
+ * Per keypoint: u = (int)kps[i].x, v = (int)kps[i].y (the DISTORTED keypoint: padded-image coordinates on a fork handle, image
+ * coordinates on an ORBX_PYRAMID_UPSTREAM handle, where every keypoint lies inside the depth image and F7 does not arise); the
  * sample is byte o = v * pitch + 4 * u of that float image (pitch = 4 * W for u16, `stride` for f32; a u beyond the row wraps
  * into the next row, as in the reference).  F7: o + 4 > (H - 1) * pitch + 4 * W lies past the image's
  * memory and gives no depth, and so do negative, non-finite or too-large coordinates.  d > 0: depth[i] = d,
@@ -562,7 +574,7 @@ const char *orbx_kernel_name(int kernel_id);
 orbx_status orbx_debug_candidates(orbx_handle *h, int frame, int level, orbx_keypoint *out, int cap, int *n);
 /* keypoints of (frame, level) after quadtree + orientation, level coordinates, list order */
 orbx_status orbx_debug_level_keypoints(orbx_handle *h, int frame, int level, orbx_keypoint *out, int cap, int *n);
-/* blurred padded level */
+/* blurred level: GaussianBlur of mvImagePyramid[level] (fork: the padded level; upstream: the un-padded view) */
 orbx_status orbx_debug_blur_copy(orbx_handle *h, int frame, int level, uint8_t *dst, int dst_stride);
 
 #ifdef __cplusplus

@@ -15,6 +15,7 @@ assert KP_DTYPE.itemsize == 28
 
 OK, EMPTY_IMAGE, BAD_ARGUMENT, BAD_ASPECT, CAPACITY, HIP_ERROR, NO_DEVICE, UNSUPPORTED = range(8)
 FP_GCC_FMA, FP_STRICT = 0, 1
+PYRAMID_FORK_PADDED, PYRAMID_UPSTREAM = 0, 1   # orbx_params.pyramid_mode: what mvImagePyramid[level] is (include/orbx.h)
 FMT_GRAY8, FMT_RGB8, FMT_BGR8, FMT_RGBA8, FMT_BGRA8 = range(5)
 DEPTH_U16, DEPTH_F32 = 0, 1
 K_NAMES = ("k_pyr_l0", "k_pyr_resize", "k_fast_rows", "k_quadtree", "k_orient", "k_blur", "k_describe",

@@ -245,7 +245,7 @@ static orbx_status configure(orbx_handle *h, int width, int height) {
         D.qt_w = L.qt_w; D.qt_h = L.qt_h; D.nini = L.nini; D.hx = L.hx;
         D.nfeat = L.nfeat; D.kp_cap = L.kp_cap; D.kp_begin = L.kp_begin; D.cand_cap = L.cand_cap;
         D.tapx = L.tapx_begin; D.tapy = L.tapy_begin; D.scale = L.scale; D.size = L.size;
-        D.off = L.off; D.cand_begin = L.cand_begin;
+        D.off = L.off; D.cand_begin = L.cand_begin; D.org = L.org;
         D.blur_tx = (L.pw + 127) / 128;  // k_blur tile = 128 x 32
         D.blur_tile_begin = tiles;
         tiles += D.blur_tx * ((L.ph + 31) / 32);
@@ -364,7 +364,8 @@ extern "C" orbx_status orbx_create(const orbx_params *params, orbx_handle **out)
     if (params->nlevels < 1 || params->nlevels > ORBX_MAX_LEVELS) return fail(ORBX_BAD_ARGUMENT, "nlevels out of range [1,16]");
     if (params->nfeatures < 1 || params->nfeatures > 16000) return fail(ORBX_BAD_ARGUMENT, "nfeatures out of range [1,16000]");
     if (!(params->scale_factor > 1.0f)) return fail(ORBX_BAD_ARGUMENT, "scale_factor must be > 1");
-    if (params->pyramid_mode != ORBX_PYRAMID_FORK_PADDED) return fail(ORBX_UNSUPPORTED, "only ORBX_PYRAMID_FORK_PADDED is implemented");
+    if (params->pyramid_mode != ORBX_PYRAMID_FORK_PADDED && params->pyramid_mode != ORBX_PYRAMID_UPSTREAM)
+        return fail(ORBX_UNSUPPORTED, "pyramid_mode: ORBX_PYRAMID_FORK_PADDED and ORBX_PYRAMID_UPSTREAM are implemented");
     if (params->fp_mode != ORBX_FP_GCC_FMA && params->fp_mode != ORBX_FP_STRICT) return fail(ORBX_BAD_ARGUMENT, "fp_mode");
     orbx_handle *h = new orbx_handle();
     h->p = *params;
@@ -509,9 +510,10 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
     const DGeom &g = h->dg;
     // In-place level 0: only the device entry with grey, un-rectified, dword-aligned frames of at least ORBX_IP_MIN_W x
     // ORBX_IP_MIN_H pixels whose level-1 raw tap table passed the narrow check (geom.l1_inplace covers the last two); the fork
-    // knob resizes level 1 on its own path.  Everything else runs k_pyr_l0 as before.
+    // knob resizes level 1 on its own path.  Everything else runs k_pyr_l0 as before -- upstream handles included, whose geometry
+    // carries no raw-coordinate tap table (geom.l1_inplace is false for them).
     const bool inplace = device_entry && h->l0_inplace && !h->l0_eager_sticky && !h->d_rect && h->input_format == ORBX_FMT_GRAY8 &&
-                         h->geom.l1_inplace && !h->resize_legacy && h->fork_level == 0 && ((uintptr_t)d_imgs & 3) == 0 &&
+                         h->p.pyramid_mode == ORBX_PYRAMID_FORK_PADDED && h->geom.l1_inplace && !h->resize_legacy && h->fork_level == 0 && ((uintptr_t)d_imgs & 3) == 0 &&
                          (stride & 3) == 0 && (frame_stride & 3) == 0 && frame_stride >= 0 && W == h->geom.width && H == h->geom.height;
     h->l0_pending = false;
     hipStream_t s = h->stream;
@@ -1085,6 +1087,8 @@ extern "C" orbx_status orbx_extract(orbx_handle *h, const uint8_t *img, int widt
 }
 
 // ---------------------------------------------------------------- pyramid access
+// byte offset of mvImagePyramid[level] inside one frame's slab: the padded level, or the view at (org, org) of it
+static inline size_t level_view_off(const OrbxLevelGeom &L) { return (size_t)L.off + (size_t)L.org * L.pitch + L.org; }
 static orbx_status check_level(orbx_handle *h, int frame, int level) {
     if (!h) return fail(ORBX_BAD_ARGUMENT, "null handle");
     if (!h->configured || h->last_batch == 0) return fail(ORBX_BAD_ARGUMENT, "no frame extracted yet");
@@ -1094,8 +1098,8 @@ static orbx_status check_level(orbx_handle *h, int frame, int level) {
 extern "C" orbx_status orbx_pyramid_level_info(orbx_handle *h, int level, int *width, int *height, int *pitch) {
     orbx_status st = check_level(h, 0, level);
     if (st != ORBX_OK) return st;
-    if (width) *width = h->geom.lv[level].pw;
-    if (height) *height = h->geom.lv[level].ph;
+    if (width) *width = h->geom.lv[level].vw;    // mvImagePyramid[level]: the padded level (fork) or the view inside it (upstream)
+    if (height) *height = h->geom.lv[level].vh;
     if (pitch) *pitch = h->geom.lv[level].pitch;
     return ORBX_OK;
 }
@@ -1119,21 +1123,21 @@ extern "C" orbx_status orbx_pyramid_level_device(orbx_handle *h, int frame, int 
         st = ensure_level0(h);
         if (st != ORBX_OK) return st;
     }
-    *d_ptr = h->d_pyr + (size_t)frame * h->geom.pyr_bytes + h->geom.lv[level].off;
+    *d_ptr = h->d_pyr + (size_t)frame * h->geom.pyr_bytes + level_view_off(h->geom.lv[level]);
     return ORBX_OK;
 }
 static orbx_status copy_level(orbx_handle *h, const uint8_t *slab, int frame, int level, uint8_t *dst, int dst_stride) {
     orbx_status st = check_level(h, frame, level);
     if (st != ORBX_OK) return st;
     const OrbxLevelGeom &L = h->geom.lv[level];
-    if (!dst || dst_stride < L.pw) return fail(ORBX_BAD_ARGUMENT, "dst / dst_stride");
+    if (!dst || dst_stride < L.vw) return fail(ORBX_BAD_ARGUMENT, "dst / dst_stride");
     HIPCHK(hipSetDevice(h->dev));
     if (level == 0 && slab == h->d_pyr) {   // (the blurred slab's level 0 was built behind its own ensure_level0)
         st = ensure_level0(h);
         if (st != ORBX_OK) return st;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy2D(dst, dst_stride, slab + (size_t)frame * h->geom.pyr_bytes + L.off, L.pitch, L.pw, L.ph,
+    HIPCHK(hipMemcpy2D(dst, dst_stride, slab + (size_t)frame * h->geom.pyr_bytes + level_view_off(L), L.pitch, L.vw, L.vh,
                        hipMemcpyDeviceToHost));
     return ORBX_OK;
 }
@@ -1737,6 +1741,19 @@ extern "C" orbx_status orbx_search_for_initialization(orbx_handle *h, const orbx
 }
 
 // ---------------------------------------------------------------- a16: ComputeStereoMatches (src/Frame.cc:880-1176)
+// mvImagePyramid of both eyes as the match reads it: the padded levels (fork) or the views inside them (upstream)
+static OrbxStereoGeom stereo_geom(const orbx_handle *hl, float mb, float mbf) {
+    OrbxStereoGeom sg;
+    memset(&sg, 0, sizeof(sg));
+    sg.nlevels = hl->p.nlevels; sg.nrows0 = hl->geom.lv[0].vh; sg.mb = mb; sg.mbf = mbf;
+    for (int l = 0; l < sg.nlevels; ++l) {
+        const OrbxLevelGeom &L = hl->geom.lv[l];
+        sg.scale[l] = hl->tab.scale[l]; sg.inv_scale[l] = hl->tab.inv_scale[l];
+        sg.pw[l] = L.vw; sg.ph[l] = L.vh; sg.pitch[l] = L.pitch;
+        sg.off[l] = (long long)level_view_off(L);
+    }
+    return sg;
+}
 extern "C" orbx_status orbx_stereo_match(orbx_handle *hl, orbx_handle *hr, int frame_left, int frame_right,
                                          const orbx_keypoint *kl, const uint8_t *dl, int nl, const orbx_keypoint *kr,
                                          const uint8_t *dr, int nr, float mb, float mbf, float *u_right, float *depth,
@@ -1750,8 +1767,8 @@ extern "C" orbx_status orbx_stereo_match(orbx_handle *hl, orbx_handle *hr, int f
     st = check_level(hr, frame_right, 0);
     if (st != ORBX_OK) return st;
     if (hl->dev != hr->dev || hl->geom.width != hr->geom.width || hl->geom.height != hr->geom.height ||
-        hl->p.nlevels != hr->p.nlevels || hl->p.scale_factor != hr->p.scale_factor)
-        return fail(ORBX_BAD_ARGUMENT, "left and right extractor must share device, image size and pyramid parameters");
+        hl->p.nlevels != hr->p.nlevels || hl->p.scale_factor != hr->p.scale_factor || hl->p.pyramid_mode != hr->p.pyramid_mode)
+        return fail(ORBX_BAD_ARGUMENT, "left and right extractor must share device, image size, pyramid parameters and pyramid_mode");
     if (nmatches_out) *nmatches_out = 0;
     if (nl == 0) return ORBX_OK;
     HIPCHK(hipSetDevice(hl->dev));
@@ -1761,14 +1778,7 @@ extern "C" orbx_status orbx_stereo_match(orbx_handle *hl, orbx_handle *hr, int f
         if (st != ORBX_OK) return st;
     }
     HIPCHK(hipStreamSynchronize(hr->stream));   // the right pyramid is read from the left handle's stream
-    OrbxStereoGeom sg;
-    memset(&sg, 0, sizeof(sg));
-    sg.nlevels = hl->p.nlevels; sg.nrows0 = hl->geom.lv[0].ph; sg.mb = mb; sg.mbf = mbf;
-    for (int l = 0; l < sg.nlevels; ++l) {
-        sg.scale[l] = hl->tab.scale[l]; sg.inv_scale[l] = hl->tab.inv_scale[l];
-        sg.pw[l] = hl->geom.lv[l].pw; sg.ph[l] = hl->geom.lv[l].ph; sg.pitch[l] = hl->geom.lv[l].pitch;
-        sg.off[l] = hl->geom.lv[l].off;
-    }
+    const OrbxStereoGeom sg = stereo_geom(hl, mb, mbf);
     st = scratch_reserve(hl, pad256((size_t)nl * sizeof(orbx_keypoint)) + pad256((size_t)nl * 32) +
                                  pad256((size_t)std::max(nr, 1) * sizeof(orbx_keypoint)) + pad256((size_t)std::max(nr, 1) * 32) +
                                  3 * pad256((size_t)nl * sizeof(float)) + pad256((size_t)(sg.nrows0 + 1) * sizeof(int)) +
@@ -1833,8 +1843,8 @@ extern "C" orbx_status orbx_stereo_match_batch_device(orbx_handle *hl, orbx_hand
     st = check_level(hr, npairs - 1, 0);
     if (st != ORBX_OK) return st;
     if (hl->dev != hr->dev || hl->geom.width != hr->geom.width || hl->geom.height != hr->geom.height ||
-        hl->p.nlevels != hr->p.nlevels || hl->p.scale_factor != hr->p.scale_factor)
-        return fail(ORBX_BAD_ARGUMENT, "left and right extractor must share device, image size and pyramid parameters");
+        hl->p.nlevels != hr->p.nlevels || hl->p.scale_factor != hr->p.scale_factor || hl->p.pyramid_mode != hr->p.pyramid_mode)
+        return fail(ORBX_BAD_ARGUMENT, "left and right extractor must share device, image size, pyramid parameters and pyramid_mode");
     HIPCHK(hipSetDevice(hl->dev));
     // The match reads the padded level 0 of both eyes: an in-place batch writes it now, on its own handle's stream, and the
     // handle goes back to the eager k_pyr_l0 for its later batches (a stereo pipeline would pay the late copy every time)
@@ -1850,14 +1860,7 @@ extern "C" orbx_status orbx_stereo_match_batch_device(orbx_handle *hl, orbx_hand
         HIPCHK(hipEventRecord(hr->ev_stereo, hr->stream));
         HIPCHK(hipStreamWaitEvent(hl->stream, hr->ev_stereo, 0));
     }
-    OrbxStereoGeom sg;
-    memset(&sg, 0, sizeof(sg));
-    sg.nlevels = hl->p.nlevels; sg.nrows0 = hl->geom.lv[0].ph; sg.mb = mb; sg.mbf = mbf;
-    for (int l = 0; l < sg.nlevels; ++l) {
-        sg.scale[l] = hl->tab.scale[l]; sg.inv_scale[l] = hl->tab.inv_scale[l];
-        sg.pw[l] = hl->geom.lv[l].pw; sg.ph[l] = hl->geom.lv[l].ph; sg.pitch[l] = hl->geom.lv[l].pitch;
-        sg.off[l] = hl->geom.lv[l].off;
-    }
+    const OrbxStereoGeom sg = stereo_geom(hl, mb, mbf);
     const size_t ipp = (size_t)orbx_stereo_items_per_pair(sg, cap);
     st = scratch_reserve(hl, pad256((size_t)npairs * cap * sizeof(int)) + pad256((size_t)npairs * (sg.nrows0 + 1) * sizeof(int)) +
                                  pad256((size_t)npairs * ipp * sizeof(uint2)));

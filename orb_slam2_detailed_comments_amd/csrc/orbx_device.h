@@ -15,6 +15,8 @@ struct DLevel {
     int tapx, tapy;
     float scale, size;
     int blur_tile_begin, blur_tx;  // flattened blur tile table
+    int org;                       // mvImagePyramid[level] starts at (org, org) of the padded level: 0 (fork), ORBX_EDGE (upstream);
+                                   // its size is (pw - 2 org) x (ph - 2 org).  (Fills the padding in front of `off`.)
     long long off;                 // byte offset in the per-frame pyramid slab
     long long cand_begin;          // record offset in the per-frame candidate table
 };
@@ -27,7 +29,8 @@ struct DGeom {
     DLevel lv[ORBX_MAX_LEVELS];
 };
 
-// geometry of the two pyramids ComputeStereoMatches reads (both handles share it: same image size / params)
+// geometry of the two pyramids ComputeStereoMatches reads (both handles share it: same image size / params).
+// pw / ph / off describe mvImagePyramid[level]: the padded level (fork) or the un-padded view inside it (upstream; same pitch)
 struct OrbxStereoGeom {
     int nlevels, nrows0;
     float mb, mbf;

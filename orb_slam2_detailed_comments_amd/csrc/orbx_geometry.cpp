@@ -10,6 +10,7 @@
 #include "orbx_internal.h"
 #include "orbx_inplace.h"
 #include <cmath>
+#include <cstdio>
 #include <algorithm>
 
 static inline int cv_round_f(float v) { return (int)lrintf(v); }      // cvRound: half-to-even
@@ -59,7 +60,9 @@ void orbx_build_tables(const orbx_params &p, OrbxTables &t) {
 
 // taps for destination coordinates 0..pdst-1 of a padded axis whose centre has `dcentre` samples,
 // resized from `ssize` source samples.  horizontal: weights zeroed when clamped; vertical: kept.
-static void build_axis_taps(std::vector<OrbxTap> &out, int pdst, int dcentre, int ssize, bool horizontal) {
+// sorg: where source sample 0 sits in the buffer the kernel indexes (0: the source IS the padded level, the fork; ORBX_EDGE:
+// the source is the un-padded view inside it, upstream) -- added after the clamp, so no tap leaves [sorg, sorg + ssize - 1]
+static void build_axis_taps(std::vector<OrbxTap> &out, int pdst, int dcentre, int ssize, bool horizontal, int sorg) {
     const double inv_scale = (double)dcentre / ssize;
     const double scale = 1. / inv_scale;
     for (int P = 0; P < pdst; ++P) {
@@ -77,6 +80,8 @@ static void build_axis_taps(std::vector<OrbxTap> &out, int pdst, int dcentre, in
             tap.s0 = (int16_t)std::min(std::max(s, 0), ssize - 1);
             tap.s1 = (int16_t)std::min(std::max(s + 1, 0), ssize - 1);
         }
+        tap.s0 = (int16_t)(tap.s0 + sorg);
+        tap.s1 = (int16_t)(tap.s1 + sorg);
         tap.a0 = sat16(cv_round_f((1.f - f) * 2048));
         tap.a1 = sat16(cv_round_f(f * 2048));
         out.push_back(tap);
@@ -87,6 +92,10 @@ orbx_status orbx_build_geometry(const orbx_params &p, const OrbxTables &t, int w
                                 const char **why) {
     g = OrbxGeom();
     g.width = width; g.height = height; g.nlevels = p.nlevels;
+    // ORBX_PYRAMID_UPSTREAM: a level is the sw x sh view at (19, 19) of its padded buffer.  The slab keeps the padded layout;
+    // the FAST region, the cells, the quadtree region and the resize source are those of the view.
+    const bool upstream = p.pyramid_mode == ORBX_PYRAMID_UPSTREAM;
+    static thread_local char why_buf[96];
     int64_t off = 0, cand_off = 0;
     int kp_off = 0;
     for (int l = 0; l < p.nlevels; ++l) {
@@ -97,6 +106,9 @@ orbx_status orbx_build_geometry(const orbx_params &p, const OrbxTables &t, int w
         L.pw = L.sw + 2 * ORBX_EDGE;
         L.ph = L.sh + 2 * ORBX_EDGE;
         L.pitch = (L.pw + 63) & ~63;
+        L.org = upstream ? ORBX_EDGE : 0;
+        L.vw = upstream ? L.sw : L.pw;
+        L.vh = upstream ? L.sh : L.ph;
         L.off = off;
         off += (int64_t)L.pitch * L.ph;
         off = (off + 255) & ~(int64_t)255;
@@ -105,7 +117,13 @@ orbx_status orbx_build_geometry(const orbx_params &p, const OrbxTables &t, int w
         L.nfeat = t.nfeat[l];
         // cell grid
         const int minB = ORBX_EDGE - 3;
-        const int maxBX = L.pw - ORBX_EDGE + 3, maxBY = L.ph - ORBX_EDGE + 3;
+        const int maxBX = L.vw - ORBX_EDGE + 3, maxBY = L.vh - ORBX_EDGE + 3;
+        if (maxBX - minB <= 0 || maxBY - minB <= 0) {   // only a view can be this small (sw < 33 or sh < 33): the reference is undefined
+            snprintf(why_buf, sizeof(why_buf), "pyramid level %d (%d x %d) has an empty FAST region: %d x %d", l, L.sw, L.sh,
+                     maxBX - minB, maxBY - minB);
+            *why = why_buf;
+            return ORBX_UNSUPPORTED;
+        }
         const float fw = (float)(maxBX - minB), fh = (float)(maxBY - minB);
         L.ncols = (int)(fw / 30.f);
         L.nrows = (int)(fh / 30.f);
@@ -129,7 +147,7 @@ orbx_status orbx_build_geometry(const orbx_params &p, const OrbxTables &t, int w
                     if (iniX >= maxBX - 6) continue;
                     if (maxX > maxBX) maxX = (float)maxBX;
                     OrbxCell c;
-                    c.x0 = (int16_t)iniX; c.y0 = (int16_t)iniY;
+                    c.x0 = (int16_t)((int)iniX + L.org); c.y0 = (int16_t)((int)iniY + L.org);   // slab coordinates
                     c.cw = (int16_t)((int)maxX - (int)iniX); c.ch = (int16_t)((int)maxY - (int)iniY);
                     c.offx = (int16_t)(j * L.wcell); c.offy = (int16_t)(i * L.hcell);
                     c.level = (int16_t)l;
@@ -164,15 +182,15 @@ orbx_status orbx_build_geometry(const orbx_params &p, const OrbxTables &t, int w
         cand_off += L.cand_cap;
         g.node_cap = std::max(g.node_cap, (L.kp_cap + 8 + 3) & ~3);   // multiple of 4: LDS arrays stay 16-byte aligned
         g.max_cand_cap = std::max(g.max_cand_cap, L.cand_cap);
-        // resize taps (level > 0: source is the PADDED previous level)
+        // resize taps (level > 0: source is the PADDED previous level; upstream: its un-padded view)
         L.tapx_begin = L.tapy_begin = 0;
         L.narrow_taps = false;
         if (l > 0) {
             const OrbxLevelGeom &S = g.lv[l - 1];
             L.tapx_begin = (int)g.taps.size();
-            build_axis_taps(g.taps, L.pw, L.sw, S.pw, true);
+            build_axis_taps(g.taps, L.pw, L.sw, S.vw, true, S.org);
             L.tapy_begin = (int)g.taps.size();
-            build_axis_taps(g.taps, L.ph, L.sh, S.ph, false);
+            build_axis_taps(g.taps, L.ph, L.sh, S.vh, false, S.org);
             L.narrow_taps = true;
             for (int X = 0; X < L.pw; X += 4) {
                 int lo = 0x7fff, hi = 0;
@@ -187,7 +205,7 @@ orbx_status orbx_build_geometry(const orbx_params &p, const OrbxTables &t, int w
         }
     }
     // level-1 taps in raw coordinates (in-place mode): padded source index s of level 0 holds raw pixel reflect101(s - 19)
-    if (p.nlevels >= 2 && width >= ORBX_IP_MIN_W && height >= ORBX_IP_MIN_H && width <= 0x7fff && height <= 0x7fff) {
+    if (!upstream && p.nlevels >= 2 && width >= ORBX_IP_MIN_W && height >= ORBX_IP_MIN_H && width <= 0x7fff && height <= 0x7fff) {
         const OrbxLevelGeom &L = g.lv[1];
         const size_t nx = (size_t)L.pw, ny = (size_t)L.ph;
         g.l1_tap_begin = (int)g.taps.size();

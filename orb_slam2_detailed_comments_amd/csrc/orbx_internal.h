@@ -12,7 +12,7 @@
 
 // One FAST cell (reference src/ORBextractor.cc:1465-1503): sub-image [y0,y0+ch) x [x0,x0+cw) of the padded level.
 struct OrbxCell {
-    int16_t x0, y0, cw, ch;  // sub-mat origin and size (padded-level coordinates)
+    int16_t x0, y0, cw, ch;  // sub-mat origin and size (padded-level = slab coordinates; upstream: view coordinate + 19)
     int16_t offx, offy;      // j*wCell, i*hCell  (added to the sub-mat-local keypoint, :1540-1541)
     int16_t level;
     int16_t idx_in_level;    // row-major ordinal of the cell inside its level (emission order)
@@ -47,6 +47,8 @@ struct OrbxTap {
 struct OrbxLevelGeom {
     int sw, sh;          // un-padded size
     int pw, ph, pitch;   // padded size and row pitch in bytes
+    int org;             // where mvImagePyramid[level] starts inside the padded level: 0 (fork) or ORBX_EDGE (upstream), both axes
+    int vw, vh;          // size of mvImagePyramid[level]: pw x ph (fork) or sw x sh (upstream)
     int64_t off;         // byte offset of this level inside one frame's pyramid slab
     int ncols, nrows, wcell, hcell;
     int cell_begin, cell_count;  // range in the per-frame cell table

@@ -1609,7 +1609,9 @@ __global__ __launch_bounds__(256) void k_blur(DGeom g, const uint8_t *__restrict
     const int cg = tid & 31, rg = tid >> 5;
     const int X = X0 + 4 * cg;
     if (X >= L.pw) return;
-    const int wv = L.pw & ~3;
+    // the SSE2 column path covers the columns x < (w & ~3) of the image GaussianBlur is given: the padded level (fork) or the
+    // clone of the un-padded view (upstream: columns org .. org + sw - 1 here; its reflect-101 border is the level's own)
+    const int wv = L.org + ((L.pw - 2 * L.org) & ~3);
     const float k0 = 55.f / 65536.f, k1 = 49.f / 65536.f, k2 = 34.f / 65536.f, k3 = 18.f / 65536.f;
     int hh[10][4];
 #pragma unroll
@@ -1820,10 +1822,11 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
     const uint8_t *img = ip0 ? raw.img + (long long)f * raw.frame_stride : pyr + (long long)f * g.pyr_bytes + L.off;
     const int spitch = ip0 ? raw.stride : L.pitch;
     // patch origin in the coordinates of the image the patch is staged from
-    const int px0 = x - DS_R - (ip0 ? ORBX_EDGE : 0), py0 = y - DS_R - (ip0 ? ORBX_EDGE : 0);
+    // (x, y are coordinates of mvImagePyramid[level]; that image starts at (L.org, L.org) of the slab's padded level)
+    const int px0 = x - DS_R + (ip0 ? -ORBX_EDGE : L.org), py0 = y - DS_R + (ip0 ? -ORBX_EDGE : L.org);
     const int xa = px0 & ~3;
     const bool interior = ip0 ? orbx_ip_desc_interior(px0, py0, raw.W, raw.H)
-                              : px0 >= 0 && py0 >= 0 && xa + 48 <= L.pitch && x + DS_R < L.pw && y + DS_R < L.ph;
+                              : px0 >= 0 && py0 >= 0 && xa + 48 <= L.pitch && px0 + 2 * DS_R < L.pw && py0 + 2 * DS_R < L.ph;
     {
         // ---- stage the 43x43 patch (rows y-21.., columns x-21..): 12 ALIGNED dwords cover the 44 bytes of a patch
         // row; dword d of the LDS row = funnel shift of aligned dwords d, d+1.  A lane loads 3 aligned dwords (one
@@ -2027,7 +2030,7 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
         // columns take its integer tail (I + 2^15) >> 16.  Every float product and every partial sum below 2^24 units of
         // 2^-16 is exact, and a total >= 2^24 saturates to 255 either way, so the float path IS round-half-even(I / 65536)
         // with I = 55 r0 + 49 r1 + 34 r2 + 18 r3: one integer formula serves both, the tail only changes the tie rule.
-        const int wvec = L.pw & ~3;
+        const int wvec = (L.pw - 2 * L.org) & ~3;   // of the image GaussianBlur is given (fork: the padded level; upstream: the view)
         const int pw4[4] = {pat.x, pat.y, pat.z, pat.w};
         unsigned long long words[4];
         if (x + (DS_R - 3) < wvec) {

@@ -14,13 +14,15 @@ class ORBextractor:
     HARRIS_SCORE, FAST_SCORE = 0, 1  # include/ORBextractor.h:99-103
 
     def __init__(self, nfeatures=1000, scaleFactor=1.2, nlevels=8, iniThFAST=20, minThFAST=7, *,
-                 fp_mode=_capi.FP_GCC_FMA, device=-1, max_batch=1, max_cand_per_cell=0):
+                 fp_mode=_capi.FP_GCC_FMA, device=-1, max_batch=1, max_cand_per_cell=0,
+                 pyramid_mode=_capi.PYRAMID_FORK_PADDED):
         self._L = lib()
         p = Params()
         self._L.orbx_default_params(C.byref(p))
         p.nfeatures, p.scale_factor, p.nlevels = int(nfeatures), float(scaleFactor), int(nlevels)
         p.ini_th_fast, p.min_th_fast = int(iniThFAST), int(minThFAST)
         p.fp_mode, p.device, p.max_batch, p.max_cand_per_cell = fp_mode, device, max_batch, max_cand_per_cell
+        p.pyramid_mode = int(pyramid_mode)   # _capi.PYRAMID_UPSTREAM: un-padded levels, keypoints in image coordinates
         self.params = p
         self._h = C.c_void_p()
         check(self._L.orbx_create(C.byref(p), C.byref(self._h)))
@@ -172,6 +174,7 @@ class ORBextractor:
 
     # ---- mvImagePyramid (include/ORBextractor.h:185)
     def pyramid_level(self, level, frame=0, blur=False):
+        """mvImagePyramid[level] of `frame`: the padded level of a fork handle, the un-padded view of an upstream handle"""
         w, h, p = C.c_int(), C.c_int(), C.c_int()
         check(self._L.orbx_pyramid_level_info(self._h, level, C.byref(w), C.byref(h), C.byref(p)))
         out = np.zeros((h.value, w.value), np.uint8)
