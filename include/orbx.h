@@ -576,6 +576,8 @@ orbx_status orbx_debug_candidates(orbx_handle *h, int frame, int level, orbx_key
 orbx_status orbx_debug_level_keypoints(orbx_handle *h, int frame, int level, orbx_keypoint *out, int cap, int *n);
 /* blurred level: GaussianBlur of mvImagePyramid[level] (fork: the padded level; upstream: the un-padded view) */
 orbx_status orbx_debug_blur_copy(orbx_handle *h, int frame, int level, uint8_t *dst, int dst_stride);
+/* FAST groups (waves' work items of k_fast_rows) per frame of the configured geometry: those of level 0, and all of them */
+orbx_status orbx_debug_fast_groups(orbx_handle *h, int *level0, int *total);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@ struct orbx_handle {
     // side stream of the batched extraction (high priority): the small pyramid levels are a chain of short, latency-bound
     // launches; they run here, next to the issue-bound FAST kernel of the large levels on the main stream
     hipStream_t side_stream = nullptr;
+    hipStream_t plan_stream = nullptr;   // side stream of the FAST-first plan (low priority: its resize chains fill what FAST leaves)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_stereo = nullptr;   // orders the batched stereo match with the OTHER eye's stream (two extractors, two streams)
     int fork_level = 0;       // first level whose resize + FAST run on the side stream (0 = no fork)
@@ -57,6 +58,15 @@ struct orbx_handle {
                               // even split is 0.3 % faster on the default line but 1.8 % slower on the merged EuRoC stereo batch
     bool fast_room = false;   // k_fast_rows capped at ORBX_FAST_PIPE_WAVES waves per CU while the pipeline runs (measured slower)
     hipEvent_t ev_pipe[ORBX_PIPE_MAX] = {};   // pyramid of sub-batch k done (side stream) -> its FAST launch (main stream)
+    // FAST-first plan of run_chunk (ORBX_PLAN=fastfirst|pipeline|serial, ORBX_PLAN_SUB=S, ORBX_PLAN_HEAD=0|1, ORBX_PLAN_MIN_FRAMES;
+    // ORBX_PLAN_PRIORITY=low|normal|high is read when the handle is created);
+    // an explicit ORBX_PIPELINE overrides ORBX_PLAN and selects the serial sequence or the sub-batch pipeline as they were
+    bool fast_first = true;   // the default plan of a batch of >= plan_min_frames frames (profiles/fast_first_plan.md)
+    int plan_sub = 3;         // resize-chain sub-batches of the plan (the sweep of profiles/fast_first_plan.md)
+    bool plan_head = false;   // the first of them is half the size of the others
+    int plan_min_frames = ORBX_PIPE_MIN_FRAMES;   // smaller batches keep the serial sequence
+    int l0_groups = 0;        // FAST groups of level 0 (the groups are ordered by level)
+    int max_ch_l0 = 0, max_ch_rest = 0;   // tallest cell of the level-0 groups / of the others
     // geometry-dependent device state
     uint8_t *d_pyr = nullptr, *d_blur = nullptr;
     OrbxCell *d_cells = nullptr;
@@ -215,9 +225,10 @@ static orbx_status configure(orbx_handle *h, int width, int height) {
     if (h->configured && h->geom.width == width && h->geom.height == height) return ORBX_OK;
     if (h->host_only) return fail(ORBX_NO_DEVICE, "host-only handle (device = -2) cannot extract");
     HIPCHK(hipSetDevice(h->dev));
-    if (h->configured) {   // nothing queued on either of the handle's streams may still read the buffers that are about to go
+    if (h->configured) {   // nothing queued on any of the handle's streams may still read the buffers that are about to go
         HIPCHK(hipStreamSynchronize(h->stream));
         if (h->side_stream) HIPCHK(hipStreamSynchronize(h->side_stream));
+        if (h->plan_stream) HIPCHK(hipStreamSynchronize(h->plan_stream));
         free_geometry_buffers(h);
     }
     const char *why = "";
@@ -312,13 +323,35 @@ static orbx_status configure(orbx_handle *h, int width, int height) {
     }
     // The sub-batch pipeline (run_chunk) and the fork exclude each other, both use the side stream: an explicit
     // ORBX_FORK_LEVEL > 0 (an A/B knob) selects the fork and the serial sub-batch sequence.
+    h->pipeline = 2;
     if (const char *e = getenv("ORBX_PIPELINE")) h->pipeline = std::min(std::max(atoi(e), 0), ORBX_PIPE_MAX);
     h->l0_inplace = true;
     if (const char *e = getenv("ORBX_LEVEL0_INPLACE")) h->l0_inplace = atoi(e) != 0;
     h->l0_eager_sticky = false;   // a new geometry starts over
     if (const char *e = getenv("ORBX_PIPELINE_HEAD")) h->pipe_head = atoi(e) != 0;
     if (const char *e = getenv("ORBX_FAST_ROOM")) h->fast_room = atoi(e) != 0;
-    if (h->fork_level > 0) h->pipeline = 0;
+    h->fast_first = true;
+    if (getenv("ORBX_PIPELINE")) {
+        h->fast_first = false;
+    } else if (const char *e = getenv("ORBX_PLAN")) {   // "pipeline": the sub-batch pipeline with its own defaults
+        h->fast_first = strcmp(e, "fastfirst") == 0;
+        if (strcmp(e, "serial") == 0) h->pipeline = 0;
+    }
+    if (const char *e = getenv("ORBX_PLAN_SUB")) h->plan_sub = std::min(std::max(atoi(e), 1), ORBX_PIPE_MAX);
+    if (const char *e = getenv("ORBX_PLAN_HEAD")) h->plan_head = atoi(e) != 0;
+    h->plan_min_frames = ORBX_PIPE_MIN_FRAMES;
+    if (const char *e = getenv("ORBX_PLAN_MIN_FRAMES")) h->plan_min_frames = std::max(atoi(e), 1);
+    if (h->fork_level > 0) { h->pipeline = 0; h->fast_first = false; }
+    h->l0_groups = 0;
+    h->max_ch_l0 = h->max_ch_rest = 7;
+    for (const OrbxFastGroup &fg : hg.fast_groups) {
+        const bool l0 = hg.cells[(size_t)fg.cell0].level == 0;
+        if (l0) ++h->l0_groups;
+        for (int c = 0; c < fg.ncell; ++c) {
+            int &m = l0 ? h->max_ch_l0 : h->max_ch_rest;
+            m = std::max<int>(m, hg.cells[(size_t)fg.cell0 + c].ch);
+        }
+    }
     auto setup = [&]() -> hipError_t {
         hipError_t e;
 #define ORBX_TRY(expr) do { e = (expr); if (e != hipSuccess) return e; } while (0)
@@ -393,6 +426,12 @@ extern "C" orbx_status orbx_create(const orbx_params *params, orbx_handle **out)
         int lo = 0, hi = 0;
         e = hipDeviceGetStreamPriorityRange(&lo, &hi);   // hi = numerically lowest = highest priority
         if (e == hipSuccess) e = hipStreamCreateWithPriority(&h->side_stream, hipStreamNonBlocking, hi);
+        // the FAST-first plan's resize chains: LOW priority by default (lo = numerically highest), ORBX_PLAN_PRIORITY=low|normal|high
+        // for A/B runs.  FAST is bound by the waves a CU holds; at high priority the resize waves take their slots first and
+        // FAST stretches by nearly the time the chains take, at low priority they fill what FAST leaves (profiles/fast_first_plan.md)
+        int prio = lo;
+        if (const char *pe = getenv("ORBX_PLAN_PRIORITY")) prio = strcmp(pe, "high") == 0 ? hi : strcmp(pe, "normal") == 0 ? 0 : lo;
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&h->plan_stream, hipStreamNonBlocking, prio);
         // device-scope release: the two streams exchange device memory only (a system-scope fence per record costs ~10 us)
         unsigned evflags = hipEventDisableTiming | hipEventReleaseToDevice;
         if (const char *ef = getenv("ORBX_EVENT_FLAGS")) evflags = (unsigned)strtoul(ef, nullptr, 0);
@@ -427,6 +466,7 @@ extern "C" void orbx_destroy(orbx_handle *h) {
         }
         if (h->s_in) hipStreamDestroy(h->s_in);
         if (h->side_stream) { hipStreamSynchronize(h->side_stream); hipStreamDestroy(h->side_stream); }
+        if (h->plan_stream) { hipStreamSynchronize(h->plan_stream); hipStreamDestroy(h->plan_stream); }
         if (h->ev_fork) hipEventDestroy(h->ev_fork);
         if (h->ev_join) hipEventDestroy(h->ev_join);
         if (h->ev_stereo) hipEventDestroy(h->ev_stereo);
@@ -530,7 +570,8 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
     // pyramid, status, candidate lists and counters, quadtree output, keypoints, descriptors) from a base pointer, so a
     // sub-batch is the same launch on offset base pointers.
     const int ngroups = (int)h->geom.fast_groups.size();
-    auto pyramid = [&](hipStream_t st, int f0, int b, int l_end) {
+    // chain_only (the FAST-first plan): levels >= 1 alone -- no eager level-0 launch, and no status / cursor reset from level 1
+    auto pyramid = [&](hipStream_t st, int f0, int b, int l_end, bool chain_only = false) {
         const uint8_t *im = d_imgs + (int64_t)f0 * frame_stride;
         uint8_t *pyr = h->d_pyr + (size_t)f0 * h->geom.pyr_bytes;
         int32_t *stp = d_status + f0;
@@ -538,14 +579,16 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
         if (inplace) {   // no level-0 launch: level 1 reads the image and takes over the status / cursor reset
             { ProfScope ps(h, ORBX_K_PYR_RESIZE, st);
               const OrbxRaw0 raw = {im, (long long)frame_stride, W, H, stride};
-              orbx_launch_pyr_resize_l1(st, g, b, h->d_taps + h->geom.l1_tap_begin, raw, pyr, h->geom.l1_tail_bx, stp, cc); }
+              orbx_launch_pyr_resize_l1(st, g, b, h->d_taps + h->geom.l1_tap_begin, raw, pyr, h->geom.l1_tail_bx,
+                                        chain_only ? nullptr : stp, chain_only ? nullptr : cc); }
             for (int l = 2; l < l_end; ++l) {
                 ProfScope ps(h, ORBX_K_PYR_RESIZE, st);
                 orbx_launch_pyr_resize(st, g, b, l, h->d_taps, pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy);
             }
             return;
         }
-        { ProfScope ps(h, ORBX_K_PYR_L0, st);
+        if (!chain_only) {
+          ProfScope ps(h, ORBX_K_PYR_L0, st);
           if (h->d_rect) {   // cv::remap of the EuRoC rectification fused into level 0
               orbx_launch_pyr_l0_remap(st, g, b, im, W, H, stride, frame_stride, pyr, h->d_rect, stp, cc);
           } else if (h->input_format == ORBX_FMT_GRAY8) {
@@ -560,12 +603,15 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
             orbx_launch_pyr_resize(st, g, b, l, h->d_taps, pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy);
         }
     };
-    auto fast = [&](hipStream_t st, int f0, int b, int g0, int ng, int lds_floor) {
+    // part: 0 = any groups (mixed kernel when in place), 1 = level-0 groups only, 2 = groups of levels >= 1 only (the two launches
+    // of the FAST-first plan: each sized from its own tallest cell, the second never in place)
+    auto fast = [&](hipStream_t st, int f0, int b, int g0, int ng, int lds_floor, int part = 0) {
         ProfScope ps(h, ORBX_K_FAST, st);
         const OrbxRaw0 raw = {d_imgs + (int64_t)f0 * frame_stride, (long long)frame_stride, W, H, stride};
         orbx_launch_fast_rows(st, g, b, h->d_cells, h->d_groups + g0, ng, h->d_pyr + (size_t)f0 * h->geom.pyr_bytes,
-                              h->d_dense + (size_t)f0 * g.cand_total, h->d_cand_count + (size_t)f0 * NL, d_status + f0, h->max_ch,
-                              h->fast_lcap, h->fast_stop, lds_floor, inplace ? &raw : nullptr);
+                              h->d_dense + (size_t)f0 * g.cand_total, h->d_cand_count + (size_t)f0 * NL, d_status + f0,
+                              part == 1 ? h->max_ch_l0 : part == 2 ? h->max_ch_rest : h->max_ch,
+                              h->fast_lcap, h->fast_stop, lds_floor, inplace && part != 2 ? &raw : nullptr, part == 1);
     };
     auto finish = [&](int f0, int b) {
         { ProfScope ps(h, ORBX_K_QUADTREE);
@@ -593,16 +639,47 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
     // (more than one bit of the profiling mask) runs the serial sequence below, so that each kernel's time is its own; a
     // single-kernel profile keeps the pipeline and times each of the S launches of that kernel from its stream, which includes
     // the time it shares the CUs with the other stream's kernels.
-    const int S = h->pipeline > 1 && B >= ORBX_PIPE_MIN_FRAMES && __builtin_popcount(h->prof_mask) <= 1 ? h->pipeline : 1;
-    if (S > 1) {
+    //
+    // FAST-first plan (the default of large batches): the level-0 FAST groups need no pyramid level this
+    // call builds on the side stream -- in place they read the caller's image, otherwise the padded level 0 the main stream has just
+    // written -- so FAST starts at once and all of FAST is the window the resize chains of the sub-batches run under; the FAST
+    // groups of levels >= 1 follow per sub-batch as its chain completes.  Quadtree and descriptors run once over the batch, after
+    // the last chain: the pyramid shares the CUs with FAST only (the kernel it slows least, profiles/r04_pipeline.md).  A late
+    // chain makes the main stream wait and then runs alone, so the plan is never much worse than the serial sequence.  Level 1's
+    // in-place launch would reset status / cursors beside the level-0 FAST groups that update them: one k_clear does it up front.
+    if (h->fast_first && B >= h->plan_min_frames && __builtin_popcount(h->prof_mask) <= 1) {
         int off[ORBX_PIPE_MAX + 1];
-        const int units = h->pipe_head ? 2 * S - 1 : S;
-        off[0] = 0;
-        for (int k = 0; k + 1 < S; ++k) {   // multiples of 8 frames (k_describe deals frames over the 8 XCDs); the last takes the rest
-            const int share = (int)((long long)B * (h->pipe_head && k > 0 ? 2 : 1) / units);
-            off[k + 1] = off[k] + std::max(8, share & ~7);
+        const int n = orbx_split_batch(B, h->plan_sub, h->plan_head, off);
+        const int ng0 = h->l0_groups;
+        hipStream_t s2 = h->plan_stream;
+        if (inplace) {
+            ProfScope ps(h, ORBX_K_MISC);
+            orbx_launch_clear(s, d_status, B, h->d_cand_count, B * NL, nullptr, 0);
+        } else {
+            pyramid(s, 0, B, 1);   // the eager level 0 of the whole batch (resets status and cursors itself)
         }
-        off[S] = B;
+        if (hipEventRecord(h->ev_fork, s) != hipSuccess || hipStreamWaitEvent(s2, h->ev_fork, 0) != hipSuccess)
+            { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, "plan fork event"); }
+        for (int k = 0; k < n; ++k) {
+            pyramid(s2, off[k], off[k + 1] - off[k], NL, true);
+            if (hipEventRecord(h->ev_pipe[k], s2) != hipSuccess)
+                { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, "plan event"); }
+        }
+        fast(s, 0, B, 0, ng0, 0, 1);
+        for (int k = 0; k < n; ++k) {
+            if (hipStreamWaitEvent(s, h->ev_pipe[k], 0) != hipSuccess)
+                { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, "plan event wait"); }
+            fast(s, off[k], off[k + 1] - off[k], ng0, ngroups - ng0, 0, 2);
+        }
+        finish(0, B);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, std::string("kernel launch: ") + hipGetErrorString(e)); }
+        h->last_batch = B;
+        return ORBX_OK;
+    }
+    if (h->pipeline > 1 && B >= ORBX_PIPE_MIN_FRAMES && __builtin_popcount(h->prof_mask) <= 1) {
+        int off[ORBX_PIPE_MAX + 1];
+        const int S = orbx_split_batch(B, h->pipeline, h->pipe_head, off);   // = h->pipeline: B >= ORBX_PIPE_MIN_FRAMES
         hipStream_t s2 = h->side_stream;
         // the side stream starts behind everything queued on the main stream so far (the frames' upload, the previous batch's
         // readers of the pyramid and of the outputs); every sub-batch's FAST launch waits for its pyramid, and the last of those
@@ -646,6 +723,11 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
         fast(s, 0, B, 0, h->fork_group, 0);
         if (hipEventRecord(h->ev_join, s2) != hipSuccess || hipStreamWaitEvent(s, h->ev_join, 0) != hipSuccess)
             { hipStreamSynchronize(s2); return fail(ORBX_HIP_ERROR, "join event"); }   // the side stream's work reads the handle's buffers: never leave it unjoined
+    } else if (h->fast_first && B >= h->plan_min_frames) {
+        // the calibration pass of a batch the FAST-first plan would take (more than one bit of the profiling mask): the plan's
+        // two FAST kernels, one after the other and alone on the chip, so that the k_fast_rows slot is theirs
+        fast(s, 0, B, 0, h->l0_groups, 0, 1);
+        fast(s, 0, B, h->l0_groups, ngroups - h->l0_groups, 0, 2);
     } else {
         fast(s, 0, B, 0, ngroups, 0);
     }
@@ -1210,6 +1292,13 @@ extern "C" orbx_status orbx_debug_level_keypoints(orbx_handle *h, int frame, int
         out[i] = k;
     }
     if (cnt > cap) return fail(ORBX_CAPACITY, "output capacity");
+    return ORBX_OK;
+}
+
+extern "C" orbx_status orbx_debug_fast_groups(orbx_handle *h, int *level0, int *total) {
+    if (!h || !h->configured) return fail(ORBX_BAD_ARGUMENT, "no batch has been extracted on this handle");
+    if (level0) *level0 = h->l0_groups;
+    if (total) *total = (int)h->geom.fast_groups.size();
     return ORBX_OK;
 }
 

@@ -37,6 +37,25 @@ struct OrbxFastGroup {
 #define ORBX_FAST_PIPE_WAVES 16
 #define ORBX_PIPE_MAX 8            // most sub-batches per batch
 #define ORBX_PIPE_MIN_FRAMES 256   // smaller batches keep the serial sequence
+// Sub-batch offsets of a batch of B frames, shared by the sub-batch pipeline and the FAST-first plan of run_chunk: up to S
+// sub-batches [off[k], off[k + 1]), off[0] = 0, off[n] = B; returns n (off holds ORBX_PIPE_MAX + 1 entries).  Every offset but
+// the last is a multiple of 8 frames (k_describe deals frames over the 8 XCDs) and the last sub-batch takes the rest; `head`
+// makes the first sub-batch half the size of the others.  No sub-batch is smaller than 8 frames: a batch too small for S of
+// them gets fewer (one, below 16 frames).
+static inline int orbx_split_batch(int B, int S, bool head, int *off) {
+    S = S < 1 ? 1 : S > ORBX_PIPE_MAX ? ORBX_PIPE_MAX : S;
+    const int units = head ? 2 * S - 1 : S;
+    int n = 0;
+    off[0] = 0;
+    while (n + 1 < S) {
+        const int share = (int)((long long)B * (head && n > 0 ? 2 : 1) / units) & ~7;
+        const int next = off[n] + (share > 8 ? share : 8);
+        if (B - next < 8) break;
+        off[++n] = next;
+    }
+    off[++n] = B;
+    return n;
+}
 
 // resize tap for one padded destination coordinate (border folded in by reflect-101)
 struct OrbxTap {

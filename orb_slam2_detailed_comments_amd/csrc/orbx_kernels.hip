@@ -513,7 +513,7 @@ __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows_l1(DGeom g, con
     const int f = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
     const bool first = blockIdx.x == 0 && blockIdx.y == 0;
 #endif
-    if (first && threadIdx.y == 0) {   // one block per frame, as k_pyr_l0 does in the eager mode
+    if (first && threadIdx.y == 0 && status) {   // one block per frame, as k_pyr_l0 does in the eager mode; null: the caller has reset them
         if (lane == 0) status[f] = 0;
         if (lane < g.nlevels) cand_cursor[f * g.nlevels + lane] = 0;
     }
@@ -897,7 +897,10 @@ __device__ __forceinline__ void fr_ip_store(uint32_t *d, const orbx_uint3_u &v, 
 // instruction of the walk / ring test / NMS, is the same as in the slab form.
 // (Two kernels, k_fast_rows and k_fast_rows_ip, share this body, so that the slab form keeps its name and its staging code; fr_nms's
 // seam maxima changed for both: two kernels with the fused form would double the quarter-rate v_max3_u16 in the code object.)
-template <bool INPLACE>
+// MODE: 0 = slab form (k_fast_rows), 1 = mixed (k_fast_rows_ip: the level-0 groups in place, the others from the slab), 2 = a
+// launch of level-0 groups only, all in place (k_fast_rows_l0, the FAST-first plan of run_chunk): no slab staging path and no
+// per-group level test.
+template <int MODE>
 __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__restrict__ cells,
                                           const OrbxFastGroup *__restrict__ groups,
                                           const uint8_t *__restrict__ pyr, uint2 *__restrict__ cand,
@@ -908,6 +911,7 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
 #ifndef ORBX_TIMING_KNOBS
     dbg_stop = 0;
 #endif
+    constexpr bool INPLACE = MODE != 0, L0ONLY = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) uint8_t fast_smem[];
     uint32_t *s_tile = (uint32_t *)fast_smem;
     // tile | score map (16-byte aligned: cleared with 16-byte stores) | work list (lcap entries + one private dummy dword per
@@ -934,7 +938,7 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
     const uint8_t *fbase = pyr + (long long)f * g.pyr_bytes;
     const uint8_t *rbase = INPLACE ? raw.img + (long long)f * raw.frame_stride : nullptr;
 #define FR_PREFETCH()                                                                                                     \
-    if (INPLACE && c0_n.level == 0) {                                                                                     \
+    if (L0ONLY || (INPLACE && c0_n.level == 0)) {                                                                         \
         int dsh_, shr_;                                                                                                   \
         const int xb_ = orbx_ip_fast_xb(c0_n.x0, &dsh_);                                                                  \
         const int col_ = orbx_ip_fast_piece_col(xb_, dq, raw.W, &shr_);                                                   \
@@ -971,12 +975,13 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
   for (int gi = 0; gi < ng; ++gi) {
     const OrbxFastGroup grp = grp_n;
     const OrbxCell c0 = c0_n, c1 = c1_n;
-    const DLevel &L = g.lv[c0.level];
+    const int level = L0ONLY ? 0 : (int)c0.level;
+    const DLevel &L = g.lv[level];
     const int tw = c1.x0 + c1.cw - c0.x0, th_rows = c0.ch;
     const int niw = tw - 6;                                   // interior columns of the group (<= 64)
     const int iw0 = grp.ncell == 2 ? c0.cw - 6 : 64;
     // ---- stage the tile: prefetched registers -> LDS
-    const bool ip0 = INPLACE && c0.level == 0;   // wave-uniform
+    const bool ip0 = L0ONLY || (INPLACE && c0.level == 0);   // wave-uniform
     if (ip0) {
         int dsh, shr;
         const int xb = orbx_ip_fast_xb(c0.x0, &dsh);
@@ -1056,7 +1061,7 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
     gc.ord0 = c0.idx_in_level; gc.ord1 = c1.idx_in_level;
     gc.cap0 = c0.slot_cap; gc.cap1 = c1.slot_cap;
     gc.out = cand + (long long)f * g.cand_total + L.cand_begin;
-    gc.cursor = cand_cursor + f * g.nlevels + c0.level;
+    gc.cursor = cand_cursor + f * g.nlevels + level;
     gc.out_cap = L.cand_cap;
     orbx_wave_sync();
     if (dbg_stop == 1) continue;
@@ -1227,14 +1232,20 @@ __global__ __launch_bounds__(64, FR_WPS) void k_fast_rows(DGeom g, const OrbxCel
                                                           int *__restrict__ cand_cursor, int *__restrict__ status, int rows,
                                                           int lcap, int ngroups, int gpw, int dbg_stop, int ccap) {
     const OrbxRaw0 none = {nullptr, 0, 0, 0, 0};
-    fr_kernel<false>(g, cells, groups, pyr, cand, cand_cursor, status, rows, lcap, ngroups, gpw, dbg_stop, ccap, none);
+    fr_kernel<0>(g, cells, groups, pyr, cand, cand_cursor, status, rows, lcap, ngroups, gpw, dbg_stop, ccap, none);
 }
 __global__ __launch_bounds__(64, FR_WPS) void k_fast_rows_ip(DGeom g, const OrbxCell *__restrict__ cells,
                                                              const OrbxFastGroup *__restrict__ groups,
                                                              const uint8_t *__restrict__ pyr, uint2 *__restrict__ cand,
                                                              int *__restrict__ cand_cursor, int *__restrict__ status, int rows,
                                                              int lcap, int ngroups, int gpw, int dbg_stop, int ccap, OrbxRaw0 raw) {
-    fr_kernel<true>(g, cells, groups, pyr, cand, cand_cursor, status, rows, lcap, ngroups, gpw, dbg_stop, ccap, raw);
+    fr_kernel<1>(g, cells, groups, pyr, cand, cand_cursor, status, rows, lcap, ngroups, gpw, dbg_stop, ccap, raw);
+}
+__global__ __launch_bounds__(64, FR_WPS) void k_fast_rows_l0(DGeom g, const OrbxCell *__restrict__ cells,
+                                                             const OrbxFastGroup *__restrict__ groups, uint2 *__restrict__ cand,
+                                                             int *__restrict__ cand_cursor, int *__restrict__ status, int rows,
+                                                             int lcap, int ngroups, int gpw, int dbg_stop, int ccap, OrbxRaw0 raw) {
+    fr_kernel<2>(g, cells, groups, nullptr, cand, cand_cursor, status, rows, lcap, ngroups, gpw, dbg_stop, ccap, raw);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3621,7 +3632,7 @@ void orbx_launch_pyr_resize_l1(hipStream_t s, const DGeom &g, int B, const OrbxT
 }
 void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell *cells, const OrbxFastGroup *groups,
                            int ngroups, const uint8_t *pyr, uint2 *cand, int *cand_cursor, int *status, int max_ch, int lcap,
-                           int dbg_stop, int lds_floor, const OrbxRaw0 *raw) {
+                           int dbg_stop, int lds_floor, const OrbxRaw0 *raw, bool l0_only) {
     if (ngroups <= 0) return;
     lcap = (max(lcap, 64) + 1) & ~1;
     // LDS per wave decides how many waves a CU holds: the corner list of a group is sized for its usual load, FR_CCAP entries (the
@@ -3638,7 +3649,10 @@ void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell 
     // groups per wave: FR_GPW when the launch has waves to spare (the second group's tile is prefetched while the first
     // is processed); one per wave for small batches, where the serial length of a wave is what the caller waits for
     const int gpw = (long long)B * ngroups >= 16384 ? FR_GPW : 1;
-    if (raw)
+    if (raw && l0_only)
+        hipLaunchKernelGGL(k_fast_rows_l0, dim3(B, (ngroups + gpw - 1) / gpw), dim3(64), smem, s, g, cells, groups, cand,
+                           cand_cursor, status, max_ch, lcap, ngroups, gpw, dbg_stop, ccap, *raw);
+    else if (raw)
         hipLaunchKernelGGL(k_fast_rows_ip, dim3(B, (ngroups + gpw - 1) / gpw), dim3(64), smem, s, g, cells, groups, pyr, cand,
                            cand_cursor, status, max_ch, lcap, ngroups, gpw, dbg_stop, ccap, *raw);
     else

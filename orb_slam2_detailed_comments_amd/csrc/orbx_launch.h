@@ -17,9 +17,11 @@ void orbx_launch_pyr_l0_remap(hipStream_t s, const DGeom &g, int B, const uint8_
 void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, const OrbxTap *taps, uint8_t *pyr, bool narrow);
 void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell *cells, const OrbxFastGroup *groups,
                            int ngroups, const uint8_t *pyr, uint2 *cand, int *cand_cursor, int *status, int max_ch, int lcap,
-                           int dbg_stop, int lds_floor = 0, const OrbxRaw0 *raw = nullptr);
+                           int dbg_stop, int lds_floor = 0, const OrbxRaw0 *raw = nullptr, bool l0_only = false);
+// (raw: the level-0 groups read the caller's image; l0_only with raw: every group of the launch is a level-0 group.  max_ch is
+// the tallest cell of the groups of THIS launch: it sizes the LDS tile and score map.)
 // in-place mode (orbx_inplace.h): level 1 from the caller's grey image `raw`; also resets status[f] and cand_cursor[f][*] as
-// k_pyr_l0 does.  taps_l1 = the level's raw-coordinate tap table (pw horizontal records, then ph vertical ones).
+// k_pyr_l0 does, unless `status` is null (the FAST-first plan resets them before its first FAST launch).  taps_l1 = the level's raw-coordinate tap table (pw horizontal records, then ph vertical ones).
 void orbx_launch_pyr_resize_l1(hipStream_t s, const DGeom &g, int B, const OrbxTap *taps_l1, const OrbxRaw0 &raw, uint8_t *pyr,
                                int tail_bx, int *status, int *cand_cursor);
 void orbx_launch_undistort(hipStream_t s, int B, int max_n, int cap, const double *K4, const double *k14, int identity,
