@@ -252,6 +252,51 @@ orbx_status orbx_search_by_projection_mappoints(orbx_handle *h, const orbx_frame
                                                 const int32_t *frame_observations, const orbx_mappoint_view *mps,
                                                 float th, float nnratio, int32_t *assigned, int *nmatches);
 
+/* Batched, device-resident forms of the two tracking matchers above: nproblems problems in one call, asynchronous on the
+ * handle's stream.  The current frames are read where the device batch left them: d_keys_un / d_desc / d_u_right / d_counts are
+ * the buffers of orbx_extract_batch_device, orbx_undistort_keypoints_device and orbx_stereo_match_batch_device or
+ * orbx_rgbd_depth_device (nframes frames, records `cap` apart; d_u_right == NULL: every feature monocular, -1), d_cell_begin /
+ * d_items the grids orbx_grid_build_device built over them with the same bounds4 and cap.  Problem k names its current frame;
+ * several problems may name the same one (TrackWithMotionModel's retry with 2 * th is a second call).  Only the small host-side
+ * state of each problem is uploaded -- all problems' arrays through one page-locked staging block, consumed before the call
+ * returns -- and only the results are written, on the device: row k of the output ([nproblems][cap]) and d_nmatches[k].  The
+ * first min(count[frame], cap) entries of row k and d_nmatches[k] are bit for bit what the single call returns for that
+ * frame's keypoints, descriptors and u_right and the same views, in both fp_modes; entries past the frame's count are not
+ * written.  The candidate search, the order-dependent selection and the rotation check all run on the device (k_track_project,
+ * k_track_cand, k_track_select); no result is waited for (the host waits only where the staging block or the device arena has
+ * to grow, or where the upload of the previous call of this kind has not left the staging block yet).  A call of ONE problem is
+ * slower than the single call (the ordered pass is one wave per problem): the calls pay off from a few problems on, DESIGN.md
+ * section 6.0t.  Everything is validated before any device work: ORBX_BAD_ARGUMENT for
+ * nproblems < 0, a null field of a non-empty view, a frame outside [0, nframes), cap <= 0, or an octave / level outside
+ * [0, nlevels) on a point that has a MapPoint / is in view; ORBX_UNSUPPORTED for cap > 65535.  nproblems == 0 launches nothing. */
+typedef struct orbx_track_frame_problem {
+    int32_t frame;                  /* CurrentFrame = this frame of the device batch */
+    float th;
+    int32_t mono;                   /* bMono */
+    float Tcw[16];                  /* CurrentFrame.mTcw, row major 4x4 */
+    orbx_last_frame_view last;      /* host arrays */
+} orbx_track_frame_problem;
+/* camera4 = fx, fy, cx, cy; bounds4 = mnMinX, mnMaxX, mnMinY, mnMaxY; mb, mbf as orbx_frame_view */
+orbx_status orbx_search_by_projection_frame_batch_device(orbx_handle *h, int nproblems, const orbx_track_frame_problem *problems,
+                                                         int nframes, const orbx_keypoint *d_keys_un, const uint8_t *d_desc,
+                                                         const float *d_u_right, const int32_t *d_counts, int cap,
+                                                         const int32_t *d_cell_begin, const uint16_t *d_items,
+                                                         const float *camera4, const float *bounds4, float mb, float mbf,
+                                                         int check_orientation, int32_t *d_matched_last, int32_t *d_nmatches);
+typedef struct orbx_track_points_problem {
+    int32_t frame;
+    float th;
+    const int32_t *frame_observations;  /* host, cap entries (those past the frame's count are ignored); NULL: all -1 */
+    orbx_mappoint_view points;          /* host arrays */
+} orbx_track_points_problem;
+orbx_status orbx_search_by_projection_mappoints_batch_device(orbx_handle *h, int nproblems,
+                                                             const orbx_track_points_problem *problems, int nframes,
+                                                             const orbx_keypoint *d_keys_un, const uint8_t *d_desc,
+                                                             const float *d_u_right, const int32_t *d_counts, int cap,
+                                                             const int32_t *d_cell_begin, const uint16_t *d_items,
+                                                             const float *bounds4, float nnratio, int32_t *d_assigned,
+                                                             int32_t *d_nmatches);
+
 /* ---- BoW-guided policies.  Host code keeps the pointer chasing (KeyFrame / MapPoint /
  * DBoW2 containers) and hands the fields the policies read as arrays; the Hamming distances come from the GPU, the
  * order-dependent selection runs on the host exactly as the reference does. */

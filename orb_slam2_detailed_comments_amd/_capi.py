@@ -47,6 +47,15 @@ class MapPointView(C.Structure):
                 ("view_cos", C.c_void_p), ("desc", C.c_void_p), ("observations", C.c_void_p)]
 
 
+class TrackFrameProblem(C.Structure):   # orbx_track_frame_problem
+    _fields_ = [("frame", C.c_int32), ("th", C.c_float), ("mono", C.c_int32), ("Tcw", C.c_float * 16),
+                ("last", LastFrameView)]
+
+
+class TrackPointsProblem(C.Structure):   # orbx_track_points_problem
+    _fields_ = [("frame", C.c_int32), ("th", C.c_float), ("frame_observations", C.c_void_p), ("points", MapPointView)]
+
+
 class FeatVecView(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("node_id", C.c_void_p), ("begin", C.c_void_p), ("index", C.c_void_p)]
 
@@ -91,7 +100,8 @@ SYMBOLS = [
     "orbx_kernel_name", "orbx_debug_candidates", "orbx_debug_level_keypoints", "orbx_debug_blur_copy", "orbx_debug_fast_groups",
     "orbx_grid_create", "orbx_grid_destroy", "orbx_grid_query", "orbx_three_maxima",
     "orbx_search_for_initialization", "orbx_stereo_match", "orbx_search_by_projection_frame",
-    "orbx_search_by_projection_mappoints", "orbx_set_input_format", "orbx_search_by_bow_keyframe_frame",
+    "orbx_search_by_projection_mappoints", "orbx_search_by_projection_frame_batch_device",
+    "orbx_search_by_projection_mappoints_batch_device", "orbx_set_input_format", "orbx_search_by_bow_keyframe_frame",
     "orbx_search_by_bow_keyframes", "orbx_search_by_bow_keyframe_frame_batch", "orbx_search_by_bow_keyframes_batch", "orbx_search_for_triangulation", "orbx_triangulation_batch_create", "orbx_triangulation_batch_select", "orbx_triangulation_batch_destroy", "orbx_fuse", "orbx_fuse_sim3", "orbx_fuse_batch", "orbx_fuse_sim3_batch",
     "orbx_search_by_projection_sim3", "orbx_search_by_sim3", "orbx_search_by_projection_keyframe",
     "orbx_stereo_match_batch_device", "orbx_host_alloc", "orbx_host_free", "orbx_set_rectification", "orbx_undistort_keypoints_device",
@@ -166,6 +176,11 @@ def lib():
     L.orbx_search_by_projection_mappoints.restype = i32
     L.orbx_search_by_projection_mappoints.argtypes = [vp, C.POINTER(FrameView), vp, C.POINTER(MapPointView), f32, f32, vp,
                                                       C.POINTER(i32)]
+    L.orbx_search_by_projection_frame_batch_device.restype = i32
+    L.orbx_search_by_projection_frame_batch_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, f32, f32,
+                                                               i32, vp, vp]
+    L.orbx_search_by_projection_mappoints_batch_device.restype = i32
+    L.orbx_search_by_projection_mappoints_batch_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, f32, vp, vp]
     L.orbx_set_input_format.restype = i32; L.orbx_set_input_format.argtypes = [vp, i32]
     L.orbx_search_by_bow_keyframe_frame.restype = i32
     L.orbx_search_by_bow_keyframe_frame.argtypes = [vp, C.POINTER(KeyFrameView), vp, vp, i32, C.POINTER(FeatVecView), f32,

@@ -16,6 +16,7 @@
 #include "orbx_internal.h"
 #include "orbx_launch.h"
 #include "orbx_gate.h"
+#include "orbx_track.h"
 
 static thread_local std::string g_last_error;
 // orbx_extract_rgbd_batch with page-locked, device-mapped depth: read it in place (true) or upload it (false) by default;
@@ -98,6 +99,10 @@ struct orbx_handle {
     uint32_t *d_gate_items = nullptr; size_t gate_items_cap = 0;   // candidate lists of k_gate / distance blocks of k_block_dist (grow-only)
     uint8_t *pin = nullptr; size_t pin_bytes = 0;                  // page-locked staging of the host-buffer policy entry points (grow-only)
     size_t gate_guess = 4096;                                      // entries the speculative download of the candidate lists covers
+    // page-locked staging of the batched tracking matchers (grow-only) and the event behind their upload: these calls return
+    // before the copy has run, so the block is theirs alone and is not written again before that event has passed
+    uint8_t *track_pin = nullptr; size_t track_pin_bytes = 0;
+    hipEvent_t ev_track = nullptr; bool track_pending = false;
     // grow-only scratch arena for the host-buffer convenience entry points (match / matrix / stereo): no hipMalloc
     // on the steady-state path and nothing to leak on an error return
     uint8_t *d_scratch = nullptr; size_t scratch_bytes = 0, scratch_used = 0;
@@ -456,6 +461,8 @@ extern "C" void orbx_destroy(orbx_handle *h) {
         free_geometry_buffers(h);
         hipFree(h->d_match_ws); hipFree(h->d_scratch); hipFree(h->d_rect); hipFree(h->d_gate_items);
         if (h->pin) hipHostFree(h->pin);
+        if (h->track_pin) hipHostFree(h->track_pin);
+        if (h->ev_track) hipEventDestroy(h->ev_track);
         if (h->pin_stat) hipHostFree(h->pin_stat);
         for (int s = 0; s < 2; ++s) {
             hipFree(h->st_in[s]); hipFree(h->st_kps[s]);   // st_desc / st_cnt live inside the st_kps allocation
@@ -2141,6 +2148,120 @@ extern "C" orbx_status orbx_search_by_projection_mappoints(orbx_handle *h, const
         }
     }
     *nmatches_out = nmatches;
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------- a14 / (f)1 batched and device-resident (orbx_track.h)
+// One call: validation and layout (orbx_track_pack.cpp), all problems' host arrays packed into the page-locked block, ONE upload,
+// k_track_project (frame policy) + k_track_cand + k_track_select on the handle's stream.  Nothing is downloaded and nothing is
+// waited for, with two exceptions that steady state does not meet: a block or an arena that has to grow, and a call issued
+// while the upload of the call before it has not yet left the staging block.
+static orbx_status track_stage(orbx_handle *h, const OrbxTrackPlan &plan, uint8_t **pin, uint8_t **dev) {
+    HIPCHK(hipSetDevice(h->dev));
+    if (!h->ev_track) HIPCHK(hipEventCreateWithFlags(&h->ev_track, hipEventDisableTiming));
+    if (h->track_pending) { HIPCHK(hipEventSynchronize(h->ev_track)); h->track_pending = false; }
+    if (plan.in_bytes > h->track_pin_bytes) {
+        if (h->track_pin) hipHostFree(h->track_pin);
+        h->track_pin = nullptr; h->track_pin_bytes = 0;
+        const size_t want = std::max(plan.in_bytes + plan.in_bytes / 2, (size_t)1 << 20);
+        HIPCHK(hipHostMalloc((void **)&h->track_pin, want, hipHostMallocDefault));
+        h->track_pin_bytes = want;
+    }
+    const orbx_status st = scratch_reserve(h, plan.dev_bytes + 256);
+    if (st != ORBX_OK) return st;
+    *pin = h->track_pin;
+    *dev = scratch_take<uint8_t>(h, plan.dev_bytes);
+    return ORBX_OK;
+}
+static orbx_status track_upload(orbx_handle *h, const OrbxTrackPlan &plan, const uint8_t *pin, uint8_t *dev) {
+    HIPCHK(hipMemcpyAsync(dev, pin, plan.in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->ev_track, h->stream));
+    h->track_pending = true;
+    return ORBX_OK;
+}
+static bool track_frames(OrbxTrackFrames &F, const orbx_keypoint *d_keys_un, const uint8_t *d_desc, const float *d_u_right,
+                         const int32_t *d_counts, int cap, const int32_t *d_cell_begin, const uint16_t *d_items, const float *bounds4) {
+    if (!grid_params(bounds4[0], bounds4[1], bounds4[2], bounds4[3], F.gp)) return false;
+    for (int i = 0; i < 4; ++i) F.bounds[i] = bounds4[i];
+    F.kps = d_keys_un; F.desc = d_desc; F.ur = d_u_right; F.counts = d_counts; F.cap = cap;
+    F.cell_begin = d_cell_begin; F.items = d_items;
+    return true;
+}
+
+extern "C" orbx_status orbx_search_by_projection_frame_batch_device(orbx_handle *h, int nproblems, const orbx_track_frame_problem *problems,
+                                                                    int nframes, const orbx_keypoint *d_keys_un, const uint8_t *d_desc,
+                                                                    const float *d_u_right, const int32_t *d_counts, int cap,
+                                                                    const int32_t *d_cell_begin, const uint16_t *d_items,
+                                                                    const float *camera4, const float *bounds4, float mb, float mbf,
+                                                                    int check_orientation, int32_t *d_matched_last, int32_t *d_nmatches) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "no handle");
+    const OrbxTrackBatchArgs a = {nframes, cap, h->p.nlevels,
+                                  nproblems <= 0 || (d_keys_un && d_desc && d_counts && d_cell_begin && d_items && camera4 && bounds4 &&
+                                                     d_matched_last && d_nmatches)};
+    OrbxTrackPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_track_frame_plan(nproblems, problems, a, plan, &why);
+    if (st != ORBX_OK) return fail(st, why);
+    OrbxTrackFrames F;
+    if (nproblems > 0 && !track_frames(F, d_keys_un, d_desc, d_u_right, d_counts, cap, d_cell_begin, d_items, bounds4))
+        return fail(ORBX_BAD_ARGUMENT, "bad image bounds");
+    if (nproblems == 0) return ORBX_OK;
+    if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = track_stage(h, plan, &pin, &d);
+    if (st != ORBX_OK) return st;
+    orbx_track_frame_pack(nproblems, problems, plan, h->tab.scale, mb, pin);
+    st = track_upload(h, plan, pin, d);
+    if (st != ORBX_OK) return st;
+    const DTrackProb *dp = (const DTrackProb *)(d + plan.o_prob);
+    DTrackQ *dq = (DTrackQ *)(d + plan.o_q);
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_track_project(h->stream, F, camera4, mbf, h->p.fp_mode == ORBX_FP_GCC_FMA ? 1 : 0, dp, dq, (int)plan.nq); }
+    { ProfScope ps(h, ORBX_K_MATCH);
+      orbx_launch_track_cand(h->stream, false, F, dp, dq, d + plan.o_desc, (int)plan.nq, (uint4 *)(d + plan.o_cand)); }
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_track_select(h->stream, false, F, nproblems, dp, dq, d + plan.o_desc, (const uint4 *)(d + plan.o_cand), nullptr, 0.f,
+                               check_orientation ? 1 : 0, (int32_t *)(d + plan.o_ev), d_matched_last, d_nmatches); }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
+    return ORBX_OK;
+}
+
+extern "C" orbx_status orbx_search_by_projection_mappoints_batch_device(orbx_handle *h, int nproblems,
+                                                                        const orbx_track_points_problem *problems, int nframes,
+                                                                        const orbx_keypoint *d_keys_un, const uint8_t *d_desc,
+                                                                        const float *d_u_right, const int32_t *d_counts, int cap,
+                                                                        const int32_t *d_cell_begin, const uint16_t *d_items,
+                                                                        const float *bounds4, float nnratio, int32_t *d_assigned,
+                                                                        int32_t *d_nmatches) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "no handle");
+    const OrbxTrackBatchArgs a = {nframes, cap, h->p.nlevels,
+                                  nproblems <= 0 || (d_keys_un && d_desc && d_counts && d_cell_begin && d_items && bounds4 && d_assigned &&
+                                                     d_nmatches)};
+    OrbxTrackPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_track_points_plan(nproblems, problems, a, plan, &why);
+    if (st != ORBX_OK) return fail(st, why);
+    OrbxTrackFrames F;
+    if (nproblems > 0 && !track_frames(F, d_keys_un, d_desc, d_u_right, d_counts, cap, d_cell_begin, d_items, bounds4))
+        return fail(ORBX_BAD_ARGUMENT, "bad image bounds");
+    if (nproblems == 0) return ORBX_OK;
+    if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = track_stage(h, plan, &pin, &d);
+    if (st != ORBX_OK) return st;
+    orbx_track_points_pack(nproblems, problems, plan, h->tab.scale, cap, pin);
+    st = track_upload(h, plan, pin, d);
+    if (st != ORBX_OK) return st;
+    const DTrackProb *dp = (const DTrackProb *)(d + plan.o_prob);
+    const DTrackQ *dq = (const DTrackQ *)(d + plan.o_q);
+    { ProfScope ps(h, ORBX_K_MATCH);
+      orbx_launch_track_cand(h->stream, true, F, dp, dq, d + plan.o_desc, (int)plan.nq, (uint4 *)(d + plan.o_cand)); }
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_track_select(h->stream, true, F, nproblems, dp, dq, d + plan.o_desc, (const uint4 *)(d + plan.o_cand),
+                               (const uint32_t *)(d + plan.o_seed), nnratio, 0, (int32_t *)(d + plan.o_ev), d_assigned, d_nmatches); }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
     return ORBX_OK;
 }
 

@@ -8,6 +8,7 @@
 // __builtin_fmaf calls of the descriptor taps (fp_mode GCC_FMA) and the fma() of the pinned sincos.
 #include "orbx_device.h"
 #include "orbx_inplace.h"
+#include "orbx_track.h"
 #include "../../include/orbx_pattern_data.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -3318,6 +3319,239 @@ __global__ __launch_bounds__(BOW_ROT_THREADS) void k_bow_rot(int nout, const uin
     if (t == 0) counts[k] = total;
 }
 
+// ------------------------------------------------------------------------------------------------
+// K12: the two tracking matchers, batched and device-resident (orbx_track.h): SearchByProjection(CurrentFrame, LastFrame, th,
+// bMono) (reference src/ORBmatcher.cc:1702-1871) and SearchByProjection(F, vpMapPoints, th) (:69-184) for many (frame, point
+// set) problems in one call.  The current frames are the device batch buffers and the grids of k_grid_build.
+//   k_track_project (frame policy): one thread per last-frame point, the projection of :1742-1783 in the arithmetic of
+//     orbx_search_by_projection_frame; the packed record becomes the GetFeaturesInArea query in place.
+//   k_track_cand: one wave per point walks the query's buckets in k_gate's order and keeps, instead of a candidate list, the
+//     smallest key dist << 16 | visiting position (the two smallest for the map-point policy) over the candidates that pass
+//     the tests that do not depend on the selection state: window, level band, u_right gate.
+//   k_track_select: one wave per problem takes the points in order with the blocked features (assigned to a point with
+//     Observations() > 0) as a bitmap in LDS.  Removing candidates cannot change the smallest keys among the others, so a
+//     point whose stored candidates are all unblocked at its turn has the reference's result; otherwise the wave walks that
+//     point's buckets again with the blocked test.  Frame policy: the rotation check over the accept events follows.
+// ------------------------------------------------------------------------------------------------
+#define TRK_NONE 0xffffffffu
+#define TRK_TH_HIGH 100u
+struct TrackBest { uint32_t k1, p1, k2, p2; };   // key, payload (feature index | octave << 16) of the best and the second
+// the walk of k_gate over the buckets of Q's window in frame (kps, desc, ur, cb, items; n features): every lane keeps its
+// smallest keys, the wave reduces them (keys are unique: the visiting position is).  blocked != nullptr: features whose bit is
+// set do not count.  All 64 lanes must be active.
+template <bool TWO>
+__device__ __forceinline__ TrackBest track_scan(const DGrid &gp, const DTrackQ &Q, const uint4 qa, const uint4 qb,
+                                                const orbx_keypoint *__restrict__ kps, const uint8_t *__restrict__ desc,
+                                                const float *__restrict__ ur, const int *__restrict__ cb,
+                                                const uint16_t *__restrict__ items, int n, const uint32_t *blocked, int lane) {
+    const int x0 = max(0, (int)floorf((Q.x - gp.minx - Q.r) * gp.winv));
+    const int x1 = min(GR_COLS - 1, (int)ceilf((Q.x - gp.minx + Q.r) * gp.winv));
+    const int y0 = max(0, (int)floorf((Q.y - gp.miny - Q.r) * gp.hinv));
+    const int y1 = min(GR_ROWS - 1, (int)ceilf((Q.y - gp.miny + Q.r) * gp.hinv));
+    const bool live = Q.r >= 0.f && x0 < GR_COLS && x1 >= 0 && y0 < GR_ROWS && y1 >= 0;
+    const bool check = (Q.min_level > 0) || (Q.max_level >= 0);
+    uint32_t b1 = TRK_NONE, b2 = TRK_NONE, pay1 = 0, pay2 = 0;
+    if (live) {
+        int pos = 0;
+        for (int ix = x0; ix <= x1; ++ix) {
+            // a grid that does not belong to these buffers must not lead outside them
+            const int b = max(cb[ix * GR_ROWS + y0], 0), e = min(cb[ix * GR_ROWS + y1 + 1], n);
+            for (int j0 = b; j0 < e; j0 += 64) {
+                const int j = j0 + lane;
+                if (j < e) {
+                    const int i2 = items[j];
+                    if (i2 < n) {
+                        const orbx_keypoint *kp = kps + i2;
+                        const int oct = kp->octave;
+                        bool pass = fabsf(kp->x - Q.x) < Q.r && fabsf(kp->y - Q.y) < Q.r;
+                        if (check) pass = pass && !(oct < Q.min_level) && !(Q.max_level >= 0 && oct > Q.max_level);
+                        if (pass && blocked) pass = !((blocked[i2 >> 5] >> (i2 & 31)) & 1u);
+                        if (pass && ur) {
+                            const float u2 = ur[i2];
+                            if (u2 > 0 && fabsf(Q.ur - u2) > Q.r) pass = false;
+                        }
+                        if (pass) {
+                            const uint4 *tp = (const uint4 *)(desc + (long long)i2 * 32);
+                            const uint4 ta = tp[0], tb = tp[1];
+                            const uint32_t d = __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) +
+                                               __popc(qb.x ^ tb.x) + __popc(qb.y ^ tb.y) + __popc(qb.z ^ tb.z) + __popc(qb.w ^ tb.w);
+                            const uint32_t key = (d << 16) | (uint32_t)(pos + (j - b)), pay = (uint32_t)i2 | ((uint32_t)(oct & 0xff) << 16);
+                            if (key < b1) { b2 = b1; pay2 = pay1; b1 = key; pay1 = pay; }
+                            else if (TWO && key < b2) { b2 = key; pay2 = pay; }
+                        }
+                    }
+                }
+            }
+            pos += e > b ? e - b : 0;
+        }
+    }
+    TrackBest R;
+    R.k1 = orbx_wave_min(b1);
+    const bool own1 = b1 == R.k1 && R.k1 != TRK_NONE;
+    R.p1 = orbx_wave_min(own1 ? pay1 : TRK_NONE);
+    R.k2 = TRK_NONE; R.p2 = TRK_NONE;
+    if (TWO) {
+        const uint32_t c = own1 ? b2 : b1, cp = own1 ? pay2 : pay1;
+        R.k2 = orbx_wave_min(c);
+        R.p2 = orbx_wave_min(c == R.k2 && R.k2 != TRK_NONE ? cp : TRK_NONE);
+    }
+    return R;
+}
+
+struct DTrackCam { float fx, fy, cx, cy, minx, maxx, miny, maxy, mbf; int fma_mode; };
+__global__ __launch_bounds__(256) void k_track_project(DTrackCam cam, const DTrackProb *__restrict__ probs, DTrackQ *__restrict__ q,
+                                                       int nq) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq) return;
+    DTrackQ Q = q[i];
+    if (!(Q.r >= 0.f)) return;
+    const DTrackProb P = probs[Q.prob];
+    const float w[3] = {Q.x, Q.y, Q.ur};
+    float pc[3];
+    for (int r = 0; r < 3; ++r) {   // cv::gemm 3x3 * 3x1 float special case
+        const float t = P.Rcw[3 * r] * w[0] + P.Rcw[3 * r + 1] * w[1] + P.Rcw[3 * r + 2] * w[2];
+        pc[r] = (float)((double)t * 1.0 + (double)P.tcw[r] * 1.0);
+    }
+    const float invzc = (float)(1.0 / (double)pc[2]);
+    bool ok = !(invzc < 0);
+    float u = 0.f, v = 0.f, ur = 0.f;
+    if (ok) {
+        if (cam.fma_mode) { u = __builtin_fmaf(cam.fx * pc[0], invzc, cam.cx); v = __builtin_fmaf(cam.fy * pc[1], invzc, cam.cy); }
+        else { u = cam.fx * pc[0] * invzc + cam.cx; v = cam.fy * pc[1] * invzc + cam.cy; }
+        ok = !(u < cam.minx || u > cam.maxx || v < cam.miny || v > cam.maxy);
+        ur = cam.fma_mode ? __builtin_fmaf(-cam.mbf, invzc, u) : u - cam.mbf * invzc;
+    }
+    const int oct = Q.min_level;
+    if (!ok) { Q.r = -1.0f; Q.min_level = Q.max_level = -1; }
+    else if (P.dir == 1) { Q.min_level = oct; Q.max_level = -1; }
+    else if (P.dir == 2) { Q.min_level = 0; Q.max_level = oct; }
+    else { Q.min_level = oct - 1; Q.max_level = oct + 1; }
+    Q.x = u; Q.y = v; Q.ur = ur;
+    q[i] = Q;
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(256) void k_track_cand(DGrid gp, const DTrackProb *__restrict__ probs, const DTrackQ *__restrict__ q,
+                                                    const uint8_t *__restrict__ qdesc, int nq, const orbx_keypoint *__restrict__ kps,
+                                                    const uint8_t *__restrict__ desc, const float *__restrict__ ur,
+                                                    const int *__restrict__ counts, int cap, const int *__restrict__ cell_begin,
+                                                    const uint16_t *__restrict__ items, uint4 *__restrict__ cand) {
+    const int lane = threadIdx.x & 63;
+    const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (g >= nq) return;
+    const DTrackQ Q = q[g];
+    TrackBest B = {TRK_NONE, TRK_NONE, TRK_NONE, TRK_NONE};
+    if (Q.r >= 0.f) {
+        const long long f = probs[Q.prob].frame;
+        const int n = min(counts[f], cap);
+        const uint4 *qp = (const uint4 *)(qdesc + (long long)g * 32);
+        B = track_scan<TWO>(gp, Q, qp[0], qp[1], kps + f * cap, desc + f * cap * 32, ur ? ur + f * cap : nullptr,
+                            cell_begin + f * (GR_CELLS + 1), items + f * cap, n, nullptr, lane);
+    }
+    if (lane == 0) cand[g] = make_uint4(B.k1, B.p1, B.k2, B.p2);
+}
+
+// One wave per problem.  Dynamic LDS: the blocked bitmap (`words` words, >= ceil(cap / 32)) | the 30 bins of the histogram.
+// MP = the map-point policy (two stored candidates, level-aware ratio test, bitmap seeded from frame_observations).
+template <bool MP>
+__global__ __launch_bounds__(64) void k_track_select(DGrid gp, const DTrackProb *__restrict__ probs, const DTrackQ *__restrict__ q,
+                                                     const uint8_t *__restrict__ qdesc, const uint4 *__restrict__ cand,
+                                                     const uint32_t *__restrict__ seed, int words,
+                                                     const orbx_keypoint *__restrict__ kps, const uint8_t *__restrict__ desc,
+                                                     const float *__restrict__ ur, const int *__restrict__ counts, int cap,
+                                                     const int *__restrict__ cell_begin, const uint16_t *__restrict__ items,
+                                                     float nnratio, int check, int32_t *__restrict__ ev, int32_t *__restrict__ out,
+                                                     int32_t *__restrict__ nmatches) {
+    extern __shared__ uint32_t trk_lds[];
+    uint32_t *blocked = trk_lds;
+    int *hist = (int *)(trk_lds + words);
+    const int lane = threadIdx.x;
+    const int k = blockIdx.x;
+    const DTrackProb P = probs[k];
+    const long long f = P.frame;
+    const int n = min(counts[f], cap);
+    kps += f * cap; desc += f * cap * 32; items += f * cap; cell_begin += f * (GR_CELLS + 1);
+    if (ur) ur += f * cap;
+    int32_t *o = out + (long long)k * cap;
+    q += P.q_begin; qdesc += (long long)P.q_begin * 32; cand += P.q_begin; ev += P.q_begin;
+    for (int w = lane; w < words; w += 64) blocked[w] = MP ? seed[(long long)k * words + w] : 0u;
+    for (int i = lane; i < n; i += 64) o[i] = -1;
+    if (lane < 30) hist[lane] = 0;
+    __syncthreads();
+    int total = 0;
+    for (int p0 = 0; p0 < P.nq; p0 += 64) {
+        uint4 c = make_uint4(TRK_NONE, TRK_NONE, TRK_NONE, TRK_NONE);
+        int obsv = 0;
+        if (p0 + lane < P.nq) { c = cand[p0 + lane]; obsv = q[p0 + lane].obs; }
+        int evv = -1;
+        const int nb = min(64, P.nq - p0);
+        for (int rr = 0; rr < nb; ++rr) {
+            uint32_t k1 = (uint32_t)__builtin_amdgcn_readlane((int)c.x, rr);
+            if ((k1 >> 16) > TRK_TH_HIGH) continue;   // no candidate, or none within TH_HIGH: a second walk cannot find a closer one
+            uint32_t p1 = (uint32_t)__builtin_amdgcn_readlane((int)c.y, rr), k2 = TRK_NONE, p2 = TRK_NONE;
+            const uint32_t i1 = p1 & 0xffffu;
+            uint32_t hit = (blocked[i1 >> 5] >> (i1 & 31)) & 1u;
+            if (MP) {
+                k2 = (uint32_t)__builtin_amdgcn_readlane((int)c.z, rr);
+                p2 = (uint32_t)__builtin_amdgcn_readlane((int)c.w, rr);
+                if (k2 != TRK_NONE) { const uint32_t i2 = p2 & 0xffffu; hit |= (blocked[i2 >> 5] >> (i2 & 31)) & 1u; }
+            }
+            if (__builtin_amdgcn_readfirstlane((int)hit)) {   // the same in every lane: the branch stays scalar
+                const uint4 *qp = (const uint4 *)(qdesc + (long long)(p0 + rr) * 32);
+                const TrackBest B = track_scan<MP>(gp, q[p0 + rr], qp[0], qp[1], kps, desc, ur, cell_begin, items, n, blocked, lane);
+                k1 = B.k1; p1 = B.p1; k2 = B.k2; p2 = B.p2;
+                if ((k1 >> 16) > TRK_TH_HIGH) continue;
+            }
+            if (MP) {
+                const int l1 = (int)((p1 >> 16) & 0xffu), l2 = k2 == TRK_NONE ? -1 : (int)((p2 >> 16) & 0xffu);
+                const int d1 = (int)(k1 >> 16), d2 = k2 == TRK_NONE ? 256 : (int)(k2 >> 16);
+                if (l1 == l2 && (float)d1 > nnratio * (float)d2) continue;
+            }
+            const uint32_t idx = p1 & 0xffffu;
+            if (lane == 0) o[idx] = p0 + rr;
+            // every lane writes the (same) word: each then reads its own store back in the next test
+            if (__builtin_amdgcn_readlane(obsv, rr) > 0) blocked[idx >> 5] |= 1u << (idx & 31);
+            if (lane == rr) evv = (int)idx;
+            ++total;
+        }
+        if (!MP && p0 + lane < P.nq) ev[p0 + lane] = evv;
+    }
+    if (MP) {
+        if (lane == 0) nmatches[k] = total;
+        return;
+    }
+    // the rotation check over the accept events (src/ORBmatcher.cc:1842-1868): an event in a dropped bin takes the feature's
+    // match away and one off the count, also where a later event had taken the feature over
+    int dropped = 0;
+    if (check) {
+        __syncthreads();   // the events and the assignments written above
+        for (int i = lane; i < P.nq; i += 64) {
+            const int i2 = ev[i];
+            if (i2 < 0) continue;
+            const int b = bow_rot_bin(q[i].angle, kps[i2].angle);
+            if (b >= 0) atomicAdd(&hist[b], 1);
+        }
+        __syncthreads();
+        int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;   // orbx_three_maxima
+        for (int i = 0; i < 30; ++i) {
+            const int s = hist[i];
+            if (s > max1) { max3 = max2; max2 = max1; max1 = s; i3 = i2; i2 = i1; i1 = i; }
+            else if (s > max2) { max3 = max2; max2 = s; i3 = i2; i2 = i; }
+            else if (s > max3) { max3 = s; i3 = i; }
+        }
+        if (max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+        else if (max3 < 0.1f * (float)max1) { i3 = -1; }
+        for (int i = lane; i < P.nq; i += 64) {
+            const int j = ev[i];
+            if (j < 0) continue;
+            const int b = bow_rot_bin(q[i].angle, kps[j].angle);
+            if (b >= 0 && b != i1 && b != i2 && b != i3) { o[j] = -1; ++dropped; }
+        }
+    }
+    const int nd = orbx_wave_sum(dropped);
+    if (lane == 0) nmatches[k] = total - nd;
+}
+
 __global__ void k_clear(int *a, int na, int *b, int nb, int *c, int nc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < na) a[i] = 0;
@@ -3770,6 +4004,27 @@ void orbx_launch_gate(hipStream_t s, const DGrid &gp, const orbx_keypoint *kps, 
     if (nq <= 0) return;
     hipLaunchKernelGGL(k_gate, dim3((nq + 3) / 4), dim3(256), 0, s, gp, kps, desc, cell_begin, items, q, qdesc, nq, span, cursor,
                        out_items, cap, fstride);
+}
+void orbx_launch_track_project(hipStream_t s, const OrbxTrackFrames &F, const float *camera4, float mbf, int fma_mode,
+                               const DTrackProb *probs, DTrackQ *q, int nq) {
+    if (nq <= 0) return;
+    const DTrackCam cam = {camera4[0], camera4[1], camera4[2], camera4[3], F.bounds[0], F.bounds[1], F.bounds[2], F.bounds[3], mbf, fma_mode};
+    hipLaunchKernelGGL(k_track_project, dim3((nq + 255) / 256), dim3(256), 0, s, cam, probs, q, nq);
+}
+void orbx_launch_track_cand(hipStream_t s, bool two, const OrbxTrackFrames &F, const DTrackProb *probs, const DTrackQ *q,
+                            const uint8_t *qdesc, int nq, uint4 *cand) {
+    if (nq <= 0) return;
+    if (two) hipLaunchKernelGGL(k_track_cand<true>, dim3((nq + 3) / 4), dim3(256), 0, s, F.gp, probs, q, qdesc, nq, F.kps, F.desc, F.ur, F.counts, F.cap, F.cell_begin, F.items, cand);
+    else hipLaunchKernelGGL(k_track_cand<false>, dim3((nq + 3) / 4), dim3(256), 0, s, F.gp, probs, q, qdesc, nq, F.kps, F.desc, F.ur, F.counts, F.cap, F.cell_begin, F.items, cand);
+}
+void orbx_launch_track_select(hipStream_t s, bool mp, const OrbxTrackFrames &F, int nproblems, const DTrackProb *probs, const DTrackQ *q,
+                              const uint8_t *qdesc, const uint4 *cand, const uint32_t *seed, float nnratio, int check, int32_t *ev,
+                              int32_t *out, int32_t *nmatches) {
+    if (nproblems <= 0) return;
+    const int words = (F.cap + 31) / 32;
+    const size_t smem = ((size_t)words + 32) * sizeof(uint32_t);   // blocked bitmap | histogram; cap <= 65535: at most 8.1 KB
+    if (mp) hipLaunchKernelGGL(k_track_select<true>, dim3(nproblems), dim3(64), smem, s, F.gp, probs, q, qdesc, cand, seed, words, F.kps, F.desc, F.ur, F.counts, F.cap, F.cell_begin, F.items, nnratio, check, ev, out, nmatches);
+    else hipLaunchKernelGGL(k_track_select<false>, dim3(nproblems), dim3(64), smem, s, F.gp, probs, q, qdesc, cand, seed, words, F.kps, F.desc, F.ur, F.counts, F.cap, F.cell_begin, F.items, nnratio, check, ev, out, nmatches);
 }
 void orbx_launch_block_dist(hipStream_t s, const uint8_t *d1, const uint8_t *d2, const DDistRow *rows, const uint32_t *col_idx,
                             int nrows, uint16_t *out) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "orbx_device.h"
 #include "orbx_inplace.h"
+#include "orbx_track.h"
 
 hipError_t orbx_upload_pattern();
 size_t orbx_quadtree_smem(int ncap, int lds_keys);
@@ -62,6 +63,24 @@ void orbx_launch_bow_select(hipStream_t s, bool kk, const DBowItem *items, int n
                             const uint8_t *hmp, float nnratio, int words, int32_t *out);
 void orbx_launch_bow_rot(hipStream_t s, bool kk, int nproblems, int nout, const uint32_t *cand_base, const float *ang, int check,
                          int32_t *out, int32_t *counts);
+// batched tracking matchers (orbx_track.h).  OrbxTrackFrames = the device batch the problems' current frames live in: keypoints,
+// descriptors, u_right (nullptr: all -1) and counts of `cap`-strided frames, their grids, the image bounds.
+struct OrbxTrackFrames {
+    DGrid gp; float bounds[4];
+    const orbx_keypoint *kps; const uint8_t *desc; const float *ur; const int *counts; int cap;
+    const int *cell_begin; const uint16_t *items;
+};
+// frame policy: the packed points (world positions) become queries in place
+void orbx_launch_track_project(hipStream_t s, const OrbxTrackFrames &F, const float *camera4, float mbf, int fma_mode,
+                               const DTrackProb *probs, DTrackQ *q, int nq);
+// one wave per point: the smallest key (two = the two smallest, map-point policy) of its window -> cand[point]
+void orbx_launch_track_cand(hipStream_t s, bool two, const OrbxTrackFrames &F, const DTrackProb *probs, const DTrackQ *q,
+                            const uint8_t *qdesc, int nq, uint4 *cand);
+// one wave per problem: the ordered selection (mp = map-point policy: seeds, ratio test; otherwise TH_HIGH and the rotation
+// check over the accept events `ev`), outputs out[nproblems][cap] / nmatches[nproblems]
+void orbx_launch_track_select(hipStream_t s, bool mp, const OrbxTrackFrames &F, int nproblems, const DTrackProb *probs, const DTrackQ *q,
+                              const uint8_t *qdesc, const uint4 *cand, const uint32_t *seed, float nnratio, int check, int32_t *ev,
+                              int32_t *out, int32_t *nmatches);
 void orbx_launch_hamming_matrix(hipStream_t s, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *dist);
 
 void orbx_launch_stereo_batch(hipStream_t s, const OrbxStereoGeom &sg, int npairs, int cap, const orbx_keypoint *kL,

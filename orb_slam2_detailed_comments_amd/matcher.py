@@ -105,6 +105,65 @@ class ORBmatcher:
                                                           float(self.mfNNratio), ptr(out), C.byref(n)))
         return n.value, out[:F.N].copy()
 
+    # ---- the two tracking matchers, batched and device-resident (include/orbx.h: orbx_search_by_projection_*_batch_device)
+    @staticmethod
+    def _batch_args(batch):
+        """batch: dict nframes, keys_un, desc, u_right (or None), counts, cap, cell_begin, items -- device pointers (torch
+        tensors or addresses) of the extraction batch and of orbx_grid_build_device -- and bounds (minx, maxx, miny, maxy)"""
+        bounds = np.asarray(batch["bounds"], np.float32)
+        return bounds, (int(batch["nframes"]), ptr(batch["keys_un"]), ptr(batch["desc"]), ptr(batch.get("u_right")),
+                        ptr(batch["counts"]), int(batch["cap"]), ptr(batch["cell_begin"]), ptr(batch["items"]))
+
+    def SearchByProjectionBatchDevice(self, problems, batch, *, K, mb, mbf, d_matched_last, d_nmatches):
+        """SearchByProjection(CurrentFrame, LastFrame, th, bMono) for many problems in one asynchronous call.  problems: dicts
+        frame, th, mono, Tcw and the last frame's keys_un, Tlw, has_map_point, world_pos, mp_desc, observations (host arrays,
+        consumed before the call returns).  d_matched_last [len(problems)][cap] int32 and d_nmatches [len(problems)] int32 are
+        written on the device, on the extractor's stream."""
+        n = len(problems)
+        arr = (_capi.TrackFrameProblem * max(n, 1))()
+        keep = []
+        for P, p in zip(arr, problems):
+            P.frame, P.th, P.mono = int(p["frame"]), float(p["th"]), int(p["mono"])
+            P.Tcw[:] = [float(v) for v in np.asarray(p["Tcw"], np.float32).reshape(16)]
+            a = [np.ascontiguousarray(x, t) for x, t in ((p["keys_un"], _capi.KP_DTYPE), (p["has_map_point"], np.uint8),
+                                                          (p["world_pos"], np.float32), (p["mp_desc"], np.uint8),
+                                                          (p["observations"], np.int32))]
+            keep += a
+            lv = P.last
+            lv.n = len(a[0])
+            lv.keys_un, lv.has_map_point, lv.world_pos, lv.mp_desc, lv.observations = (x.ctypes.data for x in a)
+            lv.Tcw[:] = [float(v) for v in np.asarray(p["Tlw"], np.float32).reshape(16)]
+        bounds, dev = self._batch_args(batch)
+        cam = np.asarray(K, np.float32)
+        check(self._L.orbx_search_by_projection_frame_batch_device(
+            self._ex.handle, n, arr, *dev, ptr(cam), ptr(bounds), float(mb), float(mbf), int(self.mbCheckOrientation),
+            ptr(d_matched_last), ptr(d_nmatches)))
+
+    def SearchByProjectionMapPointsBatchDevice(self, problems, batch, *, d_assigned, d_nmatches):
+        """SearchByProjection(F, vpMapPoints, th) for many problems in one asynchronous call.  problems: dicts frame, th,
+        frame_observations (cap entries, or None: all -1) and the MapPoint fields in_view, proj, level, view_cos, mp_desc,
+        observations (host arrays, consumed before the call returns).  d_assigned [len(problems)][cap] int32 and d_nmatches are
+        written on the device, on the extractor's stream."""
+        n = len(problems)
+        arr = (_capi.TrackPointsProblem * max(n, 1))()
+        keep = []
+        for P, p in zip(arr, problems):
+            P.frame, P.th = int(p["frame"]), float(p["th"])
+            if p.get("frame_observations") is not None:
+                fo = np.ascontiguousarray(p["frame_observations"], np.int32)
+                assert len(fo) >= int(batch["cap"]), "frame_observations holds cap entries"
+                keep.append(fo); P.frame_observations = fo.ctypes.data
+            a = [np.ascontiguousarray(x, t) for x, t in ((p["in_view"], np.uint8), (p["proj"], np.float32), (p["level"], np.int32),
+                                                          (p["view_cos"], np.float32), (p["mp_desc"], np.uint8),
+                                                          (p["observations"], np.int32))]
+            keep += a
+            mv = P.points
+            mv.n = len(a[0])
+            mv.in_view, mv.proj, mv.level, mv.view_cos, mv.desc, mv.observations = (x.ctypes.data for x in a)
+        bounds, dev = self._batch_args(batch)
+        check(self._L.orbx_search_by_projection_mappoints_batch_device(
+            self._ex.handle, n, arr, *dev, ptr(bounds), float(self.mfNNratio), ptr(d_assigned), ptr(d_nmatches)))
+
     # ---- BoW-guided policies (src/ORBmatcher.cc:248-410, 722-866, 879-1087)
     @staticmethod
     def _featvec(fv, keep):
