@@ -297,6 +297,71 @@ orbx_status orbx_search_by_projection_mappoints_batch_device(orbx_handle *h, int
                                                              const float *bounds4, float nnratio, int32_t *d_assigned,
                                                              int32_t *d_nmatches);
 
+/* MapPoint::PredictScale(currentDist, Frame*) (src/MapPoint.cc:706-721) without a logarithm at run time.  The level
+ *   nScale = (int)ceilf(logf(ratio) / logf(scaleFactor)), clamped to [0, nlevels - 1],  ratio = mfMaxDistance / currentDist
+ * is a non-decreasing step function of the float `ratio`.  orbx_create finds, with the host's own libm and by bisection over the
+ * float bit patterns, thr[k] = the smallest positive finite float for which the expression gives >= k (k = 1 .. nlevels - 1;
+ * +inf where no finite float does); the level is the number of k with ratio >= thr[k].  The caller's reference code runs in the
+ * same process against the same libm, so the two agree wherever that libm's logf is monotone.
+ * OUTSIDE the parity contract: ratio = NaN, <= 0 or +inf (currentDist == 0, a non-positive mfMaxDistance) is a float -> int
+ * conversion with undefined behaviour in the reference; here the table rule applies as it stands -- NaN and <= 0 give 0, +inf
+ * gives nlevels - 1 -- and nothing faults.  Both are host functions and work on a host-only handle.
+ * orbx_predict_scale_table: thr holds n >= nlevels floats; thr[0] = 0 (not used), thr[1 .. nlevels - 1] as above.
+ * orbx_predict_scale: the level; -1 without a handle. */
+orbx_status orbx_predict_scale_table(const orbx_handle *h, float *thr, int n);
+int orbx_predict_scale(const orbx_handle *h, float max_distance, float current_dist);
+
+/* Tracking::SearchLocalPoints (src/Tracking.cc:1875-1955) for many (frame, pose, local map) problems in one call: per point
+ * Frame::isInFrustum (src/Frame.cc:529-620) with MapPoint::PredictScale, then SearchByProjection(F, vpMapPoints, th), all on the
+ * device (k_track_frustum, then k_track_cand and k_track_select exactly as orbx_search_by_projection_mappoints_batch_device
+ * runs them).  The local map is ONE pool per call, uploaded once and shared by all problems; a problem names its points as pool
+ * indices in list order and carries its pose.  The frustum stage evaluates the reference's expressions in its order: Pc = Rcw P +
+ * tcw (cv::gemm's float special case), PcZ < 0, invz = 1.0f / PcZ (a float division), u = fx PcX invz + cx and v likewise and
+ * ur = u - mbf invz (contracted under ORBX_FP_GCC_FMA as in orbx_search_by_projection_frame, separate roundings under
+ * ORBX_FP_STRICT), the four bounds tests, dist = (float)sqrt of the double sum of squares of P - Ow against [0.8f min, 1.2f max],
+ * viewCos = (float)(double dot / dist) against viewing_cos_limit, the level of orbx_predict_scale(max_distance, dist), and the
+ * matcher's window r = (viewCos > 0.998 ? 2.5f : 4.0f) (* th where th != 1.0) * mvScaleFactors[level] with the level band
+ * [level - 1, level].  The cv::Mat sums and cv::norm are OpenCV-owned arithmetic: parity with a particular OpenCV build is not
+ * pinned there (as for orbx_search_by_projection_frame).
+ * Contract of the two calls above: asynchronous on the handle's stream, one page-locked staging block consumed before the call
+ * returns, nothing downloaded.  d_assigned ([nproblems][cap]) and d_nmatches are what
+ * orbx_search_by_projection_mappoints_batch_device writes for the same frames when it is fed this stage's results.
+ * d_in_view[q] (q = the point's position in the concatenation of all problems' lists; may be NULL) = mbTrackInView, which the
+ * caller needs for IncreaseVisible() and nToMatch; d_track[q] (may be NULL) = the MapPoint's tracking fields, written only where
+ * d_in_view[q] would be 1.  Validated before any device work: ORBX_BAD_ARGUMENT for nproblems < 0, a null field of a non-empty
+ * pool, a null map with a non-empty problem, an index outside the pool, a frame outside [0, nframes), cap <= 0;
+ * ORBX_UNSUPPORTED for cap > 65535.  nproblems == 0 launches nothing; an empty pool (every problem then has npoints == 0)
+ * launches nothing that reads it. */
+typedef struct orbx_local_map_view {      /* one pool per call, uploaded once, shared by all problems */
+    int32_t n;
+    const float *world_pos;               /* GetWorldPos(), 3 per point */
+    const float *normal;                  /* GetNormal(), 3 per point */
+    const float *min_distance;            /* mfMinDistance (raw; the 0.8f is applied here) */
+    const float *max_distance;            /* mfMaxDistance (raw; the 1.2f is applied here, PredictScale uses it raw) */
+    const uint8_t *desc;                  /* GetDescriptor(), 32 per point */
+    const int32_t *observations;          /* Observations() */
+} orbx_local_map_view;
+typedef struct orbx_track_local_problem {
+    int32_t frame;                        /* this frame of the device batch */
+    float th;
+    float viewing_cos_limit;              /* 0.5f in Tracking::SearchLocalPoints */
+    float Tcw[16];                        /* mTcw, row major 4x4 (mRcw, mtcw are read from it) */
+    float Ow[3];                          /* mOw as the Frame holds it */
+    int32_t npoints;
+    const int32_t *point_index;           /* mvpLocalMapPoints as pool indices, in list order; NULL: the whole pool in order
+                                             (npoints must then equal the pool's n) */
+    const uint8_t *skip;                  /* npoints: mnLastFrameSeen == mnId || isBad(); NULL: none */
+    const int32_t *frame_observations;    /* as orbx_track_points_problem */
+} orbx_track_local_problem;
+typedef struct orbx_track_state { float proj_x, proj_y, proj_xr, view_cos; int32_t level; } orbx_track_state;
+orbx_status orbx_search_local_points_batch_device(orbx_handle *h, int nproblems, const orbx_track_local_problem *problems,
+                                                  const orbx_local_map_view *map, int nframes,
+                                                  const orbx_keypoint *d_keys_un, const uint8_t *d_desc, const float *d_u_right,
+                                                  const int32_t *d_counts, int cap, const int32_t *d_cell_begin,
+                                                  const uint16_t *d_items, const float *camera4, const float *bounds4, float mbf,
+                                                  float nnratio, int32_t *d_assigned, int32_t *d_nmatches, uint8_t *d_in_view,
+                                                  orbx_track_state *d_track);
+
 /* ---- BoW-guided policies.  Host code keeps the pointer chasing (KeyFrame / MapPoint /
  * DBoW2 containers) and hands the fields the policies read as arrays; the Hamming distances come from the GPU, the
  * order-dependent selection runs on the host exactly as the reference does. */

@@ -56,6 +56,22 @@ class TrackPointsProblem(C.Structure):   # orbx_track_points_problem
     _fields_ = [("frame", C.c_int32), ("th", C.c_float), ("frame_observations", C.c_void_p), ("points", MapPointView)]
 
 
+class LocalMapView(C.Structure):   # orbx_local_map_view
+    _fields_ = [("n", C.c_int32), ("world_pos", C.c_void_p), ("normal", C.c_void_p), ("min_distance", C.c_void_p),
+                ("max_distance", C.c_void_p), ("desc", C.c_void_p), ("observations", C.c_void_p)]
+
+
+class TrackLocalProblem(C.Structure):   # orbx_track_local_problem
+    _fields_ = [("frame", C.c_int32), ("th", C.c_float), ("viewing_cos_limit", C.c_float), ("Tcw", C.c_float * 16),
+                ("Ow", C.c_float * 3), ("npoints", C.c_int32), ("point_index", C.c_void_p), ("skip", C.c_void_p),
+                ("frame_observations", C.c_void_p)]
+
+
+TRACK_STATE_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),
+                              ("level", "<i4")])   # orbx_track_state
+assert TRACK_STATE_DTYPE.itemsize == 20
+
+
 class FeatVecView(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("node_id", C.c_void_p), ("begin", C.c_void_p), ("index", C.c_void_p)]
 
@@ -101,7 +117,8 @@ SYMBOLS = [
     "orbx_grid_create", "orbx_grid_destroy", "orbx_grid_query", "orbx_three_maxima",
     "orbx_search_for_initialization", "orbx_stereo_match", "orbx_search_by_projection_frame",
     "orbx_search_by_projection_mappoints", "orbx_search_by_projection_frame_batch_device",
-    "orbx_search_by_projection_mappoints_batch_device", "orbx_set_input_format", "orbx_search_by_bow_keyframe_frame",
+    "orbx_search_by_projection_mappoints_batch_device", "orbx_predict_scale_table", "orbx_predict_scale",
+    "orbx_search_local_points_batch_device", "orbx_set_input_format", "orbx_search_by_bow_keyframe_frame",
     "orbx_search_by_bow_keyframes", "orbx_search_by_bow_keyframe_frame_batch", "orbx_search_by_bow_keyframes_batch", "orbx_search_for_triangulation", "orbx_triangulation_batch_create", "orbx_triangulation_batch_select", "orbx_triangulation_batch_destroy", "orbx_fuse", "orbx_fuse_sim3", "orbx_fuse_batch", "orbx_fuse_sim3_batch",
     "orbx_search_by_projection_sim3", "orbx_search_by_sim3", "orbx_search_by_projection_keyframe",
     "orbx_stereo_match_batch_device", "orbx_host_alloc", "orbx_host_free", "orbx_set_rectification", "orbx_undistort_keypoints_device",
@@ -181,6 +198,11 @@ def lib():
                                                                i32, vp, vp]
     L.orbx_search_by_projection_mappoints_batch_device.restype = i32
     L.orbx_search_by_projection_mappoints_batch_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, f32, vp, vp]
+    L.orbx_predict_scale_table.restype = i32; L.orbx_predict_scale_table.argtypes = [vp, vp, i32]
+    L.orbx_predict_scale.restype = i32; L.orbx_predict_scale.argtypes = [vp, f32, f32]
+    L.orbx_search_local_points_batch_device.restype = i32
+    L.orbx_search_local_points_batch_device.argtypes = [vp, i32, vp, C.POINTER(LocalMapView), i32, vp, vp, vp, vp, i32, vp, vp,
+                                                        vp, vp, f32, f32, vp, vp, vp, vp]
     L.orbx_set_input_format.restype = i32; L.orbx_set_input_format.argtypes = [vp, i32]
     L.orbx_search_by_bow_keyframe_frame.restype = i32
     L.orbx_search_by_bow_keyframe_frame.argtypes = [vp, C.POINTER(KeyFrameView), vp, vp, i32, C.POINTER(FeatVecView), f32,

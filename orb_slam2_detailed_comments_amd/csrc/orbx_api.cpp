@@ -103,6 +103,8 @@ struct orbx_handle {
     // before the copy has run, so the block is theirs alone and is not written again before that event has passed
     uint8_t *track_pin = nullptr; size_t track_pin_bytes = 0;
     hipEvent_t ev_track = nullptr; bool track_pending = false;
+    // MapPoint::PredictScale as thresholds on mfMaxDistance / dist (orbx_track.h: orbx_predict_scale_build), built at orbx_create
+    float ps_thr[ORBX_PS_LEVELS] = {};
     // grow-only scratch arena for the host-buffer convenience entry points (match / matrix / stereo): no hipMalloc
     // on the steady-state path and nothing to leak on an error return
     uint8_t *d_scratch = nullptr; size_t scratch_bytes = 0, scratch_used = 0;
@@ -410,6 +412,8 @@ extern "C" orbx_status orbx_create(const orbx_params *params, orbx_handle **out)
     if (h->p.max_batch < 1) h->p.max_batch = 1;
     if (const char *e = getenv("ORBX_MATCH_KERNEL")) h->match_kernel = strcmp(e, "valu") == 0 ? 1 : strcmp(e, "i8") == 0 ? 2 : 0;
     orbx_build_tables(h->p, h->tab);
+    static_assert(ORBX_PS_LEVELS >= ORBX_MAX_LEVELS, "one threshold per level");
+    orbx_predict_scale_build(orbx_get_scale_factor(h), h->p.nlevels, h->ps_thr);
     if (params->device == -2) {  // host-only handle: tables and getters, no device work
         h->host_only = true;
         *out = h;
@@ -2255,6 +2259,67 @@ extern "C" orbx_status orbx_search_by_projection_mappoints_batch_device(orbx_han
     if (st != ORBX_OK) return st;
     const DTrackProb *dp = (const DTrackProb *)(d + plan.o_prob);
     const DTrackQ *dq = (const DTrackQ *)(d + plan.o_q);
+    { ProfScope ps(h, ORBX_K_MATCH);
+      orbx_launch_track_cand(h->stream, true, F, dp, dq, d + plan.o_desc, (int)plan.nq, (uint4 *)(d + plan.o_cand)); }
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_track_select(h->stream, true, F, nproblems, dp, dq, d + plan.o_desc, (const uint4 *)(d + plan.o_cand),
+                               (const uint32_t *)(d + plan.o_seed), nnratio, 0, (int32_t *)(d + plan.o_ev), d_assigned, d_nmatches); }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------- MapPoint::PredictScale (host; works on a host-only handle)
+extern "C" orbx_status orbx_predict_scale_table(const orbx_handle *h, float *thr, int n) {
+    if (!h || !thr) return fail(ORBX_BAD_ARGUMENT, "null argument");
+    if (n < h->p.nlevels) return fail(ORBX_BAD_ARGUMENT, "n < nlevels");
+    memcpy(thr, h->ps_thr, (size_t)h->p.nlevels * sizeof(float));
+    return ORBX_OK;
+}
+extern "C" int orbx_predict_scale(const orbx_handle *h, float max_distance, float current_dist) {
+    if (!h) return -1;
+    return orbx_predict_scale_level(h->ps_thr, h->p.nlevels, max_distance / current_dist);
+}
+
+// ---------------------------------------------------------------- Tracking::SearchLocalPoints, batched and device-resident:
+// k_track_frustum (isInFrustum + PredictScale + the matcher's window, one thread per (problem, point), the pool's descriptors
+// gathered per query) in front of the k_track_cand + k_track_select of the map-point policy, which run as they are.
+extern "C" orbx_status orbx_search_local_points_batch_device(orbx_handle *h, int nproblems, const orbx_track_local_problem *problems,
+                                                             const orbx_local_map_view *map, int nframes,
+                                                             const orbx_keypoint *d_keys_un, const uint8_t *d_desc,
+                                                             const float *d_u_right, const int32_t *d_counts, int cap,
+                                                             const int32_t *d_cell_begin, const uint16_t *d_items,
+                                                             const float *camera4, const float *bounds4, float mbf, float nnratio,
+                                                             int32_t *d_assigned, int32_t *d_nmatches, uint8_t *d_in_view,
+                                                             orbx_track_state *d_track) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "no handle");
+    const OrbxTrackBatchArgs a = {nframes, cap, h->p.nlevels,
+                                  nproblems <= 0 || (d_keys_un && d_desc && d_counts && d_cell_begin && d_items && camera4 && bounds4 &&
+                                                     d_assigned && d_nmatches)};
+    OrbxLocalPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_track_local_plan(nproblems, problems, map, a, plan, &why);
+    if (st != ORBX_OK) return fail(st, why);
+    OrbxTrackFrames F;
+    if (nproblems > 0 && !track_frames(F, d_keys_un, d_desc, d_u_right, d_counts, cap, d_cell_begin, d_items, bounds4))
+        return fail(ORBX_BAD_ARGUMENT, "bad image bounds");
+    if (nproblems == 0) return ORBX_OK;
+    if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
+    OrbxTrackPlan stage;   // the staging block and the arena are those of the two tracking matchers
+    stage.in_bytes = plan.in_bytes; stage.dev_bytes = plan.dev_bytes;
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = track_stage(h, stage, &pin, &d);
+    if (st != ORBX_OK) return st;
+    orbx_track_local_pack(nproblems, problems, map, plan, cap, pin);
+    st = track_upload(h, stage, pin, d);
+    if (st != ORBX_OK) return st;
+    const DTrackProb *dp = (const DTrackProb *)(d + plan.o_prob);
+    DTrackQ *dq = (DTrackQ *)(d + plan.o_q);
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_track_frustum(h->stream, F, camera4, mbf, h->p.fp_mode == ORBX_FP_GCC_FMA ? 1 : 0, h->p.nlevels, h->ps_thr,
+                                h->tab.scale, nproblems, plan.max_points, dp, (const DTrackLocal *)(d + plan.o_local),
+                                (const DTrackPoolPt *)(d + plan.o_pool), d + plan.o_pdesc, (const int32_t *)(d + plan.o_index),
+                                d + plan.o_skip, dq, d + plan.o_desc, d_in_view, d_track); }
     { ProfScope ps(h, ORBX_K_MATCH);
       orbx_launch_track_cand(h->stream, true, F, dp, dq, d + plan.o_desc, (int)plan.nq, (uint4 *)(d + plan.o_cand)); }
     { ProfScope ps(h, ORBX_K_MISC);

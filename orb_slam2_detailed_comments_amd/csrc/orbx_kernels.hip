@@ -3399,6 +3399,11 @@ __device__ __forceinline__ TrackBest track_scan(const DGrid &gp, const DTrackQ &
 }
 
 struct DTrackCam { float fx, fy, cx, cy, minx, maxx, miny, maxy, mbf; int fma_mode; };
+// one row of Rcw * x + tcw: cv::gemm's 3x3 * 3x1 float special case (oracle/orb_oracle_match.c: gemm3)
+__device__ __forceinline__ float track_gemm3(const float *a, const float *b, float c) {
+    const float t = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+    return (float)((double)t * 1.0 + (double)c * 1.0);
+}
 __global__ __launch_bounds__(256) void k_track_project(DTrackCam cam, const DTrackProb *__restrict__ probs, DTrackQ *__restrict__ q,
                                                        int nq) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -3408,10 +3413,7 @@ __global__ __launch_bounds__(256) void k_track_project(DTrackCam cam, const DTra
     const DTrackProb P = probs[Q.prob];
     const float w[3] = {Q.x, Q.y, Q.ur};
     float pc[3];
-    for (int r = 0; r < 3; ++r) {   // cv::gemm 3x3 * 3x1 float special case
-        const float t = P.Rcw[3 * r] * w[0] + P.Rcw[3 * r + 1] * w[1] + P.Rcw[3 * r + 2] * w[2];
-        pc[r] = (float)((double)t * 1.0 + (double)P.tcw[r] * 1.0);
-    }
+    for (int r = 0; r < 3; ++r) pc[r] = track_gemm3(&P.Rcw[3 * r], w, P.tcw[r]);
     const float invzc = (float)(1.0 / (double)pc[2]);
     bool ok = !(invzc < 0);
     float u = 0.f, v = 0.f, ur = 0.f;
@@ -3428,6 +3430,77 @@ __global__ __launch_bounds__(256) void k_track_project(DTrackCam cam, const DTra
     else { Q.min_level = oct - 1; Q.max_level = oct + 1; }
     Q.x = u; Q.y = v; Q.ur = ur;
     q[i] = Q;
+}
+
+// Frame::isInFrustum (src/Frame.cc:529-620) + MapPoint::PredictScale (src/MapPoint.cc:706-721) + the first lines of
+// SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:82-101, RadiusByViewingCos :187-194) for the local-map policy: one
+// thread per (problem, point) -- blockIdx.y = the problem (from prob0 on), blockIdx.x * 256 + threadIdx.x = the point in its list
+// -- turns a pool point under the problem's pose into the query k_track_cand / k_track_select read, or switches it off
+// (r = -1), and gathers the point's descriptor from the pool.  Every expression in the reference's order and arithmetic; the
+// level comes from the threshold table (orbx_predict_scale_table), which travels with the scale factors in the argument struct.
+struct DTrackFrustumArgs {
+    DTrackCam cam;
+    int nlevels;
+    float thr[ORBX_PS_LEVELS], scale[ORBX_PS_LEVELS];
+};
+__global__ __launch_bounds__(256) void k_track_frustum(DTrackFrustumArgs A, int prob0, const DTrackProb *__restrict__ probs,
+                                                       const DTrackLocal *__restrict__ locals, const DTrackPoolPt *__restrict__ pool,
+                                                       const uint8_t *__restrict__ pdesc, const int32_t *__restrict__ index,
+                                                       const uint8_t *__restrict__ skip, DTrackQ *__restrict__ q,
+                                                       uint8_t *__restrict__ qdesc, uint8_t *__restrict__ in_view,
+                                                       orbx_track_state *__restrict__ track) {
+    const int k = prob0 + blockIdx.y;
+    const DTrackProb P = probs[k];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P.nq) return;
+    const long long g = (long long)P.q_begin + i;
+    const DTrackLocal E = locals[k];
+    const DTrackCam &cam = A.cam;
+    const int pi = index[g];
+    const DTrackPoolPt T = pool[pi];
+    bool ok = !skip[g];
+    float u = 0.f, v = 0.f, ur = 0.f, viewCos = 0.f, r = -1.0f;
+    int level = 0;
+    if (ok) {
+        float pc[3];
+        for (int rr = 0; rr < 3; ++rr) pc[rr] = track_gemm3(&P.Rcw[3 * rr], T.P, P.tcw[rr]);
+        ok = !(pc[2] < 0.0f);
+        const float invz = 1.0f / pc[2];
+        if (cam.fma_mode) { u = __builtin_fmaf(cam.fx * pc[0], invz, cam.cx); v = __builtin_fmaf(cam.fy * pc[1], invz, cam.cy); }
+        else { u = cam.fx * pc[0] * invz + cam.cx; v = cam.fy * pc[1] * invz + cam.cy; }
+        ok = ok && !(u < cam.minx || u > cam.maxx) && !(v < cam.miny || v > cam.maxy);
+        const float maxDistance = 1.2f * T.dmax, minDistance = 0.8f * T.dmin;
+        const float po[3] = {T.P[0] - E.Ow[0], T.P[1] - E.Ow[1], T.P[2] - E.Ow[2]};
+        double s2 = 0.0, dot = 0.0;   // cv::norm, Mat::dot: double sums in element order (the products of floats are exact)
+        for (int c = 0; c < 3; ++c) { s2 += (double)po[c] * (double)po[c]; dot += (double)po[c] * (double)T.Pn[c]; }
+        const float dist = (float)sqrt(s2);
+        ok = ok && !(dist < minDistance || dist > maxDistance);
+        viewCos = (float)(dot / (double)dist);
+        ok = ok && !(viewCos < E.cos_limit);
+        const float ratio = T.dmax / dist;
+#pragma unroll
+        for (int l = 1; l < ORBX_PS_LEVELS; ++l) level += (l < A.nlevels && ratio >= A.thr[l]) ? 1 : 0;
+        ur = cam.fma_mode ? __builtin_fmaf(-cam.mbf, invz, u) : u - cam.mbf * invz;
+        r = (double)viewCos > 0.998 ? 2.5f : 4.0f;
+        if ((double)E.th != 1.0) r *= E.th;
+        float sc = A.scale[0];
+#pragma unroll
+        for (int l = 1; l < ORBX_PS_LEVELS; ++l) sc = level == l ? A.scale[l] : sc;   // selects: the table stays in registers
+        r *= sc;
+    }
+    DTrackQ Q;
+    Q.x = ok ? u : 0.f; Q.y = ok ? v : 0.f; Q.ur = ok ? ur : 0.f;
+    Q.r = ok ? r : -1.0f;
+    Q.min_level = ok ? level - 1 : -1; Q.max_level = ok ? level : -1;
+    Q.obs = T.obs; Q.angle = 0.f; Q.prob = k; Q.pad = 0;
+    q[g] = Q;
+    if (ok) {
+        const uint4 *sp = (const uint4 *)(pdesc + (long long)pi * 32);
+        uint4 *dp = (uint4 *)(qdesc + g * 32);
+        dp[0] = sp[0]; dp[1] = sp[1];
+        if (track) { orbx_track_state S; S.proj_x = u; S.proj_y = v; S.proj_xr = ur; S.view_cos = viewCos; S.level = level; track[g] = S; }
+    }
+    if (in_view) in_view[g] = ok ? 1 : 0;
 }
 
 template <bool TWO>
@@ -4010,6 +4083,19 @@ void orbx_launch_track_project(hipStream_t s, const OrbxTrackFrames &F, const fl
     if (nq <= 0) return;
     const DTrackCam cam = {camera4[0], camera4[1], camera4[2], camera4[3], F.bounds[0], F.bounds[1], F.bounds[2], F.bounds[3], mbf, fma_mode};
     hipLaunchKernelGGL(k_track_project, dim3((nq + 255) / 256), dim3(256), 0, s, cam, probs, q, nq);
+}
+void orbx_launch_track_frustum(hipStream_t s, const OrbxTrackFrames &F, const float *camera4, float mbf, int fma_mode, int nlevels,
+                               const float *thr, const float *scale, int nproblems, int max_points, const DTrackProb *probs,
+                               const DTrackLocal *locals, const DTrackPoolPt *pool, const uint8_t *pdesc, const int32_t *index,
+                               const uint8_t *skip, DTrackQ *q, uint8_t *qdesc, uint8_t *in_view, orbx_track_state *track) {
+    if (nproblems <= 0 || max_points <= 0) return;
+    DTrackFrustumArgs A;
+    A.cam = {camera4[0], camera4[1], camera4[2], camera4[3], F.bounds[0], F.bounds[1], F.bounds[2], F.bounds[3], mbf, fma_mode};
+    A.nlevels = nlevels;
+    for (int l = 0; l < ORBX_PS_LEVELS; ++l) { A.thr[l] = thr[l]; A.scale[l] = l < nlevels ? scale[l] : 0.f; }
+    for (int p0 = 0; p0 < nproblems; p0 += 65535)   // the y extent of a grid
+        hipLaunchKernelGGL(k_track_frustum, dim3((max_points + 255) / 256, std::min(65535, nproblems - p0)), dim3(256), 0, s, A, p0,
+                           probs, locals, pool, pdesc, index, skip, q, qdesc, in_view, track);
 }
 void orbx_launch_track_cand(hipStream_t s, bool two, const OrbxTrackFrames &F, const DTrackProb *probs, const DTrackQ *q,
                             const uint8_t *qdesc, int nq, uint4 *cand) {

@@ -73,6 +73,12 @@ struct OrbxTrackFrames {
 // frame policy: the packed points (world positions) become queries in place
 void orbx_launch_track_project(hipStream_t s, const OrbxTrackFrames &F, const float *camera4, float mbf, int fma_mode,
                                const DTrackProb *probs, DTrackQ *q, int nq);
+// k_track_frustum: isInFrustum + PredictScale + the window of the map-point policy for every (problem, point) of a local-points
+// call; thr / scale = the handle's PredictScale thresholds (ORBX_PS_LEVELS entries) and mvScaleFactors
+void orbx_launch_track_frustum(hipStream_t s, const OrbxTrackFrames &F, const float *camera4, float mbf, int fma_mode, int nlevels,
+                               const float *thr, const float *scale, int nproblems, int max_points, const DTrackProb *probs,
+                               const DTrackLocal *locals, const DTrackPoolPt *pool, const uint8_t *pdesc, const int32_t *index,
+                               const uint8_t *skip, DTrackQ *q, uint8_t *qdesc, uint8_t *in_view, orbx_track_state *track);
 // one wave per point: the smallest key (two = the two smallest, map-point policy) of its window -> cand[point]
 void orbx_launch_track_cand(hipStream_t s, bool two, const OrbxTrackFrames &F, const DTrackProb *probs, const DTrackQ *q,
                             const uint8_t *qdesc, int nq, uint4 *cand);

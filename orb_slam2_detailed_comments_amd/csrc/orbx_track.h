@@ -1,7 +1,8 @@
 // orbx_track.h -- batched, device-resident SearchByProjection of the two tracking matchers
-// (orbx_search_by_projection_frame_batch_device / orbx_search_by_projection_mappoints_batch_device): the records the host packs
+// (orbx_search_by_projection_frame_batch_device / orbx_search_by_projection_mappoints_batch_device) and of
+// Tracking::SearchLocalPoints whole (orbx_search_local_points_batch_device): the records the host packs
 // and the kernels read, and the packing / validation unit (orbx_track_pack.cpp).  No HIP in here: the packing unit builds alone
-// (tests/san_track_pack.cpp).
+// (tests/san_track_pack.cpp, tests/san_local_pack.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -47,3 +48,42 @@ void orbx_track_frame_pack(int nproblems, const orbx_track_frame_problem *proble
                            float mb, uint8_t *dst);
 void orbx_track_points_pack(int nproblems, const orbx_track_points_problem *problems, const OrbxTrackPlan &plan, const float *scale,
                             int cap, uint8_t *dst);
+
+// ---- orbx_search_local_points_batch_device: Frame::isInFrustum + MapPoint::PredictScale in front of the map-point policy.
+// One point of the local-map pool, shared by all problems of a call; its descriptor is row `index` of the pool's descriptors.
+struct DTrackPoolPt {
+    float P[3], Pn[3];     // GetWorldPos(), GetNormal()
+    float dmin, dmax;      // mfMinDistance, mfMaxDistance (raw)
+    int32_t obs;           // Observations()
+};
+// What k_track_frustum reads of a problem beside its DTrackProb (frame, q_begin, nq, Rcw, tcw)
+struct DTrackLocal {
+    float Ow[3], th, cos_limit;
+    int32_t pad[3];
+};
+static_assert(sizeof(DTrackPoolPt) == 36 && sizeof(DTrackLocal) == 32, "packed for the device");
+// Layout of one call.  Uploaded block (one copy): problems | their DTrackLocal | pool points | pool descriptors | per query the
+// pool index | per query the skip flag | blocked-feature seeds.  Device only, after it: the queries k_track_frustum writes
+// (DTrackQ) | their gathered descriptors | stored candidates | accept events.
+struct OrbxLocalPlan {
+    int nproblems = 0, seed_words = 0, npool = 0, max_points = 0;
+    size_t nq = 0;
+    size_t o_prob = 0, o_local = 0, o_pool = 0, o_pdesc = 0, o_index = 0, o_skip = 0, o_seed = 0, in_bytes = 0;
+    size_t o_q = 0, o_desc = 0, o_cand = 0, o_ev = 0, dev_bytes = 0;
+};
+orbx_status orbx_track_local_plan(int nproblems, const orbx_track_local_problem *problems, const orbx_local_map_view *map,
+                                  const OrbxTrackBatchArgs &a, OrbxLocalPlan &plan, const char **why);
+void orbx_track_local_pack(int nproblems, const orbx_track_local_problem *problems, const orbx_local_map_view *map,
+                           const OrbxLocalPlan &plan, int cap, uint8_t *dst);
+
+// ---- MapPoint::PredictScale as a table (include/orbx.h: orbx_predict_scale_table).  thr[0] = 0, thr[k] = the smallest positive
+// finite float ratio whose level (int)ceilf(logf(ratio) / logf(scale_factor)) is >= k, +inf where none is; `thr` holds
+// ORBX_PS_LEVELS entries, those from nlevels on are +inf.
+enum { ORBX_PS_LEVELS = 16 };
+void orbx_predict_scale_build(float scale_factor, int nlevels, float *thr);
+// the number of k in [1, nlevels) with ratio >= thr[k]
+static inline int orbx_predict_scale_level(const float *thr, int nlevels, float ratio) {
+    int lvl = 0;
+    for (int k = 1; k < nlevels; ++k) lvl += ratio >= thr[k] ? 1 : 0;
+    return lvl;
+}

@@ -164,6 +164,64 @@ class ORBmatcher:
         check(self._L.orbx_search_by_projection_mappoints_batch_device(
             self._ex.handle, n, arr, *dev, ptr(bounds), float(self.mfNNratio), ptr(d_assigned), ptr(d_nmatches)))
 
+    # ---- Tracking::SearchLocalPoints on the device (include/orbx.h: orbx_search_local_points_batch_device)
+    def PredictScale(self, max_distance, current_dist):
+        """MapPoint::PredictScale(currentDist, &Frame) for a MapPoint whose mfMaxDistance is max_distance: the level from the
+        handle's threshold table (PredictScaleTable), no logarithm.  Host function; works on a host-only handle."""
+        return int(self._L.orbx_predict_scale(self._ex.handle, float(max_distance), float(current_dist)))
+
+    def PredictScaleTable(self):
+        """thr[nlevels]: thr[k] = the smallest mfMaxDistance / dist that PredictScale maps to level >= k (thr[0] = 0)"""
+        thr = np.zeros(self._L.orbx_get_levels(self._ex.handle), np.float32)
+        check(self._L.orbx_predict_scale_table(self._ex.handle, ptr(thr), len(thr)))
+        return thr
+
+    def SearchLocalPointsBatchDevice(self, problems, local_map, batch, *, K, mbf, d_assigned, d_nmatches, d_in_view=None,
+                                     d_track=None):
+        """Tracking::SearchLocalPoints for many problems in one asynchronous call: Frame::isInFrustum + PredictScale per
+        (problem, point), then SearchByProjection(F, vpMapPoints, th), all on the device.  local_map: dict of the pool's
+        world_pos [M,3], normal [M,3], min_distance, max_distance (raw mfMinDistance / mfMaxDistance), mp_desc [M,32],
+        observations (or None: no pool).  problems: dicts frame, th, Tcw, Ow and optionally viewing_cos_limit (0.5),
+        point_index (pool indices in list order; None: the whole pool), skip, frame_observations.  Host arrays are consumed before
+        the call returns.  d_in_view (uint8) / d_track (_capi.TRACK_STATE_DTYPE records) hold one entry per listed point,
+        problem after problem."""
+        import ctypes as C
+        n = len(problems)
+        keep = []
+        mv = None
+        M = 0
+        if local_map is not None:
+            a = [np.ascontiguousarray(local_map[k], t) for k, t in (("world_pos", np.float32), ("normal", np.float32),
+                                                                     ("min_distance", np.float32), ("max_distance", np.float32),
+                                                                     ("mp_desc", np.uint8), ("observations", np.int32))]
+            keep += a
+            mv = _capi.LocalMapView()
+            M = mv.n = len(a[2])
+            mv.world_pos, mv.normal, mv.min_distance, mv.max_distance, mv.desc, mv.observations = (
+                x.ctypes.data if x.size else None for x in a)
+        arr = (_capi.TrackLocalProblem * max(n, 1))()
+        for P, p in zip(arr, problems):
+            P.frame, P.th, P.viewing_cos_limit = int(p["frame"]), float(p["th"]), float(p.get("viewing_cos_limit", 0.5))
+            P.Tcw[:] = [float(v) for v in np.asarray(p["Tcw"], np.float32).reshape(16)]
+            P.Ow[:] = [float(v) for v in np.asarray(p["Ow"], np.float32).reshape(3)]
+            P.npoints = M
+            if p.get("point_index") is not None:
+                pi = np.ascontiguousarray(p["point_index"], np.int32)
+                keep.append(pi); P.npoints = len(pi); P.point_index = pi.ctypes.data if len(pi) else None
+            if p.get("skip") is not None:
+                sk = np.ascontiguousarray(p["skip"], np.uint8)
+                assert len(sk) == P.npoints, "skip holds one flag per listed point"
+                keep.append(sk); P.skip = sk.ctypes.data if len(sk) else None
+            if p.get("frame_observations") is not None:
+                fo = np.ascontiguousarray(p["frame_observations"], np.int32)
+                assert len(fo) >= int(batch["cap"]), "frame_observations holds cap entries"
+                keep.append(fo); P.frame_observations = fo.ctypes.data
+        bounds, dev = self._batch_args(batch)
+        cam = np.asarray(K, np.float32)
+        check(self._L.orbx_search_local_points_batch_device(
+            self._ex.handle, n, arr, C.byref(mv) if mv is not None else None, *dev, ptr(cam), ptr(bounds), float(mbf),
+            float(self.mfNNratio), ptr(d_assigned), ptr(d_nmatches), ptr(d_in_view), ptr(d_track)))
+
     # ---- BoW-guided policies (src/ORBmatcher.cc:248-410, 722-866, 879-1087)
     @staticmethod
     def _featvec(fv, keep):
