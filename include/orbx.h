@@ -362,6 +362,42 @@ orbx_status orbx_search_local_points_batch_device(orbx_handle *h, int nproblems,
                                                   float nnratio, int32_t *d_assigned, int32_t *d_nmatches, uint8_t *d_in_view,
                                                   orbx_track_state *d_track);
 
+/* ---- MapPoint::ComputeDistinctiveDescriptors / MapPoint::UpdateNormalAndDepth for the loops that end with them
+ * (LocalMapping::ProcessNewKeyFrame, CreateNewMapPoints, SearchInNeighbors, LoopClosing::CorrectLoop, the keyframe insertion of
+ * Tracking): inside these loops the points are independent, so one ragged batch equals the loop.  Point p owns the rows
+ * obs_begin[p] .. obs_begin[p + 1] (obs_begin[0] == 0, npoints + 1 entries, not decreasing); N is their count.
+ *
+ * Descriptors (src/MapPoint.cc:468-515; kernels k_mp_distinct for N <= 16, four points per wave, and k_mp_distinct_wide, one
+ * workgroup per point, for every other N): D[i][j] = popcount(row i ^ row j), D[i][i] = 0 belongs to row i; median_i = element
+ * (N - 1) / 2 of row i sorted ascending; best_idx = the FIRST i with the smallest median.  The rows are those of the caller's
+ * std::map<KeyFrame*, size_t> in ITS iteration order with the bad keyframes already left out: the order decides between equal
+ * medians, so it is part of the contract.  N == 0: best_idx = best_median = -1 and the best_desc row is left as it was.
+ * best_median and best_desc may be NULL.  The _device form names the rows instead of copying them: row t is
+ * d_pool[obs_row[t]], d_pool a device buffer of pool_rows x 32 bytes, 16-byte aligned, whose contents are complete with respect to the handle's
+ * stream when the call is made; the results still land on the host.
+ *
+ * Normal and depth (src/MapPoint.cc:570-638 with cv::Mat's arithmetic as tests/compat_runtime/opencv2/core/core.hpp states it;
+ * kernel k_mp_normal_depth, sixteen lanes per point): for every row in order, bad keyframes INCLUDED, d = pos - center (float),
+ * nrm = sqrt(d.d) summed in double in element order, normal = normal + (float)((double)d / nrm) one float addition per row in
+ * row order; then dist = (float)norm(pos - ref_center), max_distance = dist * mvScaleFactors[ref_level], min_distance =
+ * max_distance / mvScaleFactors[nlevels - 1], normal = (float)((double)normal / (double)N).  The scale factors are the
+ * handle's (orbx_get_scale_tables).  No multiply-add pair occurs: both fp_modes give the same bits.  N == 0: the point's
+ * normal / min_distance / max_distance are left as they were and its ref_level is not looked at.
+ *
+ * All three: synchronous, on the handle's stream; one upload from one page-locked block, the launches, one download.
+ * Validated before any device work (a host-only handle can be used to test a call): ORBX_BAD_ARGUMENT for npoints < 0, a NULL
+ * required pointer, obs_begin[0] != 0 or a decreasing obs_begin, pool_rows < 0, an obs_row outside [0, pool_rows), a d_pool
+ * that is not 16-byte aligned, a ref_level outside [0, nlevels) on a point with rows.  npoints == 0 succeeds and does nothing;
+ * well-formed input on a host-only handle returns ORBX_NO_DEVICE. */
+orbx_status orbx_distinctive_descriptors_batch(orbx_handle *h, int npoints, const int32_t *obs_begin, const uint8_t *desc,
+                                               int32_t *best_idx, int32_t *best_median, uint8_t *best_desc);
+orbx_status orbx_distinctive_descriptors_batch_device(orbx_handle *h, const uint8_t *d_pool, int64_t pool_rows, int npoints,
+                                                      const int32_t *obs_begin, const int64_t *obs_row, int32_t *best_idx,
+                                                      int32_t *best_median, uint8_t *best_desc);
+orbx_status orbx_update_normal_and_depth_batch(orbx_handle *h, int npoints, const int32_t *obs_begin, const float *pos,
+                                               const float *centers, const float *ref_center, const int32_t *ref_level,
+                                               float *normal, float *min_distance, float *max_distance);
+
 /* ---- BoW-guided policies.  Host code keeps the pointer chasing (KeyFrame / MapPoint /
  * DBoW2 containers) and hands the fields the policies read as arrays; the Hamming distances come from the GPU, the
  * order-dependent selection runs on the host exactly as the reference does. */

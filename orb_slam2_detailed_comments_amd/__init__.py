@@ -9,3 +9,5 @@ from .matcher import ORBmatcher  # noqa: F401
 from .frame import Frame, depth_map_factor  # noqa: F401
 from .vocabulary import ORBVocabulary  # noqa: F401
 from .keyframe_db import KeyFrameDatabase, bow_score  # noqa: F401
+from .mappoint import (distinctive_descriptors_batch, distinctive_descriptors_batch_device,  # noqa: F401
+                       update_normal_and_depth_batch)

@@ -128,6 +128,7 @@ SYMBOLS = [
     "orbx_vocabulary_scoring", "orbx_bow_score", "orbx_kfdb_create", "orbx_kfdb_destroy", "orbx_kfdb_clear", "orbx_kfdb_size",
     "orbx_kfdb_add", "orbx_kfdb_erase", "orbx_kfdb_score_entries", "orbx_kfdb_query_reloc", "orbx_kfdb_query_loop",
     "orbx_kfdb_query_matches", "orbx_kfdb_query_touched", "orbx_kfdb_select_groups", "orbx_kfdb_state",
+    "orbx_distinctive_descriptors_batch", "orbx_distinctive_descriptors_batch_device", "orbx_update_normal_and_depth_batch",
 ]
 
 _lib = None
@@ -167,6 +168,12 @@ def lib():
     L.orbx_match_bruteforce_device.argtypes = [vp, i32, vp, vp, i64, vp, vp, i64, vp, vp, vp, i32]
     L.orbx_match_bruteforce.restype = i32; L.orbx_match_bruteforce.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp]
     L.orbx_hamming_matrix.restype = i32; L.orbx_hamming_matrix.argtypes = [vp, vp, i32, vp, i32, vp]
+    L.orbx_distinctive_descriptors_batch.restype = i32
+    L.orbx_distinctive_descriptors_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.orbx_distinctive_descriptors_batch_device.restype = i32
+    L.orbx_distinctive_descriptors_batch_device.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp]
+    L.orbx_update_normal_and_depth_batch.restype = i32
+    L.orbx_update_normal_and_depth_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_get_stream.restype = vp; L.orbx_get_stream.argtypes = [vp]
     L.orbx_set_stream.restype = i32; L.orbx_set_stream.argtypes = [vp, vp]
     L.orbx_synchronize.restype = i32; L.orbx_synchronize.argtypes = [vp]

@@ -13,8 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liborbx.so")
-SOURCES = ["orbx_kernels.hip", "orbx_api.cpp", "orbx_geometry.cpp", "orbx_policies.cpp", "orbx_kfdb.cpp", "orbx_track_pack.cpp"]
-HEADERS = ["orbx_device.h", "orbx_inplace.h", "orbx_internal.h", "orbx_launch.h", "orbx_sincos.h", "orbx_track.h",
+SOURCES = ["orbx_kernels.hip", "orbx_api.cpp", "orbx_geometry.cpp", "orbx_policies.cpp", "orbx_kfdb.cpp", "orbx_track_pack.cpp",
+           "orbx_mappoint.cpp"]
+HEADERS = ["orbx_device.h", "orbx_inplace.h", "orbx_internal.h", "orbx_launch.h", "orbx_sincos.h", "orbx_track.h", "orbx_mappoint.h",
            os.path.join("..", "..", "include", "orbx.h"), os.path.join("..", "..", "include", "orbx_pattern_data.h")]
 
 
@@ -24,7 +25,8 @@ def kernels_hash():
     kernels or other launch plans read as 'not measured' in bench.py instead of as stale numbers"""
     import hashlib
     h = hashlib.sha256()
-    for f in ("orbx_kernels.hip", "orbx_device.h", "orbx_api.cpp", "orbx_launch.h", "orbx_internal.h", "orbx_track.h"):
+    for f in ("orbx_kernels.hip", "orbx_device.h", "orbx_api.cpp", "orbx_launch.h", "orbx_internal.h", "orbx_track.h",
+              "orbx_mappoint.h", "orbx_mappoint.cpp"):
         h.update(open(os.path.join(CSRC, f), "rb").read())
     return h.hexdigest()[:16]
 

@@ -2330,6 +2330,85 @@ extern "C" orbx_status orbx_search_local_points_batch_device(orbx_handle *h, int
     return ORBX_OK;
 }
 
+// ---------------------------------------------------------------- MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth,
+// batched (orbx_mappoint.h).  One call: validation and plan (orbx_mappoint.cpp), the caller's arrays packed into the page-locked
+// block of the tracking matchers, ONE upload, the launches on the handle's stream, ONE download into the same block, the wait,
+// and the scatter into the caller's arrays.
+static orbx_status mp_run_begin(orbx_handle *h, size_t in_bytes, size_t out_bytes, size_t dev_bytes, uint8_t **pin, uint8_t **dev) {
+    OrbxTrackPlan stage;
+    stage.in_bytes = std::max(in_bytes, out_bytes); stage.dev_bytes = dev_bytes;
+    return track_stage(h, stage, pin, dev);
+}
+static orbx_status mp_run_end(orbx_handle *h, uint8_t *pin, const uint8_t *d_out, size_t out_bytes) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(pin, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
+    return ORBX_OK;
+}
+static orbx_status mp_distinct(orbx_handle *h, bool device_form, const uint8_t *d_pool, int64_t pool_rows, int npoints,
+                               const int32_t *obs_begin, const uint8_t *desc, const int64_t *obs_row, int32_t *best_idx,
+                               int32_t *best_median, uint8_t *best_desc) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxMpPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_mp_distinct_plan(npoints, obs_begin, desc, device_form, d_pool, pool_rows, obs_row, best_idx, plan, &why);
+    if (st != ORBX_OK) return fail(st, why);
+    if (npoints == 0) return ORBX_OK;
+    if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = mp_run_begin(h, plan.in_bytes, plan.out_bytes, plan.dev_bytes, &pin, &d);
+    if (st != ORBX_OK) return st;
+    if (plan.n_small + plan.n_wide > 0) {
+        orbx_mp_distinct_pack(obs_begin, desc, device_form ? obs_row : nullptr, plan, pin);
+        HIPCHK(hipMemcpyAsync(d, pin, plan.in_bytes, hipMemcpyHostToDevice, h->stream));
+        { ProfScope ps(h, ORBX_K_MATCH);
+          orbx_launch_mp_distinct(h->stream, (const int32_t *)(d + plan.o_begin), device_form ? d_pool : d + plan.o_rows,
+                                  device_form ? (const int64_t *)(d + plan.o_rows) : nullptr, (const int32_t *)(d + plan.o_order),
+                                  plan.n_small, plan.n_wide, (int32_t *)(d + plan.o_idx), (int32_t *)(d + plan.o_med),
+                                  d + plan.o_desc); }
+        st = mp_run_end(h, pin, d + plan.o_idx, plan.out_bytes);
+        if (st != ORBX_OK) return st;
+    }
+    orbx_mp_distinct_unpack(obs_begin, plan, pin, best_idx, best_median, best_desc);   // (reads no entry of a point without rows)
+    return ORBX_OK;
+}
+extern "C" orbx_status orbx_distinctive_descriptors_batch(orbx_handle *h, int npoints, const int32_t *obs_begin, const uint8_t *desc,
+                                                          int32_t *best_idx, int32_t *best_median, uint8_t *best_desc) {
+    return mp_distinct(h, false, nullptr, 0, npoints, obs_begin, desc, nullptr, best_idx, best_median, best_desc);
+}
+extern "C" orbx_status orbx_distinctive_descriptors_batch_device(orbx_handle *h, const uint8_t *d_pool, int64_t pool_rows, int npoints,
+                                                                 const int32_t *obs_begin, const int64_t *obs_row, int32_t *best_idx,
+                                                                 int32_t *best_median, uint8_t *best_desc) {
+    return mp_distinct(h, true, d_pool, pool_rows, npoints, obs_begin, nullptr, obs_row, best_idx, best_median, best_desc);
+}
+extern "C" orbx_status orbx_update_normal_and_depth_batch(orbx_handle *h, int npoints, const int32_t *obs_begin, const float *pos,
+                                                          const float *centers, const float *ref_center, const int32_t *ref_level,
+                                                          float *normal, float *min_distance, float *max_distance) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxMpNormalPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_mp_normal_plan(npoints, obs_begin, pos, centers, ref_center, ref_level, h->p.nlevels, normal, min_distance,
+                                         max_distance, plan, &why);
+    if (st != ORBX_OK) return fail(st, why);
+    if (npoints == 0) return ORBX_OK;
+    if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
+    if (plan.nrows == 0) return ORBX_OK;                             // no point has rows: nothing is written
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = mp_run_begin(h, plan.in_bytes, plan.out_bytes, plan.dev_bytes, &pin, &d);
+    if (st != ORBX_OK) return st;
+    orbx_mp_normal_pack(obs_begin, pos, centers, ref_center, ref_level, h->tab.scale, plan, pin);
+    HIPCHK(hipMemcpyAsync(d, pin, plan.in_bytes, hipMemcpyHostToDevice, h->stream));
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_mp_normal_depth(h->stream, (const int32_t *)(d + plan.o_begin), (const DMpPoint *)(d + plan.o_points),
+                                  (const float *)(d + plan.o_centers), npoints, h->tab.scale[h->p.nlevels - 1],
+                                  (float *)(d + plan.o_out)); }
+    st = mp_run_end(h, pin, d + plan.o_out, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    orbx_mp_normal_unpack(obs_begin, plan, pin, normal, min_distance, max_distance);
+    return ORBX_OK;
+}
+
 // ---------------------------------------------------------------- (f)3: DBoW2 transform (Frame::ComputeBoW, src/Frame.cc:750-765)
 // TemplatedVocabulary<FORB>::transform(features, BowVector&, FeatureVector&, levelsup)
 // (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1136-1216): the tree descent of every descriptor runs on the GPU

@@ -3824,6 +3824,185 @@ __global__ __launch_bounds__(256) void k_kfdb_score_slots(const uint32_t *__rest
 }
 
 // ------------------------------------------------------------------------------------------------
+// MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth over a ragged batch of points (orbx_mappoint.h)
+// ------------------------------------------------------------------------------------------------
+#include "orbx_mappoint.h"
+// rows: obs_row == nullptr: row t is desc + 32 t (the uploaded block); otherwise desc is the caller's pool and row t is
+// desc + 32 obs_row[t].  Either way 16-byte aligned.
+struct DMpDistinct {
+    const int32_t *obs_begin; const uint8_t *desc; const int64_t *obs_row;
+    const int32_t *order; int count;          // the points of this launch
+    int32_t *best_idx, *best_median; uint4 *best_desc;
+};
+__device__ __forceinline__ const uint4 *mp_row(const DMpDistinct &A, long long t) {
+    return (const uint4 *)(A.desc + 32 * (A.obs_row ? (long long)A.obs_row[t] : t));
+}
+__device__ __forceinline__ uint32_t mp_dist(const uint4 &qa, const uint4 &qb, const uint4 &ta, const uint4 &tb) {
+    return __popc(qa.x ^ ta.x) + __popc(qa.y ^ ta.y) + __popc(qa.z ^ ta.z) + __popc(qa.w ^ ta.w) +
+           __popc(qb.x ^ tb.x) + __popc(qb.y ^ tb.y) + __popc(qb.z ^ tb.z) + __popc(qb.w ^ tb.w);
+}
+// N <= ORBX_MP_GROUP = 16: a group of 16 lanes serves a point, four points per wave.  Lane i owns row i of D: its descriptor
+// in registers, the others broadcast from LDS, the row packed two distances per register (0xffff beyond N, above every
+// threshold).  Distances are at most 256, so the median needs no sort: it is the smallest v with count(D[i][.] <= v) >=
+// (N - 1) / 2 + 1, found in nine bisection steps over [0, 256].  BestIdx = the group minimum of median << 22 | i: the first of
+// equal medians wins, as the reference's strict `<` has it.  Every lane runs to the end (the row reduction wants whole rows).
+__global__ __launch_bounds__(256) void k_mp_distinct(DMpDistinct A) {
+    __shared__ uint4 s_lo[256], s_hi[256];
+    const int tid = threadIdx.x, i = tid & (ORBX_MP_GROUP - 1), g0 = tid & ~(ORBX_MP_GROUP - 1);
+    const int slot = blockIdx.x * (256 / ORBX_MP_GROUP) + (tid >> 4);
+    int p = -1, N = 0;
+    long long b = 0;
+    if (slot < A.count) {
+        p = A.order[slot];
+        b = A.obs_begin[p];
+        N = min(A.obs_begin[p + 1] - (int)b, (int)ORBX_MP_GROUP);   // the plan sends no larger point here
+    }
+    uint4 qa = make_uint4(0, 0, 0, 0), qb = qa;
+    if (i < N) { const uint4 *r = mp_row(A, b + i); qa = r[0]; qb = r[1]; }
+    s_lo[tid] = qa; s_hi[tid] = qb;
+    orbx_wave_sync();                                               // a group lies inside one wave
+    uint32_t dd[ORBX_MP_GROUP / 2];
+#pragma unroll
+    for (int w = 0; w < ORBX_MP_GROUP / 2; ++w) {
+        const uint32_t d0 = mp_dist(qa, qb, s_lo[g0 + 2 * w], s_hi[g0 + 2 * w]);
+        const uint32_t d1 = mp_dist(qa, qb, s_lo[g0 + 2 * w + 1], s_hi[g0 + 2 * w + 1]);
+        dd[w] = (2 * w < N ? d0 : 0xffffu) | (2 * w + 1 < N ? d1 : 0xffffu) << 16;
+    }
+    const uint32_t need = (uint32_t)((N - 1) >> 1) + 1u;
+    uint32_t lo = 0, hi = 256;
+#pragma unroll 1
+    for (int step = 0; step < 9; ++step) {                          // 257 values: nine halvings; lo == hi stays put
+        const uint32_t mid = (lo + hi) >> 1;
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int w = 0; w < ORBX_MP_GROUP / 2; ++w) cnt += ((dd[w] & 0xffffu) <= mid ? 1u : 0u) + ((dd[w] >> 16) <= mid ? 1u : 0u);
+        const bool ge = cnt >= need;
+        hi = ge ? mid : hi;
+        lo = ge ? lo : mid + 1;
+    }
+    uint32_t key = i < N ? lo << 22 | (uint32_t)i : 0xffffffffu;
+    key = orbx_row16_min(key);
+    if (p >= 0 && N > 0) {
+        const int best = (int)(key & 0x3fffffu);
+        if (i == 0) { A.best_idx[p] = best; A.best_median[p] = (int)(key >> 22); }
+        if (i == 1) A.best_desc[2 * (long long)p] = s_lo[g0 + best];
+        if (i == 2) A.best_desc[2 * (long long)p + 1] = s_hi[g0 + best];
+    }
+}
+// Every other N: one workgroup per point, one wave per row i of D (rows i = wave, wave + 4, ...), lane l holding D[i][64 s + l]
+// in register s.  The count of a bisection step is a sum of ballots, so the bisection is wave-uniform.  The point's descriptors
+// are staged in LDS as two planes of 16 bytes (consecutive lanes read consecutive slots) while N <= ORBX_MP_LDS_ROWS; a larger
+// point keeps nothing and recomputes its row from global memory in each step, which is correct for any N.
+__global__ __launch_bounds__(256) void k_mp_distinct_wide(DMpDistinct A) {
+    __shared__ uint4 s_lo[ORBX_MP_LDS_ROWS], s_hi[ORBX_MP_LDS_ROWS];
+    __shared__ unsigned long long s_key[4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if ((int)blockIdx.x >= A.count) return;
+    const int p = A.order[blockIdx.x];
+    const long long b = A.obs_begin[p];
+    const int N = A.obs_begin[p + 1] - (int)b;
+    if (N <= 0) return;                                             // (uniform; the plan sends no such point)
+    const bool staged = N <= ORBX_MP_LDS_ROWS;
+    if (staged)
+        for (int r = tid; r < N; r += 256) { const uint4 *g = mp_row(A, b + r); s_lo[r] = g[0]; s_hi[r] = g[1]; }
+    __syncthreads();
+    const uint32_t need = (uint32_t)((N - 1) >> 1) + 1u;
+    const int ns = (N + 63) >> 6;
+    unsigned long long best = ~0ull;
+    for (int i = wave; i < N; i += 4) {
+        uint32_t lo = 0, hi = 256;
+        if (staged) {
+            const uint4 qa = s_lo[i], qb = s_hi[i];
+            uint32_t dd[ORBX_MP_SLOTS];
+#pragma unroll
+            for (int s = 0; s < ORBX_MP_SLOTS; ++s) {
+                dd[s] = 0xffffu;
+                if (s < ns) {
+                    const int j = s * 64 + lane;
+                    if (j < N) dd[s] = mp_dist(qa, qb, s_lo[j], s_hi[j]);
+                }
+            }
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                uint32_t cnt = 0;
+#pragma unroll
+                for (int s = 0; s < ORBX_MP_SLOTS; ++s)
+                    if (s < ns) cnt += (uint32_t)__popcll(orbx_ballot(dd[s] <= mid));
+                if (cnt >= need) hi = mid; else lo = mid + 1;
+            }
+        } else {
+            const uint4 *q = mp_row(A, b + i);
+            const uint4 qa = q[0], qb = q[1];
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                uint32_t cnt = 0;
+                for (int j0 = 0; j0 < N; j0 += 64) {
+                    const int j = j0 + lane;
+                    bool le = false;
+                    if (j < N) { const uint4 *t = mp_row(A, b + j); le = mp_dist(qa, qb, t[0], t[1]) <= mid; }
+                    cnt += (uint32_t)__popcll(orbx_ballot(le));
+                }
+                if (cnt >= need) hi = mid; else lo = mid + 1;
+            }
+        }
+        const unsigned long long key = (unsigned long long)lo << 32 | (uint32_t)i;
+        best = key < best ? key : best;                             // rows ascend per wave; the minimum over waves is taken below
+    }
+    if (lane == 0) s_key[wave] = best;
+    __syncthreads();
+    best = s_key[0];
+    for (int w = 1; w < 4; ++w) best = s_key[w] < best ? s_key[w] : best;
+    const int bi = (int)(uint32_t)best;
+    if (tid == 0) { A.best_idx[p] = bi; A.best_median[p] = (int)(best >> 32); }
+    if (tid == 1 || tid == 2) A.best_desc[2 * (long long)p + (tid - 1)] = mp_row(A, b + bi)[tid - 1];
+}
+// MapPoint::UpdateNormalAndDepth: sixteen lanes per point.  The lanes compute sixteen rows' unit vectors side by side (the
+// double square root and divisions are the correctly rounded sequences, as in k_kfdb_score); every lane of the group then adds
+// them to its copy of `normal` one after the other in row order: float addition is not associative, so no tree.
+__global__ __launch_bounds__(256) void k_mp_normal_depth(const int32_t *__restrict__ obs_begin, const DMpPoint *__restrict__ pts,
+                                                         const float *__restrict__ centers, int npoints, float scale_last,
+                                                         float *__restrict__ out) {
+    const int tid = threadIdx.x, i = tid & 15;
+    const int p = blockIdx.x * 16 + (tid >> 4);
+    if (p >= npoints) return;                                       // whole groups leave; the shuffles below stay inside a group
+    const long long b = obs_begin[p];
+    const int N = obs_begin[p + 1] - (int)b;
+    if (N <= 0) return;
+    const DMpPoint P = pts[p];
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    for (int j0 = 0; j0 < N; j0 += 16) {
+        const int j = j0 + i;
+        float tx = 0.f, ty = 0.f, tz = 0.f;
+        if (j < N) {
+            const float *c = centers + 3 * (b + j);
+            const float dx = P.pos[0] - c[0], dy = P.pos[1] - c[1], dz = P.pos[2] - c[2];
+            double s = 0.0;                                         // cv::norm: a double sum in element order
+            s += (double)dx * (double)dx; s += (double)dy * (double)dy; s += (double)dz * (double)dz;
+            const double nrm = sqrt(s);
+            tx = (float)((double)dx / nrm); ty = (float)((double)dy / nrm); tz = (float)((double)dz / nrm);
+        }
+        const int cnt = min(16, N - j0);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const float vx = __shfl(tx, k, 16), vy = __shfl(ty, k, 16), vz = __shfl(tz, k, 16);
+            if (k < cnt) { nx = nx + vx; ny = ny + vy; nz = nz + vz; }
+        }
+    }
+    if (i == 0) {
+        const float dx = P.pos[0] - P.ref[0], dy = P.pos[1] - P.ref[1], dz = P.pos[2] - P.ref[2];
+        double s = 0.0;
+        s += (double)dx * (double)dx; s += (double)dy * (double)dy; s += (double)dz * (double)dz;
+        const float dist = (float)sqrt(s);
+        const float maxd = dist * P.level_scale;
+        float *o = out + 5 * (long long)p;
+        o[0] = (float)((double)nx / (double)N); o[1] = (float)((double)ny / (double)N); o[2] = (float)((double)nz / (double)N);
+        o[3] = maxd / scale_last;
+        o[4] = maxd;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // launch wrappers (called from orbx_api.cpp)
 // ------------------------------------------------------------------------------------------------
 #include "orbx_launch.h"
@@ -4229,4 +4408,18 @@ void orbx_launch_kfdb_score_slots(hipStream_t s, const uint32_t *slot_list, int 
     if (g > 8192) g = 8192;
     hipLaunchKernelGGL(k_kfdb_score_slots, dim3(g), dim3(256), 0, s, slot_list, n, slots, pool_w, pool_v, qw, qv, nq, scoring,
                        fma_mode, out);
+}
+void orbx_launch_mp_distinct(hipStream_t s, const int32_t *obs_begin, const uint8_t *desc, const int64_t *obs_row,
+                             const int32_t *order, int n_small, int n_wide, int32_t *best_idx, int32_t *best_median,
+                             uint8_t *best_desc) {
+    DMpDistinct A = {obs_begin, desc, obs_row, order, n_small, best_idx, best_median, (uint4 *)best_desc};
+    const int per_block = 256 / ORBX_MP_GROUP;
+    if (n_small > 0) hipLaunchKernelGGL(k_mp_distinct, dim3((n_small + per_block - 1) / per_block), dim3(256), 0, s, A);
+    A.order = order + n_small; A.count = n_wide;
+    if (n_wide > 0) hipLaunchKernelGGL(k_mp_distinct_wide, dim3(n_wide), dim3(256), 0, s, A);
+}
+void orbx_launch_mp_normal_depth(hipStream_t s, const int32_t *obs_begin, const DMpPoint *pts, const float *centers, int npoints,
+                                 float scale_last, float *out) {
+    if (npoints <= 0) return;
+    hipLaunchKernelGGL(k_mp_normal_depth, dim3((npoints + 15) / 16), dim3(256), 0, s, obs_begin, pts, centers, npoints, scale_last, out);
 }

@@ -4,6 +4,7 @@
 #include "orbx_device.h"
 #include "orbx_inplace.h"
 #include "orbx_track.h"
+#include "orbx_mappoint.h"
 
 hipError_t orbx_upload_pattern();
 size_t orbx_quadtree_smem(int ncap, int lds_keys);
@@ -87,6 +88,14 @@ void orbx_launch_track_cand(hipStream_t s, bool two, const OrbxTrackFrames &F, c
 void orbx_launch_track_select(hipStream_t s, bool mp, const OrbxTrackFrames &F, int nproblems, const DTrackProb *probs, const DTrackQ *q,
                               const uint8_t *qdesc, const uint4 *cand, const uint32_t *seed, float nnratio, int check, int32_t *ev,
                               int32_t *out, int32_t *nmatches);
+// batched MapPoint refresh (orbx_mappoint.h).  order = the points with rows, n_small of the lane-group class (k_mp_distinct) and
+// behind them n_wide of the workgroup class (k_mp_distinct_wide); obs_row == nullptr: row t is desc + 32 t, otherwise desc is the
+// pool and row t is desc + 32 obs_row[t].  out = 5 floats per point (normal, min_distance, max_distance).
+void orbx_launch_mp_distinct(hipStream_t s, const int32_t *obs_begin, const uint8_t *desc, const int64_t *obs_row,
+                             const int32_t *order, int n_small, int n_wide, int32_t *best_idx, int32_t *best_median,
+                             uint8_t *best_desc);
+void orbx_launch_mp_normal_depth(hipStream_t s, const int32_t *obs_begin, const DMpPoint *pts, const float *centers, int npoints,
+                                 float scale_last, float *out);
 void orbx_launch_hamming_matrix(hipStream_t s, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *dist);
 
 void orbx_launch_stereo_batch(hipStream_t s, const OrbxStereoGeom &sg, int npairs, int cap, const orbx_keypoint *kL,
