@@ -725,6 +725,69 @@ orbx_status orbx_debug_blur_copy(orbx_handle *h, int frame, int level, uint8_t *
 /* FAST groups (waves' work items of k_fast_rows) per frame of the configured geometry: those of level 0, and all of them */
 orbx_status orbx_debug_fast_groups(orbx_handle *h, int *level0, int *total);
 
+/* ---- Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:363-607), the reader of the tracking matchers' rows
+ * (TrackWithMotionModel, TrackReferenceKeyFrame, TrackLocalMap, Relocalization), for many (frame, pose, matches) problems in
+ * one call: one 6-DoF vertex, unary mono / stereo edges in feature order, four rounds of at most ten Levenberg-Marquardt
+ * iterations of at most ten trials, inlier test after each round (k_pose_opt: one wave per problem).
+ * CONTRACT: the device rows equal the library's host path (ORBX_POSE=host in the environment, read per call; host-only handles)
+ * and the numpy restatement tests/pose_model.py bit for bit, in both fp_modes.  Parity with a g2o + Eigen build is NOT pinned:
+ * DESIGN.md section 2 (F11) lists what follows the reference's source and every order of arithmetic this library fixes where
+ * the reference leaves it to Eigen or libm (sums per edge and across edges, the 6x6 solve, powers, sin / cos).
+ * The frames are read where the device batch left them (d_keys_un / d_u_right / d_counts as for the tracking matchers,
+ * d_u_right == NULL: every edge monocular; mvuRight[i] < 0 is a monocular edge).  Row k of d_point ([nproblems][cap]) gives per
+ * feature of problem k's frame -1 (no MapPoint) or the position of its MapPoint in the problem's list: a d_assigned row of
+ * orbx_search_by_projection_mappoints_batch_device / orbx_search_local_points_batch_device is accepted as it stands (with the
+ * same point_index); a d_matched_last row of orbx_search_by_projection_frame_batch_device maps the other way (last-frame point
+ * -> current feature) and has to be inverted by the caller first.  The pool of world positions (host, 3 floats per point) is
+ * uploaded once per call and shared by all problems; point_index == NULL: list position = pool index (npoints <= npool).
+ * Results, on the device: d_Tcw row k = the optimised pose (Converter::toCvMat), d_outlier[k][i] = mvbOutlier[i] for every
+ * feature i < min(count, cap) that has a MapPoint (other entries are not written), d_ninliers[k] = the return value.  Fewer
+ * than 3 correspondences: d_ninliers[k] = 0, the d_Tcw row is NOT written (the reference returns before SetPose) and the outlier
+ * entries of features with a MapPoint are 0, as the reference leaves them.  Asynchronous on the handle's stream, one
+ * page-locked staging block consumed before the call returns, nothing downloaded.  Several problems may name one frame.
+ * Validated before any device work: ORBX_BAD_ARGUMENT for nproblems < 0, a null array, a frame outside [0, nframes), cap <= 0,
+ * npoints < 0, a point_index entry outside the pool; ORBX_UNSUPPORTED for cap > 65535.  The host cannot see device rows: a
+ * d_point entry >= npoints or an octave outside [0, nlevels) makes the kernel treat that feature as one without a MapPoint (no
+ * read leaves the pool or the level table); where the rows are host arrays (orbx_pose_optimization, host-only handles) both are
+ * ORBX_BAD_ARGUMENT and nothing is written.  nproblems == 0 launches nothing.
+ * On a host-only handle (device = -2) every "d_" argument is a HOST array and the host path runs.
+ * OUTSIDE the contract: a point at z = 0 in the camera frame or non-finite input gives non-finite terms in the reference too.
+ * The rule here: the same bounded loops run, a trial whose chi2 is not finite is never accepted (g2o_isfinite(tempChi)), a
+ * 6x6 system with a pivot that is not positive and finite counts as a failed solve (chi2 = DBL_MAX, the step is rejected), and
+ * a NaN chi2 in the inlier test compares as "not greater" (inlier), as the reference's float comparison does.  A point behind
+ * the camera with finite terms is inside the contract. */
+typedef struct orbx_pose_problem {
+    int32_t frame;              /* this frame of the device batch */
+    float   Tcw[16];            /* pFrame->mTcw on entry, row major */
+    const int32_t *point_index; /* optional: list position -> pool index (as orbx_track_local_problem) */
+    int32_t npoints;
+} orbx_pose_problem;
+orbx_status orbx_pose_optimization_batch_device(orbx_handle *h, int nproblems, const orbx_pose_problem *problems, int npool,
+                                                const float *world_pos, int nframes, const orbx_keypoint *d_keys_un,
+                                                const float *d_u_right, const int32_t *d_counts, int cap, const int32_t *d_point,
+                                                const float *camera4, float mbf, const float *inv_level_sigma2, int nlevels,
+                                                float *d_Tcw, uint8_t *d_outlier, int32_t *d_ninliers);
+/* One frame, host arrays in and out, run on the library's host path (measured: one problem per call takes 0.24-3.3 ms on the
+ * device against 53-586 us on the host path, profiles/pose_batch.md); works on a host-only handle.  point[i] = -1 or the pool index of feature i's MapPoint; Tcw is read
+ * and, with at least 3 correspondences, overwritten; outlier[n]; *ninliers = the return value of the reference. */
+orbx_status orbx_pose_optimization(orbx_handle *h, float *Tcw, int n, const orbx_keypoint *keys_un, const float *u_right,
+                                   const int32_t *point, int npool, const float *world_pos, const float *camera4, float mbf,
+                                   const float *inv_level_sigma2, int nlevels, uint8_t *outlier, int32_t *ninliers);
+/* Parity tests only: the inlier test that ends a round (src/Optimizer.cc:534-592), alone, for the problems of a call shaped like
+ * orbx_pose_optimization_batch_device.  Tcw_est / Tcw_last: host, [nproblems][16], the estimate and the pose at which
+ * computeActiveErrors ran last (after a rejected trial the two differ, and the edges keep the rejected trial's errors).  Row k of
+ * d_outlier holds the flags on entry (0 / 1 where a MapPoint exists): a flagged edge is tested at Tcw_est, every other edge at
+ * Tcw_last; the new flags are written back and d_ninliers[k] = edges - flagged.  Device path, ORBX_POSE=host and host-only
+ * handles as for the batch call. */
+orbx_status orbx_debug_pose_inlier_test(orbx_handle *h, int nproblems, const orbx_pose_problem *problems, int npool,
+                                        const float *world_pos, int nframes, const orbx_keypoint *d_keys_un, const float *d_u_right,
+                                        const int32_t *d_counts, int cap, const int32_t *d_point, const float *camera4, float mbf,
+                                        const float *inv_level_sigma2, int nlevels, const float *Tcw_est, const float *Tcw_last,
+                                        uint8_t *d_outlier, int32_t *d_ninliers);
+/* sin and cos as SE3Quat::exp gets them in both paths (csrc/orbx_pose.h: *, +, fma only; theta >= 0).  Exported for
+ * tests/pose_model.py, which takes this one primitive from the library. */
+void orbx_pose_sin_cos(double theta, double *s, double *c);
+
 #ifdef __cplusplus
 }
 #endif

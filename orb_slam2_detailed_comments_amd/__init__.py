@@ -11,3 +11,4 @@ from .vocabulary import ORBVocabulary  # noqa: F401
 from .keyframe_db import KeyFrameDatabase, bow_score  # noqa: F401
 from .mappoint import (distinctive_descriptors_batch, distinctive_descriptors_batch_device,  # noqa: F401
                        update_normal_and_depth_batch)
+from .optimizer import pose_optimization, pose_optimization_batch  # noqa: F401

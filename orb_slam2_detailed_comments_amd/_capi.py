@@ -67,6 +67,10 @@ class TrackLocalProblem(C.Structure):   # orbx_track_local_problem
                 ("frame_observations", C.c_void_p)]
 
 
+class PoseProblem(C.Structure):   # orbx_pose_problem
+    _fields_ = [("frame", C.c_int32), ("Tcw", C.c_float * 16), ("point_index", C.c_void_p), ("npoints", C.c_int32)]
+
+
 TRACK_STATE_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),
                               ("level", "<i4")])   # orbx_track_state
 assert TRACK_STATE_DTYPE.itemsize == 20
@@ -129,6 +133,8 @@ SYMBOLS = [
     "orbx_kfdb_add", "orbx_kfdb_erase", "orbx_kfdb_score_entries", "orbx_kfdb_query_reloc", "orbx_kfdb_query_loop",
     "orbx_kfdb_query_matches", "orbx_kfdb_query_touched", "orbx_kfdb_select_groups", "orbx_kfdb_state",
     "orbx_distinctive_descriptors_batch", "orbx_distinctive_descriptors_batch_device", "orbx_update_normal_and_depth_batch",
+    "orbx_pose_optimization_batch_device", "orbx_pose_optimization", "orbx_pose_sin_cos",
+    "orbx_debug_pose_inlier_test",
 ]
 
 _lib = None
@@ -174,6 +180,14 @@ def lib():
     L.orbx_distinctive_descriptors_batch_device.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp]
     L.orbx_update_normal_and_depth_batch.restype = i32
     L.orbx_update_normal_and_depth_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_pose_optimization_batch_device.restype = i32
+    L.orbx_pose_optimization_batch_device.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, f32, vp, i32, vp, vp, vp]
+    L.orbx_pose_optimization.restype = i32
+    L.orbx_pose_optimization.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, f32, vp, i32, vp, C.POINTER(i32)]
+    L.orbx_debug_pose_inlier_test.restype = i32
+    L.orbx_debug_pose_inlier_test.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, f32, vp, i32, vp, vp, vp, vp]
+    L.orbx_pose_sin_cos.restype = None
+    L.orbx_pose_sin_cos.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.orbx_get_stream.restype = vp; L.orbx_get_stream.argtypes = [vp]
     L.orbx_set_stream.restype = i32; L.orbx_set_stream.argtypes = [vp, vp]
     L.orbx_synchronize.restype = i32; L.orbx_synchronize.argtypes = [vp]

@@ -14,9 +14,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liborbx.so")
 SOURCES = ["orbx_kernels.hip", "orbx_api.cpp", "orbx_geometry.cpp", "orbx_policies.cpp", "orbx_kfdb.cpp", "orbx_track_pack.cpp",
-           "orbx_mappoint.cpp"]
+           "orbx_mappoint.cpp", "orbx_pose.cpp"]
 HEADERS = ["orbx_device.h", "orbx_inplace.h", "orbx_internal.h", "orbx_launch.h", "orbx_sincos.h", "orbx_track.h", "orbx_mappoint.h",
-           os.path.join("..", "..", "include", "orbx.h"), os.path.join("..", "..", "include", "orbx_pattern_data.h")]
+           "orbx_pose.h", os.path.join("..", "..", "include", "orbx.h"), os.path.join("..", "..", "include", "orbx_pattern_data.h")]
 
 
 def kernels_hash():
@@ -26,7 +26,7 @@ def kernels_hash():
     import hashlib
     h = hashlib.sha256()
     for f in ("orbx_kernels.hip", "orbx_device.h", "orbx_api.cpp", "orbx_launch.h", "orbx_internal.h", "orbx_track.h",
-              "orbx_mappoint.h", "orbx_mappoint.cpp"):
+              "orbx_mappoint.h", "orbx_mappoint.cpp", "orbx_pose.h", "orbx_pose.cpp"):
         h.update(open(os.path.join(CSRC, f), "rb").read())
     return h.hexdigest()[:16]
 

@@ -2409,6 +2409,128 @@ extern "C" orbx_status orbx_update_normal_and_depth_batch(orbx_handle *h, int np
     return ORBX_OK;
 }
 
+// ---------------------------------------------------------------- Optimizer::PoseOptimization(Frame*), batched (orbx_pose.h).
+// Device path: validation and layout (orbx_pose.cpp), all problems' host state and the pool packed into the page-locked block of
+// the tracking matchers, ONE upload, k_pose_opt on the handle's stream; nothing downloaded, nothing waited for.  Host path
+// (ORBX_POSE=host, read per call; host-only handles, where the "d_" arguments are host arrays): the same header compiled by
+// the host compiler.  On a device handle it downloads the rows it needs, runs, and uploads the results -- a cross-check, not a
+// fast path.
+static bool pose_host_selected() {
+    const char *e = getenv("ORBX_POSE");
+    return e && strcmp(e, "host") == 0;
+}
+static orbx_status pose_batch(orbx_handle *h, int nproblems, const orbx_pose_problem *problems, int npool, const float *world_pos,
+                              int nframes, const orbx_keypoint *d_keys_un, const float *d_u_right, const int32_t *d_counts, int cap,
+                              const int32_t *d_point, const float *camera4, float mbf, const float *inv_level_sigma2, int nlevels,
+                              float *d_Tcw, uint8_t *d_outlier, int32_t *d_ninliers, const float *dbg_est, const float *dbg_last) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxPoseCall c;
+    c.npool = npool; c.nframes = nframes; c.cap = cap; c.nlevels = nlevels;
+    c.world_pos = world_pos; c.camera4 = camera4; c.inv_level_sigma2 = inv_level_sigma2; c.mbf = mbf;
+    c.keys_un = d_keys_un; c.u_right = d_u_right; c.counts = d_counts; c.point = d_point;
+    c.Tcw = d_Tcw; c.outlier = d_outlier; c.ninliers = d_ninliers; c.dbg_est = dbg_est; c.dbg_last = dbg_last;
+    OrbxPosePlan plan;
+    const char *why = "";
+    orbx_status st = orbx_pose_plan(nproblems, problems, c, plan, &why);
+    if (st != ORBX_OK) return fail(st, why);
+    if (nproblems == 0) return ORBX_OK;
+    if (h->host_only) {
+        st = orbx_pose_check_rows(nproblems, problems, c, &why);
+        if (st != ORBX_OK) return fail(st, why);
+        orbx_pose_host_run(nproblems, problems, c);
+        return ORBX_OK;
+    }
+    if (pose_host_selected()) {
+        HIPCHK(hipSetDevice(h->dev));
+        const size_t fr = (size_t)nframes * cap, pr = (size_t)nproblems * cap;
+        std::vector<orbx_keypoint> keys(fr);
+        std::vector<float> ur(d_u_right ? fr : 0), T((size_t)nproblems * 16);
+        std::vector<int32_t> counts((size_t)nframes), point(pr), nin((size_t)nproblems);
+        std::vector<uint8_t> outl(pr);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpy(keys.data(), d_keys_un, fr * sizeof(orbx_keypoint), hipMemcpyDeviceToHost));
+        if (d_u_right) HIPCHK(hipMemcpy(ur.data(), d_u_right, fr * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(counts.data(), d_counts, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(point.data(), d_point, pr * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(outl.data(), d_outlier, pr, hipMemcpyDeviceToHost));
+        if (!dbg_est) HIPCHK(hipMemcpy(T.data(), d_Tcw, T.size() * sizeof(float), hipMemcpyDeviceToHost));
+        // the kernel's rule for what the host cannot validate on device rows: such a feature has no MapPoint (orbx_pose_load)
+        c.keys_un = keys.data(); c.u_right = d_u_right ? ur.data() : nullptr; c.counts = counts.data(); c.point = point.data();
+        c.Tcw = T.data(); c.outlier = outl.data(); c.ninliers = nin.data();
+        orbx_pose_host_run(nproblems, problems, c);
+        HIPCHK(hipMemcpy(d_outlier, outl.data(), pr, hipMemcpyHostToDevice));
+        if (!dbg_est) HIPCHK(hipMemcpy(d_Tcw, T.data(), T.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_ninliers, nin.data(), nin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        return ORBX_OK;
+    }
+    OrbxTrackPlan stage;   // the staging block and the arena are those of the tracking matchers
+    stage.in_bytes = plan.in_bytes; stage.dev_bytes = plan.in_bytes;
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = track_stage(h, stage, &pin, &d);
+    if (st != ORBX_OK) return st;
+    orbx_pose_pack(problems, c, plan, pin);
+    st = track_upload(h, stage, pin, d);
+    if (st != ORBX_OK) return st;
+    DPoseArgs a;
+    a.prob = (const DPoseProb *)(d + plan.o_prob);
+    a.index = (const int32_t *)(d + plan.o_index);
+    a.world = (const float *)(d + plan.o_world);
+    a.sig = (const float *)(d + plan.o_sig);
+    a.kps = d_keys_un; a.ur = d_u_right; a.counts = d_counts; a.point = d_point;
+    a.cap = cap; a.nlevels = nlevels; a.nproblems = nproblems;
+    a.fx = camera4[0]; a.fy = camera4[1]; a.cx = camera4[2]; a.cy = camera4[3]; a.mbf = mbf;
+    a.Tcw = d_Tcw; a.outlier = d_outlier; a.ninliers = d_ninliers;
+    a.dbg = dbg_est ? (const float *)(d + plan.o_dbg) : nullptr;
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_pose_opt(h->stream, a); }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
+    return ORBX_OK;
+}
+extern "C" orbx_status orbx_pose_optimization_batch_device(orbx_handle *h, int nproblems, const orbx_pose_problem *problems, int npool,
+                                                           const float *world_pos, int nframes, const orbx_keypoint *d_keys_un,
+                                                           const float *d_u_right, const int32_t *d_counts, int cap,
+                                                           const int32_t *d_point, const float *camera4, float mbf,
+                                                           const float *inv_level_sigma2, int nlevels, float *d_Tcw,
+                                                           uint8_t *d_outlier, int32_t *d_ninliers) {
+    return pose_batch(h, nproblems, problems, npool, world_pos, nframes, d_keys_un, d_u_right, d_counts, cap, d_point, camera4, mbf,
+                      inv_level_sigma2, nlevels, d_Tcw, d_outlier, d_ninliers, nullptr, nullptr);
+}
+extern "C" orbx_status orbx_debug_pose_inlier_test(orbx_handle *h, int nproblems, const orbx_pose_problem *problems, int npool,
+                                                   const float *world_pos, int nframes, const orbx_keypoint *d_keys_un,
+                                                   const float *d_u_right, const int32_t *d_counts, int cap, const int32_t *d_point,
+                                                   const float *camera4, float mbf, const float *inv_level_sigma2, int nlevels,
+                                                   const float *Tcw_est, const float *Tcw_last, uint8_t *d_outlier,
+                                                   int32_t *d_ninliers) {
+    if (!Tcw_est || !Tcw_last) return fail(ORBX_BAD_ARGUMENT, "null pose array");
+    float unused[16];   // the pose rows are not written by the inlier test; the plan only wants a non-null pointer
+    return pose_batch(h, nproblems, problems, npool, world_pos, nframes, d_keys_un, d_u_right, d_counts, cap, d_point, camera4, mbf,
+                      inv_level_sigma2, nlevels, unused, d_outlier, d_ninliers, Tcw_est, Tcw_last);
+}
+extern "C" orbx_status orbx_pose_optimization(orbx_handle *h, float *Tcw, int n, const orbx_keypoint *keys_un, const float *u_right,
+                                              const int32_t *point, int npool, const float *world_pos, const float *camera4,
+                                              float mbf, const float *inv_level_sigma2, int nlevels, uint8_t *outlier,
+                                              int32_t *ninliers) {
+    if (!h) return fail(ORBX_BAD_ARGUMENT, "no handle");
+    if (!Tcw || n <= 0) return fail(ORBX_BAD_ARGUMENT, !Tcw ? "null Tcw" : "n <= 0");
+    orbx_pose_problem P;
+    P.frame = 0; P.point_index = nullptr; P.npoints = npool;
+    memcpy(P.Tcw, Tcw, sizeof(P.Tcw));
+    const int32_t count = n;
+    OrbxPoseCall c;
+    c.npool = npool; c.nframes = 1; c.cap = n; c.nlevels = nlevels; c.batch_form = false;
+    c.world_pos = world_pos; c.camera4 = camera4; c.inv_level_sigma2 = inv_level_sigma2; c.mbf = mbf;
+    c.keys_un = keys_un; c.u_right = u_right; c.counts = &count; c.point = point;
+    c.Tcw = Tcw; c.outlier = outlier; c.ninliers = ninliers;
+    OrbxPosePlan plan;
+    const char *why = "";
+    orbx_status st = orbx_pose_plan(1, &P, c, plan, &why);
+    if (st == ORBX_OK) st = orbx_pose_check_rows(1, &P, c, &why);
+    if (st != ORBX_OK) return fail(st, why);
+    orbx_pose_host_run(1, &P, c);
+    return ORBX_OK;
+}
+
 // ---------------------------------------------------------------- (f)3: DBoW2 transform (Frame::ComputeBoW, src/Frame.cc:750-765)
 // TemplatedVocabulary<FORB>::transform(features, BowVector&, FeatureVector&, levelsup)
 // (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1136-1216): the tree descent of every descriptor runs on the GPU

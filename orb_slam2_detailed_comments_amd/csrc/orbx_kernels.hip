@@ -4002,6 +4002,164 @@ __global__ __launch_bounds__(256) void k_mp_normal_depth(const int32_t *__restri
     }
 }
 
+#include "orbx_pose.h"
+// Optimizer::PoseOptimization, batched (orbx_pose.h): one wave per problem, one problem per workgroup (problems share
+// nothing).  The lanes take the frame's features 64 at a time; a lane whose feature carries an active edge computes the edge's
+// 28 terms (21 of H, 6 of b, rho0) into LDS, then lane t < 28 adds term t of the chunk's active edges to its accumulator in
+// feature order -- the reference's edge order, 28 chains side by side, no atomics.  The 6x6 solve, exp, the pose update and the
+// Levenberg-Marquardt bookkeeping (orbx_pose_rounds) run redundantly in every lane on the broadcast sums, so every branch
+// around a barrier is uniform.  The outlier flags live in the output row (each lane re-reads what it wrote itself); the stale
+// errors of a rejected trial are recomputed from the pose they were taken at.  Every loop is bounded (4 x 10 x 10 passes over
+// at most cap features) and nothing waits on another wave.
+struct PoseEvDev {
+    OrbxPoseView v;
+    OrbxPoseCam K;
+    uint8_t *outlier;
+    double *s_term;     // [28][65]: term t of lane k at t * 65 + k (65: the summing lanes hit different banks)
+    double *s_acc;      // [28]
+    int lane, nactive;
+    __device__ int active() const { return nactive; }
+    __device__ void system(const OrbxPoseSE3 &T, bool robust, double *acc) {
+        double a = 0.0;
+        for (int base = 0; base < v.n; base += 64) {
+            const int i = base + lane;
+            OrbxPoseEdge e;
+            const bool act = i < v.n && orbx_pose_load(v, i, e) && !outlier[i];
+            const unsigned long long mask = orbx_ballot(act);
+            if (mask == 0ull) continue;
+            if (act) {
+                double t[ORBX_POSE_TERMS];
+                orbx_pose_terms(T, K, e, robust, t);
+#pragma unroll
+                for (int k = 0; k < ORBX_POSE_TERMS; ++k) s_term[k * 65 + lane] = t[k];
+            }
+            __syncthreads();
+            if (lane < ORBX_POSE_TERMS) {
+                unsigned long long m = mask;
+                while (m) {
+                    const int k = __builtin_ctzll(m);
+                    m &= m - 1;
+                    a = orbx_pose_accumulate(lane, a, s_term[lane * 65 + k]);
+                }
+            }
+            __syncthreads();
+        }
+        if (lane < ORBX_POSE_TERMS) s_acc[lane] = a;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < ORBX_POSE_TERMS; ++k) acc[k] = s_acc[k];
+        __syncthreads();
+    }
+    __device__ double chi(const OrbxPoseSE3 &T, bool robust) {
+        double a = 0.0;
+        for (int base = 0; base < v.n; base += 64) {
+            const int i = base + lane;
+            OrbxPoseEdge e;
+            const bool act = i < v.n && orbx_pose_load(v, i, e) && !outlier[i];
+            const unsigned long long mask = orbx_ballot(act);
+            if (mask == 0ull) continue;
+            if (act) {
+                double pc[3], err[3], rho1;
+                s_term[lane] = orbx_pose_huber(orbx_pose_error(T, K, e, pc, err), e.stereo, robust, &rho1);
+            }
+            __syncthreads();
+            if (lane == 0) {
+                unsigned long long m = mask;
+                while (m) {
+                    const int k = __builtin_ctzll(m);
+                    m &= m - 1;
+                    a = a + s_term[k];
+                }
+            }
+            __syncthreads();
+        }
+        if (lane == 0) s_acc[0] = a;
+        __syncthreads();
+        const double r = s_acc[0];
+        __syncthreads();
+        return r;
+    }
+    __device__ int classify(const OrbxPoseSE3 &T, const OrbxPoseSE3 &Tlast) {
+        int nbad = 0, ngood = 0;
+        for (int base = 0; base < v.n; base += 64) {
+            const int i = base + lane;
+            OrbxPoseEdge e;
+            const bool has = i < v.n && orbx_pose_load(v, i, e);
+            bool bad = false;
+            if (has) {
+                double pc[3], err[3];
+                const float chi2 = (float)orbx_pose_error(outlier[i] ? T : Tlast, K, e, pc, err);
+                bad = chi2 > (e.stereo ? 7.815f : 5.991f);
+                outlier[i] = bad ? 1 : 0;
+            }
+            nbad += __popcll(orbx_ballot(has && bad));
+            ngood += __popcll(orbx_ballot(has && !bad));
+        }
+        nactive = ngood;
+        return nbad;
+    }
+};
+__global__ __launch_bounds__(64) void k_pose_opt(const DPoseArgs A) {
+    __shared__ double s_term[ORBX_POSE_TERMS * 65];
+    __shared__ double s_acc[ORBX_POSE_TERMS];
+    const int p = blockIdx.x;
+    if (p >= A.nproblems) return;
+    const DPoseProb &P = A.prob[p];
+    PoseEvDev ev;
+    ev.lane = threadIdx.x;
+    const int cnt = A.counts[P.frame];
+    ev.v.n = cnt < 0 ? 0 : cnt < A.cap ? cnt : A.cap;
+    ev.v.kp = A.kps + (long long)P.frame * A.cap;
+    ev.v.ur = A.ur ? A.ur + (long long)P.frame * A.cap : nullptr;
+    ev.v.pt = A.point + (long long)p * A.cap;
+    ev.v.index = P.index_off >= 0 ? A.index + P.index_off : nullptr;
+    ev.v.world = A.world;
+    ev.v.sig = A.sig;
+    ev.v.nlevels = A.nlevels;
+    ev.v.npoints = P.npoints;
+    ev.K.fx = (double)A.fx; ev.K.fy = (double)A.fy; ev.K.cx = (double)A.cx; ev.K.cy = (double)A.cy; ev.K.bf = (double)A.mbf;
+    ev.outlier = A.outlier + (long long)p * A.cap;
+    ev.s_term = s_term; ev.s_acc = s_acc;
+    int nedges = 0;
+    if (A.dbg) {                                               // orbx_debug_pose_inlier_test: the inlier test alone (uniform)
+        for (int base = 0; base < ev.v.n; base += 64) {
+            const int i = base + ev.lane;
+            OrbxPoseEdge e;
+            nedges += __popcll(orbx_ballot(i < ev.v.n && orbx_pose_load(ev.v, i, e)));
+        }
+        float Te[16], Tl[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { Te[k] = A.dbg[16 * (long long)p + k]; Tl[k] = A.dbg[16 * ((long long)A.nproblems + p) + k]; }
+        const int nb = ev.classify(orbx_pose_from_tcw(Te), orbx_pose_from_tcw(Tl));
+        if (ev.lane == 0) A.ninliers[p] = nedges - nb;
+        return;
+    }
+    for (int base = 0; base < ev.v.n; base += 64) {           // mvbOutlier[i] = false wherever a MapPoint exists
+        const int i = base + ev.lane;
+        OrbxPoseEdge e;
+        const bool has = i < ev.v.n && orbx_pose_load(ev.v, i, e);
+        if (has) ev.outlier[i] = 0;
+        nedges += __popcll(orbx_ballot(has));
+    }
+    ev.nactive = nedges;
+    if (nedges < 3) {                                          // (uniform) the pose row stays as it is
+        if (ev.lane == 0) A.ninliers[p] = 0;
+        return;
+    }
+    float Tin[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) Tin[k] = P.Tcw[k];
+    OrbxPoseSE3 T;
+    const int nbad = orbx_pose_rounds(ev, Tin, nedges, &T);
+    if (ev.lane == 0) {
+        float M[16];
+        orbx_pose_to_tcw(T, M);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) A.Tcw[16 * (long long)p + k] = M[k];
+        A.ninliers[p] = nedges - nbad;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from orbx_api.cpp)
 // ------------------------------------------------------------------------------------------------
@@ -4422,4 +4580,8 @@ void orbx_launch_mp_normal_depth(hipStream_t s, const int32_t *obs_begin, const 
                                  float scale_last, float *out) {
     if (npoints <= 0) return;
     hipLaunchKernelGGL(k_mp_normal_depth, dim3((npoints + 15) / 16), dim3(256), 0, s, obs_begin, pts, centers, npoints, scale_last, out);
+}
+void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a) {
+    if (a.nproblems <= 0) return;
+    hipLaunchKernelGGL(k_pose_opt, dim3(a.nproblems), dim3(64), 0, s, a);
 }

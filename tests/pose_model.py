@@ -1,0 +1,402 @@
+"""Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:363-607) restated in numpy float64, independent of
+csrc/orbx_pose.h: what g2o executes for one VertexSE3Expmap with unary EdgeSE3ProjectXYZOnlyPose /
+EdgeStereoSE3ProjectXYZOnlyPose edges (SparseOptimizer::optimize, OptimizationAlgorithmLevenberg::solve, BlockSolver::buildSystem,
+BaseUnaryEdge::constructQuadraticForm, RobustKernelHuber, SE3Quat, Converter).  Every operation is an IEEE double operation in
+the written order (numpy elementwise arithmetic over the edges is the same operation per edge); sums over edges run in edge
+order, one addition after the other.  The one primitive taken from the library is sin / cos of SE3Quat::exp
+(orbx_pose_sin_cos), as DESIGN.md section 2 (F11) states.  `trace`, when given, receives what the tests assert branch coverage
+from."""
+import ctypes as C
+
+import numpy as np
+
+F64 = np.float64
+F32 = np.float32
+DELTA_MONO = F64(F32(np.sqrt(F64(5.991))))      # const float deltaMono = sqrt(5.991)
+DELTA_STEREO = F64(F32(np.sqrt(F64(7.815))))
+CHI2_MONO = F32(5.991)
+CHI2_STEREO = F32(7.815)
+DBL_MAX = F64(np.finfo(np.float64).max)
+
+
+def _sincos(theta):
+    from orb_slam2_detailed_comments_amd import _capi
+    s, c = C.c_double(), C.c_double()
+    _capi.lib().orbx_pose_sin_cos(C.c_double(float(theta)), C.byref(s), C.byref(c))
+    return F64(s.value), F64(c.value)
+
+
+# ----------------------------------------------------------------------------------------------- SE3Quat: q = (x, y, z, w), t
+def _normalize(q):
+    x, y, z, w = q
+    if w < 0:
+        x, y, z, w = x * F64(-1), y * F64(-1), z * F64(-1), w * F64(-1)
+    n = np.sqrt(x * x + y * y + z * z + w * w)
+    return (x / n, y / n, z / n, w / n)
+
+
+def _quat_from_R(m):
+    """Eigen::Quaterniond(Matrix3d); m[r][c]"""
+    t = m[0][0] + m[1][1] + m[2][2]
+    if t > 0:
+        t = np.sqrt(t + F64(1))
+        w = F64(0.5) * t
+        t = F64(0.5) / t
+        return ((m[2][1] - m[1][2]) * t, (m[0][2] - m[2][0]) * t, (m[1][0] - m[0][1]) * t, w)
+    if m[0][0] >= m[1][1] and m[0][0] >= m[2][2]:
+        i = 0
+    elif m[1][1] > m[0][0] and m[1][1] >= m[2][2]:
+        i = 1
+    else:
+        i = 2
+    j, k = (i + 1) % 3, (i + 2) % 3
+    t = np.sqrt(m[i][i] - m[j][j] - m[k][k] + F64(1))
+    q = [None] * 4
+    q[i] = F64(0.5) * t
+    t = F64(0.5) / t
+    q[3] = (m[k][j] - m[j][k]) * t
+    q[j] = (m[j][i] + m[i][j]) * t
+    q[k] = (m[k][i] + m[i][k]) * t
+    return tuple(q)
+
+
+def _R_from_quat(q):
+    x, y, z, w = q
+    tx, ty, tz = F64(2) * x, F64(2) * y, F64(2) * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    one = F64(1)
+    return [[one - (tyy + tzz), txy - twz, txz + twy],
+            [txy + twz, one - (txx + tzz), tyz - twx],
+            [txz - twy, tyz + twx, one - (txx + tyy)]]
+
+
+def _rotate(q, vx, vy, vz):
+    """Quaterniond * Vector3d: uv = 2 (q.vec x v); v + w uv + q.vec x uv.  v may be arrays over the edges"""
+    x, y, z, w = q
+    ux, uy, uz = y * vz - z * vy, z * vx - x * vz, x * vy - y * vx
+    ux, uy, uz = ux + ux, uy + uy, uz + uz
+    return ((vx + w * ux) + (y * uz - z * uy), (vy + w * uy) + (z * ux - x * uz), (vz + w * uz) + (x * uy - y * ux))
+
+
+def to_se3quat(Tcw):
+    """Converter::toSE3Quat"""
+    M = np.asarray(Tcw, np.float32).reshape(4, 4)
+    m = [[F64(M[r, c]) for c in range(3)] for r in range(3)]
+    return _normalize(_quat_from_R(m)), (F64(M[0, 3]), F64(M[1, 3]), F64(M[2, 3]))
+
+
+def to_cvmat(T):
+    """Converter::toCvMat(SE3Quat)"""
+    q, t = T
+    R = _R_from_quat(q)
+    M = np.zeros((4, 4), np.float32)
+    for r in range(3):
+        for c in range(3):
+            M[r, c] = F32(R[r][c])
+        M[r, 3] = F32(t[r])
+    M[3, 3] = F32(1)
+    return M
+
+
+def _mul(a, b):
+    """SE3Quat::operator*"""
+    (ax, ay, az, aw), at = a
+    (bx, by, bz, bw), bt = b
+    v = _rotate(a[0], bt[0], bt[1], bt[2])
+    t = (at[0] + v[0], at[1] + v[1], at[2] + v[2])
+    w = aw * bw - ax * bx - ay * by - az * bz
+    x = aw * bx + ax * bw + ay * bz - az * by
+    y = aw * by + ay * bw + az * bx - ax * bz
+    z = aw * bz + az * bw + ax * by - ay * bx
+    return _normalize((x, y, z, w)), t
+
+
+def se3_exp(u, trace=None):
+    """SE3Quat::exp(update), update = (omega, upsilon)"""
+    o0, o1, o2 = u[0], u[1], u[2]
+    theta = np.sqrt(o0 * o0 + o1 * o1 + o2 * o2)
+    zero, one = F64(0), F64(1)
+    Om = [[zero, -o2, o1], [o2, zero, -o0], [-o1, o0, zero]]
+    Om2 = [[Om[i][0] * Om[0][j] + Om[i][1] * Om[1][j] + Om[i][2] * Om[2][j] for j in range(3)] for i in range(3)]
+    I = [[one if i == j else zero for j in range(3)] for i in range(3)]
+    if theta < F64(0.00001):
+        if trace is not None:
+            trace["theta_small"] = trace.get("theta_small", 0) + 1
+        R = [[(I[i][j] + Om[i][j]) + Om2[i][j] for j in range(3)] for i in range(3)]
+        V = R
+    else:
+        sn, cs = _sincos(theta)
+        t2 = theta * theta
+        a, b, c = sn / theta, (one - cs) / t2, (theta - sn) / (t2 * theta)
+        R = [[(I[i][j] + a * Om[i][j]) + b * Om2[i][j] for j in range(3)] for i in range(3)]
+        V = [[(I[i][j] + b * Om[i][j]) + c * Om2[i][j] for j in range(3)] for i in range(3)]
+    t = tuple(V[i][0] * u[3] + V[i][1] * u[4] + V[i][2] * u[5] for i in range(3))
+    return _normalize(_quat_from_R(R)), t
+
+
+# ----------------------------------------------------------------------------------------------- edges (arrays over the edges)
+class Edges:
+    def __init__(self, idx, ox, oy, our, w, X, Y, Z, stereo):
+        self.idx, self.ox, self.oy, self.our, self.w, self.X, self.Y, self.Z, self.stereo = idx, ox, oy, our, w, X, Y, Z, stereo
+
+    def take(self, sel):
+        return Edges(*[a[sel] for a in (self.idx, self.ox, self.oy, self.our, self.w, self.X, self.Y, self.Z, self.stereo)])
+
+    def __len__(self):
+        return len(self.idx)
+
+
+def _error(T, K, e):
+    """computeError and chi2 of every edge of e at T; returns (pc, err, chi2)"""
+    fx, fy, cx, cy, bf = K
+    q, t = T
+    px, py, pz = _rotate(q, e.X, e.Y, e.Z)
+    px, py, pz = px + t[0], py + t[1], pz + t[2]
+    st = e.stereo
+    invz_f = (F64(1) / pz).astype(np.float32).astype(np.float64)      # const float invz = 1.0f / trans_xyz[2]
+    u_s = px * invz_f * fx + cx
+    e0 = np.where(st, e.ox - u_s, e.ox - ((px / pz) * fx + cx))
+    e1 = np.where(st, e.oy - (py * invz_f * fy + cy), e.oy - ((py / pz) * fy + cy))
+    e2 = np.where(st, e.our - (u_s - bf * invz_f), F64(0))
+    c2 = e0 * (e.w * e0) + e1 * (e.w * e1)
+    chi2 = np.where(st, c2 + e2 * (e.w * e2), c2)
+    return (px, py, pz), (e0, e1, e2), chi2
+
+
+def _huber(chi2, stereo, robust):
+    """RobustKernelHuber::robustify -> rho0, rho1"""
+    if not robust:
+        return chi2, np.ones_like(chi2)
+    delta = np.where(stereo, DELTA_STEREO, DELTA_MONO)
+    dsqr = delta * delta
+    sq = np.sqrt(chi2)
+    inl = chi2 <= dsqr
+    return np.where(inl, chi2, F64(2) * sq * delta - dsqr), np.where(inl, F64(1), delta / sq)
+
+
+def _seq_sum(terms, sign=1):
+    """acc = 0; acc = acc (+|-) t, edge after edge"""
+    acc = F64(0)
+    if sign > 0:
+        for v in terms:
+            acc = acc + v
+    else:
+        for v in terms:
+            acc = acc - v
+    return acc
+
+
+def _system(T, K, e, robust):
+    """computeActiveErrors + activeRobustChi2 + buildSystem: H (6x6 upper as dict), b[6], chi"""
+    fx, fy, cx, cy, bf = K
+    (x, y, z), (e0, e1, e2), chi2 = _error(T, K, e)
+    rho0, rho1 = _huber(chi2, e.stereo, robust)
+    invz = F64(1) / z
+    invz_2 = invz * invz
+    zero = np.zeros_like(x)
+    J0 = [x * y * invz_2 * fx, -(F64(1) + (x * x * invz_2)) * fx, y * invz * fx, -invz * fx, zero, x * invz_2 * fx]
+    J1 = [(F64(1) + y * y * invz_2) * fy, -x * y * invz_2 * fy, -x * invz * fy, zero, -invz * fy, y * invz_2 * fy]
+    J2 = [J0[0] - bf * y * invz_2, J0[1] + bf * x * invz_2, J0[2], J0[3], zero, J0[5] - bf * invz_2]
+    W = rho1 * e.w
+    we0, we1, we2 = e.w * e0, e.w * e1, e.w * e2
+    st = e.stereo
+    H = {}
+    for j in range(6):
+        for k in range(j, 6):
+            s = (J0[j] * W) * J0[k] + (J1[j] * W) * J1[k]
+            s = np.where(st, s + (J2[j] * W) * J2[k], s)
+            H[(j, k)] = _seq_sum(s)
+    b = []
+    for j in range(6):
+        s = J0[j] * we0 + J1[j] * we1
+        s = np.where(st, s + J2[j] * we2, s)
+        b.append(_seq_sum(rho1 * s, -1))
+    return H, b, _seq_sum(rho0), rho1
+
+
+def _chi(T, K, e, robust):
+    return _seq_sum(_huber(_error(T, K, e)[2], e.stereo, robust)[0])
+
+
+def solve6(H, lam, b):
+    """(H + lam I) x = b, unpivoted L D L^T; positive = every pivot > 0 and finite, otherwise (False, 0)"""
+    A = [[(H[(min(i, j), max(i, j))] + lam) if i == j else H[(min(i, j), max(i, j))] for j in range(6)] for i in range(6)]
+    L = [[F64(0)] * 6 for _ in range(6)]
+    d = [F64(0)] * 6
+    ok = True
+    for j in range(6):
+        w = [L[j][k] * d[k] for k in range(j)]
+        s = A[j][j]
+        for k in range(j):
+            s = s - L[j][k] * w[k]
+        d[j] = s
+        if not (s > 0 and s <= DBL_MAX):
+            ok = False
+        for i in range(j + 1, 6):
+            t = A[i][j]
+            for k in range(j):
+                t = t - L[i][k] * w[k]
+            L[i][j] = t / s
+    if not ok:
+        return False, [F64(0)] * 6
+    y = [F64(0)] * 6
+    for i in range(6):
+        s = b[i]
+        for k in range(i):
+            s = s - L[i][k] * y[k]
+        y[i] = s
+    x = [F64(0)] * 6
+    for i in range(5, -1, -1):
+        s = y[i] / d[i]
+        for k in range(i + 1, 6):
+            s = s - L[k][i] * x[k]
+        x[i] = s
+    return True, x
+
+
+def pose_optimization(Tcw, keys_xy, octave, u_right, point, world, camera4, mbf, inv_level_sigma2, outlier_in=None, trace=None):
+    """-> (Tcw_out float32 4x4, outlier uint8[n], ninliers).  point[i] = -1 or the pool index of feature i's MapPoint;
+    u_right None: all mono.  outlier entries of features without a point keep outlier_in (zeros when not given)."""
+    with np.errstate(all="ignore"):
+        return _pose_optimization(Tcw, keys_xy, octave, u_right, point, world, camera4, mbf, inv_level_sigma2, outlier_in, trace)
+
+
+def _pose_optimization(Tcw, keys_xy, octave, u_right, point, world, camera4, mbf, sig, outlier_in, trace):
+    keys_xy = np.asarray(keys_xy, np.float32).reshape(-1, 2)
+    n = len(keys_xy)
+    point = np.asarray(point, np.int64)
+    world = np.asarray(world, np.float32).reshape(-1, 3)
+    sig = np.asarray(sig, np.float32)
+    ur = np.full(n, -1, np.float32) if u_right is None else np.asarray(u_right, np.float32)
+    idx = np.nonzero(point >= 0)[0]
+    pp = point[idx]
+    e = Edges(idx, keys_xy[idx, 0].astype(F64), keys_xy[idx, 1].astype(F64), ur[idx].astype(F64),
+              sig[np.asarray(octave)[idx]].astype(F64), world[pp, 0].astype(F64), world[pp, 1].astype(F64),
+              world[pp, 2].astype(F64), ~(ur[idx] < 0))
+    K = tuple(F64(F32(v)) for v in (camera4[0], camera4[1], camera4[2], camera4[3], mbf))
+    outlier = np.zeros(n, np.uint8) if outlier_in is None else np.array(outlier_in, np.uint8)
+    outlier[idx] = 0
+    Tout = np.array(Tcw, np.float32).reshape(4, 4)
+    nedges = len(e)
+    if trace is not None:
+        trace["rounds"] = []
+    if nedges < 3:
+        return Tout, outlier, 0
+    init = to_se3quat(Tcw)
+    flags = np.zeros(nedges, bool)                      # outlier flag per edge (level 1)
+    third, two_thirds = F64(1) / F64(3), F64(2) / F64(3)
+    nbad = 0
+    est = init
+    for rnd in range(4):
+        est = init
+        last = init
+        robust = rnd < 3
+        act = e.take(~flags)
+        tr = {"round": rnd, "nactive": len(act), "iters": [], "flags_before": flags.copy()}
+        if len(act) > 0:
+            lam, nu, stall = F64(0), F64(2), 0
+            for it in range(10):
+                H, b, cur, rho1 = _system(est, K, act, robust)
+                last = est
+                ini = cur
+                itr = {"trials": [], "end": "ok"}
+                if it == 0:
+                    m = F64(0)
+                    for j in range(6):
+                        a = np.abs(H[(j, j)])
+                        m = m if a < m else a
+                    lam, nu, stall = F64(1e-5) * m, F64(2), 0
+                    if rnd == 3:      # what the Huber weights of the first three rounds would be here
+                        tr["nonunit_huber"] = int(np.count_nonzero(_huber(_error(est, K, act)[2], act.stereo, True)[1] != 1))
+                rho = F64(0)
+                q = 0
+                while True:
+                    backup = est
+                    ok, x = solve6(H, lam, b)
+                    est = _mul(se3_exp(x, trace), est)
+                    tmp = _chi(est, K, act, robust)
+                    last = est
+                    if not ok:
+                        tmp = DBL_MAX
+                    rho = cur - tmp
+                    scale = F64(0)
+                    for j in range(6):
+                        scale = scale + x[j] * (lam * x[j] + b[j])
+                    scale = scale + F64(1e-3)
+                    rho = rho / scale
+                    accepted = bool(rho > 0 and np.isfinite(tmp))
+                    itr["trials"].append({"ok": ok, "rho": float(rho), "accepted": accepted, "nu": float(nu), "chi": float(tmp)})
+                    if accepted:
+                        r2 = F64(2) * rho - F64(1)
+                        alpha = F64(1) - (r2 * r2) * r2
+                        alpha = two_thirds if two_thirds < alpha else alpha
+                        sf = alpha if third < alpha else third
+                        lam = lam * sf
+                        nu = F64(2)
+                        cur = tmp
+                    else:
+                        lam = lam * nu
+                        nu = nu * F64(2)
+                        est = backup
+                    q += 1
+                    if not (rho < 0 and q < 10):
+                        break
+                tr["iters"].append(itr)
+                if q == 10 or rho == 0:
+                    itr["end"] = "trials" if q == 10 else "rho0"
+                    break
+                if (ini - cur) * F64(1e3) < ini:
+                    stall += 1
+                else:
+                    stall = 0
+                if stall >= 3:
+                    itr["end"] = "stall"
+                    break
+        # the inlier test: an outlier edge is recomputed at the estimate; every other edge keeps the errors of the pose where
+        # computeActiveErrors ran last (a rejected trial's, when the last trial was rejected)
+        chi_est = _error(est, K, e)[2]
+        chi_last = _error(last, K, e)[2]
+        chi2 = np.where(flags, chi_est, chi_last).astype(np.float32)
+        thr = np.where(e.stereo, CHI2_STEREO, CHI2_MONO).astype(np.float32)
+        new = chi2 > thr
+        fresh = chi_est.astype(np.float32) > thr
+        tr["stale_flips"] = int(np.count_nonzero((new != fresh) & ~flags))
+        tr["last_rejected"] = bool(tr["iters"]) and not tr["iters"][-1]["trials"][-1]["accepted"]
+        tr["last_differs"] = last is not est and any(a != b for a, b in zip(last[0] + last[1], est[0] + est[1]))
+        tr["flags_after"] = new.copy()
+        tr["chi_est"], tr["chi_last"] = chi_est, chi_last            # per edge, in edge order (float64)
+        tr["reentered"] = int(np.count_nonzero(flags & ~new))
+        flags = new
+        nbad = int(np.count_nonzero(flags))
+        if trace is not None:
+            trace["rounds"].append(tr)
+        if nedges < 10:
+            break
+    outlier[idx] = flags.astype(np.uint8)
+    return to_cvmat(est), outlier, nedges - nbad
+
+
+def inlier_test(Tcw_est, Tcw_last, flags_in, keys_xy, octave, u_right, point, world, camera4, mbf, inv_level_sigma2):
+    """the inlier test that ends a round, alone (src/Optimizer.cc:534-592): an edge flagged outlier is recomputed at the estimate,
+    every other edge keeps the errors of the pose where computeActiveErrors ran last.  flags_in / result: uint8 per feature (only
+    features with a point are read / written).  -> (flags, ninliers)"""
+    with np.errstate(all="ignore"):
+        keys_xy = np.asarray(keys_xy, np.float32).reshape(-1, 2)
+        point = np.asarray(point, np.int64)
+        world = np.asarray(world, np.float32).reshape(-1, 3)
+        sig = np.asarray(inv_level_sigma2, np.float32)
+        ur = np.full(len(keys_xy), -1, np.float32) if u_right is None else np.asarray(u_right, np.float32)
+        idx = np.nonzero(point >= 0)[0]
+        pp = point[idx]
+        e = Edges(idx, keys_xy[idx, 0].astype(F64), keys_xy[idx, 1].astype(F64), ur[idx].astype(F64),
+                  sig[np.asarray(octave)[idx]].astype(F64), world[pp, 0].astype(F64), world[pp, 1].astype(F64),
+                  world[pp, 2].astype(F64), ~(ur[idx] < 0))
+        K = tuple(F64(F32(v)) for v in (camera4[0], camera4[1], camera4[2], camera4[3], mbf))
+        was = np.asarray(flags_in, np.uint8)[idx] != 0
+        chi2 = np.where(was, _error(to_se3quat(Tcw_est), K, e)[2], _error(to_se3quat(Tcw_last), K, e)[2]).astype(np.float32)
+        new = chi2 > np.where(e.stereo, CHI2_STEREO, CHI2_MONO).astype(np.float32)
+        out = np.array(flags_in, np.uint8)
+        out[idx] = new.astype(np.uint8)
+        return out, len(idx) - int(np.count_nonzero(new))
