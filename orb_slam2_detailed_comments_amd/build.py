@@ -13,20 +13,21 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liborbx.so")
+# the ONE list of what the library is built from: the build, the rebuild check, kernels_hash() and tools/build_variant.sh use it
 SOURCES = ["orbx_kernels.hip", "orbx_api.cpp", "orbx_geometry.cpp", "orbx_policies.cpp", "orbx_kfdb.cpp", "orbx_track_pack.cpp",
            "orbx_mappoint.cpp", "orbx_pose.cpp"]
 HEADERS = ["orbx_device.h", "orbx_inplace.h", "orbx_internal.h", "orbx_launch.h", "orbx_sincos.h", "orbx_track.h", "orbx_mappoint.h",
-           "orbx_pose.h", os.path.join("..", "..", "include", "orbx.h"), os.path.join("..", "..", "include", "orbx_pattern_data.h")]
+           "orbx_pose.h", "orbx_handle.h", "orbx_gate.h", os.path.join("..", "..", "include", "orbx.h"),
+           os.path.join("..", "..", "include", "orbx_pattern_data.h")]
 
 
 def kernels_hash():
-    """identity of the device code AND of what decides its launch geometry (kernel source, device header, the launch plans in
-    orbx_api.cpp / orbx_launch.h / orbx_internal.h): profiles/*_traffic.json and *_sq.json carry it, so counters taken on other
-    kernels or other launch plans read as 'not measured' in bench.py instead of as stale numbers"""
+    """identity of the device code AND of what decides its launch geometry (kernel source, device headers, the launch plans of
+    orbx_api.cpp): every file of SOURCES and HEADERS, so none can be missed.  profiles/*_traffic.json and *_sq.json carry it,
+    so counters taken on other kernels or other launch plans read as 'not measured' in bench.py instead of as stale numbers"""
     import hashlib
     h = hashlib.sha256()
-    for f in ("orbx_kernels.hip", "orbx_device.h", "orbx_api.cpp", "orbx_launch.h", "orbx_internal.h", "orbx_track.h",
-              "orbx_mappoint.h", "orbx_mappoint.cpp", "orbx_pose.h", "orbx_pose.cpp"):
+    for f in SOURCES + HEADERS:
         h.update(open(os.path.join(CSRC, f), "rb").read())
     return h.hexdigest()[:16]
 
@@ -45,17 +46,19 @@ def needs_build():
     return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
 
 
-def build(force=False, verbose=False, extra=()):
-    if not force and not needs_build():
+def build(force=False, verbose=False, extra=(), out=None):
+    """out: build a variant library there (always; extra carries its flags) instead of the package's own"""
+    if out is None and not force and not needs_build():
         return LIB
-    os.makedirs(LIBDIR, exist_ok=True)
+    lib = out or LIB
+    os.makedirs(os.path.dirname(os.path.abspath(lib)), exist_ok=True)
     cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-x", "hip",
            "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value",
-           *extra, *[os.path.join(CSRC, s) for s in SOURCES], "-o", LIB]
+           *extra, *[os.path.join(CSRC, s) for s in SOURCES], "-o", lib]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
-    return LIB
+    return lib
 
 
 if __name__ == "__main__":

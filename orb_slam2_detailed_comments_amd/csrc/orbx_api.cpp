@@ -4,19 +4,14 @@
 // Launch sequence per batch (all on one HIP stream, no host synchronisation in the device entry point):
 //   clear counters -> K0 border L0 -> K1 resize x (nlevels-1) -> K2 FAST cells -> K3 quadtree ->
 //   K4 orientation -> K5 blur -> K6 descriptors + assembly.
-#include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
 #include <algorithm>
 #include <cmath>
-#include "orbx_internal.h"
-#include "orbx_launch.h"
+#include "orbx_handle.h"
 #include "orbx_gate.h"
-#include "orbx_track.h"
 
 static thread_local std::string g_last_error;
 // orbx_extract_rgbd_batch with page-locked, device-mapped depth: read it in place (true) or upload it (false) by default;
@@ -28,109 +23,7 @@ static orbx_status fail(orbx_status s, const std::string &msg) {
     g_last_error = msg;
     return s;
 }
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess)                                                                     \
-            return fail(ORBX_HIP_ERROR, std::string(#expr) + ": " + hipGetErrorString(_e));      \
-    } while (0)
-
-struct ProfPair { hipEvent_t a, b; int kid; };
-
-struct orbx_handle {
-    orbx_params p;
-    OrbxTables tab;
-    OrbxGeom geom;
-    DGeom dg;
-    bool host_only = false, configured = false;
-    int dev = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    // side stream of the batched extraction (high priority): the small pyramid levels are a chain of short, latency-bound
-    // launches; they run here, next to the issue-bound FAST kernel of the large levels on the main stream
-    hipStream_t side_stream = nullptr;
-    hipStream_t plan_stream = nullptr;   // side stream of the FAST-first plan (low priority: its resize chains fill what FAST leaves)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_stereo = nullptr;   // orders the batched stereo match with the OTHER eye's stream (two extractors, two streams)
-    int fork_level = 0;       // first level whose resize + FAST run on the side stream (0 = no fork)
-    int fork_group = 0;       // first FAST group of that level
-    // sub-batch pipeline of run_chunk (ORBX_PIPELINE=0|S, ORBX_PIPELINE_HEAD=0|1, ORBX_FAST_ROOM=0|1 for A/B runs)
-    int pipeline = 2;         // sub-batches of a batch of >= ORBX_PIPE_MIN_FRAMES frames (<= 1: the serial sequence)
-    bool pipe_head = true;    // the first sub-batch is half the size of the others (its pyramid is the one nothing hides): the
-                              // even split is 0.3 % faster on the default line but 1.8 % slower on the merged EuRoC stereo batch
-    bool fast_room = false;   // k_fast_rows capped at ORBX_FAST_PIPE_WAVES waves per CU while the pipeline runs (measured slower)
-    hipEvent_t ev_pipe[ORBX_PIPE_MAX] = {};   // pyramid of sub-batch k done (side stream) -> its FAST launch (main stream)
-    // FAST-first plan of run_chunk (ORBX_PLAN=fastfirst|pipeline|serial, ORBX_PLAN_SUB=S, ORBX_PLAN_HEAD=0|1, ORBX_PLAN_MIN_FRAMES;
-    // ORBX_PLAN_PRIORITY=low|normal|high is read when the handle is created);
-    // an explicit ORBX_PIPELINE overrides ORBX_PLAN and selects the serial sequence or the sub-batch pipeline as they were
-    bool fast_first = true;   // the default plan of a batch of >= plan_min_frames frames (profiles/fast_first_plan.md)
-    int plan_sub = 3;         // resize-chain sub-batches of the plan (the sweep of profiles/fast_first_plan.md)
-    bool plan_head = false;   // the first of them is half the size of the others
-    int plan_min_frames = ORBX_PIPE_MIN_FRAMES;   // smaller batches keep the serial sequence
-    int l0_groups = 0;        // FAST groups of level 0 (the groups are ordered by level)
-    int max_ch_l0 = 0, max_ch_rest = 0;   // tallest cell of the level-0 groups / of the others
-    // geometry-dependent device state
-    uint8_t *d_pyr = nullptr, *d_blur = nullptr;
-    OrbxCell *d_cells = nullptr;
-    OrbxFastGroup *d_groups = nullptr;
-    bool resize_legacy = false;   // ORBX_RESIZE_IMPL=legacy: k_pyr_resize for every level (A/B runs)
-    int match_kernel = 0;         // ORBX_MATCH_KERNEL, read ONCE when the handle is created: 0 = matrix pipe with FP4 operands (default), 1 = "valu" (vector pipe), 2 = "i8" (matrix pipe, int8 operands) -- A/B runs, parity tests
-    int fast_stop = 0;      // ORBX_FAST_STOP: only read in -DORBX_TIMING_KNOBS builds
-    int fast_lcap = 640;    // LDS work-list entries of k_fast_rows (ORBX_FAST_LCAP; tests shrink it to force the flush paths)
-    OrbxTap *d_taps = nullptr;
-    uint2 *d_dense = nullptr;   // dense per-(frame, level) key arrays, appended to by k_fast_rows (fill counts in d_cand_count)
-    int *d_cand_count = nullptr, *d_lvl_count = nullptr, *d_status = nullptr;
-    uint32_t *d_lvl_kp = nullptr;
-    float *d_lvl_angle = nullptr;
-    uint16_t *d_knode = nullptr;
-    int max_cw = 0, max_ch = 0, ncap = 0, lds_keys = 0, lds_keys_few = 0;
-    // staging for the host entry points
-    uint8_t *st_in[2] = {nullptr, nullptr}; size_t d_in_bytes = 0;
-    orbx_keypoint *st_kps[2] = {nullptr, nullptr}; uint8_t *st_desc[2] = {nullptr, nullptr}; int *st_cnt[2] = {nullptr, nullptr};
-    int out_cap = 0, stage_chunk = 0;
-    int *pin_stat = nullptr; size_t pin_stat_ints = 0;   // page-locked landing place of the per-frame counts | status words of a call (grow-only)
-    hipStream_t s_in = nullptr;   // the ONE copy stream of the pipelined host-buffer call (uploads and downloads in turn)
-    hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    // staging of orbx_extract_rgbd_batch (grow-only): the depth frames of a chunk; kps_un | u_right | depth of a chunk (one block)
-    uint8_t *st_dep[2] = {nullptr, nullptr}; size_t dep_bytes = 0;
-    uint8_t *st_rg[2] = {nullptr, nullptr}; size_t rg_bytes = 0;
-    int last_batch = 0;
-    int mk_w = 0, mk_h = 0, mk_total = 0;   // orbx_max_keypoints cache
-    void *d_match_ws = nullptr; size_t match_ws_bytes = 0;   // partial (best, second) keys of k_match
-    uint32_t *d_gate_items = nullptr; size_t gate_items_cap = 0;   // candidate lists of k_gate / distance blocks of k_block_dist (grow-only)
-    uint8_t *pin = nullptr; size_t pin_bytes = 0;                  // page-locked staging of the host-buffer policy entry points (grow-only)
-    size_t gate_guess = 4096;                                      // entries the speculative download of the candidate lists covers
-    // page-locked staging of the batched tracking matchers (grow-only) and the event behind their upload: these calls return
-    // before the copy has run, so the block is theirs alone and is not written again before that event has passed
-    uint8_t *track_pin = nullptr; size_t track_pin_bytes = 0;
-    hipEvent_t ev_track = nullptr; bool track_pending = false;
-    // MapPoint::PredictScale as thresholds on mfMaxDistance / dist (orbx_track.h: orbx_predict_scale_build), built at orbx_create
-    float ps_thr[ORBX_PS_LEVELS] = {};
-    // grow-only scratch arena for the host-buffer convenience entry points (match / matrix / stereo): no hipMalloc
-    // on the steady-state path and nothing to leak on an error return
-    uint8_t *d_scratch = nullptr; size_t scratch_bytes = 0, scratch_used = 0;
-    uint2 *d_rect = nullptr; int rect_w = 0, rect_h = 0;   // pre-digested rectification maps (orbx_set_rectification)
-    int input_format = ORBX_FMT_GRAY8;        // pixel format of the frames handed to the extract entry points
-    bool blur_valid = false;                // d_blur holds the blurred pyramid of the last batch
-    // in-place level 0 (orbx_inplace.h): grey batches of orbx_extract_batch_device read level 0 from the caller's image and
-    // never write the slab's padded copy; whoever needs that copy afterwards calls ensure_level0() first
-    bool l0_inplace = true;                 // ORBX_LEVEL0_INPLACE=0 forces the eager k_pyr_l0 everywhere (A/B runs)
-    bool l0_eager_sticky = false;           // a stereo match needed the padded copy: this handle's later batches write it eagerly
-    bool l0_pending = false;                // the slab's level 0 of the last batch has not been written
-    OrbxRaw0 l0_src = {nullptr, 0, 0, 0, 0};   // ... and this is the input it would be written from (must stay valid and unchanged)
-    int *d_l0_scratch = nullptr;            // status / cursor words the late k_pyr_l0 may reset instead of the batch's own
-    // profiling
-    uint32_t prof_mask = 0;
-    std::vector<ProfPair> pending;
-    std::vector<hipEvent_t> pool;
-    float ms[ORBX_K_COUNT] = {0};
-    int launches[ORBX_K_COUNT] = {0};
-};
-
-// shared with orbx_policies.cpp
-orbx_status orbx_fail(orbx_status s, const std::string &msg) { return fail(s, msg); }
-int orbx_handle_fp_mode(const orbx_handle *h) { return h->p.fp_mode; }
-bool orbx_handle_host_only(const orbx_handle *h) { return h->host_only; }   // orbx_kfdb.cpp
-int orbx_handle_device(const orbx_handle *h) { return h->dev; }
+orbx_status orbx_fail(orbx_status s, const std::string &msg) { return fail(s, msg); }   // for the other units (orbx_handle.h)
 
 static const char *k_names[ORBX_K_COUNT] = {"k_pyr_l0", "k_pyr_resize", "k_fast_rows", "k_quadtree", "k_orient",
                                             "k_blur",   "k_describe",   "k_match",      "misc"};
@@ -179,29 +72,11 @@ struct Roctx {
     }
 };
 static const Roctx &roctx() { static Roctx r; return r; }
+// ProfScope (orbx_handle.h) reaches the two entry points through these
+bool orbx_roctx_push(const char *name) { if (!roctx().push) return false; roctx().push(name); return true; }
+void orbx_roctx_pop() { roctx().pop(); }
 
-struct ProfScope {
-    orbx_handle *h; int kid; bool on; hipStream_t st; hipEvent_t a = nullptr, b = nullptr; bool marked = false;
-    ProfScope(orbx_handle *h_, int kid_, hipStream_t st_ = nullptr)
-        : h(h_), kid(kid_), on(((h_->prof_mask >> kid_) & 1u) != 0), st(st_ ? st_ : h_->stream) {
-        if (roctx().push) { roctx().push(orbx_kernel_name(kid)); marked = true; }
-        if (!on) return;
-        a = grab(); b = grab();
-        hipEventRecord(a, st);   // events are recorded on the stream the kernel is launched on
-    }
-    hipEvent_t grab() {
-        if (!h->pool.empty()) { hipEvent_t e = h->pool.back(); h->pool.pop_back(); return e; }
-        hipEvent_t e; hipEventCreate(&e); return e;
-    }
-    ~ProfScope() {
-        if (marked) roctx().pop();
-        if (!on) return;
-        hipEventRecord(b, st);
-        h->pending.push_back({a, b, kid});
-    }
-};
-
-static void prof_drain(orbx_handle *h) {
+void prof_drain(orbx_handle *h) {
     if (h->pending.empty()) return;
     hipStreamSynchronize(h->stream);
     for (auto &pp : h->pending) {
@@ -211,8 +86,6 @@ static void prof_drain(orbx_handle *h) {
     }
     h->pending.clear();
 }
-
-static orbx_status pin_reserve(orbx_handle *h, size_t bytes);   // page-locked host staging (defined with the policy plumbing)
 
 // ---------------------------------------------------------------- workspace
 static void free_geometry_buffers(orbx_handle *h) {
@@ -465,8 +338,8 @@ extern "C" void orbx_destroy(orbx_handle *h) {
         free_geometry_buffers(h);
         hipFree(h->d_match_ws); hipFree(h->d_scratch); hipFree(h->d_rect); hipFree(h->d_gate_items);
         if (h->pin) hipHostFree(h->pin);
-        if (h->track_pin) hipHostFree(h->track_pin);
-        if (h->ev_track) hipEventDestroy(h->ev_track);
+        if (h->pin_early) hipHostFree(h->pin_early);
+        if (h->ev_stage) hipEventDestroy(h->ev_stage);
         if (h->pin_stat) hipHostFree(h->pin_stat);
         for (int s = 0; s < 2; ++s) {
             hipFree(h->st_in[s]); hipFree(h->st_kps[s]);   // st_desc / st_cnt live inside the st_kps allocation
@@ -994,7 +867,7 @@ static orbx_status extract_host(orbx_handle *h, int nframes, const uint8_t *imgs
     const size_t in_bytes_q = (size_t)nframes * fbytes;
     const bool stage_in = in_bytes_q <= ((size_t)1 << 20);   // beyond ~1 MB the host-side memcpy costs more than the runtime's own staging
     const bool quick = !rg && !piped && nframes == h->stage_chunk && cap == h->out_cap && out_bytes <= ((size_t)4 << 20) &&
-                       pin_reserve(h, (stage_in ? in_bytes_q : 0) + out_bytes) == ORBX_OK;
+                       stage_pin(h, (stage_in ? in_bytes_q : 0) + out_bytes) == ORBX_OK;
     if (quick) {
         uint8_t *pin_in = h->pin, *pin_out = h->pin + (stage_in ? in_bytes_q : 0);
         if (stage_in) {
@@ -1069,7 +942,12 @@ extern "C" orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uin
 }
 
 // ---------------------------------------------------------------- RGB-D Frame: Frame::ComputeStereoFromRGBD (k_rgbd)
-static void undistort_args(const float *camera4, const float *dist, int ndist, double *K4, double *k14, int *identity);
+// camera4 / dist as the doubles k_undistort and k_rgbd take (section (f)2 below); dist[0] == 0: identity
+static void undistort_args(const float *camera4, const float *dist, int ndist, double *K4, double *k14, int *identity) {
+    for (int i = 0; i < 4; ++i) K4[i] = (double)camera4[i];
+    for (int i = 0; i < 14; ++i) k14[i] = i < ndist ? (double)dist[i] : 0.0;
+    *identity = (ndist < 1 || dist[0] == 0.0f) ? 1 : 0;
+}
 // argument rules shared by the three RGB-D entry points (checked before any device work)
 static orbx_status rgbd_check(int nframes, const void *depth, int format, int width, int height, int stride, int64_t frame_stride) {
     if (format != ORBX_DEPTH_U16 && format != ORBX_DEPTH_F32) return fail(ORBX_BAD_ARGUMENT, "unknown depth format");
@@ -1108,8 +986,6 @@ extern "C" orbx_status orbx_rgbd_depth_device(orbx_handle *h, int nframes, const
     return ORBX_OK;
 }
 
-static orbx_status scratch_reserve(orbx_handle *h, size_t bytes);
-template <typename T> static T *scratch_take(orbx_handle *h, size_t count);
 extern "C" orbx_status orbx_rgbd_depth(orbx_handle *h, const orbx_keypoint *kps, const orbx_keypoint *kps_un, int n, const void *depth,
                                        int depth_format, int width, int height, int stride, float depth_scale, float mbf,
                                        float *u_right, float *depth_out) {
@@ -1313,40 +1189,62 @@ extern "C" orbx_status orbx_debug_fast_groups(orbx_handle *h, int *level0, int *
     return ORBX_OK;
 }
 
-// ---------------------------------------------------------------- scratch arena
-static orbx_status scratch_reserve(orbx_handle *h, size_t bytes) {
-    h->scratch_used = 0;
-    if (bytes <= h->scratch_bytes) return ORBX_OK;
+
+// ---------------------------------------------------------------- staging (orbx_handle.h): device arena + page-locked block
+orbx_status dev_grow(orbx_handle *h, void **p, size_t *cap, size_t need, size_t want, size_t elem) {
+    if (need <= *cap) return ORBX_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
-    hipFree(h->d_scratch); h->d_scratch = nullptr; h->scratch_bytes = 0;
-    const size_t want = std::max(bytes, (size_t)1 << 20);
-    HIPCHK(hipMalloc(&h->d_scratch, want));
-    h->scratch_bytes = want;
+    hipFree(*p); *p = nullptr; *cap = 0;
+    HIPCHK(hipMalloc(p, want * elem));
+    *cap = want;
     return ORBX_OK;
 }
-template <typename T> static T *scratch_take(orbx_handle *h, size_t count) {
-    T *p = (T *)(h->d_scratch + h->scratch_used);
-    h->scratch_used += (count * sizeof(T) + 255) & ~(size_t)255;
-    return p;
+orbx_status scratch_reserve(orbx_handle *h, size_t bytes) {
+    h->scratch_used = 0;
+    return dev_grow(h, (void **)&h->d_scratch, &h->scratch_bytes, bytes, std::max(bytes, (size_t)1 << 20));
 }
-static inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+static orbx_status pin_grow(orbx_handle *h, uint8_t **p, size_t *cap, size_t bytes) {   // the one growth rule of both blocks
+    if (bytes <= *cap) return ORBX_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (*p) hipHostFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 20);
+    HIPCHK(hipHostMalloc((void **)p, want, hipHostMallocDefault));
+    *cap = want;
+    return ORBX_OK;
+}
+orbx_status stage_pin(orbx_handle *h, size_t bytes) { return pin_grow(h, &h->pin, &h->pin_bytes, bytes); }
+// (a call that returns early leaves h->pin_early pending: the next one waits for that copy here; steady state does not meet it)
+orbx_status stage_begin(orbx_handle *h, size_t pin_bytes, size_t dev_bytes, uint8_t **pin, uint8_t **dev, bool returns_early) {
+    HIPCHK(hipSetDevice(h->dev));
+    h->stage_early = returns_early;
+    if (returns_early && h->stage_pending) { HIPCHK(hipEventSynchronize(h->ev_stage)); h->stage_pending = false; }
+    orbx_status st = returns_early ? pin_grow(h, &h->pin_early, &h->pin_early_bytes, pin_bytes) : stage_pin(h, pin_bytes);
+    if (st == ORBX_OK) st = scratch_reserve(h, dev_bytes + 256);
+    if (st != ORBX_OK) return st;
+    *pin = returns_early ? h->pin_early : h->pin;
+    *dev = scratch_take<uint8_t>(h, dev_bytes);
+    return ORBX_OK;
+}
+orbx_status stage_upload(orbx_handle *h, const uint8_t *pin, uint8_t *dev, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, h->stream));
+    if (!h->stage_early) return ORBX_OK;
+    if (!h->ev_stage) HIPCHK(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(h->ev_stage, h->stream));
+    h->stage_pending = true;
+    return ORBX_OK;
+}
+orbx_status stage_download_wait(orbx_handle *h, uint8_t *pin, const uint8_t *d_out, size_t bytes) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(pin, d_out, bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
+    return ORBX_OK;
+}
 
 // ---------------------------------------------------------------- device grid + gated candidate lists (orbx_gate.h)
 static orbx_status gate_items_reserve(orbx_handle *h, size_t words) {
-    if (words <= h->gate_items_cap) return ORBX_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    hipFree(h->d_gate_items); h->d_gate_items = nullptr; h->gate_items_cap = 0;
-    const size_t want = std::max(words + words / 2, (size_t)1 << 16);
-    HIPCHK(hipMalloc(&h->d_gate_items, want * sizeof(uint32_t)));
-    h->gate_items_cap = want;
-    return ORBX_OK;
-}
-static bool grid_params(float min_x, float max_x, float min_y, float max_y, DGrid &gp) {
-    if (!(max_x > min_x) || !(max_y > min_y)) return false;
-    gp.minx = min_x; gp.miny = min_y;
-    gp.winv = 64.0f / (max_x - min_x);     // mfGridElementWidthInv (src/Frame.cc:96-99): FRAME_GRID_COLS / (mnMaxX - mnMinX)
-    gp.hinv = 48.0f / (max_y - min_y);
-    return true;
+    return dev_grow(h, (void **)&h->d_gate_items, &h->gate_items_cap, words, std::max(words + words / 2, (size_t)1 << 16), sizeof(uint32_t));
 }
 
 // Frame::AssignFeaturesToGrid on the device, for the buffers orbx_extract_batch_device (or orbx_undistort_keypoints_device)
@@ -1363,17 +1261,6 @@ extern "C" orbx_status orbx_grid_build_device(orbx_handle *h, int nframes, const
       orbx_launch_grid_build(h->stream, gp, nframes, d_kps, d_counts, 0, cap, d_cell_begin, d_items); }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
-    return ORBX_OK;
-}
-
-static orbx_status pin_reserve(orbx_handle *h, size_t bytes) {
-    if (bytes <= h->pin_bytes) return ORBX_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->pin) hipHostFree(h->pin);
-    h->pin = nullptr; h->pin_bytes = 0;
-    const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 20);
-    HIPCHK(hipHostMalloc((void **)&h->pin, want, hipHostMallocDefault));
-    h->pin_bytes = want;
     return ORBX_OK;
 }
 
@@ -1410,7 +1297,7 @@ orbx_status orbx_gate_lists_batch(orbx_handle *h, const OrbxGateTarget *tg, int 
     if (st != ORBX_OK) return st;
     const size_t span_bytes = (size_t)nq * sizeof(uint2);
     size_t guess = std::min(h->gate_guess, h->gate_items_cap);
-    st = pin_reserve(h, in_bytes + span_bytes + 256 + h->gate_items_cap * 4);
+    st = stage_pin(h, in_bytes + span_bytes + 256 + h->gate_items_cap * 4);   // (sized by the candidate buffer, which may grow again below)
     if (st != ORBX_OK) return st;
     uint8_t *pin_in = h->pin, *pin_out = h->pin + in_bytes;   // pin_out: spans | cursor (256) | items
     memset(pin_in + o_cur, 0, 256);
@@ -1443,7 +1330,7 @@ orbx_status orbx_gate_lists_batch(orbx_handle *h, const OrbxGateTarget *tg, int 
         // the lists did not fit the buffer: nothing beyond the spans was trusted; grow, reset the cursor, run k_gate again
         if (attempt == 1) return fail(ORBX_CAPACITY, "candidate lists");
         st = gate_items_reserve(h, total);
-        if (st == ORBX_OK) st = pin_reserve(h, in_bytes + span_bytes + 256 + h->gate_items_cap * 4);
+        if (st == ORBX_OK) st = stage_pin(h, in_bytes + span_bytes + 256 + h->gate_items_cap * 4);
         if (st != ORBX_OK) return st;
         pin_in = h->pin; pin_out = h->pin + in_bytes;
         HIPCHK(hipMemsetAsync(dcur, 0, 4, s));
@@ -1493,29 +1380,25 @@ orbx_status orbx_block_distances(orbx_handle *h, const uint8_t *d1, int n1, cons
     out.assign(total, 0);
     if (!h || h->host_only) return fail(h ? ORBX_NO_DEVICE : ORBX_BAD_ARGUMENT, "no device handle");
     if (rows.empty() || total == 0) return ORBX_OK;
-    HIPCHK(hipSetDevice(h->dev));
     const size_t o_a = 0, o_b = o_a + pad256((size_t)n1 * 32), o_r = o_b + pad256((size_t)n2 * 32),
                  o_c = o_r + pad256(rows.size() * sizeof(DDistRow)), in_bytes = o_c + pad256(col_idx.size() * 4);
-    orbx_status st = scratch_reserve(h, in_bytes + 256);
+    uint8_t *pin_in = nullptr, *d = nullptr;
+    orbx_status st = stage_begin(h, in_bytes + pad256(total * sizeof(uint16_t)), in_bytes, &pin_in, &d, false);
     if (st == ORBX_OK) st = gate_items_reserve(h, (total + 1) / 2);
-    if (st == ORBX_OK) st = pin_reserve(h, in_bytes + pad256(total * sizeof(uint16_t)));
     if (st != ORBX_OK) return st;
-    uint8_t *pin_in = h->pin, *pin_out = h->pin + in_bytes;
+    uint8_t *pin_out = pin_in + in_bytes;
     memcpy(pin_in + o_a, d1, (size_t)n1 * 32);
     memcpy(pin_in + o_b, d2, (size_t)n2 * 32);
     memcpy(pin_in + o_r, rows.data(), rows.size() * sizeof(DDistRow));
     memcpy(pin_in + o_c, col_idx.data(), col_idx.size() * 4);
-    uint8_t *d = scratch_take<uint8_t>(h, in_bytes);
-    hipStream_t s = h->stream;
-    HIPCHK(hipMemcpyAsync(d, pin_in, in_bytes, hipMemcpyHostToDevice, s));
+    st = stage_upload(h, pin_in, d, in_bytes);
+    if (st != ORBX_OK) return st;
     { ProfScope ps(h, ORBX_K_MATCH);
-      orbx_launch_block_dist(s, d + o_a, d + o_b, (const DDistRow *)(d + o_r), (const uint32_t *)(d + o_c), (int)rows.size(),
+      orbx_launch_block_dist(h->stream, d + o_a, d + o_b, (const DDistRow *)(d + o_r), (const uint32_t *)(d + o_c), (int)rows.size(),
                              (uint16_t *)h->d_gate_items); }
-    HIPCHK(hipMemcpyAsync(pin_out, h->d_gate_items, total * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    st = stage_download_wait(h, pin_out, (const uint8_t *)h->d_gate_items, total * sizeof(uint16_t));
+    if (st != ORBX_OK) return st;
     memcpy(out.data(), pin_out, total * sizeof(uint16_t));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
     return ORBX_OK;
 }
 
@@ -1532,16 +1415,14 @@ orbx_status orbx_bow_select_batch(orbx_handle *h, bool kk, const OrbxBowSet *set
     }
     if (nfeat > 0xffffffffull / 32 || nidx > 0xffffffffull || (size_t)K * nout > 0xffffffffull)
         return fail(ORBX_UNSUPPORTED, "batch too large for 32-bit offsets");
-    HIPCHK(hipSetDevice(h->dev));
     // counts | outputs (the download) | descriptors | angles | MapPoint flags | indices | work items | candidate bases
     const size_t o_cnt = 0, o_out = pad256((size_t)K * 4), o_desc = o_out + pad256((size_t)K * nout * 4),
                  o_ang = o_desc + pad256(nfeat * 32), o_hmp = o_ang + pad256(nfeat * 4), o_idx = o_hmp + pad256(nfeat),
                  o_it = o_idx + pad256(nidx * 4), o_cb = o_it + pad256(items.size() * sizeof(DBowItem)),
                  in_bytes = o_cb + pad256((size_t)K * 4), down_bytes = o_out + (size_t)K * nout * 4;
-    orbx_status st = scratch_reserve(h, in_bytes + 256);
-    if (st == ORBX_OK) st = pin_reserve(h, in_bytes);
+    uint8_t *pin = nullptr, *d = nullptr;
+    orbx_status st = stage_begin(h, in_bytes, in_bytes, &pin, &d, false);
     if (st != ORBX_OK) return st;
-    uint8_t *pin = h->pin;
     memset(pin + o_cnt, 0, (size_t)K * 4);
     memset(pin + o_out, 0xff, (size_t)K * nout * 4);
     size_t fb = 0, ib = 0;
@@ -1560,18 +1441,16 @@ orbx_status orbx_bow_select_batch(orbx_handle *h, bool kk, const OrbxBowSet *set
         fb += (size_t)S.n; ib += ni;
     }
     if (!items.empty()) memcpy(pin + o_it, items.data(), items.size() * sizeof(DBowItem));
-    uint8_t *d = scratch_take<uint8_t>(h, in_bytes);
     hipStream_t s = h->stream;
-    HIPCHK(hipMemcpyAsync(d, pin, in_bytes, hipMemcpyHostToDevice, s));
+    st = stage_upload(h, pin, d, in_bytes);
+    if (st != ORBX_OK) return st;
     { ProfScope ps(h, ORBX_K_MATCH);
       orbx_launch_bow_select(s, kk, (const DBowItem *)(d + o_it), (int)items.size(), (const uint32_t *)(d + o_idx), d + o_desc,
                              d + o_hmp, nnratio, std::max(1, (max_ncol + 31) / 32), (int32_t *)(d + o_out));
       orbx_launch_bow_rot(s, kk, K, nout, (const uint32_t *)(d + o_cb), (const float *)(d + o_ang), check_orientation ? 1 : 0,
                           (int32_t *)(d + o_out), (int32_t *)(d + o_cnt)); }
-    HIPCHK(hipMemcpyAsync(pin, d, down_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
+    st = stage_download_wait(h, pin, d, down_bytes);
+    if (st != ORBX_OK) return st;
     for (int k = 0; k < K; ++k) {
         nmatches[k] = ((const int32_t *)(pin + o_cnt))[k];
         if (nout > 0) memcpy(outs[k], pin + o_out + (size_t)k * nout * 4, (size_t)nout * 4);
@@ -1589,12 +1468,8 @@ extern "C" orbx_status orbx_match_bruteforce_device(orbx_handle *h, int npairs, 
         return fail(ORBX_BAD_ARGUMENT, "bad argument");
     HIPCHK(hipSetDevice(h->dev));
     const size_t need = orbx_match_workspace_bytes(npairs, out_stride);
-    if (need > h->match_ws_bytes) {   // grows only when a larger problem than ever before arrives
-        HIPCHK(hipStreamSynchronize(h->stream));
-        hipFree(h->d_match_ws); h->d_match_ws = nullptr; h->match_ws_bytes = 0;
-        HIPCHK(hipMalloc(&h->d_match_ws, need));
-        h->match_ws_bytes = need;
-    }
+    const orbx_status st = dev_grow(h, &h->d_match_ws, &h->match_ws_bytes, need, need);   // grows only when a larger problem than ever before arrives
+    if (st != ORBX_OK) return st;
     { ProfScope ps(h, ORBX_K_MATCH);
       orbx_launch_match(h->stream, npairs, out_stride, d_q, d_nq, q_stride, d_t, d_nt, t_stride, d_best_idx, d_best_dist,
                         d_second_dist, out_stride, h->d_match_ws, h->match_kernel); }
@@ -2160,29 +2035,6 @@ extern "C" orbx_status orbx_search_by_projection_mappoints(orbx_handle *h, const
 // k_track_project (frame policy) + k_track_cand + k_track_select on the handle's stream.  Nothing is downloaded and nothing is
 // waited for, with two exceptions that steady state does not meet: a block or an arena that has to grow, and a call issued
 // while the upload of the call before it has not yet left the staging block.
-static orbx_status track_stage(orbx_handle *h, const OrbxTrackPlan &plan, uint8_t **pin, uint8_t **dev) {
-    HIPCHK(hipSetDevice(h->dev));
-    if (!h->ev_track) HIPCHK(hipEventCreateWithFlags(&h->ev_track, hipEventDisableTiming));
-    if (h->track_pending) { HIPCHK(hipEventSynchronize(h->ev_track)); h->track_pending = false; }
-    if (plan.in_bytes > h->track_pin_bytes) {
-        if (h->track_pin) hipHostFree(h->track_pin);
-        h->track_pin = nullptr; h->track_pin_bytes = 0;
-        const size_t want = std::max(plan.in_bytes + plan.in_bytes / 2, (size_t)1 << 20);
-        HIPCHK(hipHostMalloc((void **)&h->track_pin, want, hipHostMallocDefault));
-        h->track_pin_bytes = want;
-    }
-    const orbx_status st = scratch_reserve(h, plan.dev_bytes + 256);
-    if (st != ORBX_OK) return st;
-    *pin = h->track_pin;
-    *dev = scratch_take<uint8_t>(h, plan.dev_bytes);
-    return ORBX_OK;
-}
-static orbx_status track_upload(orbx_handle *h, const OrbxTrackPlan &plan, const uint8_t *pin, uint8_t *dev) {
-    HIPCHK(hipMemcpyAsync(dev, pin, plan.in_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipEventRecord(h->ev_track, h->stream));
-    h->track_pending = true;
-    return ORBX_OK;
-}
 static bool track_frames(OrbxTrackFrames &F, const orbx_keypoint *d_keys_un, const uint8_t *d_desc, const float *d_u_right,
                          const int32_t *d_counts, int cap, const int32_t *d_cell_begin, const uint16_t *d_items, const float *bounds4) {
     if (!grid_params(bounds4[0], bounds4[1], bounds4[2], bounds4[3], F.gp)) return false;
@@ -2212,10 +2064,10 @@ extern "C" orbx_status orbx_search_by_projection_frame_batch_device(orbx_handle 
     if (nproblems == 0) return ORBX_OK;
     if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
     uint8_t *pin = nullptr, *d = nullptr;
-    st = track_stage(h, plan, &pin, &d);
+    st = stage_begin(h, plan.in_bytes, plan.dev_bytes, &pin, &d, true);
     if (st != ORBX_OK) return st;
     orbx_track_frame_pack(nproblems, problems, plan, h->tab.scale, mb, pin);
-    st = track_upload(h, plan, pin, d);
+    st = stage_upload(h, pin, d, plan.in_bytes);
     if (st != ORBX_OK) return st;
     const DTrackProb *dp = (const DTrackProb *)(d + plan.o_prob);
     DTrackQ *dq = (DTrackQ *)(d + plan.o_q);
@@ -2252,10 +2104,10 @@ extern "C" orbx_status orbx_search_by_projection_mappoints_batch_device(orbx_han
     if (nproblems == 0) return ORBX_OK;
     if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
     uint8_t *pin = nullptr, *d = nullptr;
-    st = track_stage(h, plan, &pin, &d);
+    st = stage_begin(h, plan.in_bytes, plan.dev_bytes, &pin, &d, true);
     if (st != ORBX_OK) return st;
     orbx_track_points_pack(nproblems, problems, plan, h->tab.scale, cap, pin);
-    st = track_upload(h, plan, pin, d);
+    st = stage_upload(h, pin, d, plan.in_bytes);
     if (st != ORBX_OK) return st;
     const DTrackProb *dp = (const DTrackProb *)(d + plan.o_prob);
     const DTrackQ *dq = (const DTrackQ *)(d + plan.o_q);
@@ -2305,13 +2157,11 @@ extern "C" orbx_status orbx_search_local_points_batch_device(orbx_handle *h, int
         return fail(ORBX_BAD_ARGUMENT, "bad image bounds");
     if (nproblems == 0) return ORBX_OK;
     if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
-    OrbxTrackPlan stage;   // the staging block and the arena are those of the two tracking matchers
-    stage.in_bytes = plan.in_bytes; stage.dev_bytes = plan.dev_bytes;
     uint8_t *pin = nullptr, *d = nullptr;
-    st = track_stage(h, stage, &pin, &d);
+    st = stage_begin(h, plan.in_bytes, plan.dev_bytes, &pin, &d, true);
     if (st != ORBX_OK) return st;
     orbx_track_local_pack(nproblems, problems, map, plan, cap, pin);
-    st = track_upload(h, stage, pin, d);
+    st = stage_upload(h, pin, d, plan.in_bytes);
     if (st != ORBX_OK) return st;
     const DTrackProb *dp = (const DTrackProb *)(d + plan.o_prob);
     DTrackQ *dq = (DTrackQ *)(d + plan.o_q);
@@ -2332,20 +2182,8 @@ extern "C" orbx_status orbx_search_local_points_batch_device(orbx_handle *h, int
 
 // ---------------------------------------------------------------- MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth,
 // batched (orbx_mappoint.h).  One call: validation and plan (orbx_mappoint.cpp), the caller's arrays packed into the page-locked
-// block of the tracking matchers, ONE upload, the launches on the handle's stream, ONE download into the same block, the wait,
-// and the scatter into the caller's arrays.
-static orbx_status mp_run_begin(orbx_handle *h, size_t in_bytes, size_t out_bytes, size_t dev_bytes, uint8_t **pin, uint8_t **dev) {
-    OrbxTrackPlan stage;
-    stage.in_bytes = std::max(in_bytes, out_bytes); stage.dev_bytes = dev_bytes;
-    return track_stage(h, stage, pin, dev);
-}
-static orbx_status mp_run_end(orbx_handle *h, uint8_t *pin, const uint8_t *d_out, size_t out_bytes) {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(pin, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(ORBX_HIP_ERROR, hipGetErrorString(e));
-    return ORBX_OK;
-}
+// block, ONE upload, the launches on the handle's stream, ONE download into the same block, the wait, and the scatter into the
+// caller's arrays.
 static orbx_status mp_distinct(orbx_handle *h, bool device_form, const uint8_t *d_pool, int64_t pool_rows, int npoints,
                                const int32_t *obs_begin, const uint8_t *desc, const int64_t *obs_row, int32_t *best_idx,
                                int32_t *best_median, uint8_t *best_desc) {
@@ -2357,17 +2195,18 @@ static orbx_status mp_distinct(orbx_handle *h, bool device_form, const uint8_t *
     if (npoints == 0) return ORBX_OK;
     if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
     uint8_t *pin = nullptr, *d = nullptr;
-    st = mp_run_begin(h, plan.in_bytes, plan.out_bytes, plan.dev_bytes, &pin, &d);
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), plan.dev_bytes, &pin, &d, false);
     if (st != ORBX_OK) return st;
     if (plan.n_small + plan.n_wide > 0) {
         orbx_mp_distinct_pack(obs_begin, desc, device_form ? obs_row : nullptr, plan, pin);
-        HIPCHK(hipMemcpyAsync(d, pin, plan.in_bytes, hipMemcpyHostToDevice, h->stream));
+        st = stage_upload(h, pin, d, plan.in_bytes);
+        if (st != ORBX_OK) return st;
         { ProfScope ps(h, ORBX_K_MATCH);
           orbx_launch_mp_distinct(h->stream, (const int32_t *)(d + plan.o_begin), device_form ? d_pool : d + plan.o_rows,
                                   device_form ? (const int64_t *)(d + plan.o_rows) : nullptr, (const int32_t *)(d + plan.o_order),
                                   plan.n_small, plan.n_wide, (int32_t *)(d + plan.o_idx), (int32_t *)(d + plan.o_med),
                                   d + plan.o_desc); }
-        st = mp_run_end(h, pin, d + plan.o_idx, plan.out_bytes);
+        st = stage_download_wait(h, pin, d + plan.o_idx, plan.out_bytes);
         if (st != ORBX_OK) return st;
     }
     orbx_mp_distinct_unpack(obs_begin, plan, pin, best_idx, best_median, best_desc);   // (reads no entry of a point without rows)
@@ -2395,23 +2234,24 @@ extern "C" orbx_status orbx_update_normal_and_depth_batch(orbx_handle *h, int np
     if (h->host_only) return fail(ORBX_NO_DEVICE, "no device handle");
     if (plan.nrows == 0) return ORBX_OK;                             // no point has rows: nothing is written
     uint8_t *pin = nullptr, *d = nullptr;
-    st = mp_run_begin(h, plan.in_bytes, plan.out_bytes, plan.dev_bytes, &pin, &d);
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), plan.dev_bytes, &pin, &d, false);
     if (st != ORBX_OK) return st;
     orbx_mp_normal_pack(obs_begin, pos, centers, ref_center, ref_level, h->tab.scale, plan, pin);
-    HIPCHK(hipMemcpyAsync(d, pin, plan.in_bytes, hipMemcpyHostToDevice, h->stream));
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
     { ProfScope ps(h, ORBX_K_MISC);
       orbx_launch_mp_normal_depth(h->stream, (const int32_t *)(d + plan.o_begin), (const DMpPoint *)(d + plan.o_points),
                                   (const float *)(d + plan.o_centers), npoints, h->tab.scale[h->p.nlevels - 1],
                                   (float *)(d + plan.o_out)); }
-    st = mp_run_end(h, pin, d + plan.o_out, plan.out_bytes);
+    st = stage_download_wait(h, pin, d + plan.o_out, plan.out_bytes);
     if (st != ORBX_OK) return st;
     orbx_mp_normal_unpack(obs_begin, plan, pin, normal, min_distance, max_distance);
     return ORBX_OK;
 }
 
 // ---------------------------------------------------------------- Optimizer::PoseOptimization(Frame*), batched (orbx_pose.h).
-// Device path: validation and layout (orbx_pose.cpp), all problems' host state and the pool packed into the page-locked block of
-// the tracking matchers, ONE upload, k_pose_opt on the handle's stream; nothing downloaded, nothing waited for.  Host path
+// Device path: validation and layout (orbx_pose.cpp), all problems' host state and the pool packed into the page-locked
+// block, ONE upload, k_pose_opt on the handle's stream; nothing downloaded, nothing waited for.  Host path
 // (ORBX_POSE=host, read per call; host-only handles, where the "d_" arguments are host arrays): the same header compiled by
 // the host compiler.  On a device handle it downloads the rows it needs, runs, and uploads the results -- a cross-check, not a
 // fast path.
@@ -2463,13 +2303,11 @@ static orbx_status pose_batch(orbx_handle *h, int nproblems, const orbx_pose_pro
         HIPCHK(hipMemcpy(d_ninliers, nin.data(), nin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         return ORBX_OK;
     }
-    OrbxTrackPlan stage;   // the staging block and the arena are those of the tracking matchers
-    stage.in_bytes = plan.in_bytes; stage.dev_bytes = plan.in_bytes;
     uint8_t *pin = nullptr, *d = nullptr;
-    st = track_stage(h, stage, &pin, &d);
+    st = stage_begin(h, plan.in_bytes, plan.in_bytes, &pin, &d, true);
     if (st != ORBX_OK) return st;
     orbx_pose_pack(problems, c, plan, pin);
-    st = track_upload(h, stage, pin, d);
+    st = stage_upload(h, pin, d, plan.in_bytes);
     if (st != ORBX_OK) return st;
     DPoseArgs a;
     a.prob = (const DPoseProb *)(d + plan.o_prob);
@@ -2696,11 +2534,6 @@ extern "C" orbx_status orbx_bow_vectors(const orbx_vocabulary *voc, const uint32
 // ---------------------------------------------------------------- (f)2: Frame::UndistortKeyPoints / ComputeImageBounds
 // (src/Frame.cc:770-865): cv::undistortPoints(K, D, R = I, P = K) on the device (k_undistort).  camera4 = fx, fy, cx, cy
 // (mK), dist = mDistCoef (k1, k2, p1, p2[, k3 ...], up to 14).  dist[0] == 0 copies the keypoints (:772-776).
-static void undistort_args(const float *camera4, const float *dist, int ndist, double *K4, double *k14, int *identity) {
-    for (int i = 0; i < 4; ++i) K4[i] = (double)camera4[i];
-    for (int i = 0; i < 14; ++i) k14[i] = i < ndist ? (double)dist[i] : 0.0;
-    *identity = (ndist < 1 || dist[0] == 0.0f) ? 1 : 0;
-}
 extern "C" orbx_status orbx_undistort_keypoints_device(orbx_handle *h, int nframes, const orbx_keypoint *d_kps,
                                                        const int32_t *d_counts, int cap, const float *camera4, const float *dist,
                                                        int ndist, orbx_keypoint *d_kps_un) {

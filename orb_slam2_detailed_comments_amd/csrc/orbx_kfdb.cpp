@@ -17,25 +17,12 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
-#include "orbx_internal.h"
-#include "orbx_launch.h"
-
-orbx_status orbx_fail(orbx_status s, const std::string &msg);   // orbx_api.cpp: records orbx_last_error()
-int orbx_handle_fp_mode(const orbx_handle *h);
-bool orbx_handle_host_only(const orbx_handle *h);
-int orbx_handle_device(const orbx_handle *h);
+#include "orbx_handle.h"
 
 namespace {
-#define KF_HIPCHK(expr)                                                                                  \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess) return orbx_fail(ORBX_HIP_ERROR, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 // ---- DBoW2 scoring (ScoringObject.cpp:23-315).  The lower_bound skips of the reference visit the same common words as this
 // plain merge, in the same ascending order.  fma_mode: `score += vi * wi` is one fused multiply-add in a GCC -O3 -march=native
 // build; the other expressions have no product feeding an addition directly.
@@ -194,13 +181,13 @@ void fold_pending(orbx_kfdb *db) {
 // repack the pool from the host copies (after enough erased words have piled up, or to grow it)
 orbx_status pool_rebuild(orbx_kfdb *db, size_t want_cap) {
     hipStream_t s = kf_stream(db);
-    KF_HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipStreamSynchronize(s));
     if (want_cap > db->pool_cap) {
         if (db->d_pool_w) hipFree(db->d_pool_w);
         if (db->d_pool_v) hipFree(db->d_pool_v);
         db->d_pool_w = nullptr; db->d_pool_v = nullptr; db->pool_cap = 0;
-        KF_HIPCHK(hipMalloc((void **)&db->d_pool_w, want_cap * sizeof(uint32_t)));
-        KF_HIPCHK(hipMalloc((void **)&db->d_pool_v, want_cap * sizeof(double)));
+        HIPCHK(hipMalloc((void **)&db->d_pool_w, want_cap * sizeof(uint32_t)));
+        HIPCHK(hipMalloc((void **)&db->d_pool_v, want_cap * sizeof(double)));
         db->pool_cap = want_cap;
     }
     db->stage_w.clear(); db->stage_v.clear();
@@ -229,14 +216,14 @@ orbx_status pool_flush(orbx_kfdb *db) {
     }
     const size_t n = db->pool_used - db->pool_uploaded;
     if (n > 0) {
-        KF_HIPCHK(hipMemcpyAsync(db->d_pool_w + db->pool_uploaded, db->stage_w.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        KF_HIPCHK(hipMemcpyAsync(db->d_pool_v + db->pool_uploaded, db->stage_v.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(db->d_pool_w + db->pool_uploaded, db->stage_w.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(db->d_pool_v + db->pool_uploaded, db->stage_v.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
     }
     if (db->slots_dirty && !db->slots.empty()) {
-        KF_HIPCHK(db->d_slots.need(db->slots.size()));
-        KF_HIPCHK(hipMemcpyAsync(db->d_slots.p, db->slots.data(), db->slots.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
+        HIPCHK(db->d_slots.need(db->slots.size()));
+        HIPCHK(hipMemcpyAsync(db->d_slots.p, db->slots.data(), db->slots.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
     }
-    if (n > 0 || db->slots_dirty) KF_HIPCHK(hipStreamSynchronize(s));   // the staging vectors are pageable and reused
+    if (n > 0 || db->slots_dirty) HIPCHK(hipStreamSynchronize(s));   // the staging vectors are pageable and reused
     db->stage_w.clear(); db->stage_v.clear();
     db->pool_uploaded = db->pool_used;
     db->slots_dirty = false;
@@ -304,45 +291,45 @@ orbx_status device_queries(orbx_kfdb *db, int nq, const int32_t *q_begin, const 
     if (nlive == 0 || q_begin[nq] == 0) return ORBX_OK;
     hipStream_t s = kf_stream(db);
     const size_t total = (size_t)q_begin[nq];
-    KF_HIPCHK(db->d_qw.need(total)); KF_HIPCHK(db->d_qv.need(total)); KF_HIPCHK(db->d_qbegin.need((size_t)nq + 1));
-    KF_HIPCHK(hipMemcpyAsync(db->d_qw.p, qw, total * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    KF_HIPCHK(hipMemcpyAsync(db->d_qv.p, qv, total * sizeof(double), hipMemcpyHostToDevice, s));
-    KF_HIPCHK(hipMemcpyAsync(db->d_qbegin.p, q_begin, ((size_t)nq + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(db->d_qw.need(total)); HIPCHK(db->d_qv.need(total)); HIPCHK(db->d_qbegin.need((size_t)nq + 1));
+    HIPCHK(hipMemcpyAsync(db->d_qw.p, qw, total * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(db->d_qv.p, qv, total * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(db->d_qbegin.p, q_begin, ((size_t)nq + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (connected) {
-        KF_HIPCHK(db->d_conn.need((size_t)nslots));
-        KF_HIPCHK(hipMemcpyAsync(db->d_conn.p, connected->data(), (size_t)nslots, hipMemcpyHostToDevice, s));
+        HIPCHK(db->d_conn.need((size_t)nslots));
+        HIPCHK(hipMemcpyAsync(db->d_conn.p, connected->data(), (size_t)nslots, hipMemcpyHostToDevice, s));
     }
     // the records of a launch set are bounded by its (query, live entry) pairs: a call whose pairs exceed the budget runs in
     // several sets of whole queries (one round trip each)
     const size_t budget = 8u << 20;
     int chunk = (int)std::min<size_t>(std::max<size_t>(1, budget / nlive), 32768);
-    KF_HIPCHK(db->d_qmax.need((size_t)nq + 1));
+    HIPCHK(db->d_qmax.need((size_t)nq + 1));
     for (int q0 = 0; q0 < nq; q0 += chunk) {
         const int qc = std::min(chunk, nq - q0);
         const size_t cap = (size_t)qc * nlive;
-        KF_HIPCHK(db->d_rec.need(cap));
+        HIPCHK(db->d_rec.need(cap));
         int *d_qmax = db->d_qmax.p;
         uint32_t *d_cursor = (uint32_t *)(db->d_qmax.p + nq);
-        KF_HIPCHK(hipMemsetAsync(d_qmax, 0, ((size_t)nq + 1) * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(d_qmax, 0, ((size_t)nq + 1) * sizeof(int), s));
         orbx_launch_kfdb_common(s, db->d_slots.p, nslots, db->d_pool_w, db->d_qw.p, db->d_qbegin.p, q0, qc,
                                 connected ? db->d_conn.p : nullptr, d_qmax, d_cursor, db->d_rec.p, (uint32_t)cap);
         orbx_launch_kfdb_score(s, db->d_rec.p, d_cursor, (uint32_t)cap, d_qmax, db->d_slots.p, db->d_pool_w, db->d_pool_v,
                                db->d_qw.p, db->d_qv.p, db->d_qbegin.p, db->scoring, db->fma_mode ? 1 : 0);
-        KF_HIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         uint32_t nrec = 0;
-        KF_HIPCHK(hipMemcpyAsync(&nrec, d_cursor, sizeof(nrec), hipMemcpyDeviceToHost, s));
-        KF_HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpyAsync(&nrec, d_cursor, sizeof(nrec), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
         if (nrec > cap) return orbx_fail(ORBX_HIP_ERROR, "keyframe database: more sharer records than (query, entry) pairs");
         if (nrec > db->rec_cap) {
             if (db->rec) hipHostFree(db->rec);
             db->rec = nullptr; db->rec_cap = 0;
             const size_t c = (size_t)nrec + nrec / 2 + 1024;
-            KF_HIPCHK(hipHostMalloc((void **)&db->rec, c * sizeof(DKfRec), hipHostMallocDefault));
+            HIPCHK(hipHostMalloc((void **)&db->rec, c * sizeof(DKfRec), hipHostMallocDefault));
             db->rec_cap = c;
         }
         if (nrec) {
-            KF_HIPCHK(hipMemcpyAsync(db->rec, db->d_rec.p, (size_t)nrec * sizeof(DKfRec), hipMemcpyDeviceToHost, s));
-            KF_HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(hipMemcpyAsync(db->rec, db->d_rec.p, (size_t)nrec * sizeof(DKfRec), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
         }
         const DKfRec *recs = db->rec;
         // Bucket the records by query (they arrive in no order).  The order of lKFsSharingWords = first encounter = (smallest
@@ -442,7 +429,7 @@ extern "C" orbx_status orbx_bow_score(const orbx_handle *h, int scoring, const u
                                       const uint32_t *b_word, const double *b_value, int nb, double *score) {
     if (!h || !score || scoring < 0 || scoring > 5) return orbx_fail(ORBX_BAD_ARGUMENT, "orbx_bow_score: null argument or scoring type");
     if (!bow_ok(a_word, a_value, na) || !bow_ok(b_word, b_value, nb)) return orbx_fail(ORBX_BAD_ARGUMENT, "BowVector words must ascend");
-    *score = bow_score(scoring, orbx_handle_fp_mode(h) == ORBX_FP_GCC_FMA, a_word, a_value, na, b_word, b_value, nb);
+    *score = bow_score(scoring, h->p.fp_mode == ORBX_FP_GCC_FMA, a_word, a_value, na, b_word, b_value, nb);
     return ORBX_OK;
 }
 
@@ -452,9 +439,9 @@ extern "C" orbx_status orbx_kfdb_create(orbx_handle *h, int scoring, orbx_kfdb *
     if (scoring < 0 || scoring > 5) return orbx_fail(ORBX_BAD_ARGUMENT, "scoring type out of range [0,5]");
     orbx_kfdb *db = new orbx_kfdb();
     db->h = h; db->scoring = scoring;
-    db->host_only = orbx_handle_host_only(h);
-    db->dev = orbx_handle_device(h);
-    db->fma_mode = orbx_handle_fp_mode(h) == ORBX_FP_GCC_FMA;
+    db->host_only = h->host_only;
+    db->dev = h->dev;
+    db->fma_mode = h->p.fp_mode == ORBX_FP_GCC_FMA;
     *out = db;
     return ORBX_OK;
 }
@@ -564,22 +551,22 @@ extern "C" orbx_status orbx_kfdb_score_entries(orbx_kfdb *db, const uint32_t *q_
         return ORBX_OK;
     }
     if (db->scoring == 3) return orbx_fail(ORBX_UNSUPPORTED, "KL scoring needs libm's log: use orbx_bow_score or ORBX_KFDB=host");
-    KF_HIPCHK(hipSetDevice(db->dev));
+    HIPCHK(hipSetDevice(db->dev));
     orbx_status st = pool_flush(db);
     if (st != ORBX_OK) return st;
     hipStream_t s = kf_stream(db);
-    KF_HIPCHK(db->d_qw.need((size_t)nq + 1)); KF_HIPCHK(db->d_qv.need((size_t)nq + 1));
-    KF_HIPCHK(db->d_list.need((size_t)n)); KF_HIPCHK(db->d_out.need((size_t)n));
+    HIPCHK(db->d_qw.need((size_t)nq + 1)); HIPCHK(db->d_qv.need((size_t)nq + 1));
+    HIPCHK(db->d_list.need((size_t)n)); HIPCHK(db->d_out.need((size_t)n));
     if (nq > 0) {
-        KF_HIPCHK(hipMemcpyAsync(db->d_qw.p, q_word, (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        KF_HIPCHK(hipMemcpyAsync(db->d_qv.p, q_value, (size_t)nq * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(db->d_qw.p, q_word, (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(db->d_qv.p, q_value, (size_t)nq * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    KF_HIPCHK(hipMemcpyAsync(db->d_list.p, list.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(db->d_list.p, list.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     orbx_launch_kfdb_score_slots(s, db->d_list.p, n, db->d_slots.p, db->d_pool_w, db->d_pool_v, db->d_qw.p, db->d_qv.p, nq,
                                  db->scoring, db->fma_mode ? 1 : 0, db->d_out.p);
-    KF_HIPCHK(hipGetLastError());
-    KF_HIPCHK(hipMemcpyAsync(scores, db->d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    KF_HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(scores, db->d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return ORBX_OK;
 }
 
@@ -594,7 +581,7 @@ static orbx_status check_queries(orbx_kfdb *db, int nq, const int64_t *ids, cons
     }
     if (db->scoring == 3 && use_device(db))
         return orbx_fail(ORBX_UNSUPPORTED, "KL scoring needs libm's log: use a host-only handle or ORBX_KFDB=host");
-    if (!db->host_only) KF_HIPCHK(hipSetDevice(db->dev));
+    if (!db->host_only) HIPCHK(hipSetDevice(db->dev));
     return ORBX_OK;
 }
 

@@ -10,14 +10,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <vector>
-#include "orbx_internal.h"
+#include "orbx_handle.h"
 #include "orbx_gate.h"
-
-extern "C" void orbx_three_maxima(const int32_t *sizes, int L, int *ind1, int *ind2, int *ind3);
-orbx_status orbx_fail(orbx_status s, const std::string &msg);   // orbx_api.cpp: records orbx_last_error()
-int orbx_handle_fp_mode(const orbx_handle *h);
 
 namespace {
 const int HISTO = 30, TH_LOW_ = 50;
@@ -383,7 +378,7 @@ extern "C" orbx_status orbx_search_for_triangulation(orbx_handle *h, const orbx_
     NodeBlocks nbk;
     orbx_status st = nbk.build(h, kf1->desc, kf1->n, kf1->feat_vec, kf2->desc, kf2->n, kf2->feat_vec);
     if (st != ORBX_OK) return st;
-    triangulation_select(orbx_handle_fp_mode(h) == ORBX_FP_GCC_FMA, kf1, kf2, nbk, F12, ex, ey, only_stereo, check_orientation, matches12, nmatches_out);
+    triangulation_select(h->p.fp_mode == ORBX_FP_GCC_FMA, kf1, kf2, nbk, F12, ex, ey, only_stereo, check_orientation, matches12, nmatches_out);
     return ORBX_OK;
 }
 
@@ -408,7 +403,7 @@ extern "C" orbx_status orbx_triangulation_batch_create(orbx_handle *h, const orb
     for (int k = 0; k < nproblems; ++k)
         if (!triangulation_views_ok(kf1, kf2[k])) return orbx_fail(ORBX_BAD_ARGUMENT, "bad keyframe view / malformed feature vector");
     orbx_triangulation_batch *b = new orbx_triangulation_batch();
-    b->fma_mode = orbx_handle_fp_mode(h) == ORBX_FP_GCC_FMA;
+    b->fma_mode = h->p.fp_mode == ORBX_FP_GCC_FMA;
     b->n1 = kf1->n;
     b->n2.resize((size_t)nproblems);
     b->blocks.resize((size_t)nproblems);
@@ -603,7 +598,7 @@ extern "C" orbx_status orbx_fuse(orbx_handle *h, const orbx_target_view *kf, con
     OrbxGateLists gl;
     orbx_status st = point_lists(h, kf, pts, [&](int i) { return th * kf->scale_factors[pts->level[i]]; }, [](int, int &, int &) {}, gl);
     if (st != ORBX_OK) return st;
-    fuse_select(orbx_handle_fp_mode(h) == ORBX_FP_GCC_FMA, kf, pts, gl, 0, best_idx, nfused);
+    fuse_select(h->p.fp_mode == ORBX_FP_GCC_FMA, kf, pts, gl, 0, best_idx, nfused);
     return ORBX_OK;
 }
 
@@ -636,7 +631,7 @@ static orbx_status fuse_batch_common(orbx_handle *h, int K, const orbx_target_vi
     OrbxGateLists gl;
     orbx_status st = batch_lists(h, K, kfs, pts, th, q0, gl);
     if (st != ORBX_OK) return st;
-    const bool fma_mode = orbx_handle_fp_mode(h) == ORBX_FP_GCC_FMA;
+    const bool fma_mode = h->p.fp_mode == ORBX_FP_GCC_FMA;
     for (int k = 0; k < K; ++k) {
         if (pts[k]->n == 0 || kfs[k]->n == 0) continue;
         if (sim3) pick_select(kfs[k], pts[k], gl, q0[(size_t)k], INT32_MAX, TH_LOW_, nullptr, best_idx[k], &nfused[k]);
