@@ -14,7 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liborbx.so")
 # the ONE list of what the library is built from: the build, the rebuild check, kernels_hash() and tools/build_variant.sh use it
-SOURCES = ["orbx_kernels.hip", "orbx_api.cpp", "orbx_geometry.cpp", "orbx_policies.cpp", "orbx_kfdb.cpp", "orbx_track_pack.cpp",
+SOURCES = ["orbx_kernels.hip", "orbx_api.cpp", "orbx_extract.cpp", "orbx_pyramid.cpp", "orbx_match.cpp", "orbx_tracking.cpp",
+           "orbx_map_batches.cpp", "orbx_bow.cpp", "orbx_geometry.cpp", "orbx_policies.cpp", "orbx_kfdb.cpp", "orbx_track_pack.cpp",
            "orbx_mappoint.cpp", "orbx_pose.cpp"]
 HEADERS = ["orbx_device.h", "orbx_inplace.h", "orbx_internal.h", "orbx_launch.h", "orbx_sincos.h", "orbx_track.h", "orbx_mappoint.h",
            "orbx_pose.h", "orbx_handle.h", "orbx_gate.h", os.path.join("..", "..", "include", "orbx.h"),
@@ -23,7 +24,7 @@ HEADERS = ["orbx_device.h", "orbx_inplace.h", "orbx_internal.h", "orbx_launch.h"
 
 def kernels_hash():
     """identity of the device code AND of what decides its launch geometry (kernel source, device headers, the launch plans of
-    orbx_api.cpp): every file of SOURCES and HEADERS, so none can be missed.  profiles/*_traffic.json and *_sq.json carry it,
+    orbx_extract.cpp): every file of SOURCES and HEADERS, so none can be missed.  profiles/*_traffic.json and *_sq.json carry it,
     so counters taken on other kernels or other launch plans read as 'not measured' in bench.py instead of as stale numbers"""
     import hashlib
     h = hashlib.sha256()

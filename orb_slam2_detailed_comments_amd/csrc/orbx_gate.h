@@ -1,4 +1,4 @@
-// orbx_gate.h -- device-side candidate gating shared by orbx_api.cpp and orbx_policies.cpp (internal, not part of the ABI).
+// orbx_gate.h -- device-side candidate gating shared by orbx_match.cpp, orbx_tracking.cpp and orbx_policies.cpp (internal, not part of the ABI).
 //
 // Every projection-guided ORBmatcher policy asks, per query, Frame::GetFeaturesInArea (reference src/Frame.cc:633-717) and then
 // evaluates DescriptorDistance for the returned candidates in that order.  OrbxGateLists is exactly that, for all queries of a

@@ -133,6 +133,7 @@ struct ProfScope {
 
 #pragma GCC visibility push(hidden)   // what follows is shared between the library's own units only: not exported
 void prof_drain(orbx_handle *h);
+orbx_status configure(orbx_handle *h, int width, int height);   // orbx_api.cpp: the handle's geometry and device buffers for one image size
 // ---------------------------------------------------------------- staging (orbx_api.cpp)
 // A grow-only device buffer: *cap < need frees it behind a wait for the handle's stream and allocates `want` elements (contents go).
 orbx_status dev_grow(orbx_handle *h, void **p, size_t *cap, size_t need, size_t want, size_t elem = 1);

@@ -28,7 +28,7 @@ struct OrbxFastGroup {
     int32_t cell0;
     int32_t ncell;
 };
-// Sub-batch pipeline of the batched extraction (orbx_api.cpp run_chunk): the pyramid of sub-batch k+1 runs on the side stream
+// Sub-batch pipeline of the batched extraction (orbx_extract.cpp run_chunk): the pyramid of sub-batch k+1 runs on the side stream
 // next to FAST / quadtree / descriptors of sub-batch k.  k_fast_rows (96 VGPRs, one-wave workgroups) fills every CU with 5 waves
 // per SIMD; with ORBX_FAST_ROOM=1 its LDS request is raised to ORBX_LDS_PER_CU / ORBX_FAST_PIPE_WAVES bytes, so a CU holds
 // ORBX_FAST_PIPE_WAVES of its waves and 128 registers per lane stay free for the pyramid kernels (no LDS) on every SIMD

@@ -2563,7 +2563,7 @@ __global__ __launch_bounds__(256) void k_hamming_matrix(const uint8_t *__restric
 //           index, so min over key = dist << 16 | iR reproduces the strict '<' bookkeeping (:990-1018).
 //  phase B: 11x11 patch vs 11 shifts, centre-subtracted L1 (:1040-1101) in exact integer arithmetic; the
 //           parabola (:1121-1129) uses the same single-rounded float operations as the reference.
-// The final median cut (:1160-1175) is a sort over <= N integers and stays on the host (orbx_api.cpp).
+// The final median cut (:1160-1175) is a sort over <= N integers and stays on the host (orbx_pyramid.cpp).
 // ------------------------------------------------------------------------------------------------
 // 16 lanes per LEFT keypoint, four keypoints per wave: every cross-lane step (candidate minimum, the 11 SAD sums) is a DPP
 // rotate inside a row of 16 lanes and serves four keypoints at once, and a wave's chain of dependent loads (keypoint -> row
@@ -4161,7 +4161,7 @@ __global__ __launch_bounds__(64) void k_pose_opt(const DPoseArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// launch wrappers (called from orbx_api.cpp)
+// launch wrappers (called from the C ABI units)
 // ------------------------------------------------------------------------------------------------
 #include "orbx_launch.h"
 #include <string>

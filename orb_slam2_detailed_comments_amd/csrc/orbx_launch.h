@@ -1,4 +1,4 @@
-// orbx_launch.h -- kernel launch wrappers (defined in orbx_kernels.hip, used by orbx_api.cpp)
+// orbx_launch.h -- kernel launch wrappers (defined in orbx_kernels.hip, used by the C ABI units)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "orbx_device.h"

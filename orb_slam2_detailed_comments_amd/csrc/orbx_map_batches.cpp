@@ -1,0 +1,196 @@
+// orbx_map_batches.cpp -- the batched MapPoint refresh and Optimizer::PoseOptimization behind the C ABI: staging, launches and
+// scatter.  Their HIP-free halves (validation, plans, packing, the host solver) are orbx_mappoint.cpp and orbx_pose.cpp.
+#include <cstdlib>
+#include <cstring>
+#include <algorithm>
+#include <vector>
+#include "orbx_handle.h"
+
+// ---------------------------------------------------------------- MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth,
+// batched (orbx_mappoint.h).  One call: validation and plan (orbx_mappoint.cpp), the caller's arrays packed into the page-locked
+// block, ONE upload, the launches on the handle's stream, ONE download into the same block, the wait, and the scatter into the
+// caller's arrays.
+static orbx_status mp_distinct(orbx_handle *h, bool device_form, const uint8_t *d_pool, int64_t pool_rows, int npoints,
+                               const int32_t *obs_begin, const uint8_t *desc, const int64_t *obs_row, int32_t *best_idx,
+                               int32_t *best_median, uint8_t *best_desc) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxMpPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_mp_distinct_plan(npoints, obs_begin, desc, device_form, d_pool, pool_rows, obs_row, best_idx, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (npoints == 0) return ORBX_OK;
+    if (h->host_only) return orbx_fail(ORBX_NO_DEVICE, "no device handle");
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), plan.dev_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    if (plan.n_small + plan.n_wide > 0) {
+        orbx_mp_distinct_pack(obs_begin, desc, device_form ? obs_row : nullptr, plan, pin);
+        st = stage_upload(h, pin, d, plan.in_bytes);
+        if (st != ORBX_OK) return st;
+        { ProfScope ps(h, ORBX_K_MATCH);
+          orbx_launch_mp_distinct(h->stream, (const int32_t *)(d + plan.o_begin), device_form ? d_pool : d + plan.o_rows,
+                                  device_form ? (const int64_t *)(d + plan.o_rows) : nullptr, (const int32_t *)(d + plan.o_order),
+                                  plan.n_small, plan.n_wide, (int32_t *)(d + plan.o_idx), (int32_t *)(d + plan.o_med),
+                                  d + plan.o_desc); }
+        st = stage_download_wait(h, pin, d + plan.o_idx, plan.out_bytes);
+        if (st != ORBX_OK) return st;
+    }
+    orbx_mp_distinct_unpack(obs_begin, plan, pin, best_idx, best_median, best_desc);   // (reads no entry of a point without rows)
+    return ORBX_OK;
+}
+extern "C" orbx_status orbx_distinctive_descriptors_batch(orbx_handle *h, int npoints, const int32_t *obs_begin, const uint8_t *desc,
+                                                          int32_t *best_idx, int32_t *best_median, uint8_t *best_desc) {
+    return mp_distinct(h, false, nullptr, 0, npoints, obs_begin, desc, nullptr, best_idx, best_median, best_desc);
+}
+extern "C" orbx_status orbx_distinctive_descriptors_batch_device(orbx_handle *h, const uint8_t *d_pool, int64_t pool_rows, int npoints,
+                                                                 const int32_t *obs_begin, const int64_t *obs_row, int32_t *best_idx,
+                                                                 int32_t *best_median, uint8_t *best_desc) {
+    return mp_distinct(h, true, d_pool, pool_rows, npoints, obs_begin, nullptr, obs_row, best_idx, best_median, best_desc);
+}
+extern "C" orbx_status orbx_update_normal_and_depth_batch(orbx_handle *h, int npoints, const int32_t *obs_begin, const float *pos,
+                                                          const float *centers, const float *ref_center, const int32_t *ref_level,
+                                                          float *normal, float *min_distance, float *max_distance) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxMpNormalPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_mp_normal_plan(npoints, obs_begin, pos, centers, ref_center, ref_level, h->p.nlevels, normal, min_distance,
+                                         max_distance, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (npoints == 0) return ORBX_OK;
+    if (h->host_only) return orbx_fail(ORBX_NO_DEVICE, "no device handle");
+    if (plan.nrows == 0) return ORBX_OK;                             // no point has rows: nothing is written
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), plan.dev_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_mp_normal_pack(obs_begin, pos, centers, ref_center, ref_level, h->tab.scale, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_mp_normal_depth(h->stream, (const int32_t *)(d + plan.o_begin), (const DMpPoint *)(d + plan.o_points),
+                                  (const float *)(d + plan.o_centers), npoints, h->tab.scale[h->p.nlevels - 1],
+                                  (float *)(d + plan.o_out)); }
+    st = stage_download_wait(h, pin, d + plan.o_out, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    orbx_mp_normal_unpack(obs_begin, plan, pin, normal, min_distance, max_distance);
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------- Optimizer::PoseOptimization(Frame*), batched (orbx_pose.h).
+// Device path: validation and layout (orbx_pose.cpp), all problems' host state and the pool packed into the page-locked
+// block, ONE upload, k_pose_opt on the handle's stream; nothing downloaded, nothing waited for.  Host path
+// (ORBX_POSE=host, read per call; host-only handles, where the "d_" arguments are host arrays): the same header compiled by
+// the host compiler.  On a device handle it downloads the rows it needs, runs, and uploads the results -- a cross-check, not a
+// fast path.
+static bool pose_host_selected() {
+    const char *e = getenv("ORBX_POSE");
+    return e && strcmp(e, "host") == 0;
+}
+static orbx_status pose_batch(orbx_handle *h, int nproblems, const orbx_pose_problem *problems, int npool, const float *world_pos,
+                              int nframes, const orbx_keypoint *d_keys_un, const float *d_u_right, const int32_t *d_counts, int cap,
+                              const int32_t *d_point, const float *camera4, float mbf, const float *inv_level_sigma2, int nlevels,
+                              float *d_Tcw, uint8_t *d_outlier, int32_t *d_ninliers, const float *dbg_est, const float *dbg_last) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxPoseCall c;
+    c.npool = npool; c.nframes = nframes; c.cap = cap; c.nlevels = nlevels;
+    c.world_pos = world_pos; c.camera4 = camera4; c.inv_level_sigma2 = inv_level_sigma2; c.mbf = mbf;
+    c.keys_un = d_keys_un; c.u_right = d_u_right; c.counts = d_counts; c.point = d_point;
+    c.Tcw = d_Tcw; c.outlier = d_outlier; c.ninliers = d_ninliers; c.dbg_est = dbg_est; c.dbg_last = dbg_last;
+    OrbxPosePlan plan;
+    const char *why = "";
+    orbx_status st = orbx_pose_plan(nproblems, problems, c, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (nproblems == 0) return ORBX_OK;
+    if (h->host_only) {
+        st = orbx_pose_check_rows(nproblems, problems, c, &why);
+        if (st != ORBX_OK) return orbx_fail(st, why);
+        orbx_pose_host_run(nproblems, problems, c);
+        return ORBX_OK;
+    }
+    if (pose_host_selected()) {
+        HIPCHK(hipSetDevice(h->dev));
+        const size_t fr = (size_t)nframes * cap, pr = (size_t)nproblems * cap;
+        std::vector<orbx_keypoint> keys(fr);
+        std::vector<float> ur(d_u_right ? fr : 0), T((size_t)nproblems * 16);
+        std::vector<int32_t> counts((size_t)nframes), point(pr), nin((size_t)nproblems);
+        std::vector<uint8_t> outl(pr);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpy(keys.data(), d_keys_un, fr * sizeof(orbx_keypoint), hipMemcpyDeviceToHost));
+        if (d_u_right) HIPCHK(hipMemcpy(ur.data(), d_u_right, fr * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(counts.data(), d_counts, (size_t)nframes * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(point.data(), d_point, pr * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(outl.data(), d_outlier, pr, hipMemcpyDeviceToHost));
+        if (!dbg_est) HIPCHK(hipMemcpy(T.data(), d_Tcw, T.size() * sizeof(float), hipMemcpyDeviceToHost));
+        // the kernel's rule for what the host cannot validate on device rows: such a feature has no MapPoint (orbx_pose_load)
+        c.keys_un = keys.data(); c.u_right = d_u_right ? ur.data() : nullptr; c.counts = counts.data(); c.point = point.data();
+        c.Tcw = T.data(); c.outlier = outl.data(); c.ninliers = nin.data();
+        orbx_pose_host_run(nproblems, problems, c);
+        HIPCHK(hipMemcpy(d_outlier, outl.data(), pr, hipMemcpyHostToDevice));
+        if (!dbg_est) HIPCHK(hipMemcpy(d_Tcw, T.data(), T.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_ninliers, nin.data(), nin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = stage_begin(h, plan.in_bytes, plan.in_bytes, &pin, &d, true);
+    if (st != ORBX_OK) return st;
+    orbx_pose_pack(problems, c, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    DPoseArgs a;
+    a.prob = (const DPoseProb *)(d + plan.o_prob);
+    a.index = (const int32_t *)(d + plan.o_index);
+    a.world = (const float *)(d + plan.o_world);
+    a.sig = (const float *)(d + plan.o_sig);
+    a.kps = d_keys_un; a.ur = d_u_right; a.counts = d_counts; a.point = d_point;
+    a.cap = cap; a.nlevels = nlevels; a.nproblems = nproblems;
+    a.fx = camera4[0]; a.fy = camera4[1]; a.cx = camera4[2]; a.cy = camera4[3]; a.mbf = mbf;
+    a.Tcw = d_Tcw; a.outlier = d_outlier; a.ninliers = d_ninliers;
+    a.dbg = dbg_est ? (const float *)(d + plan.o_dbg) : nullptr;
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_pose_opt(h->stream, a); }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return orbx_fail(ORBX_HIP_ERROR, hipGetErrorString(e));
+    return ORBX_OK;
+}
+extern "C" orbx_status orbx_pose_optimization_batch_device(orbx_handle *h, int nproblems, const orbx_pose_problem *problems, int npool,
+                                                           const float *world_pos, int nframes, const orbx_keypoint *d_keys_un,
+                                                           const float *d_u_right, const int32_t *d_counts, int cap,
+                                                           const int32_t *d_point, const float *camera4, float mbf,
+                                                           const float *inv_level_sigma2, int nlevels, float *d_Tcw,
+                                                           uint8_t *d_outlier, int32_t *d_ninliers) {
+    return pose_batch(h, nproblems, problems, npool, world_pos, nframes, d_keys_un, d_u_right, d_counts, cap, d_point, camera4, mbf,
+                      inv_level_sigma2, nlevels, d_Tcw, d_outlier, d_ninliers, nullptr, nullptr);
+}
+extern "C" orbx_status orbx_debug_pose_inlier_test(orbx_handle *h, int nproblems, const orbx_pose_problem *problems, int npool,
+                                                   const float *world_pos, int nframes, const orbx_keypoint *d_keys_un,
+                                                   const float *d_u_right, const int32_t *d_counts, int cap, const int32_t *d_point,
+                                                   const float *camera4, float mbf, const float *inv_level_sigma2, int nlevels,
+                                                   const float *Tcw_est, const float *Tcw_last, uint8_t *d_outlier,
+                                                   int32_t *d_ninliers) {
+    if (!Tcw_est || !Tcw_last) return orbx_fail(ORBX_BAD_ARGUMENT, "null pose array");
+    float unused[16];   // the pose rows are not written by the inlier test; the plan only wants a non-null pointer
+    return pose_batch(h, nproblems, problems, npool, world_pos, nframes, d_keys_un, d_u_right, d_counts, cap, d_point, camera4, mbf,
+                      inv_level_sigma2, nlevels, unused, d_outlier, d_ninliers, Tcw_est, Tcw_last);
+}
+extern "C" orbx_status orbx_pose_optimization(orbx_handle *h, float *Tcw, int n, const orbx_keypoint *keys_un, const float *u_right,
+                                              const int32_t *point, int npool, const float *world_pos, const float *camera4,
+                                              float mbf, const float *inv_level_sigma2, int nlevels, uint8_t *outlier,
+                                              int32_t *ninliers) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    if (!Tcw || n <= 0) return orbx_fail(ORBX_BAD_ARGUMENT, !Tcw ? "null Tcw" : "n <= 0");
+    orbx_pose_problem P;
+    P.frame = 0; P.point_index = nullptr; P.npoints = npool;
+    memcpy(P.Tcw, Tcw, sizeof(P.Tcw));
+    const int32_t count = n;
+    OrbxPoseCall c;
+    c.npool = npool; c.nframes = 1; c.cap = n; c.nlevels = nlevels; c.batch_form = false;
+    c.world_pos = world_pos; c.camera4 = camera4; c.inv_level_sigma2 = inv_level_sigma2; c.mbf = mbf;
+    c.keys_un = keys_un; c.u_right = u_right; c.counts = &count; c.point = point;
+    c.Tcw = Tcw; c.outlier = outlier; c.ninliers = ninliers;
+    OrbxPosePlan plan;
+    const char *why = "";
+    orbx_status st = orbx_pose_plan(1, &P, c, plan, &why);
+    if (st == ORBX_OK) st = orbx_pose_check_rows(1, &P, c, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    orbx_pose_host_run(1, &P, c);
+    return ORBX_OK;
+}

@@ -1,6 +1,6 @@
 // orbx_mappoint.cpp -- host side of the batched MapPoint refresh (orbx_mappoint.h): validation of a call, the size-class plan
 // of the descriptor kernels, the packing of the caller's arrays into one staging block and the scatter of the downloaded
-// block.  HIP-free: tests/san_mappoint_pack.cpp builds it alone under the sanitizers.  The entry points (orbx_api.cpp) own
+// block.  HIP-free: tests/san_mappoint_pack.cpp builds it alone under the sanitizers.  The entry points (orbx_map_batches.cpp) own
 // the staging block, the arena and the launches.
 #include <cstring>
 #include "orbx_mappoint.h"

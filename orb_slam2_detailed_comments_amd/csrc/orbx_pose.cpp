@@ -1,7 +1,7 @@
 // orbx_pose.cpp -- host side of the batched Optimizer::PoseOptimization (orbx_pose.h): validation of a call, the packing of all
 // problems' small host state into one staging block, and the library's host path -- the header's scalar code compiled by the
 // host compiler, the problems one after the other and the edges of a problem in feature order.  HIP-free:
-// tests/san_pose_pack.cpp builds it alone under the sanitizers.  The entry points (orbx_api.cpp) own the staging block, the
+// tests/san_pose_pack.cpp builds it alone under the sanitizers.  The entry points (orbx_map_batches.cpp) own the staging block, the
 // arena and the launch.
 #include <cstring>
 #include "orbx_pose.h"

@@ -1,4 +1,4 @@
-"""The FAST-first launch plan of the batched extraction (csrc/orbx_api.cpp run_chunk, ORBX_PLAN=fastfirst): FAST over the level-0
+"""The FAST-first launch plan of the batched extraction (csrc/orbx_extract.cpp run_chunk, ORBX_PLAN=fastfirst): FAST over the level-0
 groups of the whole batch starts at once on the main stream, the resize chains of the sub-batches run beside it on the side
 stream, the FAST groups of levels >= 1 follow per sub-batch, quadtree and descriptors once over the batch.  The plan changes
 launch order, residency and which FAST kernel runs, nothing else: against ORBX_PLAN=serial on a fresh handle every keypoint,

@@ -626,7 +626,7 @@ def test_setup_fills_are_ordered_with_the_first_extraction():
 
 def test_forked_launch_sequence_is_bit_exact(monkeypatch):
     """ORBX_FORK_LEVEL = l: the resizes of levels >= l and their FAST groups run on the handle's side stream next to the FAST
-    kernel of the large levels (csrc/orbx_api.cpp run_chunk).  Large batches only (>= 16384 FAST groups), so 40 frames here."""
+    kernel of the large levels (csrc/orbx_extract.cpp run_chunk).  Large batches only (>= 16384 FAST groups), so 40 frames here."""
     B = 40
     frames = synth.stream(640, 480, B, stream_id=51)
     orc = oracle.OracleExtractor(1000)

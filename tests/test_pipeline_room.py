@@ -1,4 +1,4 @@
-"""Room on the CU for the sub-batch pipeline (csrc/orbx_api.cpp run_chunk), read from the built code object: with
+"""Room on the CU for the sub-batch pipeline (csrc/orbx_extract.cpp run_chunk), read from the built code object: with
 ORBX_FAST_ROOM=1 k_fast_rows is capped at ORBX_FAST_PIPE_WAVES waves per CU by its LDS request while the pipeline runs, and the
 registers those waves leave free on every SIMD must hold pyramid waves of the other stream (without the cap FAST fills every
 SIMD with 5 waves and the pyramid gets slots as FAST waves retire).  An edit that grows a kernel's register allocation or the

@@ -1,4 +1,4 @@
-"""The sub-batch pipeline of the batched extraction (csrc/orbx_api.cpp run_chunk, ORBX_PIPELINE): the pyramids of the sub-batches
+"""The sub-batch pipeline of the batched extraction (csrc/orbx_extract.cpp run_chunk, ORBX_PIPELINE): the pyramids of the sub-batches
 run on the handle's side stream while FAST / quadtree / descriptors of the previous sub-batch run on its main stream.  It changes
 launch order and residency only: every output must be byte-identical to the serial sequence (ORBX_PIPELINE=0) -- keypoints,
 descriptors, counts, status words and the t vs t-1 match of the whole batch, seams between sub-batches included."""
