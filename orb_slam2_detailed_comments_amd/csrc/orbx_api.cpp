@@ -131,7 +131,8 @@ orbx_status configure(orbx_handle *h, int width, int height) {
         tiles += D.blur_tx * ((L.ph + 31) / 32);
     }
     d.blur_tiles = tiles;
-    // quadtree LDS plan: node tables always in LDS, key->node map in LDS when the level's candidates fit
+    // quadtree LDS plan: node tables always in LDS; keys in registers when the level's candidates fit them (qt_reg_keys below),
+    // else key->node map in LDS when they fit the key slots
     h->ncap = g.node_cap;
     // Keys of a level (position + node index, 6 bytes each) live in LDS when they fit `lds_keys` slots; denser levels fall
     // back to the global scratch map (same code path through a generic pointer).  The kernel is latency-bound (a chain of
@@ -162,6 +163,14 @@ orbx_status configure(orbx_handle *h, int width, int height) {
         // one workgroup with every level in LDS -- those levels exceed any LDS budget anyway
         if (keys == 0 && fit_at(2) >= 1024) keys = fit_at(2);
         if (keys == 0) keys = fit_at(1);
+        // Register-resident keys (k_quadtree): a workgroup of T threads keeps up to qt_reg_keys * T keys in registers and needs
+        // no key slots at all.  ORBX_QT_REG_KEYS = 0..ORBX_QT_KPT moves that boundary (tests, A/B runs); 0 is the LDS / global
+        // plan alone.  Where the registers of the smallest workgroup (256 threads) cover what the residency plan sized its
+        // slots for, the plan drops them: the node tables alone admit 8 workgroups of 256 threads per CU at 1000 features
+        // instead of 6, and a workgroup that overflows the registers takes the global key map.
+        h->qt_reg_keys = ORBX_QT_KPT;
+        if (const char *e = getenv("ORBX_QT_REG_KEYS")) h->qt_reg_keys = std::min(std::max(atoi(e), 0), ORBX_QT_KPT);
+        if ((size_t)h->qt_reg_keys * 256 >= want) keys = 0;
         if (const char *e = getenv("ORBX_QT_LDS_KEYS")) keys = std::min<size_t>((size_t)std::max(atoi(e), 0), std::min<size_t>(8192, (160 * 1024 - node_part) / 6));
         h->lds_keys = (int)keys;
         if (getenv("ORBX_QT_LDS_KEYS") || h->lds_keys_few < h->lds_keys) h->lds_keys_few = h->lds_keys;

@@ -6,6 +6,7 @@
 #include "orbx_internal.h"
 #include "orbx_sincos.h"
 
+#define ORBX_QT_KPT 6   // k_quadtree: keys per thread on the register path (reg_keys of orbx_launch_quadtree is at most this)
 struct DLevel {
     int pw, ph, pitch, sw, sh;
     int cell_begin, cell_count;

@@ -123,7 +123,7 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
         { ProfScope ps(h, ORBX_K_QUADTREE);
           orbx_launch_quadtree(s, g, b, h->d_dense + (size_t)f0 * g.cand_total, h->d_cand_count + (size_t)f0 * NL,
                                h->d_lvl_kp + (size_t)f0 * g.kp_total, h->d_lvl_count + (size_t)f0 * NL, d_status + f0,
-                               h->d_knode + (size_t)f0 * g.cand_total, h->ncap, (long long)b * NL >= 1024 ? h->lds_keys : h->lds_keys_few, 0, NL); }
+                               h->d_knode + (size_t)f0 * g.cand_total, h->ncap, (long long)b * NL >= 1024 ? h->lds_keys : h->lds_keys_few, h->qt_reg_keys, 0, NL); }
         // orientation (IC_Angle) is computed inside k_describe from the same LDS patch the descriptor uses
         { ProfScope ps(h, ORBX_K_DESC);
           const OrbxRaw0 raw = {d_imgs + (int64_t)f0 * frame_stride, (long long)frame_stride, W, H, stride};

@@ -62,7 +62,7 @@ struct orbx_handle {
     uint32_t *d_lvl_kp = nullptr;
     float *d_lvl_angle = nullptr;
     uint16_t *d_knode = nullptr;
-    int max_cw = 0, max_ch = 0, ncap = 0, lds_keys = 0, lds_keys_few = 0;
+    int max_cw = 0, max_ch = 0, ncap = 0, lds_keys = 0, lds_keys_few = 0, qt_reg_keys = 0;
     // staging for the host entry points
     uint8_t *st_in[2] = {nullptr, nullptr}; size_t d_in_bytes = 0;
     orbx_keypoint *st_kps[2] = {nullptr, nullptr}; uint8_t *st_desc[2] = {nullptr, nullptr}; int *st_cnt[2] = {nullptr, nullptr};

@@ -25,6 +25,27 @@
 #ifndef RR_FF
 #define RR_FF 1
 #endif
+// k_quadtree: keys a thread may keep in registers (the register path covers QT_KPT * workgroup size keys), and the
+// barrier-stage reductions of section 5 of DESIGN.md as build switches for A/B variants (tools/build_variant.sh)
+#define QT_KPT ORBX_QT_KPT
+#ifndef QT_DROP_STAGE_A
+#define QT_DROP_STAGE_A 1   // F bit set where a node is created; counters zeroed in stage E's interval: no stage A
+#endif
+#ifndef QT_ONE_SCAN
+#define QT_ONE_SCAN 1       // main pass: children, expandable children and survivors ranked by one two-word scan
+#endif
+#ifndef QT_REG_SIZE
+#define QT_REG_SIZE 1       // list size held by every thread, not passed through LDS
+#endif
+#ifndef QT_CENSUS_NODES
+#define QT_CENSUS_NODES 1   // register path: a list of at most this many nodes (and the root bins) is counted per wave with ballots;
+                            // 0 = atomics per key.  Measured at 1 (107 us), 4 (116) and 0 (136 us per 1024 frames of 640x480)
+#endif
+#ifndef QT_BGRP
+#define QT_BGRP 3           // stage B on the register path: keys whose node reads are in flight together (divides QT_KPT)
+#endif
+static_assert(QT_KPT % QT_BGRP == 0, "QT_BGRP must divide QT_KPT");
+#define QT_SHARED_BYTES 144
 #ifndef QT_FF
 #define QT_FF 1
 #endif
@@ -1263,6 +1284,21 @@ __global__ __launch_bounds__(64, FR_WPS) void k_fast_rows_l0(DGeom g, const Orbx
 //     sorted order finds the cut, and only the nodes before the cut are materialised;
 //   * the address tie-break of std::sort over pair<int,ExtractorNode*> is defined as creation order (F3).
 // Selection (:1387-1413) = max response, first in emission order, via one 64-bit LDS atomicMax per key.
+//
+// Where a key lives (workgroup-uniform, K = the level's candidates, T = workgroup size):
+//   K <= reg_keys * T   registers: thread tid owns keys tid + j * T, j < QT_KPT (position word, node index, stage B's quadrant);
+//   K <= lds_keys       LDS key slots kpos_lds / knode_lds;
+//   otherwise           positions re-read from the dense array, key -> node map in global scratch (knode_glob).
+// kpos / knode of a key are only ever touched by the thread that owns it, on every path.
+//
+// Stages of one pass (one barrier after each; DESIGN.md section 5 has the measurements behind the list):
+//   B  census: every key of a node that splits (F) counts itself into its quadrant (LDS atomics; per wave with ballots while
+//      the list is one node, register path: QT_CENSUS_NODES);
+//   C  ranks: main pass -- one two-word scan over the list (qt_scan_main); careful pass -- sort, speculative split, cut;
+//   D  the next list is built (children in push_front order, survivors behind them); F of a child = more than one key;
+//   E  keys follow their node; the next list's quadrant counters are zeroed in the same interval.
+// There is no stage that decides which nodes split: F is written where a node is created.  The list size is ctot + nmtot,
+// which every thread holds.
 // ------------------------------------------------------------------------------------------------
 // Workgroup size is a template parameter, picked per launch (orbx_launch_quadtree): the kernel is a chain of barrier-separated
 // stages, so many small workgroups win when the launch has several workgroups per CU to choose from (256 threads: 67 us per
@@ -1270,10 +1306,11 @@ __global__ __launch_bounds__(64, FR_WPS) void k_fast_rows_l0(DGeom g, const Orbx
 // each (1920x1080 / 4000 features, 32 frames = one workgroup per CU: 185 / 112 / 82 us with 256 / 512 / 1024 threads).
 
 struct QtShared {
-    int size, prev_size, n_expand, ctot, nmtot, jstar, m, finish;
-    uint32_t wsum[16];   // one per wave, up to 1024 threads
-    uint32_t carry;
+    int size, jstar, m, pad;
+    uint32_t wsum[16];    // one per wave, up to 1024 threads
+    uint32_t wsum2[16];   // second word of qt_scan_main
 };
+static_assert(sizeof(QtShared) <= QT_SHARED_BYTES, "QtShared outgrew its LDS slot");
 
 // exclusive prefix sum of in[0..n) -> out[0..n) (both LDS, may alias), returns total; all threads must call.
 // Two barriers per 512-element chunk: wave scan -> wave totals in LDS -> every thread adds the totals before it.
@@ -1301,6 +1338,44 @@ __device__ uint32_t qt_block_scan(const uint32_t *in, uint32_t *out, int n, QtSh
     return carry;
 }
 
+// Main-pass creation ranks in ONE scan over the list, inputs computed on the fly from the census:
+//   word a = children (low 16) | expandable children (high 16) of an expandable node, word b = 1 for a survivor.
+// t1[p] / t2[p] get the exclusive sums, the totals come back in tot_a / tot_b.  Entry p is written by the thread that
+// reads it again in stage D (p = tid + i * QT_THREADS in both), so no barrier follows the last chunk: one barrier per chunk
+// plus one between chunks (wsum reuse).  The next writer of wsum is a scan of the next pass, at least two barriers later.
+template <int QT_THREADS>
+__device__ __forceinline__ void qt_scan_main(const uint32_t *meta, const uint32_t *cc, uint32_t *t1, uint32_t *t2, int n,
+                                             QtShared *sh, uint32_t &tot_a, uint32_t &tot_b) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    uint32_t carry_a = 0, carry_b = 0;
+    for (int base = 0; base < n; base += QT_THREADS) {
+        const int i = base + tid;
+        uint32_t a = 0, b = 0;
+        if (i < n) {
+            if ((meta[i] >> 16) & 1) {
+                const uint4 c = *(const uint4 *)(cc + 4 * i);
+                const uint32_t ne = (c.x > 0) + (c.y > 0) + (c.z > 0) + (c.w > 0);
+                const uint32_t nx = (c.x > 1) + (c.y > 1) + (c.z > 1) + (c.w > 1);
+                a = ne | (nx << 16);
+            } else b = 1;
+        }
+        const uint32_t ia = (uint32_t)orbx_wave_scan((int)a), ib = (uint32_t)orbx_wave_scan((int)b);
+        if (lane == 63) { sh->wsum[w] = ia; sh->wsum2[w] = ib; }
+        __syncthreads();
+        uint32_t offa = carry_a, offb = carry_b, ta = 0, tb = 0;
+#pragma unroll
+        for (int j = 0; j < QT_THREADS / 64; ++j) {
+            const uint32_t xa = sh->wsum[j], xb = sh->wsum2[j];
+            offa += j < w ? xa : 0u;  ta += xa;
+            offb += j < w ? xb : 0u;  tb += xb;
+        }
+        if (i < n) { t1[i] = offa + ia - a; t2[i] = offb + ib - b; }
+        carry_a += ta; carry_b += tb;
+        if (base + QT_THREADS < n) __syncthreads();
+    }
+    tot_a = carry_a; tot_b = carry_b;
+}
+
 __device__ __forceinline__ int qt_quadrant(uint32_t pos, uint32_t b0, uint32_t b1) {
     const int x = pos & 0xfff, y = (pos >> 12) & 0xfff;
     const int x0 = b0 & 0xffff, y0 = b0 >> 16, x1 = b1 & 0xffff, y1 = b1 >> 16;
@@ -1317,12 +1392,14 @@ __device__ __forceinline__ void qt_child_box(uint32_t b0, uint32_t b1, int q, ui
     c1 = (uint32_t)cx1 | ((uint32_t)cy1 << 16);
 }
 
-template <int QT_THREADS>
-__global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *__restrict__ dense_all,
-                                                        const int *__restrict__ cand_count,
-                                                        uint32_t *__restrict__ lvl_kp, int *__restrict__ lvl_count,
-                                                        int *__restrict__ status, uint16_t *__restrict__ knode_glob,
-                                                        int ncap, int lds_keys, int level_begin) {
+// One workgroup's whole problem.  KEYS_IN_REG is the register path (K <= reg_keys * QT_THREADS, decided by the kernel): it is
+// a template parameter and not a run-time flag so that each copy of the pass loop keeps only its own addresses and keys live.
+template <int QT_THREADS, bool KEYS_IN_REG>
+__device__ __forceinline__ void qt_workgroup(const DGeom &g, const uint2 *__restrict__ dense_all,
+                                             const int *__restrict__ cand_count,
+                                             uint32_t *__restrict__ lvl_kp, int *__restrict__ lvl_count,
+                                             int *__restrict__ status, uint16_t *__restrict__ knode_glob,
+                                             int ncap, int lds_keys, int level_begin) {
     extern __shared__ __attribute__((aligned(16))) uint8_t qt_smem[];
     // grid: frame fastest, level 0 (the most keys) dispatched first.  With the level fastest, workgroup id % 8 = level for
     // the usual 8 levels: one XCD would get every level-0 workgroup and another every level-7 one.
@@ -1336,7 +1413,7 @@ __global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *_
     const uint2 *cand = dense_all + (long long)f * g.cand_total + L.cand_begin;
     // ---- LDS carve-up (all arrays have ncap entries unless noted)
     uint8_t *sp = qt_smem;
-    QtShared *sh = (QtShared *)sp;                 sp += 128;
+    QtShared *sh = (QtShared *)sp;                 sp += QT_SHARED_BYTES;
     uint32_t *boxA0 = (uint32_t *)sp;              sp += 4 * (size_t)ncap;
     uint32_t *boxA1 = (uint32_t *)sp;              sp += 4 * (size_t)ncap;
     uint32_t *cntA = (uint32_t *)sp;               sp += 4 * (size_t)ncap;
@@ -1361,7 +1438,18 @@ __global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *_
 
     // ---- keys: k_fast_rows appended this level's survivors to the dense array (count in cand_count); nothing to gather
     const int K = min(cand_count[f * g.nlevels + level], L.cand_cap);
-    const bool keys_in_lds = K <= lds_keys;   // wave-uniform: key positions and key->node map live in LDS
+    // workgroup-uniform: thread tid owns keys tid + j * QT_THREADS, j < QT_KPT, and keeps each one's position word and
+    // node index (low 16; the quadrant of stage B above them) in registers.  Every loop over j is fully unrolled, so the
+    // arrays are registers, not scratch; a slot without a key (k >= K) holds node 0 and is never used.
+    constexpr bool keys_in_reg = KEYS_IN_REG;
+    uint32_t rpos[QT_KPT], rnode[QT_KPT];
+#pragma unroll
+    for (int j = 0; j < QT_KPT; ++j) {
+        const int k = tid + j * QT_THREADS;
+        rpos[j] = keys_in_reg && k < K ? cand[k].x : 0u;
+        rnode[j] = 0;
+    }
+    const bool keys_in_lds = !keys_in_reg && K <= lds_keys;   // workgroup-uniform: key positions and key->node map live in LDS
     if (keys_in_lds)
         for (int k = tid; k < K; k += QT_THREADS) kpos_lds[k] = cand[k].x;
     uint16_t *knode = keys_in_lds ? knode_lds : knode_glob + ((long long)f * g.cand_total + L.cand_begin);
@@ -1372,6 +1460,23 @@ __global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *_
     const float hx = L.hx;
     for (int i = tid; i < nini; i += QT_THREADS) cc[i] = 0;
     __syncthreads();
+    if (keys_in_reg) {
+        const bool census = QT_CENSUS_NODES > 0 && nini <= 4;   // every key of the wave hits one of nini counters: count per wave
+#pragma unroll
+        for (int j = 0; j < QT_KPT; ++j)
+            if (tid + j * QT_THREADS < K) {
+                const int b = min((int)((float)(rpos[j] & 0xfff) / hx), nini - 1);
+                rnode[j] = (uint32_t)b;
+                if (!census) atomicAdd(&cc[b], 1u);
+            }
+        if (census)
+            for (int b = 0; b < nini; ++b) {
+                uint32_t n = 0;
+#pragma unroll
+                for (int j = 0; j < QT_KPT; ++j) n += __popcll(orbx_ballot(tid + j * QT_THREADS < K && rnode[j] == (uint32_t)b));
+                if ((tid & 63) == 0 && n) atomicAdd(&cc[b], n);
+            }
+    } else
     for (int k = tid; k < K; k += QT_THREADS) {
         const int x = QT_KPOS(k) & 0xfff;
         int b = (int)((float)x / hx);
@@ -1387,21 +1492,31 @@ __global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *_
                 box0[n] = (uint32_t)(int)(hx * (float)i);                       // UL.x | UL.y(=0) << 16
                 box1[n] = (uint32_t)(int)(hx * (float)(i + 1)) | ((uint32_t)L.qt_h << 16);
                 cnt[n] = cc[i];
-                meta[n] = 0;
+                meta[n] = QT_DROP_STAGE_A ? (uint32_t)(cc[i] > 1) << 16 : 0u;   // F: splits in the first pass
                 t0[i] = n++;
             } else t0[i] = 0xffff;
         }
         sh->size = n;
-        sh->finish = 0;
     }
     __syncthreads();
+    if (keys_in_reg) {
+#pragma unroll
+        for (int j = 0; j < QT_KPT; ++j) rnode[j] = tid + j * QT_THREADS < K ? t0[rnode[j]] : 0u;
+    } else
     for (int k = tid; k < K; k += QT_THREADS) knode[k] = (uint16_t)t0[knode[k]];
+    int size = sh->size;
+#if QT_DROP_STAGE_A
+    // the root counts in cc are dead (thread 0 read them before the barrier above): zero the first pass's quadrant counters
+    for (int p = tid; p < size; p += QT_THREADS) *(uint4 *)(cc + 4 * p) = make_uint4(0, 0, 0, 0);
+#endif
     __syncthreads();
 
     bool careful = false;
-    while (true) {
-        const int size = sh->size;
-        if (size == 0) break;
+    while (size > 0) {
+#if !QT_REG_SIZE
+        size = sh->size;
+#endif
+#if !QT_DROP_STAGE_A
         // ---- A: which nodes split in this pass; zero their quadrant counters
         //      main pass: every node with more than one key; careful pass: nodes created by the last pass (F)
         for (int p = tid; p < size; p += QT_THREADS) {
@@ -1410,7 +1525,36 @@ __global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *_
             cc[4 * p] = cc[4 * p + 1] = cc[4 * p + 2] = cc[4 * p + 3] = 0;
         }
         __syncthreads();
-        // ---- B: quadrant census
+#endif
+        // ---- B: quadrant census of the nodes that split in this pass (F).  F is what the pass that created the node wrote:
+        //      a root or a child with more than one key; a survivor has at most one (main phase) or was not created by the
+        //      last pass (careful phase), F = 0.  The counters were zeroed in the barrier interval of the previous stage E.
+        if (keys_in_reg) {
+            const bool census = QT_CENSUS_NODES > 0 && size <= QT_CENSUS_NODES;   // few nodes: hundreds of keys on 4 * size counters, counted per wave below
+            // the node reads of QT_BGRP keys are issued before any is used (all QT_KPT at once cost registers that the
+            // 8 waves per SIMD of the 256-thread workgroup do not have)
+#pragma unroll
+            for (int j0 = 0; j0 < QT_KPT; j0 += QT_BGRP) {
+                uint32_t m[QT_BGRP], b0[QT_BGRP], b1[QT_BGRP];
+#pragma unroll
+                for (int i = 0; i < QT_BGRP; ++i) { const int p = rnode[j0 + i]; m[i] = meta[p]; b0[i] = box0[p]; b1[i] = box1[p]; }
+#pragma unroll
+                for (int i = 0; i < QT_BGRP; ++i)
+                    if (tid + (j0 + i) * QT_THREADS < K && ((m[i] >> 16) & 1)) {
+                        const int p = rnode[j0 + i], q = qt_quadrant(rpos[j0 + i], b0[i], b1[i]);
+                        if (!census) atomicAdd(&cc[4 * p + q], 1u);
+                        rnode[j0 + i] = (uint32_t)p | ((uint32_t)q << 16) | 0x80000000u;   // stage E reuses the quadrant; bit 31: counted
+                    }
+            }
+            if (census)
+                for (int c = 0; c < 4 * size; ++c) {
+                    const uint32_t code = 0x80000000u | (uint32_t)(c >> 2) | ((uint32_t)(c & 3) << 16);
+                    uint32_t n = 0;
+#pragma unroll
+                    for (int j = 0; j < QT_KPT; ++j) n += __popcll(orbx_ballot(rnode[j] == code));
+                    if ((tid & 63) == 0 && n) atomicAdd(&cc[c], n);
+                }
+        } else
         for (int k = tid; k < K; k += QT_THREADS) {
             const int p = knode[k];
             if ((meta[p] >> 16) & 1) atomicAdd(&cc[4 * p + qt_quadrant(QT_KPOS(k), box0[p], box1[p])], 1u);
@@ -1419,6 +1563,13 @@ __global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *_
         // ---- C: creation ranks
         int ctot, nmtot, nexp_total = 0;
         if (!careful) {
+#if QT_ONE_SCAN
+            uint32_t tot, nm;
+            qt_scan_main<QT_THREADS>(meta, cc, t1, t2, size, sh, tot, nm);
+            ctot = tot & 0xffff;
+            nexp_total = tot >> 16;
+            nmtot = (int)nm;
+#else
             // pack: children (low 16) | expandable children (high 16)
             for (int p = tid; p < size; p += QT_THREADS) {
                 uint32_t ne = 0, nx = 0;
@@ -1436,6 +1587,7 @@ __global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *_
             }
             __syncthreads();
             nmtot = (int)qt_block_scan<QT_THREADS>(t0, t2, size, sh);
+#endif
         } else {
             // careful phase: order candidates by descending (count, creation rank).  The candidate keys are first
             // compacted into a dense, 16-byte aligned LDS array (scratch = newpos, rewritten in phase D anyway); each
@@ -1514,26 +1666,56 @@ __global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *_
         }
         __syncthreads();
         // ---- E: keys follow their node
+        const int new_size = ctot + nmtot;
+        if (keys_in_reg) {
+            // the quadrant is stage B's (0 for a node that did not count); a careful pass split only the nodes before the cut,
+            // and stage C rewrote F to say which
+#pragma unroll
+            for (int j = 0; j < QT_KPT; ++j) {
+                const int p = rnode[j] & 0xffff;
+                int q = (rnode[j] >> 16) & 3;
+                if (careful && !((meta[p] >> 16) & 1)) q = 0;
+                rnode[j] = tid + j * QT_THREADS < K ? (uint32_t)newpos[4 * p + q] : 0u;
+            }
+        } else
         for (int k = tid; k < K; k += QT_THREADS) {
             const int p = knode[k];
             const int q = ((meta[p] >> 16) & 1) ? qt_quadrant(QT_KPOS(k), box0[p], box1[p]) : 0;
             knode[k] = (uint16_t)newpos[4 * p + q];
         }
+#if QT_DROP_STAGE_A
+        // stage E does not read the quadrant counters: zero them for the next pass here instead of in a stage of their own
+        for (int p = tid; p < new_size; p += QT_THREADS) *(uint4 *)(cc + 4 * p) = make_uint4(0, 0, 0, 0);
+#endif
         __syncthreads();
         { uint32_t *t;
           t = box0; box0 = nbox0; nbox0 = t;  t = box1; box1 = nbox1; nbox1 = t;
           t = cnt; cnt = ncnt; ncnt = t;      t = meta; meta = nmeta; nmeta = t; }
-        const int new_size = ctot + nmtot;
+#if !QT_REG_SIZE
         if (tid == 0) sh->size = new_size;
         __syncthreads();
+#endif
         // ---- termination (:1260-1283, :1363-1372)
-        if (new_size >= N || new_size == size) break;
+        const bool done = new_size >= N || new_size == size;
         if (!careful && new_size + 3 * nexp_total > N) careful = true;
+        size = new_size;   // every thread holds ctot + nmtot: the list size needs no LDS round trip
+        if (done) break;
     }
     // ---- selection: best response, first in emission order
-    const int size = sh->size;
     for (int p = tid; p < size; p += QT_THREADS) best[p] = 0ull;
     __syncthreads();
+    if (keys_in_reg) {
+        uint32_t cy[QT_KPT];
+#pragma unroll
+        for (int j = 0; j < QT_KPT; ++j) { const int k = tid + j * QT_THREADS; cy[j] = k < K ? cand[k].y : 0u; }
+#pragma unroll
+        for (int j = 0; j < QT_KPT; ++j)
+            if (tid + j * QT_THREADS < K) {
+                const uint32_t cx = rpos[j];
+                const unsigned long long key = ((unsigned long long)(((cx >> 24) << 24) | (0xffffffu - (cy[j] & 0xffffffu))) << 32) | cx;
+                atomicMax(&best[rnode[j]], key);
+            }
+    } else
     for (int k = tid; k < K; k += QT_THREADS) {
         const uint2 c = cand[k];
         const unsigned long long key = ((unsigned long long)(((c.x >> 24) << 24) | (0xffffffu - (c.y & 0xffffffu))) << 32) | c.x;
@@ -1545,6 +1727,24 @@ __global__ __launch_bounds__(QT_THREADS) void k_quadtree(DGeom g, const uint2 *_
     uint32_t *out = lvl_kp + (long long)f * g.kp_total + L.kp_begin;
     for (int p = tid; p < nout; p += QT_THREADS) out[p] = (uint32_t)best[p];
     if (tid == 0) lvl_count[f * g.nlevels + level] = nout;
+}
+
+template <int QT_THREADS>
+__global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : QT_THREADS == 512 ? 6 : 4) void k_quadtree(DGeom g, const uint2 *__restrict__ dense_all,
+                                                        const int *__restrict__ cand_count,
+                                                        uint32_t *__restrict__ lvl_kp, int *__restrict__ lvl_count,
+                                                        int *__restrict__ status, uint16_t *__restrict__ knode_glob,
+                                                        int ncap, int lds_keys, int reg_keys, int level_begin) {
+#if QT_FF
+    const int level = level_begin + blockIdx.y, f = blockIdx.x;
+#else
+    const int level = level_begin + blockIdx.x, f = blockIdx.y;
+#endif
+    const int K = min(cand_count[f * g.nlevels + level], g.lv[level].cand_cap);
+    if (K <= reg_keys * QT_THREADS)   // workgroup-uniform
+        qt_workgroup<QT_THREADS, true>(g, dense_all, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, level_begin);
+    else
+        qt_workgroup<QT_THREADS, false>(g, dense_all, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, level_begin);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4211,7 +4411,7 @@ hipError_t orbx_upload_pattern() {
 }
 
 size_t orbx_quadtree_smem(int ncap, int lds_keys) {
-    return 128 + (size_t)ncap * (8 * 4 + 16 + 8 + 6 * 4) + 16 + (size_t)lds_keys * 6 + 16;
+    return QT_SHARED_BYTES + (size_t)ncap * (8 * 4 + 16 + 8 + 6 * 4) + 16 + (size_t)lds_keys * 6 + 16;
 }
 
 void orbx_launch_clear(hipStream_t s, int *a, int na, int *b, int nb, int *c, int nc) {
@@ -4340,8 +4540,9 @@ void orbx_launch_bow_transform(hipStream_t s, int B, int max_n, const int *child
 }
 static int g_qt_cus = 0;   // CUs of the current device (orbx_quadtree_prepare)
 void orbx_launch_quadtree(hipStream_t s, const DGeom &g, int B, const uint2 *dense, const int *cand_count, uint32_t *lvl_kp, int *lvl_count,
-                          int *status, uint16_t *knode_glob, int ncap, int lds_keys, int level_begin, int level_count) {
+                          int *status, uint16_t *knode_glob, int ncap, int lds_keys, int reg_keys, int level_begin, int level_count) {
     if (level_count <= 0) return;
+    reg_keys = reg_keys < 0 ? 0 : reg_keys > QT_KPT ? QT_KPT : reg_keys;
     const size_t smem = orbx_quadtree_smem(ncap, lds_keys);
     // workgroups per CU of this launch decide the workgroup size (see k_quadtree)
     static int forced = -1;
@@ -4353,11 +4554,11 @@ void orbx_launch_quadtree(hipStream_t s, const DGeom &g, int B, const uint2 *den
     if (forced == 256 || forced == 512 || forced == 1024) threads = forced;
     const dim3 grid = QT_FF ? dim3(B, level_count) : dim3(level_count, B);
     if (threads == 256)
-        hipLaunchKernelGGL(k_quadtree<256>, grid, dim3(256), smem, s, g, dense, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, level_begin);
+        hipLaunchKernelGGL(k_quadtree<256>, grid, dim3(256), smem, s, g, dense, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, reg_keys, level_begin);
     else if (threads == 512)
-        hipLaunchKernelGGL(k_quadtree<512>, grid, dim3(512), smem, s, g, dense, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, level_begin);
+        hipLaunchKernelGGL(k_quadtree<512>, grid, dim3(512), smem, s, g, dense, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, reg_keys, level_begin);
     else
-        hipLaunchKernelGGL(k_quadtree<1024>, grid, dim3(1024), smem, s, g, dense, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, level_begin);
+        hipLaunchKernelGGL(k_quadtree<1024>, grid, dim3(1024), smem, s, g, dense, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, reg_keys, level_begin);
 }
 hipError_t orbx_quadtree_prepare(size_t smem) {
     // The attribute belongs to (function, device), not to a handle: ORB-SLAM2 itself keeps mpIniORBextractor (2 x nFeatures)

@@ -43,7 +43,7 @@ void orbx_launch_bow_transform(hipStream_t s, int B, int max_n, const int *child
                                const uint8_t *node_desc, int n_nodes, int L, const uint8_t *desc, const int *counts,
                                long long frame_stride, int levelsup, uint32_t *out_leaf, uint32_t *out_nid, int out_stride);
 void orbx_launch_quadtree(hipStream_t s, const DGeom &g, int B, const uint2 *dense, const int *cand_count, uint32_t *lvl_kp, int *lvl_count,
-                          int *status, uint16_t *knode_glob, int ncap, int lds_keys, int level_begin, int level_count);
+                          int *status, uint16_t *knode_glob, int ncap, int lds_keys, int reg_keys, int level_begin, int level_count);
 void orbx_launch_blur(hipStream_t s, const DGeom &g, int B, const uint8_t *pyr, uint8_t *blur);
 void orbx_launch_describe(hipStream_t s, const DGeom &g, int B, const uint8_t *pyr, const uint32_t *lvl_kp,
                           const int *lvl_count, float *lvl_angle, orbx_keypoint *kps, uint8_t *desc,
