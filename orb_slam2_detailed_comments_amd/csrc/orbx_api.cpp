@@ -181,6 +181,12 @@ orbx_status configure(orbx_handle *h, int width, int height) {
     // with a non-blocking stream -- the round-1 race -- and a device-wide barrier would stall every other handle).
     // Source vectors live in h->geom (they outlive the copies).
     if (const char *e = getenv("ORBX_RESIZE_IMPL")) h->resize_legacy = strcmp(e, "legacy") == 0;
+    h->rr_rpw = 0;
+    if (const char *e = getenv("ORBX_RR_RPW")) {   // tests reach every trip shape of the row walk at tiny batches with it; sweeps
+        const int v = atoi(e);
+        if (v >= 2 && v <= 64 && (v & (v - 1)) == 0) h->rr_rpw = v;
+        else return orbx_fail(ORBX_BAD_ARGUMENT, "ORBX_RR_RPW must be a power of two in 2..64");
+    }
 #ifdef ORBX_TIMING_KNOBS   // phase-timing builds only (tools/build_variant.sh): stops k_fast_rows early, results are wrong
     if (const char *e = getenv("ORBX_FAST_STOP")) h->fast_stop = atoi(e);
 #endif

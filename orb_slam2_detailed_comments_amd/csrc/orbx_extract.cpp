@@ -86,10 +86,10 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
             { ProfScope ps(h, ORBX_K_PYR_RESIZE, st);
               const OrbxRaw0 raw = {im, (long long)frame_stride, W, H, stride};
               orbx_launch_pyr_resize_l1(st, g, b, h->d_taps + h->geom.l1_tap_begin, raw, pyr, h->geom.l1_tail_bx,
-                                        chain_only ? nullptr : stp, chain_only ? nullptr : cc); }
+                                        chain_only ? nullptr : stp, chain_only ? nullptr : cc, h->rr_rpw); }
             for (int l = 2; l < l_end; ++l) {
                 ProfScope ps(h, ORBX_K_PYR_RESIZE, st);
-                orbx_launch_pyr_resize(st, g, b, l, h->d_taps, pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy);
+                orbx_launch_pyr_resize(st, g, b, l, h->d_taps, pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy, h->rr_rpw);
             }
             return;
         }
@@ -106,7 +106,7 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
           } }
         for (int l = 1; l < l_end; ++l) {
             ProfScope ps(h, ORBX_K_PYR_RESIZE, st);
-            orbx_launch_pyr_resize(st, g, b, l, h->d_taps, pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy);
+            orbx_launch_pyr_resize(st, g, b, l, h->d_taps, pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy, h->rr_rpw);
         }
     };
     // part: 0 = any groups (mixed kernel when in place), 1 = level-0 groups only, 2 = groups of levels >= 1 only (the two launches
@@ -220,7 +220,7 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
             return orbx_fail(ORBX_HIP_ERROR, "fork event");
         for (int l = h->fork_level; l < NL; ++l) {
             ProfScope ps(h, ORBX_K_PYR_RESIZE, s2);
-            orbx_launch_pyr_resize(s2, g, B, l, h->d_taps, h->d_pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy);
+            orbx_launch_pyr_resize(s2, g, B, l, h->d_taps, h->d_pyr, h->geom.lv[l].narrow_taps && !h->resize_legacy, h->rr_rpw);
         }
         fast(s2, 0, B, h->fork_group, ngroups - h->fork_group, 0);
         // (The quadtree of the small levels was tried on the side stream behind its FAST groups: it needs CU residency the

@@ -191,6 +191,9 @@ orbx_status orbx_build_geometry(const orbx_params &p, const OrbxTables &t, int w
             build_axis_taps(g.taps, L.pw, L.sw, S.vw, true, S.org);
             L.tapy_begin = (int)g.taps.size();
             build_axis_taps(g.taps, L.ph, L.sh, S.vh, false, S.org);
+            // one record beyond the last row: the row walk fetches the vertical records two at a time (rows Y, Y + 1 with Y
+            // even), so a level of odd height reads index ph.  A repeat of the last row's record: its source rows exist
+            g.taps.push_back(g.taps.back());
             L.narrow_taps = true;
             for (int X = 0; X < L.pw; X += 4) {
                 int lo = 0x7fff, hi = 0;
@@ -216,8 +219,9 @@ orbx_status orbx_build_geometry(const orbx_params &p, const OrbxTables &t, int w
             t.s1 = (int16_t)reflect101(t.s1 - ORBX_EDGE, n);
             g.taps.push_back(t);
         }
+        g.taps.push_back(g.taps.back());   // the record beyond the last row, as above
         // narrow footprint over BOTH taps (the second is not "the next byte" inside the reflected border), per lane of every
-        // column strip -- the lanes beyond the level's width repeat its last column, as the kernel does
+        // column strip -- the lanes beyond the level's width are counted as repeating its last column (the kernel retires them)
         const int nbx = (L.pw + 255) / 256;
         bool ok = L.narrow_taps;
         g.l1_tail_bx = nbx;

@@ -53,7 +53,8 @@ struct orbx_handle {
     OrbxCell *d_cells = nullptr;
     OrbxFastGroup *d_groups = nullptr;
     bool resize_legacy = false;   // ORBX_RESIZE_IMPL=legacy: k_pyr_resize for every level (A/B runs)
-    int match_kernel = 0;         // ORBX_MATCH_KERNEL, read ONCE when the handle is created: 0 = matrix pipe with FP4 operands (default), 1 = "valu" (vector pipe), 2 = "i8" (matrix pipe, int8 operands) -- A/B runs, parity tests
+    int rr_rpw = 0;               // ORBX_RR_RPW: destination rows per wave of the row-walking resize kernels (2..64, a power of two); 0 = the launcher's choice
+    int match_kernel = 0;        // ORBX_MATCH_KERNEL, read ONCE when the handle is created: 0 = matrix pipe with FP4 operands (default), 1 = "valu" (vector pipe), 2 = "i8" (matrix pipe, int8 operands) -- A/B runs, parity tests
     int fast_stop = 0;      // ORBX_FAST_STOP: only read in -DORBX_TIMING_KNOBS builds
     int fast_lcap = 640;    // LDS work-list entries of k_fast_rows (ORBX_FAST_LCAP; tests shrink it to force the flush paths)
     OrbxTap *d_taps = nullptr;

@@ -318,6 +318,129 @@ __global__ __launch_bounds__(256) void k_pyr_resize(DGeom g, int level, const Or
 #define RR_WPB 1   // waves (column strips x row ranges) per block; nothing is shared between them, and one-wave blocks
                    // are placed as soon as any SIMD has room (201 us against 209 with 4)
 #endif
+// ---- The row walk itself, shared by k_pyr_resize_rows and k_pyr_resize_rows_l1 (which differ in how a source row is loaded
+// and in how the byte selectors are built).
+// the vertical tap records of two consecutive destination rows, at any dword address: (.x, .y) = row Y, (.z, .w) = row Y + 1,
+// each s0 | s1 << 16, a0 | a1 << 16
+typedef uint32_t orbx_tap2 __attribute__((ext_vector_type(4), aligned(4)));
+// The tap table is written by the host before any launch and never by a kernel: a pointer into it in the constant address
+// space makes every fetch of a pair a scalar load (as a global pointer the fetches behind the loop's first store became
+// vector loads + v_readfirstlane, and a wait for every load in flight)
+typedef const __attribute__((address_space(4))) orbx_tap2 *rr_tap2_ptr;
+__device__ __forceinline__ rr_tap2_ptr rr_tap_pairs(const OrbxTap *p) { return (rr_tap2_ptr)(uintptr_t)p; }
+struct RrLoad12 {   // slab rows, and body strips of the caller's image: the dword-aligned 12-byte window from column `col`
+    const uint8_t *src;
+    uint32_t pitch, col;
+    __device__ __forceinline__ orbx_uint3_a operator()(uint32_t row) const {
+        return *(const orbx_uint3_a *)(src + orbx_ip_row_off((int)row, (int)pitch, (int)col));
+    }
+};
+struct RrLoad8 {    // tail strips of the caller's image: 8 bytes at byte alignment from column `col`
+    const uint8_t *src;
+    uint32_t pitch, col;
+    __device__ __forceinline__ orbx_uint3_a operator()(uint32_t row) const {
+        const uint2 q = orbx_load8(src + orbx_ip_row_off((int)row, (int)pitch, (int)col));
+        orbx_uint3_a v;
+        v.x = q.x; v.y = q.y; v.z = 0;
+        return v;
+    }
+};
+__device__ __forceinline__ uint32_t orbx_mulhi24(uint32_t a, uint32_t b) {   // (a * b) >> 32 of two 24-bit values: v_mul_hi_u32_u24, full rate
+    return (uint32_t)(((uint64_t)(a & 0xffffffu) * (uint64_t)(b & 0xffffffu)) >> 32);
+}
+__device__ __forceinline__ uint32_t rr_pin(uint32_t v) {   // a wave-uniform loop constant: held in its scalar register, not re-read
+    asm volatile("" : "+s"(v));                            // from the kernel arguments inside the loop
+    return v;
+}
+// The lane's four horizontal tap records, addressed as the table's scalar base + a 32-bit offset
+__device__ __forceinline__ void rr_taps_x(const OrbxTap *__restrict__ tq, int X, int pw, uint2 (&t)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t[i] = *(const uint2 *)((const uint8_t *)tq + (uint32_t)min(X + i, pw - 1) * 8u);   // .x = s0 | s1 << 16, .y = a0 | a1 << 16
+}
+// Destination rows [Y, Y + n) of a column strip, n >= 1; tp = the vertical tap record of row Y (the table carries one record
+// beyond its level's last row, so the second record of the pair a range ends on may be read whatever n is); vdst = byte offset
+// of the lane's dword in row Y, dpitch = bytes between destination rows.
+//
+// Two destination rows per step.  The horizontal pass of a SOURCE row (h[i] = (a0 * p[s0] + a1 * p[s0+1]) >> 4 for the
+// lane's four columns; held as h << 4) is what cv::resize keeps in its row buffers: destination row Y+1 usually starts on the source row
+// destination row Y ended on (scale 1.2: 2.4 new source rows per two destination rows instead of 4), so the last row's
+// h values stay in registers (source row `pid`; hb[0] / hb[1] alternate as "row s0" / "row s1", nothing is copied) and only
+// rows not seen yet are loaded and filtered -- 40 % fewer loads, 22 % fewer vector instructions per pixel.  All conditions
+// are wave-uniform (scalar branches).
+// The rows of step k+1 are requested before step k is evaluated.  The two register sets this needs (A, B: tap records + up to
+// four source rows each) swap roles by code position -- a trip of the loop is two steps, A then B -- not by moving values.
+template <class LD>
+__device__ __forceinline__ void rr_walk(const LD ld, const uint32_t (&sel)[4], const uint32_t (&wgt)[4], const uint32_t sh,
+                                        rr_tap2_ptr tp, uint8_t *__restrict__ dst, uint32_t vdst,
+                                        const uint32_t dpitch, int n) {
+    // the four pixels are taken through each stage together: no v_dot2 result is shifted by the instruction behind it
+#define RR_H(h, v)                                                                                                       \
+    {                                                                                                                   \
+        const uint32_t lo_ = __builtin_amdgcn_alignbyte((v).y, (v).x, sh), hi_ = __builtin_amdgcn_alignbyte((v).z, (v).y, sh); \
+        uint32_t p_[4];                                                                                                 \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) p_[i] = __builtin_amdgcn_perm(hi_, lo_, sel[i]);                  \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) p_[i] = orbx_udot2(p_[i], wgt[i]);                                \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) h[i] = p_[i] & 0xfffff0u;   /* ((a0 p0 + a1 p1) >> 4) << 4 */     \
+    }
+    // Vertical pass, the integers of cv::resize: ((b0 * T0 >> 16) + (b1 * T1 >> 16) + 2) >> 2 with T = the horizontal value >> 4.
+    // The h values are kept as T << 4 (one v_and instead of one shift) and the 12-bit weights as b << 12, so that the high half of
+    // the 24 x 24-bit product (v_mul_hi_u32_u24) IS b * T >> 16: two multiplies and one add per pixel.  The four
+    // sums (<= 1020) are packed in pairs, get their + 2 together and are shifted by 6: byte 1 / byte 3 of a pair are its two pixels,
+    // one v_perm gathers them.
+#define RR_V(out, h0, h1, ty_)                                                                                          \
+    {                                                                                                                   \
+        const uint32_t w0_ = ((ty_) << 12) & 0xfff000u, w1_ = ((ty_) >> 4) & 0xfff000u;                                 \
+        uint32_t s_[4];                                                                                                 \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) s_[i] = orbx_mulhi24(w0_, h0[i]) + orbx_mulhi24(w1_, h1[i]);      \
+        out = __builtin_amdgcn_perm((((s_[3] << 16) + s_[2]) + 0x00020002u) << 6, (((s_[1] << 16) + s_[0]) + 0x00020002u) << 6, \
+                                    0x07050301u);                                                                      \
+    }
+    // a set's rows, skipping the rows the step before it leaves filtered in registers (`last`: that step's final source row)
+#define RR_FETCH(S, last)                                                                                               \
+    {                                                                                                                   \
+        S##t = *tp++;                                                                                                   \
+        if ((S##t.x & 0xffffu) != (uint32_t)(last)) S##u0 = ld(S##t.x & 0xffffu);                                     \
+        S##w0 = ld(S##t.x >> 16);                                                                                      \
+        if ((S##t.z & 0xffffu) != (S##t.x >> 16)) S##u1 = ld(S##t.z & 0xffffu);                                      \
+        S##w1 = ld(S##t.z >> 16);                                                                                      \
+    }
+    // the set's two destination rows (the second one stored only if the range has it: rows > 1)
+#define RR_EVAL(S, rows)                                                                                                \
+    {                                                                                                                   \
+        uint32_t v_;                                                                                                    \
+        if ((S##t.x & 0xffffu) != pid) RR_H(hb[0], S##u0)                                                              \
+        RR_H(hb[1], S##w0)                                                                                              \
+        RR_V(v_, hb[0], hb[1], S##t.y)                                                                                 \
+        *(uint32_t *)(dst + vdst) = v_;                                                                                 \
+        vdst += dpitch;                                                                                                 \
+        if ((S##t.z & 0xffffu) != (S##t.x >> 16)) RR_H(hb[1], S##u1)                                                  \
+        RR_H(hb[0], S##w1)                                                                                              \
+        RR_V(v_, hb[1], hb[0], S##t.w)                                                                                 \
+        if ((rows) > 1) *(uint32_t *)(dst + vdst) = v_;                                                                 \
+        vdst += dpitch;                                                                                                 \
+        pid = S##t.z >> 16;                                                                                            \
+    }
+    orbx_tap2 At, Bt;
+    orbx_uint3_a Au0, Aw0, Au1, Aw1, Bu0, Bw0, Bu1, Bw1;
+    Au0.x = Au0.y = Au0.z = 0;   // a row that is not loaded is not read either; the zeros only give the registers a defined value
+    Au1 = Bu0 = Bu1 = Au0;
+    uint32_t pid = 0xffffffffu;                     // source row whose horizontal pass hb[0] holds at the top of a step
+    uint32_t hb[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    RR_FETCH(A, 0xffffffffu)
+    for (;;) {
+        if (n > 2) RR_FETCH(B, At.z >> 16)
+        RR_EVAL(A, n)
+        if (n <= 2) break;
+        if (n > 4) RR_FETCH(A, Bt.z >> 16)
+        RR_EVAL(B, n - 2)
+        if (n <= 4) break;
+        n -= 4;
+    }
+#undef RR_H
+#undef RR_V
+#undef RR_FETCH
+#undef RR_EVAL
+}
 __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows(DGeom g, int level, const OrbxTap *__restrict__ taps,
                                                          uint8_t *__restrict__ pyr, int rpw) {
     const DLevel &L = g.lv[level];
@@ -335,98 +458,34 @@ __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows(DGeom g, int le
     const int y_begin = __builtin_amdgcn_readfirstlane((by * RR_WPB + threadIdx.y) * rpw);
     if (y_begin >= L.ph) return;
     const int y_end = min(y_begin + rpw, L.ph);
-    const bool on = X < L.pw;
+    if (X >= L.pw) return;   // lanes beyond the level's width (the last strip) are done: no load, no store, no mask around the stores
     uint8_t *base = pyr + (long long)f * g.pyr_bytes;
     const uint8_t *src = base + S.off;
     // Addresses = the level's wave-uniform base (the scalar operand of the loads and stores, saddr form) + a 32-bit offset
     // (scalar row * pitch + the lane's column: one v_add per access; a level is far below 4 GB) -- round 2's form paid a 64-bit
     // vector multiply-add per row load (v_mad_i64_i32) and per store (v_mad_u64_u32)
     uint8_t *dst = base + L.off;
-    const uint32_t ldst = (uint32_t)X;
+    const uint32_t spitch = rr_pin((uint32_t)S.pitch), dpitch = rr_pin((uint32_t)L.pitch);
     uint32_t sel[4], wgt[4];
     int smin = 0x7fff;
     {
-        const uint2 *tq = (const uint2 *)taps + L.tapx;
         uint2 t[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) t[i] = tq[min(X + i, L.pw - 1)];   // .x = s0 | s1 << 16, .y = a0 | a1 << 16
+        rr_taps_x(taps + L.tapx, X, L.pw, t);
 #pragma unroll
         for (int i = 0; i < 4; ++i) smin = min(smin, (int)(t[i].x & 0xffffu));
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint32_t d = (t[i].x & 0xffffu) - (uint32_t)smin;          // 0..6 (checked on the host)
-            sel[i] = d | (0x0cu << 8) | ((d + 1u) << 16) | (0x0cu << 24);
+            sel[i] = d | (0x0cu << 8) | ((d + 1u) << 16) | (0x0cu << 24);    // the second tap is the next byte; 0x0c selects the constant 0x00
             wgt[i] = t[i].y;
         }
     }
     // A lane's 8 source bytes start at byte smin of the row: read as the dword-ALIGNED 12-byte window around them and
     // funnel-shifted in registers (two v_alignbyte).  The per-lane unaligned 8-byte load this replaces (a 4.8-byte lane
     // stride, 1-byte alignment) was what bounded the kernel: the address unit serves such a wave-load lane by lane.
-    const uint32_t sh = (uint32_t)(smin & 3);
-    const uint32_t lsrc = (uint32_t)(smin & ~3);
-    const uint2 *ty = (const uint2 *)taps + L.tapy;
-    // Two destination rows per step.  The horizontal pass of a SOURCE row (h[i] = (a0 * p[s0] + a1 * p[s0+1]) >> 4 for the
-    // lane's four columns) is what cv::resize keeps in its row buffers: destination row Y+1 usually starts on the source row
-    // destination row Y ended on (scale 1.2: 2.4 new source rows per two destination rows instead of 4), so the last row's
-    // h values stay in registers (hp, source row `pid`) and only rows not seen yet are loaded and filtered -- 40 % fewer
-    // loads, 22 % fewer vector instructions per pixel.  All conditions are wave-uniform (scalar branches).
-#ifndef RR_R
-#define RR_R 2
-#endif
-#define RR_H(dst, v)                                                                                                     \
-    {                                                                                                                   \
-        const uint32_t lo_ = __builtin_amdgcn_alignbyte((v).y, (v).x, sh), hi_ = __builtin_amdgcn_alignbyte((v).z, (v).y, sh); \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
-            dst[i] = orbx_udot2(__builtin_amdgcn_perm(hi_, lo_, sel[i]), wgt[i]) >> 4;                                  \
-    }
-#define RR_V(out, h0, h1, w0, w1)                                                                                       \
-    {                                                                                                                   \
-        out = 0;                                                                                                        \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
-            out |= (((__umul24(w0, h0[i]) >> 16) + (__umul24(w1, h1[i]) >> 16) + 2u) >> 2) << (8 * i);                  \
-    }
-    // RR_R destination rows per step (even): hb[0] / hb[1] alternate as "row s0" / "row s1" so that no value is ever copied
-    uint2 t[RR_R];
-    orbx_uint3_a u[RR_R], w[RR_R];
-    int pid = -1;                                   // source row whose horizontal pass hb[0] holds at the top of a step
-    uint32_t hb[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-    for (int r = 0; r < RR_R; ++r) {
-        t[r] = ty[min(y_begin + r, L.ph - 1)];
-        u[r].x = u[r].y = u[r].z = 0;
-        if (r == 0 || (int)(t[r].x & 0xffffu) != (int)(t[r - 1].x >> 16)) u[r] = *(const orbx_uint3_a *)(src + (uint32_t)((t[r].x & 0xffffu) * (uint32_t)S.pitch + lsrc));
-        w[r] = *(const orbx_uint3_a *)(src + (uint32_t)((t[r].x >> 16) * (uint32_t)S.pitch + lsrc));
-    }
-    for (int Y = y_begin; Y < y_end; Y += RR_R) {
-        uint2 ct[RR_R];
-        orbx_uint3_a cu[RR_R], cw[RR_R];
-#pragma unroll
-        for (int r = 0; r < RR_R; ++r) { ct[r] = t[r]; cu[r] = u[r]; cw[r] = w[r]; }
-        if (Y + RR_R < y_end) {   // next step's rows, in flight while this step is evaluated; rows this step leaves in registers are skipped
-            int last = (int)(ct[RR_R - 1].x >> 16);
-#pragma unroll
-            for (int r = 0; r < RR_R; ++r) {
-                t[r] = ty[min(Y + RR_R + r, L.ph - 1)];
-                const int s0 = (int)(t[r].x & 0xffffu), s1 = (int)(t[r].x >> 16);
-                if (s0 != last) u[r] = *(const orbx_uint3_a *)(src + (uint32_t)((uint32_t)s0 * (uint32_t)S.pitch + lsrc));
-                w[r] = *(const orbx_uint3_a *)(src + (uint32_t)((uint32_t)s1 * (uint32_t)S.pitch + lsrc));
-                last = s1;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RR_R; ++r) {
-            uint32_t (&h0)[4] = hb[r & 1], (&h1)[4] = hb[(r & 1) ^ 1];
-            const int s0 = (int)(ct[r].x & 0xffffu);
-            if (s0 != pid) RR_H(h0, cu[r])
-            RR_H(h1, cw[r])
-            uint32_t v;
-            RR_V(v, h0, h1, ct[r].y & 0xfffu, (ct[r].y >> 16) & 0xfffu)
-            pid = (int)(ct[r].x >> 16);
-            if (on && Y + r < y_end) *(uint32_t *)(dst + (uint32_t)((uint32_t)(Y + r) * (uint32_t)L.pitch + ldst)) = v;
-        }
-    }
-#undef RR_H
-#undef RR_V
+    const RrLoad12 ld = {src, spitch, (uint32_t)(smin & ~3)};
+    rr_walk(ld, sel, wgt, (uint32_t)(smin & 3), rr_tap_pairs(taps + L.tapy + y_begin), dst,
+            (uint32_t)y_begin * dpitch + (uint32_t)X, dpitch, y_end - y_begin);
 }
 
 // Level 1 straight from the caller's grey image (in-place mode: no padded level-0 copy exists).  Same row walk, with
@@ -439,15 +498,12 @@ __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows(DGeom g, int le
 template <bool TAIL>
 __device__ __forceinline__ void rr_l1_body(const DLevel &L, const OrbxTap *__restrict__ taps, const uint8_t *__restrict__ src,
                                            int W, int stride, uint8_t *__restrict__ dst, int X, int y_begin, int y_end) {
-    const bool on = X < L.pw;
-    const uint32_t ldst = (uint32_t)X;
+    const uint32_t spitch = rr_pin((uint32_t)stride), dpitch = rr_pin((uint32_t)L.pitch);
     uint32_t sel[4], wgt[4];
     int lo = 0x7fff;
     {
-        const uint2 *tq = (const uint2 *)taps;
         uint2 t[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) t[i] = tq[min(X + i, L.pw - 1)];   // .x = s0 | s1 << 16, .y = a0 | a1 << 16
+        rr_taps_x(taps, X, L.pw, t);
 #pragma unroll
         for (int i = 0; i < 4; ++i) lo = min(lo, (int)min(t[i].x & 0xffffu, t[i].x >> 16));
         const int org = TAIL ? orbx_ip_rr_tail_col(lo, W) : lo;       // raw column of byte 0 of the lane's 8-byte register pair
@@ -458,69 +514,15 @@ __device__ __forceinline__ void rr_l1_body(const DLevel &L, const OrbxTap *__res
             wgt[i] = t[i].y;
         }
     }
-    const uint32_t sh = TAIL ? 0u : (uint32_t)(lo & 3);
-    const uint32_t lsrc = (uint32_t)(TAIL ? orbx_ip_rr_tail_col(lo, W) : orbx_ip_rr_body_col(lo));
-    const uint2 *ty = (const uint2 *)taps + L.pw;
-#define RR_LD(dstv, row)                                                                                                  \
-    {                                                                                                                     \
-        const uint8_t *p_ = src + orbx_ip_row_off((int)(row), stride, (int)lsrc);                                         \
-        if (TAIL) { const uint2 q_ = orbx_load8(p_); dstv.x = q_.x; dstv.y = q_.y; dstv.z = 0; }                          \
-        else dstv = *(const orbx_uint3_a *)p_;                                                                            \
+    const rr_tap2_ptr tp = rr_tap_pairs(taps + L.pw + y_begin);
+    const uint32_t vdst = (uint32_t)y_begin * dpitch + (uint32_t)X;
+    if (TAIL) {
+        const RrLoad8 ld = {src, spitch, (uint32_t)orbx_ip_rr_tail_col(lo, W)};
+        rr_walk(ld, sel, wgt, 0u, tp, dst, vdst, dpitch, y_end - y_begin);
+    } else {
+        const RrLoad12 ld = {src, spitch, (uint32_t)orbx_ip_rr_body_col(lo)};
+        rr_walk(ld, sel, wgt, (uint32_t)(lo & 3), tp, dst, vdst, dpitch, y_end - y_begin);
     }
-#define RR_H(dst, v)                                                                                                     \
-    {                                                                                                                   \
-        const uint32_t lo_ = __builtin_amdgcn_alignbyte((v).y, (v).x, sh), hi_ = __builtin_amdgcn_alignbyte((v).z, (v).y, sh); \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
-            dst[i] = orbx_udot2(__builtin_amdgcn_perm(hi_, lo_, sel[i]), wgt[i]) >> 4;                                  \
-    }
-#define RR_V(out, h0, h1, w0, w1)                                                                                       \
-    {                                                                                                                   \
-        out = 0;                                                                                                        \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                   \
-            out |= (((__umul24(w0, h0[i]) >> 16) + (__umul24(w1, h1[i]) >> 16) + 2u) >> 2) << (8 * i);                  \
-    }
-    uint2 t[RR_R];
-    orbx_uint3_a u[RR_R], w[RR_R];
-    int pid = -1;
-    uint32_t hb[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-    for (int r = 0; r < RR_R; ++r) {
-        t[r] = ty[min(y_begin + r, L.ph - 1)];
-        u[r].x = u[r].y = u[r].z = 0;
-        if (r == 0 || (int)(t[r].x & 0xffffu) != (int)(t[r - 1].x >> 16)) RR_LD(u[r], t[r].x & 0xffffu)
-        RR_LD(w[r], t[r].x >> 16)
-    }
-    for (int Y = y_begin; Y < y_end; Y += RR_R) {
-        uint2 ct[RR_R];
-        orbx_uint3_a cu[RR_R], cw[RR_R];
-#pragma unroll
-        for (int r = 0; r < RR_R; ++r) { ct[r] = t[r]; cu[r] = u[r]; cw[r] = w[r]; }
-        if (Y + RR_R < y_end) {
-            int last = (int)(ct[RR_R - 1].x >> 16);
-#pragma unroll
-            for (int r = 0; r < RR_R; ++r) {
-                t[r] = ty[min(Y + RR_R + r, L.ph - 1)];
-                const int s0 = (int)(t[r].x & 0xffffu), s1 = (int)(t[r].x >> 16);
-                if (s0 != last) RR_LD(u[r], s0)
-                RR_LD(w[r], s1)
-                last = s1;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RR_R; ++r) {
-            uint32_t (&h0)[4] = hb[r & 1], (&h1)[4] = hb[(r & 1) ^ 1];
-            const int s0 = (int)(ct[r].x & 0xffffu);
-            if (s0 != pid) RR_H(h0, cu[r])
-            RR_H(h1, cw[r])
-            uint32_t v;
-            RR_V(v, h0, h1, ct[r].y & 0xfffu, (ct[r].y >> 16) & 0xfffu)
-            pid = (int)(ct[r].x >> 16);
-            if (on && Y + r < y_end) *(uint32_t *)(dst + (uint32_t)((uint32_t)(Y + r) * (uint32_t)L.pitch + ldst)) = v;
-        }
-    }
-#undef RR_LD
-#undef RR_H
-#undef RR_V
 }
 __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows_l1(DGeom g, const OrbxTap *__restrict__ taps, OrbxRaw0 raw,
                                                             uint8_t *__restrict__ pyr, int rpw, int tail_bx,
@@ -543,6 +545,7 @@ __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows_l1(DGeom g, con
     const int y_begin = __builtin_amdgcn_readfirstlane((by * RR_WPB + threadIdx.y) * rpw);
     if (y_begin >= L.ph) return;
     const int y_end = min(y_begin + rpw, L.ph);
+    if (X >= L.pw) return;   // as k_pyr_resize_rows
     const uint8_t *src = raw.img + (long long)f * raw.frame_stride;
     uint8_t *dst = pyr + (long long)f * g.pyr_bytes + L.off;
     if (bx >= tail_bx) rr_l1_body<true>(L, taps, src, raw.W, raw.stride, dst, X, y_begin, y_end);
@@ -4444,13 +4447,20 @@ void orbx_launch_pyr_l0_remap(hipStream_t s, const DGeom &g, int B, const uint8_
     dim3 grid((L.pw + 255) / 256, (L.ph + 3) / 4, B);
     hipLaunchKernelGGL(k_pyr_l0_remap, grid, dim3(64, 4), 0, s, g, imgs, W, H, stride, frame_stride, pyr, rect, status, cand_cursor);
 }
-void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, const OrbxTap *taps, uint8_t *pyr, bool narrow) {
+// destination rows per wave of the row-walking kernels: 16 when the launch still has >= 4096 waves, fewer for small batches (the
+// rows of a wave are a serial chain of load -> evaluate -> store steps); forced (ORBX_RR_RPW: a power of two, 2..64) overrides it.
+// Always even: the walk fetches the vertical tap records of rows Y, Y + 1 together.
+static int rr_rows_per_wave(const DLevel &L, int B, int forced) {
+    if (forced > 0) return forced;
+    int rpw = 16;   // (8 / 16 / 32 / 64 rows per wave at 1024 frames: 750 / 708 / 729 / 742 us for the seven launches)
+    while (rpw > 2 && (long long)((L.pw + 255) / 256) * ((L.ph + rpw - 1) / rpw) * B < 4096) rpw >>= 1;
+    return rpw;
+}
+void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, const OrbxTap *taps, uint8_t *pyr, bool narrow,
+                            int rpw_forced) {
     const DLevel &L = g.lv[level];
     if (narrow) {
-        // destination rows per wave: 16 when the launch still has >= 4096 waves, fewer for small batches (the rows of a
-        // wave are a serial chain of load -> evaluate -> store steps)
-        int rpw = 16;   // (8 / 16 / 32 / 64 rows per wave at 1024 frames: 750 / 708 / 729 / 742 us for the seven launches)
-        while (rpw > 2 && (long long)((L.pw + 255) / 256) * ((L.ph + rpw - 1) / rpw) * B < 4096) rpw >>= 1;
+        const int rpw = rr_rows_per_wave(L, B, rpw_forced);
 #if RR_FF
         dim3 grid(B, (L.pw + 255) / 256, (L.ph + RR_WPB * rpw - 1) / (RR_WPB * rpw));
 #else
@@ -4463,10 +4473,9 @@ void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, con
     hipLaunchKernelGGL(k_pyr_resize, grid, dim3(64, 4), 0, s, g, level, taps, pyr);
 }
 void orbx_launch_pyr_resize_l1(hipStream_t s, const DGeom &g, int B, const OrbxTap *taps_l1, const OrbxRaw0 &raw, uint8_t *pyr,
-                               int tail_bx, int *status, int *cand_cursor) {
+                               int tail_bx, int *status, int *cand_cursor, int rpw_forced) {
     const DLevel &L = g.lv[1];
-    int rpw = 16;   // as orbx_launch_pyr_resize
-    while (rpw > 2 && (long long)((L.pw + 255) / 256) * ((L.ph + rpw - 1) / rpw) * B < 4096) rpw >>= 1;
+    const int rpw = rr_rows_per_wave(L, B, rpw_forced);
 #if RR_FF
     dim3 grid(B, (L.pw + 255) / 256, (L.ph + RR_WPB * rpw - 1) / (RR_WPB * rpw));
 #else

@@ -17,7 +17,9 @@ void orbx_launch_pyr_l0_color(hipStream_t s, const DGeom &g, int B, const uint8_
                               long long frame_stride, uint8_t *pyr, int nch, int r_off, int b_off, int *status, int *cand_cursor);
 void orbx_launch_pyr_l0_remap(hipStream_t s, const DGeom &g, int B, const uint8_t *imgs, int W, int H, int stride,
                               long long frame_stride, uint8_t *pyr, const uint2 *rect, int *status, int *cand_cursor);
-void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, const OrbxTap *taps, uint8_t *pyr, bool narrow);
+void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, const OrbxTap *taps, uint8_t *pyr, bool narrow,
+                            int rpw_forced = 0);
+// (rpw_forced > 0: destination rows per wave of the row-walking kernel, a power of two in 2..64 -- ORBX_RR_RPW; 0: the launcher's choice)
 void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell *cells, const OrbxFastGroup *groups,
                            int ngroups, const uint8_t *pyr, uint2 *cand, int *cand_cursor, int *status, int max_ch, int lcap,
                            int dbg_stop, int lds_floor = 0, const OrbxRaw0 *raw = nullptr, bool l0_only = false);
@@ -26,7 +28,7 @@ void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell 
 // in-place mode (orbx_inplace.h): level 1 from the caller's grey image `raw`; also resets status[f] and cand_cursor[f][*] as
 // k_pyr_l0 does, unless `status` is null (the FAST-first plan resets them before its first FAST launch).  taps_l1 = the level's raw-coordinate tap table (pw horizontal records, then ph vertical ones).
 void orbx_launch_pyr_resize_l1(hipStream_t s, const DGeom &g, int B, const OrbxTap *taps_l1, const OrbxRaw0 &raw, uint8_t *pyr,
-                               int tail_bx, int *status, int *cand_cursor);
+                               int tail_bx, int *status, int *cand_cursor, int rpw_forced = 0);
 void orbx_launch_undistort(hipStream_t s, int B, int max_n, int cap, const double *K4, const double *k14, int identity,
                            const orbx_keypoint *kps, const int *counts, orbx_keypoint *out);
 // depth input of k_rgbd (Frame::ComputeStereoFromRGBD): `depth` = frame 0, frames `frame_stride` bytes apart, rows `stride`
