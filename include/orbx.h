@@ -788,6 +788,61 @@ orbx_status orbx_debug_pose_inlier_test(orbx_handle *h, int nproblems, const orb
  * tests/pose_model.py, which takes this one primitive from the library. */
 void orbx_pose_sin_cos(double theta, double *s, double *c);
 
+/* ---- Sim3Solver (src/Sim3Solver.cc), the RANSAC between SearchByBoW and OptimizeSim3 in LoopClosing::ComputeSim3
+ * (src/LoopClosing.cc:487-577), for all candidates of the loop in one device round trip.  iterate() returns at iteration i iff
+ * count_i >= max(count_j, j < i) and count_i > mRansacMinInliers (:267-286), so every iteration of every candidate is evaluated
+ * ahead of time -- k_sim3_hypotheses: one lane per (problem, iteration) runs ComputeSim3 on the three drawn correspondences;
+ * k_sim3_inliers: one wave per (problem, iteration) runs CheckInliers over the problem's correspondences staged in LDS, the
+ * mask as 64-bit ballot words, the count as the sum of their popcounts -- and orbx_sim3_batch_iterate replays the reference's
+ * iterate(n, ...) calls on the host from the stored counts, in any interleaving, including a solver that is iterated again
+ * after its first answer was rejected.
+ * CONTRACT: hypotheses, masks and counts of the device equal the library's host path (ORBX_SIM3=host in the environment, read
+ * per call; host-only handles) and the numpy restatement tests/sim3_model.py bit for bit, in both fp_modes.  Parity with an
+ * OpenCV build is NOT pinned from N to R: DESIGN.md section 2 (F12) lists what follows the reference's source and what this
+ * library fixes where the reference leaves it to OpenCV (cv::eigen, cv::norm, the MatExpr scaling, cv::Rodrigues, the order of
+ * the 3x3 float products, cv::Mat::dot) or to libm (atan2, sin, cos).
+ * The caller supplies the draws: sets[i] = the three indices DUtils::Random::RandomInt gave iteration i, so a solver's answer
+ * is the reference's for the same draws.  Repeated indices within a set are accepted (a degenerate hypothesis).
+ * A problem with n < min_inliers launches nothing, its sets are not read (may be NULL) and its first iterate reports no_more.
+ * Validated before any device work, ORBX_BAD_ARGUMENT: nproblems < 0, a null array whose size is positive, n < 0,
+ * iterations < 1, a set index outside [0, n).  nproblems == 0 launches nothing and gives an empty batch.
+ * OUTSIDE the contract (den == 0, a degenerate triple, z == 0 after a transform, non-finite input): the same straight-line
+ * code runs, a non-finite err compares as "not less" and the point is an outlier. */
+typedef struct orbx_sim3_problem {
+    int32_t n;                        /* N of the solver: correspondences that passed the constructor's filters */
+    const float *x1c, *x2c;           /* [n][3] mvX3Dc1, mvX3Dc2 */
+    const float *max_err1, *max_err2; /* [n]   mvnMaxError1/2 */
+    float camera1[4], camera2[4];     /* fx, fy, cx, cy of mK1, mK2 */
+    int32_t fix_scale, min_inliers, iterations;   /* iterations = mRansacMaxIts AFTER SetRansacParameters */
+    const int32_t *sets;              /* [iterations][3] indices into 0..n-1, the draws in order */
+} orbx_sim3_problem;
+typedef struct orbx_sim3_batch orbx_sim3_batch;
+/* SetRansacParameters (:153-191) on the host: mRansacMaxIts for N = n (float epsilon, the host's log / pow, the
+ * min_inliers == n branch, max(1, min(., .))) */
+int32_t orbx_sim3_ransac_iterations(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations);
+/* One page-locked block up, both kernels, one block down; the batch owns host copies of the results and needs neither the
+ * handle nor the caller's arrays afterwards.  On a host-only handle the library's host path runs. */
+orbx_status orbx_sim3_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_sim3_problem *problems, orbx_sim3_batch **out);
+/* Sim3Solver::iterate(n_iterations, bNoMore, vbInliers, nInliers) of solver k as a cursor over the stored results.  Returns 1
+ * when a Sim3 is returned (T12 [16] row major = mBestT12, inliers [n] = mvbInliersi as 0 / 1, *ninliers), 0 when not (inliers
+ * all 0, *ninliers = 0, T12 untouched), -1 for a bad argument (orbx_last_error()).  mnIterations, mnBestInliers and the best
+ * hypothesis are kept per solver and updated on >= even when nothing is returned; *no_more follows :290. */
+int32_t orbx_sim3_batch_iterate(orbx_sim3_batch *b, int k, int n_iterations, int32_t *no_more, uint8_t *inliers, int32_t *ninliers,
+                                float *T12);
+/* GetEstimatedRotation / Translation / Scale of solver k: R [9] row major, t [3], *s.  ORBX_BAD_ARGUMENT before the first
+ * iteration of the solver has run (the reference returns empty matrices there). */
+orbx_status orbx_sim3_batch_best(const orbx_sim3_batch *b, int k, float *R, float *t, float *s);
+/* tests and tools: the inlier count of every iteration of solver k, counts [iterations] (nothing is written for a solver that
+ * launched nothing); *niterations, optional, receives how many were written */
+orbx_status orbx_sim3_batch_counts(const orbx_sim3_batch *b, int k, int32_t *counts, int32_t *niterations);
+/* tests and tools: hypothesis `iteration` of solver k as 48 floats (T12 [16] | T21 [16] | R [9] | t [3] | s | 3 x 0) and its
+ * mask words (uint64 [ceil(n / 64)], bit i of word w = correspondence 64 w + i); either pointer may be NULL */
+orbx_status orbx_sim3_batch_hypothesis(const orbx_sim3_batch *b, int k, int iteration, float *hyp48, uint64_t *mask_words);
+void orbx_sim3_batch_destroy(orbx_sim3_batch *b);
+/* atan2(y, x) for y >= 0 as ComputeSim3 gets it in both paths (csrc/orbx_sim3.h: *, + and IEEE division only).  Exported for
+ * tests/sim3_model.py, which takes this primitive and orbx_pose_sin_cos from the library. */
+double orbx_sim3_atan2(double y, double x);
+
 #ifdef __cplusplus
 }
 #endif

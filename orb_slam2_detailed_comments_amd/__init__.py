@@ -12,3 +12,4 @@ from .keyframe_db import KeyFrameDatabase, bow_score  # noqa: F401
 from .mappoint import (distinctive_descriptors_batch, distinctive_descriptors_batch_device,  # noqa: F401
                        update_normal_and_depth_batch)
 from .optimizer import pose_optimization, pose_optimization_batch  # noqa: F401
+from .sim3 import Sim3Ransac, compute_sim3_round_robin, ransac_iterations  # noqa: F401

@@ -71,6 +71,12 @@ class PoseProblem(C.Structure):   # orbx_pose_problem
     _fields_ = [("frame", C.c_int32), ("Tcw", C.c_float * 16), ("point_index", C.c_void_p), ("npoints", C.c_int32)]
 
 
+class Sim3Problem(C.Structure):   # orbx_sim3_problem
+    _fields_ = [("n", C.c_int32), ("x1c", C.c_void_p), ("x2c", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
+                ("camera1", C.c_float * 4), ("camera2", C.c_float * 4), ("fix_scale", C.c_int32), ("min_inliers", C.c_int32),
+                ("iterations", C.c_int32), ("sets", C.c_void_p)]
+
+
 TRACK_STATE_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),
                               ("level", "<i4")])   # orbx_track_state
 assert TRACK_STATE_DTYPE.itemsize == 20
@@ -135,6 +141,8 @@ SYMBOLS = [
     "orbx_distinctive_descriptors_batch", "orbx_distinctive_descriptors_batch_device", "orbx_update_normal_and_depth_batch",
     "orbx_pose_optimization_batch_device", "orbx_pose_optimization", "orbx_pose_sin_cos",
     "orbx_debug_pose_inlier_test",
+    "orbx_sim3_ransac_iterations", "orbx_sim3_ransac_batch_create", "orbx_sim3_batch_iterate", "orbx_sim3_batch_best",
+    "orbx_sim3_batch_counts", "orbx_sim3_batch_hypothesis", "orbx_sim3_batch_destroy", "orbx_sim3_atan2",
 ]
 
 _lib = None
@@ -188,6 +196,15 @@ def lib():
     L.orbx_debug_pose_inlier_test.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, f32, vp, i32, vp, vp, vp, vp]
     L.orbx_pose_sin_cos.restype = None
     L.orbx_pose_sin_cos.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.orbx_sim3_ransac_iterations.restype = i32; L.orbx_sim3_ransac_iterations.argtypes = [i32, C.c_double, i32, i32]
+    L.orbx_sim3_ransac_batch_create.restype = i32; L.orbx_sim3_ransac_batch_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+    L.orbx_sim3_batch_iterate.restype = i32
+    L.orbx_sim3_batch_iterate.argtypes = [vp, i32, i32, C.POINTER(i32), vp, C.POINTER(i32), vp]
+    L.orbx_sim3_batch_best.restype = i32; L.orbx_sim3_batch_best.argtypes = [vp, i32, vp, vp, C.POINTER(f32)]
+    L.orbx_sim3_batch_counts.restype = i32; L.orbx_sim3_batch_counts.argtypes = [vp, i32, vp, C.POINTER(i32)]
+    L.orbx_sim3_batch_hypothesis.restype = i32; L.orbx_sim3_batch_hypothesis.argtypes = [vp, i32, i32, vp, vp]
+    L.orbx_sim3_batch_destroy.restype = None; L.orbx_sim3_batch_destroy.argtypes = [vp]
+    L.orbx_sim3_atan2.restype = C.c_double; L.orbx_sim3_atan2.argtypes = [C.c_double, C.c_double]
     L.orbx_get_stream.restype = vp; L.orbx_get_stream.argtypes = [vp]
     L.orbx_set_stream.restype = i32; L.orbx_set_stream.argtypes = [vp, vp]
     L.orbx_synchronize.restype = i32; L.orbx_synchronize.argtypes = [vp]

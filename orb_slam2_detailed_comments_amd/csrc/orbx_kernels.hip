@@ -4363,6 +4363,80 @@ __global__ __launch_bounds__(64) void k_pose_opt(const DPoseArgs A) {
     }
 }
 
+#include "orbx_sim3.h"
+// Sim3Solver RANSAC, batched (orbx_sim3.h).  k_sim3_hypotheses: one lane per (problem, iteration) gathers the three drawn
+// correspondences and runs ComputeSim3 in registers (the Jacobi sweeps and every 3x3 product are unrolled: no per-thread array
+// is indexed at run time), then stores the hypothesis.  The lanes of a wave share no data and take no barrier, so the sweep
+// count may differ between them.
+__global__ __launch_bounds__(64) void k_sim3_hypotheses(const DSim3Args A) {
+    const int h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= A.total_iters) return;
+    const DSim3Prob &D = A.prob[A.iter_prob[h]];
+    const float *pl = A.pts + D.pts_off;
+    const long long n = D.n;
+    float P1[9], P2[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const long long idx = A.sets[3 * (long long)h + c];    // inside [0, n): checked on the host before the upload
+#pragma unroll
+        for (int r = 0; r < 3; ++r) { P1[3 * c + r] = pl[r * n + idx]; P2[3 * c + r] = pl[(3 + r) * n + idx]; }
+    }
+    OrbxSim3Hyp H;
+    orbx_sim3_compute(P1, P2, D.fix_scale, H);
+    float *o = (float *)(A.hyp + h);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { o[k] = H.T12[k]; o[16 + k] = H.T21[k]; }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[32 + k] = H.R[k];
+    o[41] = H.t[0]; o[42] = H.t[1]; o[43] = H.t[2]; o[44] = H.s; o[45] = 0.f; o[46] = 0.f; o[47] = 0.f;
+}
+// k_sim3_inliers: CheckInliers.  One workgroup = ORBX_SIM3_WAVES consecutive iterations of ONE problem, one wave each.  The
+// problem's correspondences are staged in LDS once per workgroup, ORBX_SIM3_CHUNK at a time as ORBX_SIM3_PLANES planes (lane i
+// reads word i of a plane: no bank conflict); lanes stride over the points, a 64-point word of the mask is one ballot, the
+// count is the sum of the popcounts.  Every barrier is taken by all four waves (a wave past the problem's last iteration only
+// stages).
+__global__ __launch_bounds__(64 * ORBX_SIM3_WAVES) void k_sim3_inliers(const DSim3Args A) {
+    __shared__ float s_pts[ORBX_SIM3_PLANES * ORBX_SIM3_CHUNK];
+    const int g = blockIdx.x;
+    if (g >= A.ngroups) return;
+    const DSim3Prob &D = A.prob[A.groups[2 * g]];
+    const int lane = threadIdx.x & 63;
+    const int it = A.groups[2 * g + 1] + (threadIdx.x >> 6);
+    const bool active = it < D.iterations;                     // (wave-uniform)
+    const int n = D.n;
+    const float *pl = A.pts + D.pts_off;
+    float T12[12], T21[12], K1[4], K2[4];
+    {
+        const OrbxSim3Hyp &H = A.hyp[D.iter_off + (active ? it : 0)];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { T12[k] = H.T12[k]; T21[k] = H.T21[k]; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { K1[k] = D.K1[k]; K2[k] = D.K2[k]; }
+    }
+    unsigned long long *mw = A.masks + D.word_off + (long long)(active ? it : 0) * D.nwords;
+    int cnt = 0;
+    for (int base = 0; base < n; base += ORBX_SIM3_CHUNK) {
+        const int len = n - base < ORBX_SIM3_CHUNK ? n - base : ORBX_SIM3_CHUNK;
+        __syncthreads();                                       // the previous chunk has been read by every wave
+#pragma unroll
+        for (int p = 0; p < ORBX_SIM3_PLANES; ++p)
+            for (int i = threadIdx.x; i < len; i += 64 * ORBX_SIM3_WAVES) s_pts[p * ORBX_SIM3_CHUNK + i] = pl[(long long)p * n + base + i];
+        __syncthreads();
+        if (!active) continue;
+        for (int sub = 0; sub < len; sub += 64) {
+            const int i = sub + lane;                          // < ORBX_SIM3_CHUNK; entries at or past len are masked below
+            float v[ORBX_SIM3_PLANES];
+#pragma unroll
+            for (int p = 0; p < ORBX_SIM3_PLANES; ++p) v[p] = s_pts[p * ORBX_SIM3_CHUNK + i];
+            const bool in = i < len && orbx_sim3_inlier(T12, T21, K1, K2, v, v + 3, v + 8, v + 10, v[6], v[7]);
+            const unsigned long long word = orbx_ballot(in);
+            if (lane == 0) mw[(base + sub) >> 6] = word;
+            cnt += __popcll(word);
+        }
+    }
+    if (active && lane == 0) A.counts[D.iter_off + it] = cnt;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from the C ABI units)
 // ------------------------------------------------------------------------------------------------
@@ -4794,4 +4868,9 @@ void orbx_launch_mp_normal_depth(hipStream_t s, const int32_t *obs_begin, const 
 void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a) {
     if (a.nproblems <= 0) return;
     hipLaunchKernelGGL(k_pose_opt, dim3(a.nproblems), dim3(64), 0, s, a);
+}
+void orbx_launch_sim3(hipStream_t s, const DSim3Args &a) {
+    if (a.total_iters <= 0 || a.ngroups <= 0) return;
+    hipLaunchKernelGGL(k_sim3_hypotheses, dim3((a.total_iters + 63) / 64), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_sim3_inliers, dim3(a.ngroups), dim3(64 * ORBX_SIM3_WAVES), 0, s, a);
 }

@@ -6,6 +6,7 @@
 #include "orbx_track.h"
 #include "orbx_mappoint.h"
 #include "orbx_pose.h"
+#include "orbx_sim3.h"
 
 hipError_t orbx_upload_pattern();
 size_t orbx_quadtree_smem(int ncap, int lds_keys);
@@ -100,6 +101,8 @@ void orbx_launch_mp_distinct(hipStream_t s, const int32_t *obs_begin, const uint
 void orbx_launch_mp_normal_depth(hipStream_t s, const int32_t *obs_begin, const DMpPoint *pts, const float *centers, int npoints,
                                  float scale_last, float *out);
 void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a);
+// Sim3Solver RANSAC (orbx_sim3.h): k_sim3_hypotheses over all iterations, then k_sim3_inliers over the workgroup table
+void orbx_launch_sim3(hipStream_t s, const DSim3Args &a);
 void orbx_launch_hamming_matrix(hipStream_t s, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *dist);
 
 void orbx_launch_stereo_batch(hipStream_t s, const OrbxStereoGeom &sg, int npairs, int cap, const orbx_keypoint *kL,

@@ -1,5 +1,6 @@
-// orbx_map_batches.cpp -- the batched MapPoint refresh and Optimizer::PoseOptimization behind the C ABI: staging, launches and
-// scatter.  Their HIP-free halves (validation, plans, packing, the host solver) are orbx_mappoint.cpp and orbx_pose.cpp.
+// orbx_map_batches.cpp -- the batched MapPoint refresh, Optimizer::PoseOptimization and the Sim3Solver RANSAC behind the C ABI:
+// staging, launches and scatter.  Their HIP-free halves (validation, plans, packing, the host solvers, the Sim3 cursor) are
+// orbx_mappoint.cpp, orbx_pose.cpp and orbx_sim3.cpp.
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -194,3 +195,83 @@ extern "C" orbx_status orbx_pose_optimization(orbx_handle *h, float *Tcw, int n,
     orbx_pose_host_run(1, &P, c);
     return ORBX_OK;
 }
+
+// ---------------------------------------------------------------- Sim3Solver RANSAC, batched (orbx_sim3.h).
+// Device path: validation and layout (orbx_sim3.cpp), all problems packed into the page-locked block, ONE upload,
+// k_sim3_hypotheses and k_sim3_inliers on the handle's stream, ONE download of hypotheses | masks | counts, the wait; the batch
+// keeps a host copy and iterate() is a cursor over it.  Host path (ORBX_SIM3=host, read per call; host-only handles): the same
+// header compiled by the host compiler over the same packed block.
+static bool sim3_host_selected() {
+    const char *e = getenv("ORBX_SIM3");
+    return e && strcmp(e, "host") == 0;
+}
+extern "C" orbx_status orbx_sim3_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_sim3_problem *problems,
+                                                     orbx_sim3_batch **out) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    if (!out) return orbx_fail(ORBX_BAD_ARGUMENT, "null batch pointer");
+    OrbxSim3Plan plan;
+    const char *why = "";
+    orbx_status st = orbx_sim3_plan(nproblems, problems, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (plan.nlaunch == 0) {                                   // nothing to compute: every solver reports no_more at once
+        *out = orbx_sim3_batch_new(problems, plan);
+        return ORBX_OK;
+    }
+    if (h->host_only || sim3_host_selected()) {
+        std::vector<uint8_t> in(plan.in_bytes);
+        orbx_sim3_pack(problems, plan, in.data());
+        orbx_sim3_batch *b = orbx_sim3_batch_new(problems, plan);
+        orbx_sim3_host_run(plan, in.data(), b->out.data());
+        *out = b;
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    const size_t dev_in = pad256(plan.in_bytes);
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + plan.out_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_sim3_pack(problems, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    uint8_t *d_out = d + dev_in;
+    DSim3Args a;
+    a.prob = (const DSim3Prob *)(d + plan.o_prob);
+    a.iter_prob = (const int32_t *)(d + plan.o_iter_prob);
+    a.sets = (const int32_t *)(d + plan.o_sets);
+    a.groups = (const int32_t *)(d + plan.o_groups);
+    a.pts = (const float *)(d + plan.o_pts);
+    a.total_iters = plan.total_iters; a.ngroups = plan.ngroups;
+    a.hyp = (OrbxSim3Hyp *)(d_out + plan.o_hyp);
+    a.masks = (unsigned long long *)(d_out + plan.o_masks);
+    a.counts = (int32_t *)(d_out + plan.o_counts);
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_sim3(h->stream, a); }
+    st = stage_download_wait(h, pin, d_out, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    orbx_sim3_batch *b = orbx_sim3_batch_new(problems, plan);
+    memcpy(b->out.data(), pin, plan.out_bytes);
+    *out = b;
+    return ORBX_OK;
+}
+extern "C" int32_t orbx_sim3_batch_iterate(orbx_sim3_batch *b, int k, int n_iterations, int32_t *no_more, uint8_t *inliers,
+                                           int32_t *ninliers, float *T12) {
+    const char *why = "";
+    const int32_t r = orbx_sim3_cursor_iterate(b, k, n_iterations, no_more, inliers, ninliers, T12, &why);
+    if (r < 0) orbx_fail(ORBX_BAD_ARGUMENT, why);
+    return r;
+}
+extern "C" orbx_status orbx_sim3_batch_best(const orbx_sim3_batch *b, int k, float *R, float *t, float *s) {
+    const char *why = "";
+    const orbx_status st = orbx_sim3_cursor_best(b, k, R, t, s, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" orbx_status orbx_sim3_batch_counts(const orbx_sim3_batch *b, int k, int32_t *counts, int32_t *niterations) {
+    const char *why = "";
+    const orbx_status st = orbx_sim3_cursor_counts(b, k, counts, niterations, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" orbx_status orbx_sim3_batch_hypothesis(const orbx_sim3_batch *b, int k, int iteration, float *hyp48, uint64_t *mask_words) {
+    const char *why = "";
+    const orbx_status st = orbx_sim3_cursor_hypothesis(b, k, iteration, hyp48, mask_words, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" void orbx_sim3_batch_destroy(orbx_sim3_batch *b) { delete b; }

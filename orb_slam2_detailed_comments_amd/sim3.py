@@ -1,0 +1,123 @@
+"""Sim3Solver RANSAC for the candidates of LoopClosing::ComputeSim3 (include/orbx.h: orbx_sim3_ransac_batch_create and the
+cursor calls).  ctypes marshalling only; `extractor` is the ORBextractor whose handle (stream, staging block) the batch call runs
+on.  One call evaluates every iteration of every problem on the device; iterate() then replays Sim3Solver::iterate on the host.
+On a host-only extractor (device=-2) the library's host path runs."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import check, ptr
+
+
+def ransac_iterations(n, probability=0.99, min_inliers=6, max_iterations=300):
+    """SetRansacParameters: mRansacMaxIts for a solver with n correspondences"""
+    return int(_capi.lib().orbx_sim3_ransac_iterations(int(n), float(probability), int(min_inliers), int(max_iterations)))
+
+
+class Sim3Ransac:
+    """problems: dicts with x1c, x2c [n, 3], max_err1, max_err2 [n], camera1, camera2 (fx, fy, cx, cy), fix_scale, min_inliers,
+    iterations (mRansacMaxIts after SetRansacParameters) and sets [iterations, 3] (the draws in order; not read where
+    n < min_inliers)."""
+
+    def __init__(self, extractor, problems):
+        self._L = _capi.lib()
+        self._b = C.c_void_p()
+        self.n = []
+        arr = (_capi.Sim3Problem * max(len(problems), 1))()
+        keep = []
+        for k, p in enumerate(problems):
+            x1 = np.ascontiguousarray(p["x1c"], np.float32).reshape(-1, 3)
+            x2 = np.ascontiguousarray(p["x2c"], np.float32).reshape(-1, 3)
+            e1 = np.ascontiguousarray(p["max_err1"], np.float32).reshape(-1)
+            e2 = np.ascontiguousarray(p["max_err2"], np.float32).reshape(-1)
+            n = len(x1)
+            assert len(x2) == n and len(e1) == n and len(e2) == n
+            sets = p.get("sets")
+            if sets is not None:
+                sets = np.ascontiguousarray(sets, np.int32).reshape(-1, 3)
+                assert len(sets) == int(p["iterations"])
+            keep += [x1, x2, e1, e2, sets]
+            a = arr[k]
+            a.n = n
+            a.x1c, a.x2c, a.max_err1, a.max_err2 = (v.ctypes.data if n else None for v in (x1, x2, e1, e2))
+            a.camera1[:] = np.asarray(p["camera1"], np.float32).tolist()
+            a.camera2[:] = np.asarray(p["camera2"], np.float32).tolist()
+            a.fix_scale = int(bool(p["fix_scale"]))
+            a.min_inliers = int(p["min_inliers"])
+            a.iterations = int(p["iterations"])
+            a.sets = sets.ctypes.data if sets is not None and sets.size else None
+            self.n.append(n)
+        check(self._L.orbx_sim3_ransac_batch_create(extractor.handle, len(problems), C.cast(arr, C.c_void_p), C.byref(self._b)))
+        self.iterations = [int(p["iterations"]) for p in problems]
+
+    def __len__(self):
+        return len(self.n)
+
+    def iterate(self, k, n_iterations):
+        """Sim3Solver::iterate of solver k: (T12 4x4 float32 or None, no_more, inliers bool [n], ninliers)"""
+        n = self.n[k]
+        inl = np.zeros(max(n, 1), np.uint8)
+        T = np.zeros(16, np.float32)
+        no_more, nin = C.c_int32(0), C.c_int32(0)
+        r = self._L.orbx_sim3_batch_iterate(self._b, int(k), int(n_iterations), C.byref(no_more), ptr(inl), C.byref(nin), ptr(T))
+        if r < 0:
+            check(_capi.BAD_ARGUMENT)
+        return (T.reshape(4, 4) if r == 1 else None), bool(no_more.value), inl[:n].astype(bool), int(nin.value)
+
+    def best(self, k):
+        """GetEstimatedRotation / Translation / Scale of solver k"""
+        R, t, s = np.zeros(9, np.float32), np.zeros(3, np.float32), C.c_float(0)
+        check(self._L.orbx_sim3_batch_best(self._b, int(k), ptr(R), ptr(t), C.byref(s)))
+        return R.reshape(3, 3), t, np.float32(s.value)
+
+    def counts(self, k):
+        c = np.zeros(max(self.iterations[k], 1), np.int32)
+        nit = C.c_int32(0)
+        check(self._L.orbx_sim3_batch_counts(self._b, int(k), ptr(c), C.byref(nit)))
+        return c[:nit.value]
+
+    def hypothesis(self, k, iteration):
+        """(48 floats: T12 | T21 | R | t | s | 0 0 0, mask bool [n]) of one stored iteration"""
+        n = self.n[k]
+        h = np.zeros(48, np.float32)
+        w = np.zeros(max((n + 63) // 64, 1), np.uint64)
+        check(self._L.orbx_sim3_batch_hypothesis(self._b, int(k), int(iteration), ptr(h), ptr(w)))
+        bits = np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
+        return h, bits
+
+    def close(self):
+        if self._b:
+            self._L.orbx_sim3_batch_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def compute_sim3_round_robin(ransac, accept, n_iterations=5):
+    """The candidate loop of LoopClosing::ComputeSim3 (src/LoopClosing.cc:487-577) over the solvers of `ransac` (anything with
+    __len__ and iterate(k, n)): every live solver gets iterate(n_iterations) in turn; a solver that reports no_more is
+    discarded; accept(k, T12, inliers, ninliers) -- OptimizeSim3 and the >= 20 test in the reference -- ends the loop when it
+    returns true.  Returns the accepted solver's index or -1, and the list of (k, returned, no_more, ninliers) calls made."""
+    K = len(ransac)
+    discarded = [False] * K
+    live = K
+    calls = []
+    while live > 0:
+        for k in range(K):
+            if discarded[k]:
+                continue
+            T, no_more, inl, nin = ransac.iterate(k, n_iterations)
+            calls.append((k, T is not None, no_more, nin))
+            if no_more:
+                discarded[k] = True
+                live -= 1
+            if T is not None and accept(k, T, inl, nin):
+                return k, calls
+    return -1, calls
