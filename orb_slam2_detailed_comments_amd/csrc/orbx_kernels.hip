@@ -8,6 +8,7 @@
 // __builtin_fmaf calls of the descriptor taps (fp_mode GCC_FMA) and the fma() of the pinned sincos.
 #include "orbx_device.h"
 #include "orbx_inplace.h"
+#include "orbx_fast_net.h"
 #include "orbx_track.h"
 #include "../../include/orbx_pattern_data.h"
 
@@ -603,8 +604,9 @@ __device__ __forceinline__ void orbx_wave_sync() {
 #define FR_WPS 5
 #endif
 #ifndef FR_CCAP
-#define FR_CCAP 512     // corner-list entries per group (see orbx_launch_fast_rows): 8 192 bytes of LDS per wave at 640x480, still 20 waves per CU
+#define FR_CCAP 512     // corner-list entries per group (see orbx_launch_fast_rows, which has the byte arithmetic)
 #endif
+#define FR_STACK 128    // re-run stack of fr_round, entries: the walk's 64 dummy dwords, between the work list and the corner list
 #ifndef FR_GPW
 #define FR_GPW 2        // groups per wave
 #endif
@@ -617,6 +619,20 @@ __device__ __forceinline__ fr_i16 fr_smax(fr_i16 a, fr_i16 b) { return a > b ? a
 __device__ __forceinline__ fr_i16 fr_smin(fr_i16 a, fr_i16 b) { return a < b ? a : b; }
 
 static_assert(64 + ORBX_FAST_XCOLS + 6 + 3 <= FR_TP, "a cell pair's tile row must fit the LDS tile pitch");
+// The LDS of one wave, ONE definition for the kernel's pointers and the launcher's byte count:
+//   tile | score map (each map_bytes, 16-byte aligned: cleared with 16-byte stores) | work list u16[lcap] | stack u16[FR_STACK] (one
+//   private dummy dword per lane during the walk) | corner list of the group u16[ccap]
+struct FrLds { int map_bytes, list_off, corn_off, bytes; };
+__host__ __device__ __forceinline__ FrLds fr_lds(int rows, int lcap, int ccap) {
+    FrLds l;
+    l.map_bytes = (rows * FR_TP + 15) & ~15;
+    l.list_off = 2 * l.map_bytes;
+    l.corn_off = l.list_off + 2 * (lcap + FR_STACK);
+    l.bytes = l.corn_off + 2 * ccap;
+    return l;
+}
+static_assert(2 * FR_STACK == 4 * 64, "the re-run stack is the 64 dummy dwords the walk's masked lanes write to");
+static_assert(FR_STACK >= 64 + 64, "a round pushes at most 64 entries on a stack that holds at most 64 before it");
 __device__ __forceinline__ bool colx_on_mask(unsigned act) { return (act & 2u) != 0; }   // columns >= 64 belong to the second cell
 struct FrCtx {
     const uint8_t *tile;   // LDS tile, byte (0,0) = sub-mat origin of the group's first cell
@@ -630,6 +646,9 @@ struct FrCtx {
 #ifndef FR_UNIFIED
 #define FR_UNIFIED 1
 #endif
+#ifndef FR_NET
+#define FR_NET 1        // 1: the score network of orbx_fast_net.h; 0: the earlier doubling network (A/B builds)
+#endif
 #if FR_UNIFIED
 // Corner test and score of list[0..n) at threshold th in ONE pass per candidate; corners compacted IN PLACE to the front of the
 // list, their scores written to the score map; returns the number of corners.
@@ -638,10 +657,11 @@ struct FrCtx {
 // min/max network of the score IS the test: 16-bit min / max issue at the full rate, where the ring masks of the separate test
 // (v_cmp + v_addc per ring pixel and polarity, fr_ring_and_score below) are all half-rate, and the second pass over the corners
 // (17 LDS reads per corner again) disappears.
-//   One polarity per candidate: d = ring - v, and the compass pixels (ring 0 / 4 / 8 / 12: the walk's pre-test) say which margin
-// is the larger one, s1 = min(max(d0, d8), max(d4, d12)) (brighter) or -s2 = -max(min(d0, d8), min(d4, d12)) (darker).  Darker
-// candidates run the same network on ~d = (v - ring) - 1 with the start value th - 1 (one xor per ring pixel, no negation):
-// corner <=> result > start, score = result - 1 - f with f = 0 / -1.  A candidate that passes BOTH pre-tests (a pixel half way
+//   One polarity per candidate: the compass pixels (ring 0 / 4 / 8 / 12: the walk's pre-test) say which margin is the larger one,
+// and the network runs on the raw ring bytes, complemented for the darker polarity (one xor per ring pixel), in the prefix / suffix
+// form: 57 two-input operations, the centre subtracted once at the end (orbx_fast_net.h; the earlier doubling network on
+// d = +-(ring - v), 80 operations behind 16 multiply-adds, stays selectable as FR_NET=0).
+//   A candidate that passes BOTH pre-tests (a pixel half way
 // up a strong edge: < 1 % of the candidates) and fails its larger polarity may still be a corner of the other one: it is pushed on
 // a small stack (the 64 dummy dwords the walk's masked lanes write to, free during these rounds) and re-run with the polarity
 // forced the other way in a later round; the stack is drained whenever it could not take another round's worth.
@@ -669,6 +689,18 @@ __device__ __forceinline__ void fr_round(const FrCtx &c, const uint16_t *src_mai
     }
     const int off = ((code >> 8) - 3) * FR_TP + (code & 0xff);   // window corner: row - 3, column - 3 (rows start at 3)
     const uint8_t *ptr = c.tile + off;
+#if FR_NET
+    // the network on the raw ring bytes, prefix / suffix form (orbx_fast_net.h); an entry from the stack takes the other polarity
+    const fr_u16 v = ptr[rc];
+    fr_u16 x[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) x[k] = ptr[ro[k]];
+    bool corner, both;
+    uint8_t sc;
+    orbx_fast_net(v, x, thl, !FULL && !is_main, corner, sc, both);
+#else
+    // the earlier network (A/B builds, tools/build_variant.sh NAME -DFR_NET=0): doubling on d = +-(ring - v).  FR_SGN and FR_NOMIN3
+    // describe this arm only.
 #ifndef FR_SGN
 #define FR_SGN 1
 #endif
@@ -739,10 +771,12 @@ __device__ __forceinline__ void fr_round(const FrCtx &c, const uint16_t *src_mai
 #endif
     }
     const bool corner = a0 > start;
+    const uint8_t sc = (uint8_t)(a0 - 1 - f);
+#endif
     const unsigned long long m = orbx_ballot(corner);
     if (corner) {
         c.list[ncorn + orbx_wave_rank(m)] = code;   // index < the entries already read: this round's are in registers
-        c.score[off + rc] = (uint8_t)(a0 - 1 - f);
+        c.score[off + rc] = sc;
     }
     ncorn += __popcll(m);
     // (the mask of the re-runs from the two compare masks on the scalar unit; per-lane work only inside the rare branch)
@@ -755,7 +789,7 @@ __device__ __forceinline__ void fr_round(const FrCtx &c, const uint16_t *src_mai
     }
 }
 __device__ __forceinline__ int fr_ring_and_score(const FrCtx &c, int n, int th, int dbg_stop) {
-    uint16_t *const stack = c.list + c.lcap;   // 128 entries
+    uint16_t *const stack = c.list + c.lcap;   // FR_STACK entries
     int ncorn = 0, nredo = 0, e0 = 0;
     // full rounds of the main list (a round pushes at most 64 entries: with at most 64 on the stack before it, 128 hold them)
     for (; n - e0 >= 64 && nredo <= 64; e0 += 64) fr_round<true>(c, c.list + e0, 64, stack, 0, th, stack, ncorn, nredo);
@@ -869,10 +903,12 @@ __device__ __forceinline__ void fr_nms(const FrCtx &c, const FrCells &gc, const 
         // the score map is shared by the two cells: the neighbours across the seam belong to the other cell's cv::FAST call
         // (strictly greater than all eight <=> strictly greater than their maximum: one select per side, not one per neighbour)
         const bool seam_l = col == gc.iw0, seam_r = col == gc.iw0 - 1;
-        // (two-input maxima, each intermediate in a register of its own: fused, they become the quarter-rate v_max3_u16)
-        int l01 = max(l0, l1), r01 = max(r0, r1);
-        asm("" : "+v"(l01), "+v"(r01));
-        const int ml = seam_l ? 0 : max(l01, l2), mr = seam_r ? 0 : max(r01, r2);
+        // (each side's maximum as ONE 32-bit three-input operation, written as the instruction: the scores are bytes, so from
+        // max(max(l0, l1), l2) the compiler makes the quarter-rate v_max3_u16, and an empty asm between the two costs an s_nop)
+        int ml3, mr3;
+        asm("v_max3_u32 %0, %1, %2, %3" : "=v"(ml3) : "v"(l0), "v"(l1), "v"(l2));
+        asm("v_max3_u32 %0, %1, %2, %3" : "=v"(mr3) : "v"(r0), "v"(r1), "v"(r2));
+        const int ml = seam_l ? 0 : ml3, mr = seam_r ? 0 : mr3;
         const bool keep = (int)valid & (int)(sc > max(max(ml, mr), max(u, dn)));
         const unsigned long long m = orbx_ballot(keep), msec = orbx_ballot(keep && second);
         const unsigned long long mfirst = m & ~msec;
@@ -921,7 +957,7 @@ __device__ __forceinline__ void fr_ip_store(uint32_t *d, const orbx_uint3_u &v, 
 // their (at most 3) ring columns inside the LDS tile.  Address arithmetic: orbx_inplace.h.  Every other level, and every
 // instruction of the walk / ring test / NMS, is the same as in the slab form.
 // (Two kernels, k_fast_rows and k_fast_rows_ip, share this body, so that the slab form keeps its name and its staging code; fr_nms's
-// seam maxima changed for both: two kernels with the fused form would double the quarter-rate v_max3_u16 in the code object.)
+// seam maxima are one 32-bit v_max3_u32 per side in every instance: the code object holds no three-input 16-bit min / max.)
 // MODE: 0 = slab form (k_fast_rows), 1 = mixed (k_fast_rows_ip: the level-0 groups in place, the others from the slab), 2 = a
 // launch of level-0 groups only, all in place (k_fast_rows_l0, the FAST-first plan of run_chunk): no slab staging path and no
 // per-group level test.
@@ -941,10 +977,10 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
     uint32_t *s_tile = (uint32_t *)fast_smem;
     // tile | score map (16-byte aligned: cleared with 16-byte stores) | work list (lcap entries + one private dummy dword per
     // lane) | corner list of the group (ccap entries: a group with more corners takes the dense NMS rescan)
-    const int map_bytes = (rows * FR_TP + 15) & ~15;
-    uint8_t *s_score = fast_smem + map_bytes;
-    uint16_t *s_list = (uint16_t *)(s_score + map_bytes);
-    uint16_t *s_corn = s_list + lcap + 128;
+    const FrLds lds = fr_lds(rows, lcap, ccap);
+    uint8_t *s_score = fast_smem + lds.map_bytes;
+    uint16_t *s_list = (uint16_t *)(fast_smem + lds.list_off);
+    uint16_t *s_corn = (uint16_t *)(fast_smem + lds.corn_off);
     const int lane = threadIdx.x;
     const int f = blockIdx.x;   // frame fastest: all groups of one frame share one XCD's L2
     // FR_GPW groups per wave, one after the other: the next group's tile is fetched into registers while this one
@@ -4564,14 +4600,16 @@ void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell 
     lcap = (max(lcap, 64) + 1) & ~1;
     // LDS per wave decides how many waves a CU holds: the corner list of a group is sized for its usual load, FR_CCAP entries (the
     // average group has ~130 corners), not for the work list's worst case -- a group with more corners than that runs its NMS as the
-    // dense rescan of the score map -- and tile / score map are rounded to 16 bytes, not to four rows.  At 640x480: 8 192 bytes with
-    // 512 entries = exactly 20 waves per CU, the number the registers allow (round 3, second half: 1.316 / 1.319 -> 1.286 / 1.272 ms
-    // against 256 entries = 7 680 bytes, because fewer groups take the rescan; 640 entries = 8 448 bytes = 19 waves: 1.39-1.41 ms).
+    // dense rescan of the score map -- and tile / score map are rounded to 16 bytes, not to four rows.  Bytes per wave (fr_lds) =
+    // 2 * map + 2 * lcap + 2 * FR_STACK + 2 * ccap = 2 * map + 2 560 with the default 640-entry work list and 512 corners: 8 192 for
+    // 37-row cells (the level-0 launch at 640x480: 20 waves in a CU's 160 KiB), 8 640 / 9 120 for the 40 / 43-row tiles of the
+    // launches that carry every level (18 / 17 waves).  512 was chosen by measurement, not by an occupancy step (round 3, second
+    // half: 1.316 / 1.319 -> 1.286 / 1.272 ms against 256 entries, because fewer groups take the rescan; 640 entries: 1.39-1.41 ms).
     const int ccap = min(lcap, FR_CCAP);
-    const size_t map_bytes = ((size_t)max_ch * FR_TP + 15) & ~(size_t)15;
+    const FrLds lds = fr_lds(max_ch, lcap, ccap);
     // lds_floor (the sub-batch pipeline): the request is raised to cap the waves a CU holds, leaving registers for the pyramid
     // kernels of the other stream; the kernel uses no more than it did
-    const size_t need = 2 * map_bytes + (size_t)2 * lcap + 256 + (size_t)2 * ccap;
+    const size_t need = (size_t)lds.bytes;
     const size_t smem = lds_floor > 0 && (size_t)lds_floor > need ? (size_t)lds_floor : need;
     // groups per wave: FR_GPW when the launch has waves to spare (the second group's tile is prefetched while the first
     // is processed); one per wave for small batches, where the serial length of a wave is what the caller waits for
