@@ -724,6 +724,9 @@ orbx_status orbx_debug_level_keypoints(orbx_handle *h, int frame, int level, orb
 orbx_status orbx_debug_blur_copy(orbx_handle *h, int frame, int level, uint8_t *dst, int dst_stride);
 /* FAST groups (waves' work items of k_fast_rows) per frame of the configured geometry: those of level 0, and all of them */
 orbx_status orbx_debug_fast_groups(orbx_handle *h, int *level0, int *total);
+/* the two per-lane forms of the BRIEF pattern k_describe reads, as uploaded: 64 lanes x 16 coordinates (round r of lane l =
+ * pair r*64 + l as x1, y1, x2, y2), int8 and float.  Host only: needs no handle and no device. */
+orbx_status orbx_debug_describe_pattern(int8_t *lane_i8_1024, float *lane_f32_1024);
 
 /* ---- Optimizer::PoseOptimization(Frame*) (src/Optimizer.cc:363-607), the reader of the tracking matchers' rows
  * (TrackWithMotionModel, TrackReferenceKeyFrame, TrackLocalMap, Relocalization), for many (frame, pose, matches) problems in

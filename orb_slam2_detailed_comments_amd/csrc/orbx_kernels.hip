@@ -1911,6 +1911,8 @@ __constant__ uint32_t c_orient_w[64][12];
 // B operands of the row pass on the matrix pipe (DS_MFMA): the banded 7-tap kernel, output column tile j of 16:
 // entry [j][lane][.] = the 16 bytes B[k = 16 (lane >> 4) + s][n = lane & 15] = K7[k - (16 j + n)] (0 outside the band)
 __constant__ uint32_t c_blur_b[3][64][4];
+// c_pattern_lane's coordinates as exact floats (DS_PATTERN_F32): entry [l][r] = (x1, y1, x2, y2) of pair r*64 + l
+__constant__ float4 c_pattern_f32[64][4];
 
 // The 7x7 Gaussian (reference :2039-2047) is fused in: only a 43x43 neighbourhood of each keypoint is ever sampled
 // (|tap| <= 18, +3 px filter support), so each wave stages that patch of the UN-blurred level in LDS, runs the
@@ -1966,23 +1968,64 @@ __constant__ uint32_t c_blur_b[3][64][4];
 // (Several keypoints per wave with register prefetch of the next patch was measured: 430-440 us at the 4-5 waves per
 // SIMD its registers allow against 375 us for one keypoint per wave -- every phase of this kernel is a dependent chain of
 // LDS round trips, and resident waves are what hides them.)
+// The length of one wave's dependent chain (profiles/describe_chain.md); every item is a build switch, 0 = the earlier form:
+// DS_SLOT: waves indexed by the SLOT of the per-frame level-keypoint table instead of by output position.  The level of a slot
+//   follows from the kp_begin values (kernel arguments) alone, so the level's table entry, the eight counts and the slot's
+//   position word are requested together, in front of one wait: kernel arguments, {level entry, counts, position}, patch -- three
+//   memory round trips in front of the first LDS write where the output-indexed form has eight.  A slot beyond its level's count
+//   is a dead wave; the output position is the sum of the counts below the level + the index in the level.  Slot order is
+//   level-major like the output order, so the order of the workgroups of a frame on its XCD is the same.
+// DS_EARLY_TABLES (bit 0: pattern, bit 1: c_orient_w, bit 2: c_blur_b): the constant tables are requested right behind the patch
+//   loads, before the first LDS write, instead of in front of their first use.
+// DS_TAP_BATCH (1 / 2 / 4 / 8): taps per batch; a batch forms all its addresses, issues all its LDS reads, then runs the dot
+//   products as independent chains.
+// DS_PATTERN_F32: the pattern coordinates come as floats (c_pattern_f32) instead of 16 int8 -> float conversions per lane.
+// DS_PACK_PERM: the MFMA accumulators are packed to u16 pairs by one v_perm_b32 instead of a shift and an or.
+#ifndef DS_SLOT
+#define DS_SLOT 1
+#endif
+#ifndef DS_EARLY_TABLES
+#define DS_EARLY_TABLES 7
+#endif
+#ifndef DS_TAP_BATCH
+#define DS_TAP_BATCH 1   // 2 / 4 / 8 measured slower or equal (profiles/describe_chain.md)
+#endif
+#ifndef DS_PATTERN_F32
+#define DS_PATTERN_F32 0   // measured slower: four 16-byte loads per lane in place of one cost more than 16 conversions
+#endif
+#ifndef DS_PACK_PERM
+#define DS_PACK_PERM 1
+#endif
 // FPM (fp_mode) is a template constant: as a run-time value it costs a scalar branch and both code paths in each of the 8 taps
 typedef const __attribute__((address_space(3))) uint16_t *orbx_lds_u16p;
 typedef const __attribute__((address_space(3))) uint32_t *orbx_lds_u32p;
 // I = sum_i k_i v[r][c + i], i = 0..6, for the u16 element at LDS byte address `adr` (DS_COLFIRST): the 8 elements of the
-// dword-aligned 16-byte window around them, against the weights shifted by the parity of c
-__device__ __forceinline__ uint32_t orbx_ds_tap(uint32_t adr) {
+// dword-aligned 16-byte window around them, against the weights shifted by the parity of c; I < 2^24.01.
+// N taps at once (DS_TAP_BATCH): every window read is issued before the first weight is formed, and the N dot-product chains are
+// independent of one another -- one LDS round trip per batch where tap after tap pays one each
+template <int N>
+__device__ __forceinline__ void orbx_ds_taps(const uint32_t (&adr)[N], uint32_t (&I)[N]) {
     typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    const bool odd = (adr & 2u) != 0;
-    const orbx_lds_u32p wp = (orbx_lds_u32p)(uintptr_t)(adr & ~3u);
-    const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2], d3 = wp[3];
-    const uint32_t w0 = odd ? (18u << 16) : (18u | (34u << 16)), w1 = odd ? (34u | (49u << 16)) : (49u | (55u << 16)),
-                   w2 = odd ? (55u | (49u << 16)) : (49u | (34u << 16)), w3 = odd ? (34u | (18u << 16)) : 18u;
-    uint32_t I = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, d0), __builtin_bit_cast(u16x2, w0), 0u, false);
-    I = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, d1), __builtin_bit_cast(u16x2, w1), I, false);
-    I = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, d2), __builtin_bit_cast(u16x2, w2), I, false);
-    I = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, d3), __builtin_bit_cast(u16x2, w3), I, false);
-    return I;   // < 2^24.01
+    uint32_t d[N][4];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const orbx_lds_u32p wp = (orbx_lds_u32p)(uintptr_t)(adr[k] & ~3u);
+        d[k][0] = wp[0]; d[k][1] = wp[1]; d[k][2] = wp[2]; d[k][3] = wp[3];
+    }
+    uint32_t w[N][4];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const bool odd = (adr[k] & 2u) != 0;
+        w[k][0] = odd ? (18u << 16) : (18u | (34u << 16)); w[k][1] = odd ? (34u | (49u << 16)) : (49u | (55u << 16));
+        w[k][2] = odd ? (55u | (49u << 16)) : (49u | (34u << 16)); w[k][3] = odd ? (34u | (18u << 16)) : 18u;
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) I[k] = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            I[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, d[k][i]), __builtin_bit_cast(u16x2, w[k][i]), I[k], false);
 }
 // INPLACE: level-0 keypoints stage their patch from the caller's grey image (`raw`), which holds no border: interior
 // keypoints run the slab path's code on it; a patch that leaves the raw image (about 15 % of the level-0 keypoints: the 19-pixel
@@ -2019,19 +2062,83 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
     // own 4 MB L2, and the chip holds 8 frames at a time.  (With the frame as the fastest index -- the order of the first
     // version -- every frame of the batch has a few keypoints in flight at once: at 1024 frames per launch no cache holds that,
     // and every patch came from HBM, 3.1 MB per frame.)
+#if DS_SLOT
+    // every kernel argument the path to the first patch load reads, requested in front of ONE wait (left alone, each is loaded
+    // in front of its first use: one round trip per basic block of the prologue)
+    // (the empty asm only fixes the point by which all of them have arrived.  Not volatile, and with results that are used: a
+    // volatile asm counts as a store to memory, behind which no load through a pointer argument is a scalar load any more.)
+    int kbv[8];
+#pragma unroll
+    for (int l = 0; l < 8; ++l) kbv[l] = g.lv[l].kp_begin;
+    asm("" : "+s"(nframes), "+s"(cap), "+s"(kbv[0]), "+s"(kbv[1]), "+s"(kbv[2]), "+s"(kbv[3]), "+s"(kbv[4]), "+s"(kbv[5]), "+s"(kbv[6]), "+s"(kbv[7])
+           : "s"(g.nlevels), "s"(g.kp_total), "s"(g.pyr_bytes), "s"(lvl_kp), "s"(lvl_count), "s"(pyr));
+#endif
 #if DS_ORDER == 1
     const int f = blockIdx.y * 8 + (blockIdx.x & 7);
-    const int oi = (blockIdx.x >> 3) * DS_WPB + wv_id;
+    const int wi = (blockIdx.x >> 3) * DS_WPB + wv_id;
     if (f >= nframes) return;
 #else
     const int f = blockIdx.x;   // frame fastest: one frame's patches stay in one XCD's L2
-    const int oi = blockIdx.y * DS_WPB + wv_id;
+    const int wi = blockIdx.y * DS_WPB + wv_id;
 #endif
     const int *lc = lvl_count + f * g.nlevels;
-    int total = 0, level = 0, slot = oi;
+    int total = 0, level = 0;
 #ifndef DS_LEVELS8
 #define DS_LEVELS8 1
 #endif
+#if DS_SLOT
+    // wave = slot.  (First round trip: the kernel arguments, pinned at the top of the kernel.)
+    const int slot = wi;
+    if (DS_WPB > 1 && slot >= g.kp_total) return;
+    const bool all8 = DS_LEVELS8 && g.nlevels == 8;   // every ORB-SLAM2 configuration
+    int kb = kbv[0];
+    if (all8) {
+#pragma unroll
+        for (int l = 1; l < 8; ++l)
+            if (slot >= kbv[l]) { level = l; kb = kbv[l]; }
+    } else {
+#pragma unroll
+        for (int l = 1; l < ORBX_MAX_LEVELS; ++l)
+            if (l < g.nlevels && slot >= g.lv[l].kp_begin) { level = l; kb = g.lv[l].kp_begin; }
+    }
+    // Second round trip: the level's table entry, the slot's position word and the counts, all addressable now.  (The position
+    // word of a dead slot is read and dropped: slot < kp_total lies inside the frame's table whatever the counts are.)
+    uint32_t pos = lvl_kp[(long long)f * g.kp_total + slot];
+    struct { int pw, ph, pitch, org; long long off; float scale, size; } L =
+        {g.lv[level].pw, g.lv[level].ph, g.lv[level].pitch, g.lv[level].org, g.lv[level].off, g.lv[level].scale, g.lv[level].size};
+    int base = 0, mine = 0;
+    if (all8) {
+        int4 ca = *(const int4 *)lc, cb = *(const int4 *)(lc + 4);
+        // one wait for the whole round trip: without the pin the compiler sinks each load to its first use, behind the exits below
+        asm("" : "+s"(pos), "+s"(L.pw), "+s"(L.ph), "+s"(L.pitch), "+s"(L.org), "+s"(L.off), "+s"(L.scale), "+s"(L.size),
+                 "+s"(ca.x), "+s"(ca.y), "+s"(ca.z), "+s"(ca.w), "+s"(cb.x), "+s"(cb.y), "+s"(cb.z), "+s"(cb.w));
+        const int cnt[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
+#pragma unroll
+        for (int l = 0; l < 8; ++l) {
+            if (l < level) base += cnt[l];
+            if (l == level) mine = cnt[l];
+            total += cnt[l];
+        }
+    } else {
+#pragma unroll
+        for (int l = 0; l < ORBX_MAX_LEVELS; ++l) {
+            if (l < g.nlevels) {
+                const int c = lc[l];
+                if (l < level) base += c;
+                if (l == level) mine = c;
+                total += c;
+            }
+        }
+    }
+    const int oi = base + (slot - kb);   // dense output position (level-major order of operator(), :2066-2082)
+    if (slot == 0 && lane == 0) {        // slot 0 exists in every frame, live or not
+        counts[f] = min(total, cap);
+        if (total > cap) atomicMax(&status[f], (int)ORBX_CAPACITY);
+    }
+    if (slot - kb >= mine || oi >= min(total, cap) || dbg_stop == 4) return;
+#else
+    const int oi = wi;
+    int slot = oi;
     if (DS_LEVELS8 && g.nlevels == 8) {
         // every ORB-SLAM2 configuration: the eight counts in one scalar load, then compares and selects only, and ONE table
         // load for the level found (the general loop below pays two dependent scalar loads and two branches per level:
@@ -2059,15 +2166,35 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
         if (total > cap) atomicMax(&status[f], (int)ORBX_CAPACITY);
     }
     if (oi >= min(total, cap) || dbg_stop == 4) return;
+    const uint32_t pos = lvl_kp[(long long)f * g.kp_total + slot];
+    const DLevel &L = g.lv[level];
+#endif
 #if DS_COLFIRST && DS_ALIAS
     uint32_t *patch = (uint32_t *)s_h[wv_id];
 #else
     uint32_t *patch = s_patch[wv_id];
 #endif
     uint16_t *hrow = s_h[wv_id];
-    const uint32_t pos = lvl_kp[(long long)f * g.kp_total + slot];
-    const int4 pat = c_pattern_lane[lane];
-    const DLevel &L = g.lv[level];
+    // the constant tables: requested behind the patch loads (DS_EARLY_TABLES) or in front of their first use
+#if DS_PATTERN_F32
+    float4 patf[4];
+#define DS_LOAD_PATTERN() do { _Pragma("unroll") for (int r = 0; r < 4; ++r) patf[r] = c_pattern_f32[lane][r]; } while (0)
+#else
+    int4 pat;
+#define DS_LOAD_PATTERN() do { pat = c_pattern_lane[lane]; } while (0)
+#endif
+    uint4 wa, wb, wc;
+#define DS_LOAD_ORIENT_W() do { wa = *(const uint4 *)&c_orient_w[lane][0]; wb = *(const uint4 *)&c_orient_w[lane][4]; wc = *(const uint4 *)&c_orient_w[lane][8]; } while (0)
+#if DS_COLFIRST && DS_MFMA
+    uint4 b4[3];
+#define DS_LOAD_BLUR_B() do { _Pragma("unroll") for (int j = 0; j < 3; ++j) b4[j] = *(const uint4 *)&c_blur_b[j][lane][0]; } while (0)
+#else
+#define DS_LOAD_BLUR_B() do { } while (0)
+#endif
+    // (the scheduling barrier keeps every patch load in front of the table loads: loads return in order, and the first LDS write
+    // waits for the patch alone)
+#define DS_LOAD_EARLY() do { if (DS_EARLY_TABLES) __builtin_amdgcn_sched_barrier(0); if (DS_EARLY_TABLES & 1) DS_LOAD_PATTERN(); if (DS_EARLY_TABLES & 2) DS_LOAD_ORIENT_W(); if (DS_EARLY_TABLES & 4) DS_LOAD_BLUR_B(); } while (0)
+    if (!(DS_EARLY_TABLES & 1)) DS_LOAD_PATTERN();
     const int x = (int)(pos & 0xfff) + (ORBX_EDGE - 3), y = (int)((pos >> 12) & 0xfff) + (ORBX_EDGE - 3);
     const bool ip0 = INPLACE && level == 0;   // wave-uniform
     const uint8_t *img = ip0 ? raw.img + (long long)f * raw.frame_stride : pyr + (long long)f * g.pyr_bytes + L.off;
@@ -2091,6 +2218,7 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
             orbx_uint3_u tv[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) tv[k] = *(const orbx_uint3_u *)(p0 + __mul24(min(16 * k + rq, DS_W - 1), spitch));
+            DS_LOAD_EARLY();
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const uint32_t nxt = orbx_lane_above(tv[k].x);
@@ -2115,6 +2243,7 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
 #pragma unroll
             for (int k = 0; k < 3; ++k)
                 tv[k] = *(const orbx_uint3_u *)(img + orbx_ip_row_off(orbx_ip_map(py0 + ORBX_EDGE + min(16 * k + rq, DS_W - 1), raw.H), raw.stride, ws + 12 * dq));
+            DS_LOAD_EARLY();
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const uint32_t nxt = orbx_lane_above(tv[k].x);
@@ -2152,6 +2281,7 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
         } else {
             // image edge: reflect-101 of the padded level, byte by byte
             uint8_t *pb = (uint8_t *)patch;
+            DS_LOAD_EARLY();
             for (int i = lane; i < DS_W * DS_W; i += 64) {
                 const int r = i / DS_W, c = i - r * DS_W;
                 const int sy = orbx_reflect101(py0 + r, L.ph), sx = orbx_reflect101(px0 + c, L.pw);
@@ -2167,7 +2297,7 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
             // lane = (row, half): 5 aligned dwords of patch row 21 + v, two v_dot4_u32_u8 each against the constant weights
             const int row = lane >> 1, half = lane & 1;                 // row = v + 15 (lanes 62, 63 carry zero weights)
             const uint32_t *pr = patch + min(row + (DS_R - ORBX_HALF_PATCH), DS_W - 1) * (DS_PP / 4) + 1 + 5 * half;
-            const uint4 wa = *(const uint4 *)&c_orient_w[lane][0], wb = *(const uint4 *)&c_orient_w[lane][4], wc = *(const uint4 *)&c_orient_w[lane][8];
+            if (!(DS_EARLY_TABLES & 2)) DS_LOAD_ORIENT_W();
             const uint32_t p0 = pr[0], p1 = pr[1], p2 = pr[2], p3 = pr[3], p4 = pr[4];
             uint32_t A = __builtin_amdgcn_udot4(p0, wa.x, 0u, false), S = __builtin_amdgcn_udot4(p0, wb.y, 0u, false);
             A = __builtin_amdgcn_udot4(p1, wa.y, A, false); S = __builtin_amdgcn_udot4(p1, wb.z, S, false);
@@ -2195,10 +2325,10 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
                 A[t][0] = (int)(ap[0] ^ 0x80808080u); A[t][1] = (int)(ap[1] ^ 0x80808080u);
                 A[t][2] = (int)(ap[2] ^ 0x80808080u); A[t][3] = (int)(ap[3] ^ 0x80808080u);
             }
+            if (!(DS_EARLY_TABLES & 4)) DS_LOAD_BLUR_B();
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                const uint4 b4 = *(const uint4 *)&c_blur_b[j][lane][0];
-                Bm[j][0] = (int)b4.x; Bm[j][1] = (int)b4.y; Bm[j][2] = (int)b4.z; Bm[j][3] = (int)b4.w;
+                Bm[j][0] = (int)b4[j].x; Bm[j][1] = (int)b4[j].y; Bm[j][2] = (int)b4[j].z; Bm[j][3] = (int)b4[j].w;
             }
             const i32x4 c0 = {128 * 257, 128 * 257, 128 * 257, 128 * 257};
             uint32_t *vo = (uint32_t *)hrow + m * (DS_VC / 2) + 2 * gq;   // HT[c = 16 j + m][r = 16 t + 4 gq ..]: u16 index c * 44 + r
@@ -2209,8 +2339,16 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
                     const i32x4 acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t], Bm[j], c0, 0, 0, 0);
                     // columns c < 37 and rows r < 44 exist in HT
                     if ((j < 2 || m < DS_W - 6 - 32) && (t < 2 || gq < 3))
+#if DS_PACK_PERM
+                        // every accumulator is a sum of bytes x the 8-bit kernel (<= 255 * 257, whatever bytes the don't-care rows
+                        // hold): its two low bytes are the whole value
+                        *(uint2 *)(vo + (16 * j) * (DS_VC / 2) + 8 * t) =
+                            make_uint2(__builtin_amdgcn_perm((uint32_t)acc[1], (uint32_t)acc[0], 0x05040100u),
+                                       __builtin_amdgcn_perm((uint32_t)acc[3], (uint32_t)acc[2], 0x05040100u));
+#else
                         *(uint2 *)(vo + (16 * j) * (DS_VC / 2) + 8 * t) =
                             make_uint2((uint32_t)acc[0] | ((uint32_t)acc[1] << 16), (uint32_t)acc[2] | ((uint32_t)acc[3] << 16));
+#endif
                 }
             }
         }
@@ -2282,7 +2420,15 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
         // 2^-16 is exact, and a total >= 2^24 saturates to 255 either way, so the float path IS round-half-even(I / 65536)
         // with I = 55 r0 + 49 r1 + 34 r2 + 18 r3: one integer formula serves both, the tail only changes the tie rule.
         const int wvec = (L.pw - 2 * L.org) & ~3;   // of the image GaussianBlur is given (fork: the padded level; upstream: the view)
+        // tap t = 2 r + s2: point s2 of the lane's pair of round r
+#if DS_PATTERN_F32
+#define DS_PX(t) (((t) & 1) ? patf[(t) >> 1].z : patf[(t) >> 1].x)
+#define DS_PY(t) (((t) & 1) ? patf[(t) >> 1].w : patf[(t) >> 1].y)
+#else
         const int pw4[4] = {pat.x, pat.y, pat.z, pat.w};
+#define DS_PX(t) ((float)(signed char)((pw4[(t) >> 1] >> (16 * ((t) & 1))) & 0xff))
+#define DS_PY(t) ((float)(signed char)((pw4[(t) >> 1] >> (16 * ((t) & 1) + 8)) & 0xff))
+#endif
         unsigned long long words[4];
         if (x + (DS_R - 3) < wvec) {
             // No tap of this keypoint reaches the tail columns (all but keypoints within 18 px of the right edge): the
@@ -2299,11 +2445,11 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
             float nb = -b;
             asm("" : "+v"(nb));   // a register of its own (the compiler would fold the negation back into every product)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
+            for (int t0 = 0; t0 < 8; t0 += DS_TAP_BATCH) {
+                uint32_t adr[DS_TAP_BATCH], I[DS_TAP_BATCH];
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    const float px = (float)(signed char)((pw4[r] >> (16 * s2)) & 0xff);
-                    const float py = (float)(signed char)((pw4[r] >> (16 * s2 + 8)) & 0xff);
+                for (int k = 0; k < DS_TAP_BATCH; ++k) {
+                    const float px = DS_PX(t0 + k), py = DS_PY(t0 + k);
                     float fy, fx;
                     if (FPM == ORBX_FP_GCC_FMA) {
                         fy = __builtin_fmaf(px, b, py * a);     // vfmadd132ss: x*b + rn(y*a)
@@ -2319,33 +2465,41 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
                     // LDS byte address of HT[ix+18][iy+18]: the tap's window starts here (two instructions: v_lshl_add + v_mad_u32_u24)
                     uint32_t ay = (uy << 1) + hbase;
                     asm("" : "+v"(ay));
-                    const uint32_t adr = __umul24(ux, 2u * DS_VC) + ay;
+                    adr[k] = __umul24(ux, 2u * DS_VC) + ay;
 #else
-                    const uint32_t adr = __umul24(uy, 2u * DS_VC) + ((ux << 1) + hbase);   // LDS byte address of v[iy+18][ix+18]: the tap's window starts here
+                    adr[k] = __umul24(uy, 2u * DS_VC) + ((ux << 1) + hbase);   // LDS byte address of v[iy+18][ix+18]: the tap's window starts here
 #endif
-                    const uint32_t I = orbx_ds_tap(adr);
 #else
-                    uint32_t adr = __umul24(uy, 2u * DS_HC) + ((ux << 1) + hbase);   // LDS byte address of h[iy+18][ix+18]
-                    asm("" : "+v"(adr));   // a plain address from here on: the row offsets fold into the ds_read immediates
-                    const orbx_lds_u16p hp = (orbx_lds_u16p)(uintptr_t)adr;
+                    adr[k] = __umul24(uy, 2u * DS_HC) + ((ux << 1) + hbase);   // LDS byte address of h[iy+18][ix+18]
+                    asm("" : "+v"(adr[k]));   // a plain address from here on: the row offsets fold into the ds_read immediates
+#endif
+                }
+#if DS_COLFIRST
+                orbx_ds_taps<DS_TAP_BATCH>(adr, I);
+#else
+#pragma unroll
+                for (int k = 0; k < DS_TAP_BATCH; ++k) {
+                    const orbx_lds_u16p hp = (orbx_lds_u16p)(uintptr_t)adr[k];
                     const uint32_t r0 = hp[3 * DS_HC], r1 = (uint32_t)hp[2 * DS_HC] + hp[4 * DS_HC],
                                    r2 = (uint32_t)hp[1 * DS_HC] + hp[5 * DS_HC], r3 = (uint32_t)hp[0] + hp[6 * DS_HC];
-                    const uint32_t I = __umul24(55u, r0) + __umul24(49u, r1) + __umul24(34u, r2) + __umul24(18u, r3);   // < 2^24.01
-#endif
-                    // I <= 2^24 converts exactly and I * 2^-16 is exact; above, the conversion's own rounding keeps it >= 256
-                    tv[2 * r + s2] = __builtin_fminf(__builtin_rintf((float)I * (1.f / 65536.f)), 255.f);
+                    I[k] = __umul24(55u, r0) + __umul24(49u, r1) + __umul24(34u, r2) + __umul24(18u, r3);   // < 2^24.01
                 }
+#endif
+                // I <= 2^24 converts exactly and I * 2^-16 is exact; above, the conversion's own rounding keeps it >= 256
+#pragma unroll
+                for (int k = 0; k < DS_TAP_BATCH; ++k) tv[t0 + k] = __builtin_fminf(__builtin_rintf((float)I[k] * (1.f / 65536.f)), 255.f);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) words[r] = orbx_ballot(tv[2 * r] < tv[2 * r + 1]);
         } else {
             int tval[8];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
+            for (int t0 = 0; t0 < 8; t0 += DS_TAP_BATCH) {
+                uint32_t adr[DS_TAP_BATCH], I[DS_TAP_BATCH];
+                int ixs[DS_TAP_BATCH];
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    const float px = (float)(signed char)((pw4[r] >> (16 * s2)) & 0xff);
-                    const float py = (float)(signed char)((pw4[r] >> (16 * s2 + 8)) & 0xff);
+                for (int k = 0; k < DS_TAP_BATCH; ++k) {
+                    const float px = DS_PX(t0 + k), py = DS_PY(t0 + k);
                     float fy, fx;
                     if (FPM == ORBX_FP_GCC_FMA) {
                         fy = __builtin_fmaf(px, b, py * a);
@@ -2355,21 +2509,33 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
                         fx = px * a - py * b;
                     }
                     const int iy = (int)__builtin_rintf(fy), ix = (int)__builtin_rintf(fx);
+                    ixs[k] = ix;
                     // blurred pixel (x+ix, y+iy): column pass over h rows (iy+21-3 .. iy+21+3), h column ix+18
 #if DS_COLFIRST
 #if DS_MFMA
-                    const uint32_t I = orbx_ds_tap((uint32_t)(uintptr_t)(orbx_lds_u16p)hrow + 2u * (uint32_t)(__mul24(ix + DS_R - 3, DS_VC) + (iy + DS_R - 3)));
+                    adr[k] = (uint32_t)(uintptr_t)(orbx_lds_u16p)hrow + 2u * (uint32_t)(__mul24(ix + DS_R - 3, DS_VC) + (iy + DS_R - 3));
 #else
-                    const uint32_t I = orbx_ds_tap((uint32_t)(uintptr_t)(orbx_lds_u16p)hrow + 2u * (uint32_t)(__mul24(iy + DS_R - 3, DS_VC) + (ix + DS_R - 3)));
+                    adr[k] = (uint32_t)(uintptr_t)(orbx_lds_u16p)hrow + 2u * (uint32_t)(__mul24(iy + DS_R - 3, DS_VC) + (ix + DS_R - 3));
 #endif
 #else
-                    const uint16_t *hp = hrow + __mul24(iy + DS_R - 3, DS_HC) + (ix + DS_R - 3);
+                    adr[k] = (uint32_t)(__mul24(iy + DS_R - 3, DS_HC) + (ix + DS_R - 3));   // element index in h
+#endif
+                }
+#if DS_COLFIRST
+                orbx_ds_taps<DS_TAP_BATCH>(adr, I);
+#else
+#pragma unroll
+                for (int k = 0; k < DS_TAP_BATCH; ++k) {
+                    const uint16_t *hp = hrow + adr[k];
                     const uint32_t r0 = hp[3 * DS_HC], r1 = (uint32_t)hp[2 * DS_HC] + hp[4 * DS_HC],
                                    r2 = (uint32_t)hp[1 * DS_HC] + hp[5 * DS_HC], r3 = (uint32_t)hp[0] + hp[6 * DS_HC];
-                    const uint32_t I = __umul24(55u, r0) + __umul24(49u, r1) + __umul24(34u, r2) + __umul24(18u, r3);
+                    I[k] = __umul24(55u, r0) + __umul24(49u, r1) + __umul24(34u, r2) + __umul24(18u, r3);
+                }
 #endif
-                    const uint32_t tie = x + ix >= wvec ? 1u : ((I >> 16) & 1u);   // half-up in the tail, half-even elsewhere
-                    tval[2 * r + s2] = (int)min((I + 0x7fffu + tie) >> 16, 255u);
+#pragma unroll
+                for (int k = 0; k < DS_TAP_BATCH; ++k) {
+                    const uint32_t tie = x + ixs[k] >= wvec ? 1u : ((I[k] >> 16) & 1u);   // half-up in the tail, half-even elsewhere
+                    tval[t0 + k] = (int)min((I[k] + 0x7fffu + tie) >> 16, 255u);
                 }
             }
 #pragma unroll
@@ -4482,12 +4648,19 @@ __global__ __launch_bounds__(64 * ORBX_SIM3_WAVES) void k_sim3_inliers(const DSi
 #include <cstring>
 #include <mutex>
 
-hipError_t orbx_upload_pattern() {
-    signed char t[64 * 16];
+void orbx_pattern_lane_tables(signed char *i8, float *f32) {
     for (int l = 0; l < 64; ++l)
         for (int r = 0; r < 4; ++r)
-            for (int k = 0; k < 4; ++k) t[l * 16 + r * 4 + k] = ORBX_PATTERN_I8[(r * 64 + l) * 4 + k];
+            for (int k = 0; k < 4; ++k) i8[l * 16 + r * 4 + k] = ORBX_PATTERN_I8[(r * 64 + l) * 4 + k];
+    for (int i = 0; i < 64 * 16; ++i) f32[i] = (float)i8[i];   // |coordinate| <= 127: exact
+}
+hipError_t orbx_upload_pattern() {
+    signed char t[64 * 16];
+    static float tf[64 * 16];
+    orbx_pattern_lane_tables(t, tf);
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_pattern_lane), t, sizeof(t));
+    if (e != hipSuccess) return e;
+    e = hipMemcpyToSymbol(HIP_SYMBOL(c_pattern_f32), tf, sizeof(tf));
     if (e != hipSuccess) return e;
     // IC_Angle weight table: umax of the reference's constructor (src/ORBextractor.cc:866-910) for HALF_PATCH_SIZE = 15
     orbx_params p;

@@ -9,6 +9,8 @@
 #include "orbx_sim3.h"
 
 hipError_t orbx_upload_pattern();
+// the per-lane pattern tables orbx_upload_pattern uploads, 64 lanes x 16 coordinates each: c_pattern_lane and c_pattern_f32 (host only)
+void orbx_pattern_lane_tables(signed char *i8, float *f32);
 size_t orbx_quadtree_smem(int ncap, int lds_keys);
 hipError_t orbx_quadtree_prepare(size_t smem);
 void orbx_launch_clear(hipStream_t s, int *a, int na, int *b, int nb, int *c, int nc);

@@ -139,6 +139,11 @@ extern "C" orbx_status orbx_debug_fast_groups(orbx_handle *h, int *level0, int *
     if (total) *total = (int)h->geom.fast_groups.size();
     return ORBX_OK;
 }
+extern "C" orbx_status orbx_debug_describe_pattern(int8_t *lane_i8_1024, float *lane_f32_1024) {
+    if (!lane_i8_1024 || !lane_f32_1024) return orbx_fail(ORBX_BAD_ARGUMENT, "null table");
+    orbx_pattern_lane_tables((signed char *)lane_i8_1024, lane_f32_1024);
+    return ORBX_OK;
+}
 
 // ---------------------------------------------------------------- a16: ComputeStereoMatches (src/Frame.cc:880-1176)
 // mvImagePyramid of both eyes as the match reads it: the padded levels (fork) or the views inside them (upstream)
