@@ -846,6 +846,67 @@ void orbx_sim3_batch_destroy(orbx_sim3_batch *b);
  * tests/sim3_model.py, which takes this primitive and orbx_pose_sin_cos from the library. */
 double orbx_sim3_atan2(double y, double x);
 
+/* ---- PnPsolver (src/PnPsolver.cc), the EPnP RANSAC between SearchByBoW and PoseOptimization in Tracking::Relocalization
+ * (src/Tracking.cc:2336-2366), for all candidate keyframes in one device round trip.  An iteration is an independent 4-point
+ * EPnP followed by one projection of every correspondence, so every iteration of every candidate is evaluated ahead of time --
+ * k_pnp_hypotheses: one lane per (problem, iteration) runs compute_pose on the four drawn correspondences in a lane-interleaved
+ * LDS workspace; k_pnp_inliers: one wave per (problem, iteration) runs CheckInliers over the problem's correspondences staged in
+ * LDS, the mask as 64-bit ballot words, the count as the sum of their popcounts -- and orbx_pnp_batch_iterate replays the
+ * reference's iterate(n, ...) calls on the host from the stored counts and masks, in any interleaving: the OR loop condition
+ * (:285), the strict > best update, Refine() after every qualifying iteration (on the host, cached per best mask), the
+ * fall-through return of mBestTcw.
+ * CONTRACT: hypotheses (double R and t, float Tcw, the chosen N), masks and counts of the device equal the library's host path
+ * (ORBX_PNP=host in the environment, read per call; host-only handles) and the numpy restatement tests/pnp_model.py bit for bit,
+ * in both fp_modes.  Parity with an OpenCV build is NOT pinned: DESIGN.md section 2 (F13) lists what follows the reference's
+ * source and what this library fixes where the reference leaves it to OpenCV 1.x (cvSVD, cvInvert, cvSolve, cvMulTransposed).
+ * The caller supplies the draws: sets[i] = the four indices the swap-remove draw of iteration i produced, so a solver's answer
+ * is the reference's for the same draws.
+ * A problem with n < min_inliers launches nothing, its sets are not read (may be NULL) and its first iterate reports no_more.
+ * Validated before any device work, ORBX_BAD_ARGUMENT: nproblems < 0, a null array whose size is positive, n < 0,
+ * iterations < 1, a set index outside [0, n), an index repeated within its set (the reference's draw cannot repeat).
+ * nproblems == 0 launches nothing and gives an empty batch.
+ * OUTSIDE the contract (a negative eigenvalue under sqrt, the singular branch of qr_solve, betas[0] == 0, z == 0, non-finite
+ * input): the same straight-line code runs, qr_solve's singular branch gives X = 0, a non-finite error2 is an outlier, a stored
+ * NaN is the canonical quiet NaN. */
+typedef struct orbx_pnp_problem {
+    int32_t n;                 /* N of the solver: correspondences that passed the constructor's filters */
+    const float *p3dw;         /* [n][3] mvP3Dw */
+    const float *p2d;          /* [n][2] mvP2D */
+    const float *max_err;      /* [n]    mvMaxError = mvSigma2 * th2 (float times float) */
+    double camera[4];          /* fu, fv, uc, vc */
+    int32_t min_inliers, iterations;   /* mRansacMinInliers, mRansacMaxIts AFTER SetRansacParameters */
+    const int32_t *sets;       /* [iterations][4] indices into 0..n-1, the draws in order */
+} orbx_pnp_problem;
+typedef struct orbx_pnp_batch orbx_pnp_batch;
+/* SetRansacParameters (:190-239) on the host: mRansacMinInliers and mRansacMaxIts for N = n (N * epsilon truncated, float
+ * epsilon, exponent 3, the min_inliers == N branch, max(1, min(., .))).  A double outside int's range converts as in
+ * orbx_sim3_ransac_iterations.  Either result pointer may be NULL. */
+void orbx_pnp_ransac_parameters(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations, int32_t min_set,
+                                float epsilon, int32_t *out_min_inliers, int32_t *out_iterations);
+/* One page-locked block up, both kernels, one block down; the batch owns copies of the problems and of the results and needs
+ * neither the handle nor the caller's arrays afterwards.  On a host-only handle the library's host path runs. */
+orbx_status orbx_pnp_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_pnp_problem *problems, orbx_pnp_batch **out);
+/* PnPsolver::iterate(n_iterations, bNoMore, vbInliers, nInliers) of solver k as a cursor over the stored results.  Returns 1
+ * when a pose is returned (Tcw [16] row major = mRefinedTcw or mBestTcw, inliers [n] as 0 / 1, *ninliers), 0 when not (inliers
+ * all 0, *ninliers = 0, Tcw untouched), -1 for a bad argument (orbx_last_error()), and -2 WITH THE SOLVER'S STATE UNCHANGED when
+ * the replay would need an iteration past those stored: append sets and call again. */
+int32_t orbx_pnp_batch_iterate(orbx_pnp_batch *b, int k, int n_iterations, int32_t *no_more, uint8_t *inliers, int32_t *ninliers,
+                               float *Tcw);
+/* Evaluates nsets further iterations of solver k (sets [nsets][4]) on the library's host path -- the same header code, the same
+ * bits -- and appends them to its stored results, so any call pattern is the reference's, including a solver iterated again
+ * past mRansacMaxIts after PoseOptimization rejected its answer. */
+orbx_status orbx_pnp_batch_append(orbx_pnp_batch *b, int k, int nsets, const int32_t *sets);
+/* tests and tools: mBestTcw [16], mnBestInliers and the iteration behind them (any pointer may be NULL); ORBX_BAD_ARGUMENT
+ * before an iteration of the solver has reached min_inliers */
+orbx_status orbx_pnp_batch_best(const orbx_pnp_batch *b, int k, float *Tcw, int32_t *ninliers, int32_t *iteration);
+/* tests and tools: the inlier count of every stored iteration of solver k (counts may be NULL to ask for *niterations only) */
+orbx_status orbx_pnp_batch_counts(const orbx_pnp_batch *b, int k, int32_t *counts, int32_t *niterations);
+/* tests and tools: stored iteration `iteration` of solver k: Rt12 = double R [9] | t [3], Tcw float [16], *N the chosen
+ * candidate, mask words (uint64 [ceil(n / 64)], bit i of word w = correspondence 64 w + i); any pointer may be NULL */
+orbx_status orbx_pnp_batch_hypothesis(const orbx_pnp_batch *b, int k, int iteration, double *Rt12, float *Tcw, int32_t *N,
+                                      uint64_t *mask_words);
+void orbx_pnp_batch_destroy(orbx_pnp_batch *b);
+
 #ifdef __cplusplus
 }
 #endif

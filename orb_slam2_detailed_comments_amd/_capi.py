@@ -77,6 +77,11 @@ class Sim3Problem(C.Structure):   # orbx_sim3_problem
                 ("iterations", C.c_int32), ("sets", C.c_void_p)]
 
 
+class PnpProblem(C.Structure):   # orbx_pnp_problem
+    _fields_ = [("n", C.c_int32), ("p3dw", C.c_void_p), ("p2d", C.c_void_p), ("max_err", C.c_void_p), ("camera", C.c_double * 4),
+                ("min_inliers", C.c_int32), ("iterations", C.c_int32), ("sets", C.c_void_p)]
+
+
 TRACK_STATE_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),
                               ("level", "<i4")])   # orbx_track_state
 assert TRACK_STATE_DTYPE.itemsize == 20
@@ -144,6 +149,8 @@ SYMBOLS = [
     "orbx_debug_pose_inlier_test",
     "orbx_sim3_ransac_iterations", "orbx_sim3_ransac_batch_create", "orbx_sim3_batch_iterate", "orbx_sim3_batch_best",
     "orbx_sim3_batch_counts", "orbx_sim3_batch_hypothesis", "orbx_sim3_batch_destroy", "orbx_sim3_atan2",
+    "orbx_pnp_ransac_parameters", "orbx_pnp_ransac_batch_create", "orbx_pnp_batch_iterate", "orbx_pnp_batch_append",
+    "orbx_pnp_batch_best", "orbx_pnp_batch_counts", "orbx_pnp_batch_hypothesis", "orbx_pnp_batch_destroy",
 ]
 
 _lib = None
@@ -206,6 +213,16 @@ def lib():
     L.orbx_sim3_batch_hypothesis.restype = i32; L.orbx_sim3_batch_hypothesis.argtypes = [vp, i32, i32, vp, vp]
     L.orbx_sim3_batch_destroy.restype = None; L.orbx_sim3_batch_destroy.argtypes = [vp]
     L.orbx_sim3_atan2.restype = C.c_double; L.orbx_sim3_atan2.argtypes = [C.c_double, C.c_double]
+    L.orbx_pnp_ransac_parameters.restype = None
+    L.orbx_pnp_ransac_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
+    L.orbx_pnp_ransac_batch_create.restype = i32; L.orbx_pnp_ransac_batch_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+    L.orbx_pnp_batch_iterate.restype = i32
+    L.orbx_pnp_batch_iterate.argtypes = [vp, i32, i32, C.POINTER(i32), vp, C.POINTER(i32), vp]
+    L.orbx_pnp_batch_append.restype = i32; L.orbx_pnp_batch_append.argtypes = [vp, i32, i32, vp]
+    L.orbx_pnp_batch_best.restype = i32; L.orbx_pnp_batch_best.argtypes = [vp, i32, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.orbx_pnp_batch_counts.restype = i32; L.orbx_pnp_batch_counts.argtypes = [vp, i32, vp, C.POINTER(i32)]
+    L.orbx_pnp_batch_hypothesis.restype = i32; L.orbx_pnp_batch_hypothesis.argtypes = [vp, i32, i32, vp, vp, C.POINTER(i32), vp]
+    L.orbx_pnp_batch_destroy.restype = None; L.orbx_pnp_batch_destroy.argtypes = [vp]
     L.orbx_get_stream.restype = vp; L.orbx_get_stream.argtypes = [vp]
     L.orbx_set_stream.restype = i32; L.orbx_set_stream.argtypes = [vp, vp]
     L.orbx_synchronize.restype = i32; L.orbx_synchronize.argtypes = [vp]

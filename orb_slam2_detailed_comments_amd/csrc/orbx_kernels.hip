@@ -4639,6 +4639,80 @@ __global__ __launch_bounds__(64 * ORBX_SIM3_WAVES) void k_sim3_inliers(const DSi
     if (active && lane == 0) A.counts[D.iter_off + it] = cnt;
 }
 
+#include "orbx_pnp.h"
+// PnPsolver RANSAC, batched (orbx_pnp.h).  k_pnp_hypotheses: one lane per (problem, iteration) runs compute_pose (EPnP) on the
+// four drawn correspondences.  The 12 x 12 MtM and its eigenvectors alone are 288 doubles, more than a lane's registers hold, so
+// every array of the algorithm lives in the lane's slice of an LDS workspace: element e of lane l at double index
+// e * ORBX_PNP_HYP_LANES + l, which makes every 64-bit LDS access of the wave conflict-free.  ORBX_PNP_HYP_LANES = 32 lanes per
+// workgroup keep the workspace (544 doubles per lane, 136 KiB) inside the 160 KiB of a CU.  The lanes share no data and take
+// no barrier, so sweep counts may differ between them.  The job is a few hundred to a few thousand hypotheses: latency-bound.
+__global__ __launch_bounds__(ORBX_PNP_HYP_LANES) void k_pnp_hypotheses(const DPnpArgs A) {
+    __shared__ double s_ws[ORBX_PNP_WS_DOUBLES(4) * ORBX_PNP_HYP_LANES];
+    const int h = blockIdx.x * ORBX_PNP_HYP_LANES + threadIdx.x;
+    if (h >= A.total_iters) return;
+    const DPnpProb &D = A.prob[A.iter_prob[h]];
+    const float *pl = A.pts + D.pts_off;
+    const long long n = D.n;
+    const OrbxPnpWs W = {s_ws + threadIdx.x, ORBX_PNP_HYP_LANES};
+    for (int c = 0; c < 4; ++c) {
+        const long long idx = A.sets[4 * (long long)h + c];    // inside [0, n): checked on the host before the upload
+        for (int r = 0; r < 3; ++r) W(ORBX_PNP_FIXED + 3 * c + r) = (double)pl[r * n + idx];
+        W(ORBX_PNP_FIXED + 12 + 2 * c) = (double)pl[3 * n + idx];
+        W(ORBX_PNP_FIXED + 12 + 2 * c + 1) = (double)pl[4 * n + idx];
+    }
+    const double cam[4] = {D.cam[0], D.cam[1], D.cam[2], D.cam[3]};
+    OrbxPnpHyp &H = A.hyp[h];
+    const int N = orbx_pnp_compute_pose(W, 4, cam, H.R);       // R (9) | t (3) are contiguous in the record
+    orbx_pnp_store(H.R, N, H);
+}
+// k_pnp_inliers: CheckInliers.  One workgroup = ORBX_PNP_WAVES consecutive iterations of ONE problem, one wave each.  The
+// problem's correspondences are staged in LDS once per workgroup, ORBX_PNP_CHUNK at a time as ORBX_PNP_PLANES planes; lanes
+// stride over the points, a 64-point word of the mask is one ballot, the count is the sum of the popcounts.  Every barrier is
+// taken by all four waves (a wave past the problem's last iteration only stages).
+__global__ __launch_bounds__(64 * ORBX_PNP_WAVES) void k_pnp_inliers(const DPnpArgs A) {
+    __shared__ float s_pts[ORBX_PNP_PLANES * ORBX_PNP_CHUNK];
+    const int g = blockIdx.x;
+    if (g >= A.ngroups) return;
+    const DPnpProb &D = A.prob[A.groups[2 * g]];
+    const int lane = threadIdx.x & 63;
+    const int it = A.groups[2 * g + 1] + (threadIdx.x >> 6);
+    const bool active = it < D.iterations;                     // (wave-uniform)
+    const int n = D.n;
+    const float *pl = A.pts + D.pts_off;
+    double R[9], t[3], cam[4];
+    {
+        const OrbxPnpHyp &H = A.hyp[D.iter_off + (active ? it : 0)];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = H.R[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) t[k] = H.t[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) cam[k] = D.cam[k];
+    }
+    unsigned long long *mw = A.masks + D.word_off + (long long)(active ? it : 0) * D.nwords;
+    int cnt = 0;
+    for (int base = 0; base < n; base += ORBX_PNP_CHUNK) {
+        const int len = n - base < ORBX_PNP_CHUNK ? n - base : ORBX_PNP_CHUNK;
+        __syncthreads();                                       // the previous chunk has been read by every wave
+#pragma unroll
+        for (int p = 0; p < ORBX_PNP_PLANES; ++p)
+            for (int i = threadIdx.x; i < len; i += 64 * ORBX_PNP_WAVES) s_pts[p * ORBX_PNP_CHUNK + i] = pl[(long long)p * n + base + i];
+        __syncthreads();
+        if (!active) continue;
+        for (int sub = 0; sub < len; sub += 64) {
+            const int i = sub + lane;                          // < ORBX_PNP_CHUNK; entries at or past len are masked below
+            float v[ORBX_PNP_PLANES];
+#pragma unroll
+            for (int p = 0; p < ORBX_PNP_PLANES; ++p) v[p] = s_pts[p * ORBX_PNP_CHUNK + i];
+            const bool in = i < len && orbx_pnp_inlier(R, t, cam, v[0], v[1], v[2], v[3], v[4], v[5]);
+            const unsigned long long word = orbx_ballot(in);
+            if (lane == 0) mw[(base + sub) >> 6] = word;
+            cnt += __popcll(word);
+        }
+    }
+    if (active && lane == 0) A.counts[D.iter_off + it] = cnt;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from the C ABI units)
 // ------------------------------------------------------------------------------------------------
@@ -5084,4 +5158,10 @@ void orbx_launch_sim3(hipStream_t s, const DSim3Args &a) {
     if (a.total_iters <= 0 || a.ngroups <= 0) return;
     hipLaunchKernelGGL(k_sim3_hypotheses, dim3((a.total_iters + 63) / 64), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_sim3_inliers, dim3(a.ngroups), dim3(64 * ORBX_SIM3_WAVES), 0, s, a);
+}
+void orbx_launch_pnp(hipStream_t s, const DPnpArgs &a) {
+    if (a.total_iters <= 0 || a.ngroups <= 0) return;
+    hipLaunchKernelGGL(k_pnp_hypotheses, dim3((a.total_iters + ORBX_PNP_HYP_LANES - 1) / ORBX_PNP_HYP_LANES), dim3(ORBX_PNP_HYP_LANES),
+                       0, s, a);
+    hipLaunchKernelGGL(k_pnp_inliers, dim3(a.ngroups), dim3(64 * ORBX_PNP_WAVES), 0, s, a);
 }

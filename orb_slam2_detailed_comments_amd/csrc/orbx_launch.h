@@ -7,6 +7,7 @@
 #include "orbx_mappoint.h"
 #include "orbx_pose.h"
 #include "orbx_sim3.h"
+#include "orbx_pnp.h"
 
 hipError_t orbx_upload_pattern();
 // the per-lane pattern tables orbx_upload_pattern uploads, 64 lanes x 16 coordinates each: c_pattern_lane and c_pattern_f32 (host only)
@@ -105,6 +106,8 @@ void orbx_launch_mp_normal_depth(hipStream_t s, const int32_t *obs_begin, const 
 void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a);
 // Sim3Solver RANSAC (orbx_sim3.h): k_sim3_hypotheses over all iterations, then k_sim3_inliers over the workgroup table
 void orbx_launch_sim3(hipStream_t s, const DSim3Args &a);
+// PnPsolver RANSAC (orbx_pnp.h): k_pnp_hypotheses over all iterations, then k_pnp_inliers over the workgroup table
+void orbx_launch_pnp(hipStream_t s, const DPnpArgs &a);
 void orbx_launch_hamming_matrix(hipStream_t s, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *dist);
 
 void orbx_launch_stereo_batch(hipStream_t s, const OrbxStereoGeom &sg, int npairs, int cap, const orbx_keypoint *kL,

@@ -1,6 +1,6 @@
-// orbx_map_batches.cpp -- the batched MapPoint refresh, Optimizer::PoseOptimization and the Sim3Solver RANSAC behind the C ABI:
-// staging, launches and scatter.  Their HIP-free halves (validation, plans, packing, the host solvers, the Sim3 cursor) are
-// orbx_mappoint.cpp, orbx_pose.cpp and orbx_sim3.cpp.
+// orbx_map_batches.cpp -- the batched MapPoint refresh, Optimizer::PoseOptimization, the Sim3Solver RANSAC and the PnPsolver RANSAC
+// behind the C ABI: staging, launches and scatter.  Their HIP-free halves (validation, plans, packing, the host solvers, the
+// Sim3 and PnP cursors) are orbx_mappoint.cpp, orbx_pose.cpp, orbx_sim3.cpp and orbx_pnp.cpp.
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -275,3 +275,90 @@ extern "C" orbx_status orbx_sim3_batch_hypothesis(const orbx_sim3_batch *b, int 
     return st == ORBX_OK ? st : orbx_fail(st, why);
 }
 extern "C" void orbx_sim3_batch_destroy(orbx_sim3_batch *b) { delete b; }
+
+// ---------------------------------------------------------------- PnPsolver RANSAC, batched (orbx_pnp.h).
+// Device path: validation and layout (orbx_pnp.cpp), all problems packed into the page-locked block, ONE upload,
+// k_pnp_hypotheses and k_pnp_inliers on the handle's stream, ONE download of hypotheses | masks | counts, the wait; the batch
+// keeps the results per solver and iterate() is a cursor over them.  Host path (ORBX_PNP=host, read per call; host-only
+// handles): the same header compiled by the host compiler over the same packed block.
+static bool pnp_host_selected() {
+    const char *e = getenv("ORBX_PNP");
+    return e && strcmp(e, "host") == 0;
+}
+extern "C" orbx_status orbx_pnp_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_pnp_problem *problems,
+                                                    orbx_pnp_batch **out) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    if (!out) return orbx_fail(ORBX_BAD_ARGUMENT, "null batch pointer");
+    OrbxPnpPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_pnp_plan(nproblems, problems, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (plan.nlaunch == 0) {                                   // nothing to compute: every solver reports no_more at once
+        *out = orbx_pnp_batch_new(problems, plan);
+        return ORBX_OK;
+    }
+    if (h->host_only || pnp_host_selected()) {
+        std::vector<uint8_t> in(plan.in_bytes), res(plan.out_bytes);
+        orbx_pnp_pack(problems, plan, in.data());
+        orbx_pnp_host_run(plan, in.data(), res.data());
+        orbx_pnp_batch *b = orbx_pnp_batch_new(problems, plan);
+        orbx_pnp_batch_take(b, plan, res.data());
+        *out = b;
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    const size_t dev_in = pad256(plan.in_bytes);
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + plan.out_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_pnp_pack(problems, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    uint8_t *d_out = d + dev_in;
+    DPnpArgs a;
+    a.prob = (const DPnpProb *)(d + plan.o_prob);
+    a.iter_prob = (const int32_t *)(d + plan.o_iter_prob);
+    a.sets = (const int32_t *)(d + plan.o_sets);
+    a.groups = (const int32_t *)(d + plan.o_groups);
+    a.pts = (const float *)(d + plan.o_pts);
+    a.total_iters = plan.total_iters; a.ngroups = plan.ngroups;
+    a.hyp = (OrbxPnpHyp *)(d_out + plan.o_hyp);
+    a.masks = (unsigned long long *)(d_out + plan.o_masks);
+    a.counts = (int32_t *)(d_out + plan.o_counts);
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_pnp(h->stream, a); }
+    st = stage_download_wait(h, pin, d_out, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    orbx_pnp_batch *b = orbx_pnp_batch_new(problems, plan);
+    orbx_pnp_batch_take(b, plan, pin);
+    *out = b;
+    return ORBX_OK;
+}
+extern "C" int32_t orbx_pnp_batch_iterate(orbx_pnp_batch *b, int k, int n_iterations, int32_t *no_more, uint8_t *inliers,
+                                          int32_t *ninliers, float *Tcw) {
+    const char *why = "";
+    const int32_t r = orbx_pnp_cursor_iterate(b, k, n_iterations, no_more, inliers, ninliers, Tcw, &why);
+    if (r < 0) orbx_fail(ORBX_BAD_ARGUMENT, why);
+    return r;
+}
+extern "C" orbx_status orbx_pnp_batch_append(orbx_pnp_batch *b, int k, int nsets, const int32_t *sets) {
+    const char *why = "";
+    const orbx_status st = orbx_pnp_cursor_append(b, k, nsets, sets, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" orbx_status orbx_pnp_batch_best(const orbx_pnp_batch *b, int k, float *Tcw, int32_t *ninliers, int32_t *iteration) {
+    const char *why = "";
+    const orbx_status st = orbx_pnp_cursor_best(b, k, Tcw, ninliers, iteration, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" orbx_status orbx_pnp_batch_counts(const orbx_pnp_batch *b, int k, int32_t *counts, int32_t *niterations) {
+    const char *why = "";
+    const orbx_status st = orbx_pnp_cursor_counts(b, k, counts, niterations, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" orbx_status orbx_pnp_batch_hypothesis(const orbx_pnp_batch *b, int k, int iteration, double *Rt12, float *Tcw, int32_t *N,
+                                                 uint64_t *mask_words) {
+    const char *why = "";
+    const orbx_status st = orbx_pnp_cursor_hypothesis(b, k, iteration, Rt12, Tcw, N, mask_words, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" void orbx_pnp_batch_destroy(orbx_pnp_batch *b) { delete b; }
