@@ -907,6 +907,60 @@ orbx_status orbx_pnp_batch_hypothesis(const orbx_pnp_batch *b, int k, int iterat
                                       uint64_t *mask_words);
 void orbx_pnp_batch_destroy(orbx_pnp_batch *b);
 
+/* ---- Initializer (src/Initializer.cc), the H / F RANSAC of monocular initialisation: what Initializer::Initialize runs on its
+ * two threads (:204-215) between SearchForInitialization and ReconstructH / ReconstructF, for any number of initialisation
+ * attempts in one device round trip.  An iteration is an independent eight-point DLT followed by one pass over every match, so
+ * every iteration of both models of every attempt is evaluated at once -- k_init_hypotheses: one lane per (problem, model,
+ * iteration) builds A from the eight normalised matches, takes its null vector in a lane-interleaved LDS workspace, projects F
+ * to rank 2, de-normalises and inverts H; k_init_scores: one lane per hypothesis runs CheckHomography / CheckFundamental over
+ * the problem's matches staged in LDS, the score as the float sum in match order, the mask as 64-bit words -- and the best
+ * iteration per model, the first strict maximum of the score from 0, is picked on the host after the one download.
+ * CONTRACT: Normalize's T1 and T2, hypotheses (the 3 x 3 matrix, for H its inverse), scores, masks, best iterations, RH and the
+ * model of the device equal the library's host path (ORBX_INIT=host in the environment, read per call; host-only handles) and
+ * the numpy restatement tests/init_model.py bit for bit, in both fp_modes.  Parity with an OpenCV build is NOT pinned:
+ * DESIGN.md section 2 (F14) lists what follows the reference's source and what this library fixes where the reference leaves
+ * it to OpenCV (cv::SVDecomp, cv::Mat::inv, the matrix products).
+ * Normalize runs over ALL keypoints of each frame (keys1, keys2), as in the source, not over the matched ones.  The caller
+ * supplies the draws: sets[i] = mvSets[i], so an attempt's answer is the reference's for the same draws.
+ * model is ORBX_INIT_H iff RH = SH / (SH + SF) > 0.40, else ORBX_INIT_F, and ORBX_INIT_NONE when no iteration of either
+ * requested model scored above 0 (the reference would then read an empty cv::Mat): SH = SF = 0, itH = itF = -1, H21 and F21
+ * zero, masks all false, RH the canonical NaN.  A model that was not requested has score 0, iteration -1 and an all-false mask.
+ * A problem with n < 8 launches nothing, its sets are not read (may be NULL) and it reports ORBX_INIT_NONE.
+ * Validated before any device work, ORBX_BAD_ARGUMENT: nproblems < 0, a negative count, a null array whose size is positive,
+ * iterations < 1, sigma not finite or not > 0, a bit of models outside H | F, a match index outside its frame, a set index outside
+ * [0, n), an index repeated within its set (the reference's draw cannot repeat).  nproblems == 0 gives an empty batch.
+ * OUTSIDE the contract (collinear or repeated points in a set, non-finite keypoints): the same straight-line code runs, a NaN
+ * chi-square is added to the score and leaves bIn alone as in the source, a NaN score never wins (strict >), a stored NaN is
+ * the canonical quiet NaN. */
+#define ORBX_INIT_NONE 0
+#define ORBX_INIT_H 1
+#define ORBX_INIT_F 2
+typedef struct orbx_init_problem {
+    int32_t n1, n2;  const float *keys1, *keys2;   /* [n1][2], [n2][2]: mvKeys1 / mvKeys2 pt of ALL keypoints */
+    int32_t n;       const int32_t *matches;        /* [n][2] mvMatches12 in order (index in 1, index in 2) */
+    float sigma;     int32_t iterations;            /* mSigma, mMaxIterations */
+    const int32_t *sets;                            /* [iterations][8] mvSets: the caller's draws, indices into 0..n-1 */
+    int32_t models;                                 /* ORBX_INIT_H | ORBX_INIT_F */
+} orbx_init_problem;
+typedef struct orbx_init_batch orbx_init_batch;
+/* One page-locked block up, both kernels, one block down; the batch owns copies of the results and needs neither the handle
+ * nor the caller's arrays afterwards.  On a host-only handle the library's host path runs. */
+orbx_status orbx_init_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_init_problem *problems, orbx_init_batch **out);
+/* What FindHomography and FindFundamental leave behind for problem k, and Initialize's choice: SH, SF, H21 [9], F21 [9] (row
+ * major), the best masks as 0 / 1 per match [n], the iterations behind them (-1: none), RH, model.  Any pointer may be NULL. */
+orbx_status orbx_init_batch_result(const orbx_init_batch *b, int k, float *SH, float *SF, float *H21, float *F21,
+                                   uint8_t *inliersH, uint8_t *inliersF, int32_t *itH, int32_t *itF, float *RH, int32_t *model);
+/* tests and tools: currentScore of every iteration of one model (scores may be NULL to ask for *niterations only; 0 iterations
+ * for a model that was not requested or a problem that launched nothing) */
+orbx_status orbx_init_batch_scores(const orbx_init_batch *b, int k, int model, float *scores, int32_t *niterations);
+/* tests and tools: one iteration of one model: H21i or F21i [9], H12i [9] (zeros for F), its score, its mask words (uint64
+ * [ceil(n / 64)], bit i of word w = match 64 w + i); any pointer may be NULL */
+orbx_status orbx_init_batch_hypothesis(const orbx_init_batch *b, int k, int model, int iteration, float *M9, float *Minv9,
+                                       float *score, uint64_t *mask_words);
+/* tests and tools: Normalize's T1 and T2 [9] each, row major */
+orbx_status orbx_init_batch_normalization(const orbx_init_batch *b, int k, float *T1, float *T2);
+void orbx_init_batch_destroy(orbx_init_batch *b);
+
 #ifdef __cplusplus
 }
 #endif

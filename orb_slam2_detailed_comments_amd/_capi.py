@@ -82,6 +82,14 @@ class PnpProblem(C.Structure):   # orbx_pnp_problem
                 ("min_inliers", C.c_int32), ("iterations", C.c_int32), ("sets", C.c_void_p)]
 
 
+class InitProblem(C.Structure):   # orbx_init_problem
+    _fields_ = [("n1", C.c_int32), ("n2", C.c_int32), ("keys1", C.c_void_p), ("keys2", C.c_void_p), ("n", C.c_int32),
+                ("matches", C.c_void_p), ("sigma", C.c_float), ("iterations", C.c_int32), ("sets", C.c_void_p),
+                ("models", C.c_int32)]
+
+
+INIT_NONE, INIT_H, INIT_F = 0, 1, 2
+
 TRACK_STATE_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),
                               ("level", "<i4")])   # orbx_track_state
 assert TRACK_STATE_DTYPE.itemsize == 20
@@ -151,6 +159,8 @@ SYMBOLS = [
     "orbx_sim3_batch_counts", "orbx_sim3_batch_hypothesis", "orbx_sim3_batch_destroy", "orbx_sim3_atan2",
     "orbx_pnp_ransac_parameters", "orbx_pnp_ransac_batch_create", "orbx_pnp_batch_iterate", "orbx_pnp_batch_append",
     "orbx_pnp_batch_best", "orbx_pnp_batch_counts", "orbx_pnp_batch_hypothesis", "orbx_pnp_batch_destroy",
+    "orbx_init_ransac_batch_create", "orbx_init_batch_result", "orbx_init_batch_scores", "orbx_init_batch_hypothesis",
+    "orbx_init_batch_normalization", "orbx_init_batch_destroy",
 ]
 
 _lib = None
@@ -223,6 +233,14 @@ def lib():
     L.orbx_pnp_batch_counts.restype = i32; L.orbx_pnp_batch_counts.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.orbx_pnp_batch_hypothesis.restype = i32; L.orbx_pnp_batch_hypothesis.argtypes = [vp, i32, i32, vp, vp, C.POINTER(i32), vp]
     L.orbx_pnp_batch_destroy.restype = None; L.orbx_pnp_batch_destroy.argtypes = [vp]
+    if hasattr(L, "orbx_init_ransac_batch_create"):   # (absent from an ORBX_LIB build older than the symbols: A/B runs against it)
+        L.orbx_init_ransac_batch_create.restype = i32; L.orbx_init_ransac_batch_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+        L.orbx_init_batch_result.restype = i32
+        L.orbx_init_batch_result.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.orbx_init_batch_scores.restype = i32; L.orbx_init_batch_scores.argtypes = [vp, i32, i32, vp, C.POINTER(i32)]
+        L.orbx_init_batch_hypothesis.restype = i32; L.orbx_init_batch_hypothesis.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+        L.orbx_init_batch_normalization.restype = i32; L.orbx_init_batch_normalization.argtypes = [vp, i32, vp, vp]
+        L.orbx_init_batch_destroy.restype = None; L.orbx_init_batch_destroy.argtypes = [vp]
     L.orbx_get_stream.restype = vp; L.orbx_get_stream.argtypes = [vp]
     L.orbx_set_stream.restype = i32; L.orbx_set_stream.argtypes = [vp, vp]
     L.orbx_synchronize.restype = i32; L.orbx_synchronize.argtypes = [vp]

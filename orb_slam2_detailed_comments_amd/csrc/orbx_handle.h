@@ -1,7 +1,7 @@
 // orbx_handle.h -- struct orbx_handle and what every unit that touches it shares: the error record, HIPCHK, the profiling
 // scope, and the staging of the host-buffer entry points (page-locked blocks, one device arena).  Internal, not installed.
 // The HIP-free units (orbx_geometry.cpp, orbx_track_pack.cpp, orbx_mappoint.cpp, orbx_pose.cpp, orbx_sim3.cpp,
-// orbx_pnp.cpp) do not include it.
+// orbx_pnp.cpp, orbx_init.cpp) do not include it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>

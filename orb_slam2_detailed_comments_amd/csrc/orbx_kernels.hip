@@ -4713,6 +4713,80 @@ __global__ __launch_bounds__(64 * ORBX_PNP_WAVES) void k_pnp_inliers(const DPnpA
     if (active && lane == 0) A.counts[D.iter_off + it] = cnt;
 }
 
+#include "orbx_init.h"
+// Initializer H / F RANSAC, batched (orbx_init.h).  k_init_hypotheses: one lane per (problem, model, iteration) runs the
+// eight-point DLT of ComputeH21 / ComputeF21 and what FindHomography / FindFundamental do with its result.  A (16 x 9) and V
+// (9 x 9) are indexed by the Jacobi's run-time column pair, so they live in the lane's slice of an LDS workspace: element e of
+// lane l at float index e * ORBX_INIT_HYP_LANES + l, which makes every 32-bit LDS access of the wave conflict-free.
+// ORBX_INIT_HYP_LANES = 64 lanes (one wave) take 257 floats each, 64.25 KiB per workgroup, so two workgroups share a CU's
+// 160 KiB; more lanes per workgroup would not put more waves on a CU, the LDS per lane is the limit.  The lanes share no
+// data and take no barrier, so sweep counts may differ between them.
+__global__ __launch_bounds__(ORBX_INIT_HYP_LANES) void k_init_hypotheses(const DInitArgs A) {
+    __shared__ float s_ws[ORBX_INIT_WS_FLOATS * ORBX_INIT_HYP_LANES];
+    const int h = blockIdx.x * ORBX_INIT_HYP_LANES + threadIdx.x;
+    if (h >= A.total_hyps) return;
+    const DInitProb &D = A.prob[A.hyp_prob[h]];
+    const int l = h - D.hyp_off;
+    const bool is_h = orbx_init_is_h(D, l);
+    const float *pl = A.pts + D.pts_off;
+    const long long n = D.n;
+    const int32_t *set = A.sets + D.set_off + 8 * (long long)orbx_init_iteration(D, l);
+    const OrbxInitWs W = {s_ws + threadIdx.x, ORBX_INIT_HYP_LANES};
+    for (int c = 0; c < 8; ++c) {
+        const long long idx = set[c];                          // inside [0, n): checked on the host before the upload
+        for (int r = 0; r < 4; ++r) W(ORBX_INIT_PTS + 4 * c + r) = pl[r * n + idx];
+    }
+    orbx_init_hypothesis(W, is_h, D.T1, is_h ? D.T2inv : D.T2t, A.hyp[h]);
+}
+// k_init_scores: CheckHomography / CheckFundamental.  One workgroup = one wave = ORBX_INIT_SCORE_LANES consecutive hypotheses of
+// ONE problem, one LANE each: the lane keeps its matrix in registers and walks the matches in order, so the score is the
+// source's sequential float sum by construction and every lane works through the whole fold.  The un-normalised matches are
+// staged in LDS ORBX_INIT_CHUNK at a time and read back as broadcasts (every lane reads the same address).  A lane collects 64
+// inlier bits in a register and stores the word when it is full and after the last match.
+__global__ __launch_bounds__(ORBX_INIT_SCORE_LANES) void k_init_scores(const DInitArgs A) {
+    __shared__ float s_pts[4 * ORBX_INIT_CHUNK];
+    const int g = blockIdx.x;
+    if (g >= A.ngroups) return;
+    const DInitProb &D = A.prob[A.groups[2 * g]];
+    const int nh = orbx_init_nhyp(D);
+    const int l0 = A.groups[2 * g + 1] + threadIdx.x;
+    const bool active = l0 < nh;
+    const int l = active ? l0 : nh - 1;                         // a lane past the problem's last hypothesis repeats it and stores nothing
+    const bool is_h = orbx_init_is_h(D, l);
+    const int n = D.n;
+    const float *pl = A.pts + D.pts_off + 4 * (long long)n;     // planes 4 .. 7: the raw u1 v1 u2 v2
+    float M[9], Mi[9];
+    {
+        const OrbxInitHyp &H = A.hyp[D.hyp_off + l];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { M[k] = H.M[k]; Mi[k] = H.Minv[k]; }
+    }
+    const float inv_sigma2 = D.inv_sigma2;
+    unsigned long long *mw = A.masks + D.word_off + (long long)l * D.nwords;
+    float score = 0.0f;
+    unsigned long long word = 0;
+    for (int base = 0; base < n; base += ORBX_INIT_CHUNK) {
+        const int len = n - base < ORBX_INIT_CHUNK ? n - base : ORBX_INIT_CHUNK;
+        __syncthreads();                                       // the previous chunk has been read by every lane
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            for (int i = threadIdx.x; i < len; i += ORBX_INIT_SCORE_LANES) s_pts[p * ORBX_INIT_CHUNK + i] = pl[(long long)p * n + base + i];
+        __syncthreads();
+        for (int i = 0; i < len; ++i) {
+            const float u1 = s_pts[i], v1 = s_pts[ORBX_INIT_CHUNK + i], u2 = s_pts[2 * ORBX_INIT_CHUNK + i], v2 = s_pts[3 * ORBX_INIT_CHUNK + i];
+            const bool in = is_h ? orbx_init_check_h(M, Mi, u1, v1, u2, v2, inv_sigma2, score)
+                                 : orbx_init_check_f(M, u1, v1, u2, v2, inv_sigma2, score);
+            const int m = base + i;
+            if (in) word |= 1ull << (m & 63);
+            if ((m & 63) == 63 || m + 1 == n) {
+                if (active) mw[m >> 6] = word;
+                word = 0;
+            }
+        }
+    }
+    if (active) A.scores[D.hyp_off + l] = orbx_init_canonf(score);
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from the C ABI units)
 // ------------------------------------------------------------------------------------------------
@@ -5164,4 +5238,10 @@ void orbx_launch_pnp(hipStream_t s, const DPnpArgs &a) {
     hipLaunchKernelGGL(k_pnp_hypotheses, dim3((a.total_iters + ORBX_PNP_HYP_LANES - 1) / ORBX_PNP_HYP_LANES), dim3(ORBX_PNP_HYP_LANES),
                        0, s, a);
     hipLaunchKernelGGL(k_pnp_inliers, dim3(a.ngroups), dim3(64 * ORBX_PNP_WAVES), 0, s, a);
+}
+void orbx_launch_init(hipStream_t s, const DInitArgs &a) {
+    if (a.total_hyps <= 0 || a.ngroups <= 0) return;
+    hipLaunchKernelGGL(k_init_hypotheses, dim3((a.total_hyps + ORBX_INIT_HYP_LANES - 1) / ORBX_INIT_HYP_LANES),
+                       dim3(ORBX_INIT_HYP_LANES), 0, s, a);
+    hipLaunchKernelGGL(k_init_scores, dim3(a.ngroups), dim3(ORBX_INIT_SCORE_LANES), 0, s, a);
 }

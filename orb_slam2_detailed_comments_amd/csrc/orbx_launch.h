@@ -8,6 +8,7 @@
 #include "orbx_pose.h"
 #include "orbx_sim3.h"
 #include "orbx_pnp.h"
+#include "orbx_init.h"
 
 hipError_t orbx_upload_pattern();
 // the per-lane pattern tables orbx_upload_pattern uploads, 64 lanes x 16 coordinates each: c_pattern_lane and c_pattern_f32 (host only)
@@ -108,6 +109,8 @@ void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a);
 void orbx_launch_sim3(hipStream_t s, const DSim3Args &a);
 // PnPsolver RANSAC (orbx_pnp.h): k_pnp_hypotheses over all iterations, then k_pnp_inliers over the workgroup table
 void orbx_launch_pnp(hipStream_t s, const DPnpArgs &a);
+// Initializer H / F RANSAC (orbx_init.h): k_init_hypotheses over all hypotheses, then k_init_scores over the workgroup table
+void orbx_launch_init(hipStream_t s, const DInitArgs &a);
 void orbx_launch_hamming_matrix(hipStream_t s, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *dist);
 
 void orbx_launch_stereo_batch(hipStream_t s, const OrbxStereoGeom &sg, int npairs, int cap, const orbx_keypoint *kL,

@@ -1,6 +1,7 @@
-// orbx_map_batches.cpp -- the batched MapPoint refresh, Optimizer::PoseOptimization, the Sim3Solver RANSAC and the PnPsolver RANSAC
-// behind the C ABI: staging, launches and scatter.  Their HIP-free halves (validation, plans, packing, the host solvers, the
-// Sim3 and PnP cursors) are orbx_mappoint.cpp, orbx_pose.cpp, orbx_sim3.cpp and orbx_pnp.cpp.
+// orbx_map_batches.cpp -- the batched MapPoint refresh, Optimizer::PoseOptimization, the Sim3Solver RANSAC, the PnPsolver RANSAC
+// and the Initializer H / F RANSAC behind the C ABI: staging, launches and scatter.  Their HIP-free halves (validation, plans,
+// packing, the host solvers, the Sim3 and PnP cursors, the Initializer results) are orbx_mappoint.cpp, orbx_pose.cpp,
+// orbx_sim3.cpp, orbx_pnp.cpp and orbx_init.cpp.
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -362,3 +363,85 @@ extern "C" orbx_status orbx_pnp_batch_hypothesis(const orbx_pnp_batch *b, int k,
     return st == ORBX_OK ? st : orbx_fail(st, why);
 }
 extern "C" void orbx_pnp_batch_destroy(orbx_pnp_batch *b) { delete b; }
+
+// ---------------------------------------------------------------- Initializer H / F RANSAC, batched (orbx_init.h).
+// Device path: validation and layout (orbx_init.cpp), all problems packed into the page-locked block, ONE upload,
+// k_init_hypotheses and k_init_scores on the handle's stream, ONE download of hypotheses | masks | scores, the wait; the batch
+// keeps the results per problem and picks the best iteration of each model on the host.  Host path (ORBX_INIT=host, read per
+// call; host-only handles): the same header compiled by the host compiler over the same packed block.
+static bool init_host_selected() {
+    const char *e = getenv("ORBX_INIT");
+    return e && strcmp(e, "host") == 0;
+}
+extern "C" orbx_status orbx_init_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_init_problem *problems,
+                                                     orbx_init_batch **out) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    if (!out) return orbx_fail(ORBX_BAD_ARGUMENT, "null batch pointer");
+    OrbxInitPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_init_plan(nproblems, problems, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (plan.nlaunch == 0) {                                   // nothing to compute: every problem reports ORBX_INIT_NONE
+        *out = orbx_init_batch_new(problems, plan);
+        return ORBX_OK;
+    }
+    if (h->host_only || init_host_selected()) {
+        std::vector<uint8_t> in(plan.in_bytes), res(plan.out_bytes);
+        orbx_init_pack(problems, plan, in.data());
+        orbx_init_host_run(plan, in.data(), res.data());
+        orbx_init_batch *b = orbx_init_batch_new(problems, plan);
+        orbx_init_batch_take(b, plan, res.data());
+        *out = b;
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    const size_t dev_in = pad256(plan.in_bytes);
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + plan.out_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_init_pack(problems, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    uint8_t *d_out = d + dev_in;
+    DInitArgs a;
+    a.prob = (const DInitProb *)(d + plan.o_prob);
+    a.hyp_prob = (const int32_t *)(d + plan.o_hyp_prob);
+    a.sets = (const int32_t *)(d + plan.o_sets);
+    a.groups = (const int32_t *)(d + plan.o_groups);
+    a.pts = (const float *)(d + plan.o_pts);
+    a.total_hyps = plan.total_hyps; a.ngroups = plan.ngroups;
+    a.hyp = (OrbxInitHyp *)(d_out + plan.o_hyp);
+    a.masks = (unsigned long long *)(d_out + plan.o_masks);
+    a.scores = (float *)(d_out + plan.o_scores);
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_init(h->stream, a); }
+    st = stage_download_wait(h, pin, d_out, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    orbx_init_batch *b = orbx_init_batch_new(problems, plan);
+    orbx_init_batch_take(b, plan, pin);
+    *out = b;
+    return ORBX_OK;
+}
+extern "C" orbx_status orbx_init_batch_result(const orbx_init_batch *b, int k, float *SH, float *SF, float *H21, float *F21,
+                                              uint8_t *inliersH, uint8_t *inliersF, int32_t *itH, int32_t *itF, float *RH,
+                                              int32_t *model) {
+    const char *why = "";
+    const orbx_status st = orbx_init_get_result(b, k, SH, SF, H21, F21, inliersH, inliersF, itH, itF, RH, model, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" orbx_status orbx_init_batch_scores(const orbx_init_batch *b, int k, int model, float *scores, int32_t *niterations) {
+    const char *why = "";
+    const orbx_status st = orbx_init_get_scores(b, k, model, scores, niterations, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" orbx_status orbx_init_batch_hypothesis(const orbx_init_batch *b, int k, int model, int iteration, float *M9, float *Minv9,
+                                                  float *score, uint64_t *mask_words) {
+    const char *why = "";
+    const orbx_status st = orbx_init_get_hypothesis(b, k, model, iteration, M9, Minv9, score, mask_words, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" orbx_status orbx_init_batch_normalization(const orbx_init_batch *b, int k, float *T1, float *T2) {
+    const char *why = "";
+    const orbx_status st = orbx_init_get_normalization(b, k, T1, T2, &why);
+    return st == ORBX_OK ? st : orbx_fail(st, why);
+}
+extern "C" void orbx_init_batch_destroy(orbx_init_batch *b) { delete b; }
