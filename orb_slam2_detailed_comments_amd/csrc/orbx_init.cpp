@@ -7,25 +7,20 @@
 #include <algorithm>
 #include "orbx_init.h"
 
-static inline size_t init_pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline int init_nmodels(int32_t models) { return (models & 1) + ((models >> 1) & 1); }
 static inline bool init_launches(const orbx_init_problem &P) { return P.n >= 8 && P.models != 0; }
-
-static bool init_set_ok(const int32_t *s, int32_t n) {
-    for (int c = 0; c < 8; ++c) {
-        if (s[c] < 0 || s[c] >= n) return false;
-        for (int e = 0; e < c; ++e)
-            if (s[e] == s[c]) return false;
-    }
-    return true;
+static inline OrbxRansacWalk init_walk(int32_t *hyp_prob = nullptr, int32_t *groups = nullptr) {
+    return OrbxRansacWalk(0x0fffffff, 0x3fffffff, hyp_prob, groups);
+}
+static inline OrbxRansacWalk::At init_add(OrbxRansacWalk &w, int32_t n, int32_t iterations, int32_t models) {
+    return w.add(n, (size_t)iterations * init_nmodels(models), (size_t)iterations * 8, ORBX_INIT_PLANES, ORBX_INIT_SCORE_LANES);
 }
 
 orbx_status orbx_init_plan(int nproblems, const orbx_init_problem *problems, OrbxInitPlan &plan, const char **why) {
     plan = OrbxInitPlan();
     if (nproblems < 0) { *why = "nproblems < 0"; return ORBX_BAD_ARGUMENT; }
     if (nproblems > 0 && !problems) { *why = "null problem array"; return ORBX_BAD_ARGUMENT; }
-    size_t hyps = 0, sets = 0, pts = 0, words = 0, groups = 0;
-    int nlaunch = 0;
+    OrbxRansacWalk w = init_walk();
     for (int k = 0; k < nproblems; ++k) {
         const orbx_init_problem &P = problems[k];
         if (P.n1 < 0 || P.n2 < 0 || P.n < 0) { *why = "a negative count"; return ORBX_BAD_ARGUMENT; }
@@ -41,36 +36,10 @@ orbx_status orbx_init_plan(int nproblems, const orbx_init_problem *problems, Orb
         if (!init_launches(P)) continue;
         if (!P.sets) { *why = "null sets"; return ORBX_BAD_ARGUMENT; }
         for (int i = 0; i < P.iterations; ++i)
-            if (!init_set_ok(P.sets + 8 * (size_t)i, P.n)) { *why = "set index outside [0, n) or repeated within its set"; return ORBX_BAD_ARGUMENT; }
-        const size_t nh = (size_t)P.iterations * init_nmodels(P.models);
-        ++nlaunch;
-        hyps += nh;
-        sets += (size_t)P.iterations * 8;
-        pts += (size_t)P.n * ORBX_INIT_PLANES;
-        words += nh * (size_t)((P.n + 63) / 64);
-        groups += (nh + ORBX_INIT_SCORE_LANES - 1) / ORBX_INIT_SCORE_LANES;
-        if (hyps > (size_t)0x0fffffff || sets > (size_t)0x3fffffff || pts > (size_t)0x3fffffff || words > (size_t)0x3fffffff) {
-            *why = "too many iterations or matches for 32-bit offsets";
-            return ORBX_UNSUPPORTED;
-        }
+            if (!orbx_set_ok<8>(P.sets + 8 * (size_t)i, P.n, true)) { *why = "set index outside [0, n) or repeated within its set"; return ORBX_BAD_ARGUMENT; }
+        if (!init_add(w, P.n, P.iterations, P.models).ok) { *why = "too many iterations or matches for 32-bit offsets"; return ORBX_UNSUPPORTED; }
     }
-    plan.nproblems = nproblems;
-    plan.nlaunch = nlaunch;
-    plan.total_hyps = (int)hyps;
-    plan.ngroups = (int)groups;
-    plan.total_sets = sets;
-    plan.total_pts = pts;
-    plan.total_words = words;
-    plan.o_prob = 0;
-    plan.o_hyp_prob = init_pad256((size_t)nlaunch * sizeof(DInitProb));
-    plan.o_sets = plan.o_hyp_prob + init_pad256(hyps * sizeof(int32_t));
-    plan.o_groups = plan.o_sets + init_pad256(sets * sizeof(int32_t));
-    plan.o_pts = plan.o_groups + init_pad256(groups * 2 * sizeof(int32_t));
-    plan.in_bytes = plan.o_pts + init_pad256(pts * sizeof(float));
-    plan.o_hyp = 0;
-    plan.o_masks = init_pad256(hyps * sizeof(OrbxInitHyp));
-    plan.o_scores = plan.o_masks + init_pad256(words * sizeof(uint64_t));
-    plan.out_bytes = plan.o_scores + init_pad256(hyps * sizeof(float));
+    plan = w.plan(nproblems, sizeof(DInitProb), sizeof(OrbxInitHyp));
     return ORBX_OK;
 }
 
@@ -95,41 +64,36 @@ static void init_normalize(const float *keys, int32_t N, float *T, float *mean_s
     for (int i = 0; i < 9; ++i) T[i] = i % 4 == 0 ? 1.0f : 0.0f;
     T[0] = sX;
     T[4] = sY;
-    T[2] = orbx_init_canonf(-meanX * sX);
-    T[5] = orbx_init_canonf(-meanY * sY);
-    T[0] = orbx_init_canonf(T[0]);
-    T[4] = orbx_init_canonf(T[4]);
+    T[2] = orbx_canonf(-meanX * sX);
+    T[5] = orbx_canonf(-meanY * sY);
+    T[0] = orbx_canonf(T[0]);
+    T[4] = orbx_canonf(T[4]);
     mean_scale[0] = meanX; mean_scale[1] = meanY; mean_scale[2] = sX; mean_scale[3] = sY;
 }
 
 void orbx_init_pack(const orbx_init_problem *problems, const OrbxInitPlan &plan, uint8_t *dst) {
     if (plan.nlaunch <= 0) return;
     DInitProb *dp = (DInitProb *)(dst + plan.o_prob);
-    int32_t *hyp_prob = (int32_t *)(dst + plan.o_hyp_prob);
     int32_t *sets = (int32_t *)(dst + plan.o_sets);
-    int32_t *groups = (int32_t *)(dst + plan.o_groups);
     float *pts = (float *)(dst + plan.o_pts);
-    int j = 0, g = 0;
-    size_t ho = 0, so = 0, po = 0, wo = 0;
+    OrbxRansacWalk w = init_walk((int32_t *)(dst + plan.o_hyp_prob), (int32_t *)(dst + plan.o_groups));
     for (int k = 0; k < plan.nproblems; ++k) {
         const orbx_init_problem &P = problems[k];
         if (!init_launches(P)) continue;
-        DInitProb &D = dp[j];
-        const int nh = P.iterations * init_nmodels(P.models);
-        D.n = P.n; D.iterations = P.iterations; D.nwords = (P.n + 63) / 64; D.models = P.models;
-        D.hyp_off = (int32_t)ho; D.pts_off = (int32_t)po; D.word_off = (int32_t)wo; D.set_off = (int32_t)so;
+        const OrbxRansacWalk::At at = init_add(w, P.n, P.iterations, P.models);
+        DInitProb &D = dp[at.j];
+        D.n = P.n; D.iterations = P.iterations; D.nwords = at.nwords; D.models = P.models;
+        D.hyp_off = at.hyp_off; D.pts_off = at.pts_off; D.word_off = at.word_off; D.set_off = at.set_off;
         float T2[9], ms1[4], ms2[4];
         init_normalize(P.keys1, P.n1, D.T1, ms1);
         init_normalize(P.keys2, P.n2, T2, ms2);
         orbx_init_inv3(T2, D.T2inv);
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) D.T2t[3 * r + c] = T2[3 * c + r];
-        for (int i = 0; i < 9; ++i) D.T2inv[i] = orbx_init_canonf(D.T2inv[i]);
+        for (int i = 0; i < 9; ++i) D.T2inv[i] = orbx_canonf(D.T2inv[i]);
         D.inv_sigma2 = orbx_init_inv_sigma2(P.sigma);
-        for (int i = 0; i < nh; ++i) hyp_prob[ho + i] = j;
-        memcpy(sets + so, P.sets, (size_t)P.iterations * 8 * sizeof(int32_t));
-        for (int i = 0; i < nh; i += ORBX_INIT_SCORE_LANES) { groups[2 * g] = j; groups[2 * g + 1] = i; ++g; }
-        float *pl = pts + po;
+        memcpy(sets + at.set_off, P.sets, (size_t)P.iterations * 8 * sizeof(int32_t));
+        float *pl = pts + at.pts_off;
         const size_t n = (size_t)P.n;
         for (size_t i = 0; i < n; ++i) {
             const float *a = P.keys1 + 2 * (size_t)P.matches[2 * i], *b = P.keys2 + 2 * (size_t)P.matches[2 * i + 1];
@@ -139,8 +103,6 @@ void orbx_init_pack(const orbx_init_problem *problems, const OrbxInitPlan &plan,
             pl[3 * n + i] = (b[1] - ms2[1]) * ms2[3];
             pl[4 * n + i] = a[0]; pl[5 * n + i] = a[1]; pl[6 * n + i] = b[0]; pl[7 * n + i] = b[1];
         }
-        ho += (size_t)nh; so += (size_t)P.iterations * 8; po += n * ORBX_INIT_PLANES; wo += (size_t)nh * (size_t)D.nwords;
-        ++j;
     }
 }
 
@@ -150,7 +112,7 @@ void orbx_init_host_run(const OrbxInitPlan &plan, const uint8_t *in, uint8_t *ou
     const float *pts = (const float *)(in + plan.o_pts);
     OrbxInitHyp *hyp = (OrbxInitHyp *)(out + plan.o_hyp);
     uint64_t *masks = (uint64_t *)(out + plan.o_masks);
-    float *scores = (float *)(out + plan.o_scores);
+    float *scores = (float *)(out + plan.o_tally);
     float ws[ORBX_INIT_WS_FLOATS];
     const OrbxInitWs W = {ws, 1};
     for (int j = 0; j < plan.nlaunch; ++j) {
@@ -175,7 +137,7 @@ void orbx_init_host_run(const OrbxInitPlan &plan, const uint8_t *in, uint8_t *ou
                 if (in) word |= (uint64_t)1 << (m & 63);
                 if ((m & 63) == 63 || m + 1 == n) { mw[m >> 6] = word; word = 0; }
             }
-            scores[(size_t)D.hyp_off + l] = orbx_init_canonf(score);
+            scores[(size_t)D.hyp_off + l] = orbx_canonf(score);
         }
     }
 }
@@ -191,7 +153,7 @@ orbx_init_batch *orbx_init_batch_new(const orbx_init_problem *problems, const Or
         float ms[4];
         init_normalize(P.keys1, P.n1, S.T1, ms);
         init_normalize(P.keys2, P.n2, S.T2, ms);
-        S.RH = orbx_init_canonf(S.SH / (S.SH + S.SF));          // 0 / 0 until results arrive
+        S.RH = orbx_canonf(S.SH / (S.SH + S.SF));          // 0 / 0 until results arrive
     }
     return b;
 }
@@ -209,29 +171,24 @@ static int32_t init_best(const float *s, int n, float *best) {
 void orbx_init_batch_take(orbx_init_batch *b, const OrbxInitPlan &plan, const uint8_t *out) {
     const OrbxInitHyp *hyp = (const OrbxInitHyp *)(out + plan.o_hyp);
     const uint64_t *masks = (const uint64_t *)(out + plan.o_masks);
-    const float *scores = (const float *)(out + plan.o_scores);
-    size_t ho = 0, wo = 0;
+    const float *scores = (const float *)(out + plan.o_tally);
+    OrbxRansacWalk w = init_walk();
     for (OrbxInitResult &S : b->st) {
         if (!S.launches) continue;
+        const OrbxRansacWalk::At at = init_add(w, S.n, S.iterations, S.models);
         const size_t nh = (size_t)S.iterations * init_nmodels(S.models), nw = nh * (size_t)S.nwords;
-        S.hyp.assign(hyp + ho, hyp + ho + nh);
-        S.scores.assign(scores + ho, scores + ho + nh);
-        S.masks.assign(masks + wo, masks + wo + nw);
-        ho += nh; wo += nw;
+        S.hyp.assign(hyp + at.hyp_off, hyp + at.hyp_off + nh);
+        S.scores.assign(scores + at.hyp_off, scores + at.hyp_off + nh);
+        S.masks.assign(masks + at.word_off, masks + at.word_off + nw);
         const int fo = (S.models & ORBX_INIT_H) ? S.iterations : 0;
         if (S.models & ORBX_INIT_H) S.itH = init_best(S.scores.data(), S.iterations, &S.SH);
         if (S.models & ORBX_INIT_F) S.itF = init_best(S.scores.data() + fo, S.iterations, &S.SF);
-        S.RH = orbx_init_canonf(S.SH / (S.SH + S.SF));          // float RH = SH / (SH + SF)
+        S.RH = orbx_canonf(S.SH / (S.SH + S.SF));          // float RH = SH / (SH + SF)
         if (S.itH < 0 && S.itF < 0) S.model = ORBX_INIT_NONE;
         else S.model = ((double)S.RH > 0.40) ? ORBX_INIT_H : ORBX_INIT_F;   // the float promoted against the double constant
     }
 }
 
-static const OrbxInitResult *init_state(const orbx_init_batch *b, int k, const char **why) {
-    if (!b) { *why = "no batch"; return nullptr; }
-    if (k < 0 || (size_t)k >= b->st.size()) { *why = "problem outside the batch"; return nullptr; }
-    return &b->st[k];
-}
 // first hypothesis of `model` in the problem's stored results, or -1 when the model has none
 static int init_model_off(const OrbxInitResult &S, int model) {
     if (!S.launches || !(S.models & model)) return -1;
@@ -240,13 +197,12 @@ static int init_model_off(const OrbxInitResult &S, int model) {
 static void init_unpack(const OrbxInitResult &S, int off, int it, uint8_t *inliers) {
     if (!inliers) return;
     if (it < 0) { if (S.n > 0) memset(inliers, 0, (size_t)S.n); return; }
-    const uint64_t *mw = S.masks.data() + (size_t)(off + it) * S.nwords;
-    for (int p = 0; p < S.n; ++p) inliers[p] = (uint8_t)((mw[p >> 6] >> (p & 63)) & 1u);
+    orbx_unpack_mask(S.masks.data() + (size_t)(off + it) * S.nwords, S.n, inliers);
 }
 
 orbx_status orbx_init_get_result(const orbx_init_batch *b, int k, float *SH, float *SF, float *H21, float *F21, uint8_t *inliersH,
                                  uint8_t *inliersF, int32_t *itH, int32_t *itF, float *RH, int32_t *model, const char **why) {
-    const OrbxInitResult *S = init_state(b, k, why);
+    const OrbxInitResult *S = orbx_batch_state(b, k, why);
     if (!S) return ORBX_BAD_ARGUMENT;
     const int oh = init_model_off(*S, ORBX_INIT_H), of = init_model_off(*S, ORBX_INIT_F);
     if (SH) *SH = S->SH;
@@ -269,7 +225,7 @@ static bool init_model_ok(int model, const char **why) {
 }
 
 orbx_status orbx_init_get_scores(const orbx_init_batch *b, int k, int model, float *scores, int32_t *niterations, const char **why) {
-    const OrbxInitResult *S = init_state(b, k, why);
+    const OrbxInitResult *S = orbx_batch_state(b, k, why);
     if (!S || !init_model_ok(model, why)) return ORBX_BAD_ARGUMENT;
     const int off = init_model_off(*S, model);
     if (scores && off >= 0) memcpy(scores, S->scores.data() + off, (size_t)S->iterations * sizeof(float));
@@ -279,7 +235,7 @@ orbx_status orbx_init_get_scores(const orbx_init_batch *b, int k, int model, flo
 
 orbx_status orbx_init_get_hypothesis(const orbx_init_batch *b, int k, int model, int iteration, float *M9, float *Minv9, float *score,
                                      uint64_t *mask_words, const char **why) {
-    const OrbxInitResult *S = init_state(b, k, why);
+    const OrbxInitResult *S = orbx_batch_state(b, k, why);
     if (!S || !init_model_ok(model, why)) return ORBX_BAD_ARGUMENT;
     const int off = init_model_off(*S, model);
     if (off < 0 || iteration < 0 || iteration >= S->iterations) { *why = "iteration outside the problem's stored results"; return ORBX_BAD_ARGUMENT; }
@@ -293,7 +249,7 @@ orbx_status orbx_init_get_hypothesis(const orbx_init_batch *b, int k, int model,
 }
 
 orbx_status orbx_init_get_normalization(const orbx_init_batch *b, int k, float *T1, float *T2, const char **why) {
-    const OrbxInitResult *S = init_state(b, k, why);
+    const OrbxInitResult *S = orbx_batch_state(b, k, why);
     if (!S) return ORBX_BAD_ARGUMENT;
     if (T1) memcpy(T1, S->T1, sizeof(S->T1));
     if (T2) memcpy(T2, S->T2, sizeof(S->T2));

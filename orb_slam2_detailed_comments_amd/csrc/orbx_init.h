@@ -23,6 +23,7 @@
 #pragma once
 #include <vector>
 #include "orbx_pose.h"
+#include "orbx_ransac.h"
 
 struct OrbxInitHyp {         // one hypothesis as k_init_hypotheses stores it and k_init_scores reads it
     float M[9];              // H21i or F21i, row major
@@ -51,13 +52,6 @@ struct OrbxInitWs {
     ORBX_HD float &operator()(int e) const { return p[(long long)e * stride]; }
 };
 
-ORBX_HD static inline float orbx_init_canonf(float x) {
-    uint32_t b;
-    __builtin_memcpy(&b, &x, 4);
-    if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;
-    __builtin_memcpy(&x, &b, 4);
-    return x;
-}
 ORBX_HD static inline bool orbx_init_finite(float x) {
     uint32_t b;
     __builtin_memcpy(&b, &x, 4);
@@ -197,13 +191,13 @@ ORBX_UNROLL
         float Mi[9];
         orbx_init_inv3(M, Mi);
 ORBX_UNROLL
-        for (int i = 0; i < 9; ++i) { bad = bad || !orbx_init_finite(Mi[i]); out.Minv[i] = orbx_init_canonf(Mi[i]); }
+        for (int i = 0; i < 9; ++i) { bad = bad || !orbx_init_finite(Mi[i]); out.Minv[i] = orbx_canonf(Mi[i]); }
     } else {
 ORBX_UNROLL
         for (int i = 0; i < 9; ++i) out.Minv[i] = 0.0f;
     }
 ORBX_UNROLL
-    for (int i = 0; i < 9; ++i) { bad = bad || !orbx_init_finite(M[i]); out.M[i] = orbx_init_canonf(M[i]); }
+    for (int i = 0; i < 9; ++i) { bad = bad || !orbx_init_finite(M[i]); out.M[i] = orbx_canonf(M[i]); }
     out.bad = bad ? 1 : 0;
     out.pad = 0;
 }
@@ -273,24 +267,10 @@ ORBX_HD static inline int orbx_init_nhyp(const DInitProb &D) { return D.iteratio
 // hypothesis l of a problem: which model, which iteration
 ORBX_HD static inline bool orbx_init_is_h(const DInitProb &D, int l) { return (D.models & 1) && l < D.iterations; }
 ORBX_HD static inline int orbx_init_iteration(const DInitProb &D, int l) { return l < D.iterations ? l : l - D.iterations; }
-struct DInitArgs {
-    const DInitProb *prob;
-    const int32_t *hyp_prob;        // [total_hyps] the problem of a hypothesis
-    const int32_t *sets;
-    const int32_t *groups;          // [ngroups][2]: problem, first hypothesis (within the problem) of a workgroup of k_init_scores
-    const float *pts;
-    int total_hyps, ngroups;
-    OrbxInitHyp *hyp;
-    float *scores;
-    unsigned long long *masks;
-};
-// Uploaded block (one copy): DInitProb[nlaunch] | hyp_prob | sets | groups | pts.  Downloaded block: hyp | masks | scores.
-struct OrbxInitPlan {
-    int nproblems = 0, nlaunch = 0, total_hyps = 0, ngroups = 0;
-    size_t total_sets = 0, total_pts = 0, total_words = 0;
-    size_t o_prob = 0, o_hyp_prob = 0, o_sets = 0, o_groups = 0, o_pts = 0, in_bytes = 0;
-    size_t o_hyp = 0, o_masks = 0, o_scores = 0, out_bytes = 0;
-};
+// sets: [iterations][8] per problem, shared by its H and F hypotheses; a group: ORBX_INIT_SCORE_LANES hypotheses of
+// k_init_scores; tally: the scores
+using DInitArgs = DRansacArgs<DInitProb, OrbxInitHyp, float>;
+using OrbxInitPlan = OrbxRansacPlan;
 orbx_status orbx_init_plan(int nproblems, const orbx_init_problem *problems, OrbxInitPlan &plan, const char **why);
 void orbx_init_pack(const orbx_init_problem *problems, const OrbxInitPlan &plan, uint8_t *dst);
 // the host path: reads the packed block, writes the downloaded block's layout (hyp | masks | scores) into out

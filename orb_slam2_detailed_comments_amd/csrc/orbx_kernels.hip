@@ -4566,14 +4566,44 @@ __global__ __launch_bounds__(64) void k_pose_opt(const DPoseArgs A) {
 }
 
 #include "orbx_sim3.h"
+// CheckInliers of the batched RANSACs (k_sim3_inliers, k_pnp_inliers): one workgroup = WAVES consecutive hypotheses of ONE
+// problem, one wave each.  The problem's points are staged in LDS once per workgroup, CHUNK at a time as PLANES planes (lane i
+// reads word i of a plane: no bank conflict); lanes stride over the points, test(v) judges one point from its PLANES staged
+// floats, a 64-point word of the mask is one ballot, the count is the sum of the popcounts.  Every barrier is taken by all
+// waves (a wave that is not `active`, past the problem's last hypothesis, only stages).
+template <int PLANES, int CHUNK, int WAVES, class Test>
+__device__ __forceinline__ int ransac_inliers(float *s_pts, const float *pl, int n, bool active, unsigned long long *mw, Test test) {
+    const int lane = threadIdx.x & 63;
+    int cnt = 0;
+    for (int base = 0; base < n; base += CHUNK) {
+        const int len = n - base < CHUNK ? n - base : CHUNK;
+        __syncthreads();                                       // the previous chunk has been read by every wave
+#pragma unroll
+        for (int p = 0; p < PLANES; ++p)
+            for (int i = threadIdx.x; i < len; i += 64 * WAVES) s_pts[p * CHUNK + i] = pl[(long long)p * n + base + i];
+        __syncthreads();
+        if (!active) continue;
+        for (int sub = 0; sub < len; sub += 64) {
+            const int i = sub + lane;                          // < CHUNK; entries at or past len are masked below
+            float v[PLANES];
+#pragma unroll
+            for (int p = 0; p < PLANES; ++p) v[p] = s_pts[p * CHUNK + i];
+            const bool in = i < len && test(v);
+            const unsigned long long word = orbx_ballot(in);
+            if (lane == 0) mw[(base + sub) >> 6] = word;
+            cnt += __popcll(word);
+        }
+    }
+    return cnt;
+}
 // Sim3Solver RANSAC, batched (orbx_sim3.h).  k_sim3_hypotheses: one lane per (problem, iteration) gathers the three drawn
 // correspondences and runs ComputeSim3 in registers (the Jacobi sweeps and every 3x3 product are unrolled: no per-thread array
 // is indexed at run time), then stores the hypothesis.  The lanes of a wave share no data and take no barrier, so the sweep
 // count may differ between them.
 __global__ __launch_bounds__(64) void k_sim3_hypotheses(const DSim3Args A) {
     const int h = blockIdx.x * 64 + threadIdx.x;
-    if (h >= A.total_iters) return;
-    const DSim3Prob &D = A.prob[A.iter_prob[h]];
+    if (h >= A.total_hyps) return;
+    const DSim3Prob &D = A.prob[A.hyp_prob[h]];
     const float *pl = A.pts + D.pts_off;
     const long long n = D.n;
     float P1[9], P2[9];
@@ -4592,11 +4622,7 @@ __global__ __launch_bounds__(64) void k_sim3_hypotheses(const DSim3Args A) {
     for (int k = 0; k < 9; ++k) o[32 + k] = H.R[k];
     o[41] = H.t[0]; o[42] = H.t[1]; o[43] = H.t[2]; o[44] = H.s; o[45] = 0.f; o[46] = 0.f; o[47] = 0.f;
 }
-// k_sim3_inliers: CheckInliers.  One workgroup = ORBX_SIM3_WAVES consecutive iterations of ONE problem, one wave each.  The
-// problem's correspondences are staged in LDS once per workgroup, ORBX_SIM3_CHUNK at a time as ORBX_SIM3_PLANES planes (lane i
-// reads word i of a plane: no bank conflict); lanes stride over the points, a 64-point word of the mask is one ballot, the
-// count is the sum of the popcounts.  Every barrier is taken by all four waves (a wave past the problem's last iteration only
-// stages).
+// k_sim3_inliers: CheckInliers (ransac_inliers) with the wave's T12, T21 and both cameras in registers.
 __global__ __launch_bounds__(64 * ORBX_SIM3_WAVES) void k_sim3_inliers(const DSim3Args A) {
     __shared__ float s_pts[ORBX_SIM3_PLANES * ORBX_SIM3_CHUNK];
     const int g = blockIdx.x;
@@ -4616,27 +4642,9 @@ __global__ __launch_bounds__(64 * ORBX_SIM3_WAVES) void k_sim3_inliers(const DSi
         for (int k = 0; k < 4; ++k) { K1[k] = D.K1[k]; K2[k] = D.K2[k]; }
     }
     unsigned long long *mw = A.masks + D.word_off + (long long)(active ? it : 0) * D.nwords;
-    int cnt = 0;
-    for (int base = 0; base < n; base += ORBX_SIM3_CHUNK) {
-        const int len = n - base < ORBX_SIM3_CHUNK ? n - base : ORBX_SIM3_CHUNK;
-        __syncthreads();                                       // the previous chunk has been read by every wave
-#pragma unroll
-        for (int p = 0; p < ORBX_SIM3_PLANES; ++p)
-            for (int i = threadIdx.x; i < len; i += 64 * ORBX_SIM3_WAVES) s_pts[p * ORBX_SIM3_CHUNK + i] = pl[(long long)p * n + base + i];
-        __syncthreads();
-        if (!active) continue;
-        for (int sub = 0; sub < len; sub += 64) {
-            const int i = sub + lane;                          // < ORBX_SIM3_CHUNK; entries at or past len are masked below
-            float v[ORBX_SIM3_PLANES];
-#pragma unroll
-            for (int p = 0; p < ORBX_SIM3_PLANES; ++p) v[p] = s_pts[p * ORBX_SIM3_CHUNK + i];
-            const bool in = i < len && orbx_sim3_inlier(T12, T21, K1, K2, v, v + 3, v + 8, v + 10, v[6], v[7]);
-            const unsigned long long word = orbx_ballot(in);
-            if (lane == 0) mw[(base + sub) >> 6] = word;
-            cnt += __popcll(word);
-        }
-    }
-    if (active && lane == 0) A.counts[D.iter_off + it] = cnt;
+    const int cnt = ransac_inliers<ORBX_SIM3_PLANES, ORBX_SIM3_CHUNK, ORBX_SIM3_WAVES>(s_pts, pl, n, active, mw, [&](const float *v) {
+        return orbx_sim3_inlier(T12, T21, K1, K2, v, v + 3, v + 8, v + 10, v[6], v[7]); });
+    if (active && lane == 0) A.tally[D.iter_off + it] = cnt;
 }
 
 #include "orbx_pnp.h"
@@ -4649,8 +4657,8 @@ __global__ __launch_bounds__(64 * ORBX_SIM3_WAVES) void k_sim3_inliers(const DSi
 __global__ __launch_bounds__(ORBX_PNP_HYP_LANES) void k_pnp_hypotheses(const DPnpArgs A) {
     __shared__ double s_ws[ORBX_PNP_WS_DOUBLES(4) * ORBX_PNP_HYP_LANES];
     const int h = blockIdx.x * ORBX_PNP_HYP_LANES + threadIdx.x;
-    if (h >= A.total_iters) return;
-    const DPnpProb &D = A.prob[A.iter_prob[h]];
+    if (h >= A.total_hyps) return;
+    const DPnpProb &D = A.prob[A.hyp_prob[h]];
     const float *pl = A.pts + D.pts_off;
     const long long n = D.n;
     const OrbxPnpWs W = {s_ws + threadIdx.x, ORBX_PNP_HYP_LANES};
@@ -4665,10 +4673,7 @@ __global__ __launch_bounds__(ORBX_PNP_HYP_LANES) void k_pnp_hypotheses(const DPn
     const int N = orbx_pnp_compute_pose(W, 4, cam, H.R);       // R (9) | t (3) are contiguous in the record
     orbx_pnp_store(H.R, N, H);
 }
-// k_pnp_inliers: CheckInliers.  One workgroup = ORBX_PNP_WAVES consecutive iterations of ONE problem, one wave each.  The
-// problem's correspondences are staged in LDS once per workgroup, ORBX_PNP_CHUNK at a time as ORBX_PNP_PLANES planes; lanes
-// stride over the points, a 64-point word of the mask is one ballot, the count is the sum of the popcounts.  Every barrier is
-// taken by all four waves (a wave past the problem's last iteration only stages).
+// k_pnp_inliers: CheckInliers (ransac_inliers) with the wave's R, t and the camera in registers, as doubles.
 __global__ __launch_bounds__(64 * ORBX_PNP_WAVES) void k_pnp_inliers(const DPnpArgs A) {
     __shared__ float s_pts[ORBX_PNP_PLANES * ORBX_PNP_CHUNK];
     const int g = blockIdx.x;
@@ -4690,27 +4695,9 @@ __global__ __launch_bounds__(64 * ORBX_PNP_WAVES) void k_pnp_inliers(const DPnpA
         for (int k = 0; k < 4; ++k) cam[k] = D.cam[k];
     }
     unsigned long long *mw = A.masks + D.word_off + (long long)(active ? it : 0) * D.nwords;
-    int cnt = 0;
-    for (int base = 0; base < n; base += ORBX_PNP_CHUNK) {
-        const int len = n - base < ORBX_PNP_CHUNK ? n - base : ORBX_PNP_CHUNK;
-        __syncthreads();                                       // the previous chunk has been read by every wave
-#pragma unroll
-        for (int p = 0; p < ORBX_PNP_PLANES; ++p)
-            for (int i = threadIdx.x; i < len; i += 64 * ORBX_PNP_WAVES) s_pts[p * ORBX_PNP_CHUNK + i] = pl[(long long)p * n + base + i];
-        __syncthreads();
-        if (!active) continue;
-        for (int sub = 0; sub < len; sub += 64) {
-            const int i = sub + lane;                          // < ORBX_PNP_CHUNK; entries at or past len are masked below
-            float v[ORBX_PNP_PLANES];
-#pragma unroll
-            for (int p = 0; p < ORBX_PNP_PLANES; ++p) v[p] = s_pts[p * ORBX_PNP_CHUNK + i];
-            const bool in = i < len && orbx_pnp_inlier(R, t, cam, v[0], v[1], v[2], v[3], v[4], v[5]);
-            const unsigned long long word = orbx_ballot(in);
-            if (lane == 0) mw[(base + sub) >> 6] = word;
-            cnt += __popcll(word);
-        }
-    }
-    if (active && lane == 0) A.counts[D.iter_off + it] = cnt;
+    const int cnt = ransac_inliers<ORBX_PNP_PLANES, ORBX_PNP_CHUNK, ORBX_PNP_WAVES>(s_pts, pl, n, active, mw, [&](const float *v) {
+        return orbx_pnp_inlier(R, t, cam, v[0], v[1], v[2], v[3], v[4], v[5]); });
+    if (active && lane == 0) A.tally[D.iter_off + it] = cnt;
 }
 
 #include "orbx_init.h"
@@ -4742,7 +4729,8 @@ __global__ __launch_bounds__(ORBX_INIT_HYP_LANES) void k_init_hypotheses(const D
 // ONE problem, one LANE each: the lane keeps its matrix in registers and walks the matches in order, so the score is the
 // source's sequential float sum by construction and every lane works through the whole fold.  The un-normalised matches are
 // staged in LDS ORBX_INIT_CHUNK at a time and read back as broadcasts (every lane reads the same address).  A lane collects 64
-// inlier bits in a register and stores the word when it is full and after the last match.
+// inlier bits in a register and stores the word when it is full and after the last match.  Not ransac_inliers: one lane (not
+// one wave) per hypothesis, a sequential sum, broadcast reads.
 __global__ __launch_bounds__(ORBX_INIT_SCORE_LANES) void k_init_scores(const DInitArgs A) {
     __shared__ float s_pts[4 * ORBX_INIT_CHUNK];
     const int g = blockIdx.x;
@@ -4784,7 +4772,7 @@ __global__ __launch_bounds__(ORBX_INIT_SCORE_LANES) void k_init_scores(const DIn
             }
         }
     }
-    if (active) A.scores[D.hyp_off + l] = orbx_init_canonf(score);
+    if (active) A.tally[D.hyp_off + l] = orbx_canonf(score);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -5229,13 +5217,13 @@ void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a) {
     hipLaunchKernelGGL(k_pose_opt, dim3(a.nproblems), dim3(64), 0, s, a);
 }
 void orbx_launch_sim3(hipStream_t s, const DSim3Args &a) {
-    if (a.total_iters <= 0 || a.ngroups <= 0) return;
-    hipLaunchKernelGGL(k_sim3_hypotheses, dim3((a.total_iters + 63) / 64), dim3(64), 0, s, a);
+    if (a.total_hyps <= 0 || a.ngroups <= 0) return;
+    hipLaunchKernelGGL(k_sim3_hypotheses, dim3((a.total_hyps + 63) / 64), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_sim3_inliers, dim3(a.ngroups), dim3(64 * ORBX_SIM3_WAVES), 0, s, a);
 }
 void orbx_launch_pnp(hipStream_t s, const DPnpArgs &a) {
-    if (a.total_iters <= 0 || a.ngroups <= 0) return;
-    hipLaunchKernelGGL(k_pnp_hypotheses, dim3((a.total_iters + ORBX_PNP_HYP_LANES - 1) / ORBX_PNP_HYP_LANES), dim3(ORBX_PNP_HYP_LANES),
+    if (a.total_hyps <= 0 || a.ngroups <= 0) return;
+    hipLaunchKernelGGL(k_pnp_hypotheses, dim3((a.total_hyps + ORBX_PNP_HYP_LANES - 1) / ORBX_PNP_HYP_LANES), dim3(ORBX_PNP_HYP_LANES),
                        0, s, a);
     hipLaunchKernelGGL(k_pnp_inliers, dim3(a.ngroups), dim3(64 * ORBX_PNP_WAVES), 0, s, a);
 }

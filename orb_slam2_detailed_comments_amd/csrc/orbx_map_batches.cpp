@@ -1,7 +1,7 @@
 // orbx_map_batches.cpp -- the batched MapPoint refresh, Optimizer::PoseOptimization, the Sim3Solver RANSAC, the PnPsolver RANSAC
 // and the Initializer H / F RANSAC behind the C ABI: staging, launches and scatter.  Their HIP-free halves (validation, plans,
 // packing, the host solvers, the Sim3 and PnP cursors, the Initializer results) are orbx_mappoint.cpp, orbx_pose.cpp,
-// orbx_sim3.cpp, orbx_pnp.cpp and orbx_init.cpp.
+// orbx_sim3.cpp, orbx_pnp.cpp and orbx_init.cpp; the three RANSACs go through one sequence, ransac_batch_create.
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -83,8 +83,8 @@ extern "C" orbx_status orbx_update_normal_and_depth_batch(orbx_handle *h, int np
 // (ORBX_POSE=host, read per call; host-only handles, where the "d_" arguments are host arrays): the same header compiled by
 // the host compiler.  On a device handle it downloads the rows it needs, runs, and uploads the results -- a cross-check, not a
 // fast path.
-static bool pose_host_selected() {
-    const char *e = getenv("ORBX_POSE");
+static bool host_selected(const char *var) {                  // ORBX_POSE / ORBX_SIM3 / ORBX_PNP / ORBX_INIT = host, read per call
+    const char *e = getenv(var);
     return e && strcmp(e, "host") == 0;
 }
 static orbx_status pose_batch(orbx_handle *h, int nproblems, const orbx_pose_problem *problems, int npool, const float *world_pos,
@@ -108,7 +108,7 @@ static orbx_status pose_batch(orbx_handle *h, int nproblems, const orbx_pose_pro
         orbx_pose_host_run(nproblems, problems, c);
         return ORBX_OK;
     }
-    if (pose_host_selected()) {
+    if (host_selected("ORBX_POSE")) {
         HIPCHK(hipSetDevice(h->dev));
         const size_t fr = (size_t)nframes * cap, pr = (size_t)nproblems * cap;
         std::vector<orbx_keypoint> keys(fr);
@@ -197,61 +197,63 @@ extern "C" orbx_status orbx_pose_optimization(orbx_handle *h, float *Tcw, int n,
     return ORBX_OK;
 }
 
-// ---------------------------------------------------------------- Sim3Solver RANSAC, batched (orbx_sim3.h).
-// Device path: validation and layout (orbx_sim3.cpp), all problems packed into the page-locked block, ONE upload,
-// k_sim3_hypotheses and k_sim3_inliers on the handle's stream, ONE download of hypotheses | masks | counts, the wait; the batch
-// keeps a host copy and iterate() is a cursor over it.  Host path (ORBX_SIM3=host, read per call; host-only handles): the same
-// header compiled by the host compiler over the same packed block.
-static bool sim3_host_selected() {
-    const char *e = getenv("ORBX_SIM3");
-    return e && strcmp(e, "host") == 0;
-}
-extern "C" orbx_status orbx_sim3_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_sim3_problem *problems,
-                                                     orbx_sim3_batch **out) {
+// ---------------------------------------------------------------- the batched RANSACs (orbx_ransac.h): one sequence for all.
+// Device path: validation and layout (S::plan), all problems packed into the page-locked block, ONE upload, the solver's two
+// kernels on the handle's stream (S::launch), ONE download of hypotheses | masks | tally, the wait; the batch keeps a host copy
+// (S::batch_take) and every later call reads that.  Host path (S::env = host, read per call; host-only handles): the same
+// header compiled by the host compiler over the same packed block (S::host_run).  S::keeps_block: the batch keeps the result
+// block as it is (batch->out, allocated by S::batch_new), so the host path runs straight into it.
+template <class S>
+static orbx_status ransac_batch_create(orbx_handle *h, int nproblems, const typename S::problem *problems, typename S::batch **out) {
     if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
     if (!out) return orbx_fail(ORBX_BAD_ARGUMENT, "null batch pointer");
-    OrbxSim3Plan plan;
+    OrbxRansacPlan plan;
     const char *why = "";
-    orbx_status st = orbx_sim3_plan(nproblems, problems, plan, &why);
+    orbx_status st = S::plan(nproblems, problems, plan, &why);
     if (st != ORBX_OK) return orbx_fail(st, why);
-    if (plan.nlaunch == 0) {                                   // nothing to compute: every solver reports no_more at once
-        *out = orbx_sim3_batch_new(problems, plan);
+    if (plan.nlaunch == 0) {                                   // nothing to compute: the batch says so for every problem
+        *out = S::batch_new(problems, plan);
         return ORBX_OK;
     }
-    if (h->host_only || sim3_host_selected()) {
-        std::vector<uint8_t> in(plan.in_bytes);
-        orbx_sim3_pack(problems, plan, in.data());
-        orbx_sim3_batch *b = orbx_sim3_batch_new(problems, plan);
-        orbx_sim3_host_run(plan, in.data(), b->out.data());
-        *out = b;
+    if (h->host_only || host_selected(S::env)) {
+        std::vector<uint8_t> in(plan.in_bytes), res(S::keeps_block ? 0 : plan.out_bytes);
+        S::pack(problems, plan, in.data());
+        typename S::batch *b = *out = S::batch_new(problems, plan);
+        if constexpr (S::keeps_block) S::host_run(plan, in.data(), b->out.data());   // straight into the batch's block: nothing to take
+        else { S::host_run(plan, in.data(), res.data()); S::batch_take(b, plan, res.data()); }
         return ORBX_OK;
     }
     uint8_t *pin = nullptr, *d = nullptr;
     const size_t dev_in = pad256(plan.in_bytes);
     st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + plan.out_bytes, &pin, &d, false);
     if (st != ORBX_OK) return st;
-    orbx_sim3_pack(problems, plan, pin);
+    S::pack(problems, plan, pin);
     st = stage_upload(h, pin, d, plan.in_bytes);
     if (st != ORBX_OK) return st;
-    uint8_t *d_out = d + dev_in;
-    DSim3Args a;
-    a.prob = (const DSim3Prob *)(d + plan.o_prob);
-    a.iter_prob = (const int32_t *)(d + plan.o_iter_prob);
-    a.sets = (const int32_t *)(d + plan.o_sets);
-    a.groups = (const int32_t *)(d + plan.o_groups);
-    a.pts = (const float *)(d + plan.o_pts);
-    a.total_iters = plan.total_iters; a.ngroups = plan.ngroups;
-    a.hyp = (OrbxSim3Hyp *)(d_out + plan.o_hyp);
-    a.masks = (unsigned long long *)(d_out + plan.o_masks);
-    a.counts = (int32_t *)(d_out + plan.o_counts);
     { ProfScope ps(h, ORBX_K_MISC);
-      orbx_launch_sim3(h->stream, a); }
-    st = stage_download_wait(h, pin, d_out, plan.out_bytes);
+      S::launch(h->stream, orbx_ransac_args<typename S::args>(plan, d, d + dev_in)); }
+    st = stage_download_wait(h, pin, d + dev_in, plan.out_bytes);
     if (st != ORBX_OK) return st;
-    orbx_sim3_batch *b = orbx_sim3_batch_new(problems, plan);
-    memcpy(b->out.data(), pin, plan.out_bytes);
-    *out = b;
+    *out = S::batch_new(problems, plan);
+    S::batch_take(*out, plan, pin);
     return ORBX_OK;
+}
+// fail_why(f(..., &why), why): `why` is taken by reference, so it is read here, after f has set it, whichever argument the
+// compiler evaluates first
+static orbx_status fail_why(orbx_status st, const char *const &why) { return st == ORBX_OK ? st : orbx_fail(st, why); }
+
+// ---------------------------------------------------------------- Sim3Solver RANSAC, batched (orbx_sim3.h): k_sim3_hypotheses and
+// k_sim3_inliers; the batch keeps the downloaded block as it is and iterate() is a cursor over it.
+struct Sim3Frame {
+    using problem = orbx_sim3_problem; using batch = orbx_sim3_batch; using args = DSim3Args;
+    static constexpr const char *env = "ORBX_SIM3"; static constexpr bool keeps_block = true;
+    static constexpr auto plan = orbx_sim3_plan; static constexpr auto pack = orbx_sim3_pack;
+    static constexpr auto host_run = orbx_sim3_host_run; static constexpr auto launch = orbx_launch_sim3;
+    static constexpr auto batch_new = orbx_sim3_batch_new; static constexpr auto batch_take = orbx_sim3_batch_take;
+};
+extern "C" orbx_status orbx_sim3_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_sim3_problem *problems,
+                                                     orbx_sim3_batch **out) {
+    return ransac_batch_create<Sim3Frame>(h, nproblems, problems, out);
 }
 extern "C" int32_t orbx_sim3_batch_iterate(orbx_sim3_batch *b, int k, int n_iterations, int32_t *no_more, uint8_t *inliers,
                                            int32_t *ninliers, float *T12) {
@@ -262,186 +264,88 @@ extern "C" int32_t orbx_sim3_batch_iterate(orbx_sim3_batch *b, int k, int n_iter
 }
 extern "C" orbx_status orbx_sim3_batch_best(const orbx_sim3_batch *b, int k, float *R, float *t, float *s) {
     const char *why = "";
-    const orbx_status st = orbx_sim3_cursor_best(b, k, R, t, s, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_sim3_cursor_best(b, k, R, t, s, &why), why);
 }
 extern "C" orbx_status orbx_sim3_batch_counts(const orbx_sim3_batch *b, int k, int32_t *counts, int32_t *niterations) {
     const char *why = "";
-    const orbx_status st = orbx_sim3_cursor_counts(b, k, counts, niterations, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_sim3_cursor_counts(b, k, counts, niterations, &why), why);
 }
 extern "C" orbx_status orbx_sim3_batch_hypothesis(const orbx_sim3_batch *b, int k, int iteration, float *hyp48, uint64_t *mask_words) {
     const char *why = "";
-    const orbx_status st = orbx_sim3_cursor_hypothesis(b, k, iteration, hyp48, mask_words, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_sim3_cursor_hypothesis(b, k, iteration, hyp48, mask_words, &why), why);
 }
 extern "C" void orbx_sim3_batch_destroy(orbx_sim3_batch *b) { delete b; }
 
-// ---------------------------------------------------------------- PnPsolver RANSAC, batched (orbx_pnp.h).
-// Device path: validation and layout (orbx_pnp.cpp), all problems packed into the page-locked block, ONE upload,
-// k_pnp_hypotheses and k_pnp_inliers on the handle's stream, ONE download of hypotheses | masks | counts, the wait; the batch
-// keeps the results per solver and iterate() is a cursor over them.  Host path (ORBX_PNP=host, read per call; host-only
-// handles): the same header compiled by the host compiler over the same packed block.
-static bool pnp_host_selected() {
-    const char *e = getenv("ORBX_PNP");
-    return e && strcmp(e, "host") == 0;
-}
+// ---------------------------------------------------------------- PnPsolver RANSAC, batched (orbx_pnp.h): k_pnp_hypotheses and
+// k_pnp_inliers; the batch keeps the results per solver (append() adds to them) and iterate() is a cursor over them.
+struct PnpFrame {
+    using problem = orbx_pnp_problem; using batch = orbx_pnp_batch; using args = DPnpArgs;
+    static constexpr const char *env = "ORBX_PNP"; static constexpr bool keeps_block = false;
+    static constexpr auto plan = orbx_pnp_plan; static constexpr auto pack = orbx_pnp_pack;
+    static constexpr auto host_run = orbx_pnp_host_run; static constexpr auto launch = orbx_launch_pnp;
+    static constexpr auto batch_new = orbx_pnp_batch_new; static constexpr auto batch_take = orbx_pnp_batch_take;
+};
 extern "C" orbx_status orbx_pnp_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_pnp_problem *problems,
                                                     orbx_pnp_batch **out) {
-    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
-    if (!out) return orbx_fail(ORBX_BAD_ARGUMENT, "null batch pointer");
-    OrbxPnpPlan plan;
-    const char *why = "";
-    orbx_status st = orbx_pnp_plan(nproblems, problems, plan, &why);
-    if (st != ORBX_OK) return orbx_fail(st, why);
-    if (plan.nlaunch == 0) {                                   // nothing to compute: every solver reports no_more at once
-        *out = orbx_pnp_batch_new(problems, plan);
-        return ORBX_OK;
-    }
-    if (h->host_only || pnp_host_selected()) {
-        std::vector<uint8_t> in(plan.in_bytes), res(plan.out_bytes);
-        orbx_pnp_pack(problems, plan, in.data());
-        orbx_pnp_host_run(plan, in.data(), res.data());
-        orbx_pnp_batch *b = orbx_pnp_batch_new(problems, plan);
-        orbx_pnp_batch_take(b, plan, res.data());
-        *out = b;
-        return ORBX_OK;
-    }
-    uint8_t *pin = nullptr, *d = nullptr;
-    const size_t dev_in = pad256(plan.in_bytes);
-    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + plan.out_bytes, &pin, &d, false);
-    if (st != ORBX_OK) return st;
-    orbx_pnp_pack(problems, plan, pin);
-    st = stage_upload(h, pin, d, plan.in_bytes);
-    if (st != ORBX_OK) return st;
-    uint8_t *d_out = d + dev_in;
-    DPnpArgs a;
-    a.prob = (const DPnpProb *)(d + plan.o_prob);
-    a.iter_prob = (const int32_t *)(d + plan.o_iter_prob);
-    a.sets = (const int32_t *)(d + plan.o_sets);
-    a.groups = (const int32_t *)(d + plan.o_groups);
-    a.pts = (const float *)(d + plan.o_pts);
-    a.total_iters = plan.total_iters; a.ngroups = plan.ngroups;
-    a.hyp = (OrbxPnpHyp *)(d_out + plan.o_hyp);
-    a.masks = (unsigned long long *)(d_out + plan.o_masks);
-    a.counts = (int32_t *)(d_out + plan.o_counts);
-    { ProfScope ps(h, ORBX_K_MISC);
-      orbx_launch_pnp(h->stream, a); }
-    st = stage_download_wait(h, pin, d_out, plan.out_bytes);
-    if (st != ORBX_OK) return st;
-    orbx_pnp_batch *b = orbx_pnp_batch_new(problems, plan);
-    orbx_pnp_batch_take(b, plan, pin);
-    *out = b;
-    return ORBX_OK;
+    return ransac_batch_create<PnpFrame>(h, nproblems, problems, out);
 }
 extern "C" int32_t orbx_pnp_batch_iterate(orbx_pnp_batch *b, int k, int n_iterations, int32_t *no_more, uint8_t *inliers,
                                           int32_t *ninliers, float *Tcw) {
     const char *why = "";
     const int32_t r = orbx_pnp_cursor_iterate(b, k, n_iterations, no_more, inliers, ninliers, Tcw, &why);
-    if (r < 0) orbx_fail(ORBX_BAD_ARGUMENT, why);
+    if (r < 0) orbx_fail(ORBX_BAD_ARGUMENT, why);             // -2 (append sets and call again) records its message too
     return r;
 }
 extern "C" orbx_status orbx_pnp_batch_append(orbx_pnp_batch *b, int k, int nsets, const int32_t *sets) {
     const char *why = "";
-    const orbx_status st = orbx_pnp_cursor_append(b, k, nsets, sets, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_pnp_cursor_append(b, k, nsets, sets, &why), why);
 }
 extern "C" orbx_status orbx_pnp_batch_best(const orbx_pnp_batch *b, int k, float *Tcw, int32_t *ninliers, int32_t *iteration) {
     const char *why = "";
-    const orbx_status st = orbx_pnp_cursor_best(b, k, Tcw, ninliers, iteration, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_pnp_cursor_best(b, k, Tcw, ninliers, iteration, &why), why);
 }
 extern "C" orbx_status orbx_pnp_batch_counts(const orbx_pnp_batch *b, int k, int32_t *counts, int32_t *niterations) {
     const char *why = "";
-    const orbx_status st = orbx_pnp_cursor_counts(b, k, counts, niterations, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_pnp_cursor_counts(b, k, counts, niterations, &why), why);
 }
 extern "C" orbx_status orbx_pnp_batch_hypothesis(const orbx_pnp_batch *b, int k, int iteration, double *Rt12, float *Tcw, int32_t *N,
                                                  uint64_t *mask_words) {
     const char *why = "";
-    const orbx_status st = orbx_pnp_cursor_hypothesis(b, k, iteration, Rt12, Tcw, N, mask_words, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_pnp_cursor_hypothesis(b, k, iteration, Rt12, Tcw, N, mask_words, &why), why);
 }
 extern "C" void orbx_pnp_batch_destroy(orbx_pnp_batch *b) { delete b; }
 
-// ---------------------------------------------------------------- Initializer H / F RANSAC, batched (orbx_init.h).
-// Device path: validation and layout (orbx_init.cpp), all problems packed into the page-locked block, ONE upload,
-// k_init_hypotheses and k_init_scores on the handle's stream, ONE download of hypotheses | masks | scores, the wait; the batch
-// keeps the results per problem and picks the best iteration of each model on the host.  Host path (ORBX_INIT=host, read per
-// call; host-only handles): the same header compiled by the host compiler over the same packed block.
-static bool init_host_selected() {
-    const char *e = getenv("ORBX_INIT");
-    return e && strcmp(e, "host") == 0;
-}
+// ---------------------------------------------------------------- Initializer H / F RANSAC, batched (orbx_init.h):
+// k_init_hypotheses and k_init_scores; the batch keeps the results per problem and picks the best iteration of each model on the
+// host (orbx_init_batch_take).  A problem that computes nothing reports ORBX_INIT_NONE.
+struct InitFrame {
+    using problem = orbx_init_problem; using batch = orbx_init_batch; using args = DInitArgs;
+    static constexpr const char *env = "ORBX_INIT"; static constexpr bool keeps_block = false;
+    static constexpr auto plan = orbx_init_plan; static constexpr auto pack = orbx_init_pack;
+    static constexpr auto host_run = orbx_init_host_run; static constexpr auto launch = orbx_launch_init;
+    static constexpr auto batch_new = orbx_init_batch_new; static constexpr auto batch_take = orbx_init_batch_take;
+};
 extern "C" orbx_status orbx_init_ransac_batch_create(orbx_handle *h, int nproblems, const orbx_init_problem *problems,
                                                      orbx_init_batch **out) {
-    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
-    if (!out) return orbx_fail(ORBX_BAD_ARGUMENT, "null batch pointer");
-    OrbxInitPlan plan;
-    const char *why = "";
-    orbx_status st = orbx_init_plan(nproblems, problems, plan, &why);
-    if (st != ORBX_OK) return orbx_fail(st, why);
-    if (plan.nlaunch == 0) {                                   // nothing to compute: every problem reports ORBX_INIT_NONE
-        *out = orbx_init_batch_new(problems, plan);
-        return ORBX_OK;
-    }
-    if (h->host_only || init_host_selected()) {
-        std::vector<uint8_t> in(plan.in_bytes), res(plan.out_bytes);
-        orbx_init_pack(problems, plan, in.data());
-        orbx_init_host_run(plan, in.data(), res.data());
-        orbx_init_batch *b = orbx_init_batch_new(problems, plan);
-        orbx_init_batch_take(b, plan, res.data());
-        *out = b;
-        return ORBX_OK;
-    }
-    uint8_t *pin = nullptr, *d = nullptr;
-    const size_t dev_in = pad256(plan.in_bytes);
-    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + plan.out_bytes, &pin, &d, false);
-    if (st != ORBX_OK) return st;
-    orbx_init_pack(problems, plan, pin);
-    st = stage_upload(h, pin, d, plan.in_bytes);
-    if (st != ORBX_OK) return st;
-    uint8_t *d_out = d + dev_in;
-    DInitArgs a;
-    a.prob = (const DInitProb *)(d + plan.o_prob);
-    a.hyp_prob = (const int32_t *)(d + plan.o_hyp_prob);
-    a.sets = (const int32_t *)(d + plan.o_sets);
-    a.groups = (const int32_t *)(d + plan.o_groups);
-    a.pts = (const float *)(d + plan.o_pts);
-    a.total_hyps = plan.total_hyps; a.ngroups = plan.ngroups;
-    a.hyp = (OrbxInitHyp *)(d_out + plan.o_hyp);
-    a.masks = (unsigned long long *)(d_out + plan.o_masks);
-    a.scores = (float *)(d_out + plan.o_scores);
-    { ProfScope ps(h, ORBX_K_MISC);
-      orbx_launch_init(h->stream, a); }
-    st = stage_download_wait(h, pin, d_out, plan.out_bytes);
-    if (st != ORBX_OK) return st;
-    orbx_init_batch *b = orbx_init_batch_new(problems, plan);
-    orbx_init_batch_take(b, plan, pin);
-    *out = b;
-    return ORBX_OK;
+    return ransac_batch_create<InitFrame>(h, nproblems, problems, out);
 }
 extern "C" orbx_status orbx_init_batch_result(const orbx_init_batch *b, int k, float *SH, float *SF, float *H21, float *F21,
                                               uint8_t *inliersH, uint8_t *inliersF, int32_t *itH, int32_t *itF, float *RH,
                                               int32_t *model) {
     const char *why = "";
-    const orbx_status st = orbx_init_get_result(b, k, SH, SF, H21, F21, inliersH, inliersF, itH, itF, RH, model, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_init_get_result(b, k, SH, SF, H21, F21, inliersH, inliersF, itH, itF, RH, model, &why), why);
 }
 extern "C" orbx_status orbx_init_batch_scores(const orbx_init_batch *b, int k, int model, float *scores, int32_t *niterations) {
     const char *why = "";
-    const orbx_status st = orbx_init_get_scores(b, k, model, scores, niterations, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_init_get_scores(b, k, model, scores, niterations, &why), why);
 }
 extern "C" orbx_status orbx_init_batch_hypothesis(const orbx_init_batch *b, int k, int model, int iteration, float *M9, float *Minv9,
                                                   float *score, uint64_t *mask_words) {
     const char *why = "";
-    const orbx_status st = orbx_init_get_hypothesis(b, k, model, iteration, M9, Minv9, score, mask_words, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_init_get_hypothesis(b, k, model, iteration, M9, Minv9, score, mask_words, &why), why);
 }
 extern "C" orbx_status orbx_init_batch_normalization(const orbx_init_batch *b, int k, float *T1, float *T2) {
     const char *why = "";
-    const orbx_status st = orbx_init_get_normalization(b, k, T1, T2, &why);
-    return st == ORBX_OK ? st : orbx_fail(st, why);
+    return fail_why(orbx_init_get_normalization(b, k, T1, T2, &why), why);
 }
 extern "C" void orbx_init_batch_destroy(orbx_init_batch *b) { delete b; }

@@ -7,24 +7,20 @@
 #include <algorithm>
 #include "orbx_pnp.h"
 
-static inline size_t pnp_pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline bool pnp_launches(const orbx_pnp_problem &P) { return P.n >= P.min_inliers; }
-
-static bool pnp_set_ok(const int32_t *s, int32_t n) {
-    for (int c = 0; c < 4; ++c) {
-        if (s[c] < 0 || s[c] >= n) return false;
-        for (int e = 0; e < c; ++e)
-            if (s[e] == s[c]) return false;
-    }
-    return true;
+static inline bool pnp_set_ok(const int32_t *s, int32_t n) { return orbx_set_ok<4>(s, n, true); }
+static inline OrbxRansacWalk pnp_walk(int32_t *hyp_prob = nullptr, int32_t *groups = nullptr) {
+    return OrbxRansacWalk(0x0fffffff, 0x3fffffff, hyp_prob, groups);
+}
+static inline OrbxRansacWalk::At pnp_add(OrbxRansacWalk &w, int32_t n, int32_t iterations) {
+    return w.add(n, (size_t)iterations, (size_t)iterations * 4, ORBX_PNP_PLANES, ORBX_PNP_WAVES);
 }
 
 orbx_status orbx_pnp_plan(int nproblems, const orbx_pnp_problem *problems, OrbxPnpPlan &plan, const char **why) {
     plan = OrbxPnpPlan();
     if (nproblems < 0) { *why = "nproblems < 0"; return ORBX_BAD_ARGUMENT; }
     if (nproblems > 0 && !problems) { *why = "null problem array"; return ORBX_BAD_ARGUMENT; }
-    size_t iters = 0, pts = 0, words = 0, groups = 0;
-    int nlaunch = 0;
+    OrbxRansacWalk w = pnp_walk();
     for (int k = 0; k < nproblems; ++k) {
         const orbx_pnp_problem &P = problems[k];
         if (P.n < 0) { *why = "n < 0"; return ORBX_BAD_ARGUMENT; }
@@ -34,32 +30,9 @@ orbx_status orbx_pnp_plan(int nproblems, const orbx_pnp_problem *problems, OrbxP
         if (!P.sets) { *why = "null sets"; return ORBX_BAD_ARGUMENT; }
         for (int i = 0; i < P.iterations; ++i)
             if (!pnp_set_ok(P.sets + 4 * (size_t)i, P.n)) { *why = "set index outside [0, n) or repeated within its set"; return ORBX_BAD_ARGUMENT; }
-        ++nlaunch;
-        iters += (size_t)P.iterations;
-        pts += (size_t)P.n * ORBX_PNP_PLANES;
-        words += (size_t)P.iterations * (size_t)((P.n + 63) / 64);
-        groups += (size_t)((P.iterations + ORBX_PNP_WAVES - 1) / ORBX_PNP_WAVES);
-        if (iters > (size_t)0x0fffffff || pts > (size_t)0x3fffffff || words > (size_t)0x3fffffff) {
-            *why = "too many iterations or correspondences for 32-bit offsets";
-            return ORBX_UNSUPPORTED;
-        }
+        if (!pnp_add(w, P.n, P.iterations).ok) { *why = "too many iterations or correspondences for 32-bit offsets"; return ORBX_UNSUPPORTED; }
     }
-    plan.nproblems = nproblems;
-    plan.nlaunch = nlaunch;
-    plan.total_iters = (int)iters;
-    plan.ngroups = (int)groups;
-    plan.total_pts = pts;
-    plan.total_words = words;
-    plan.o_prob = 0;
-    plan.o_iter_prob = pnp_pad256((size_t)nlaunch * sizeof(DPnpProb));
-    plan.o_sets = plan.o_iter_prob + pnp_pad256(iters * sizeof(int32_t));
-    plan.o_groups = plan.o_sets + pnp_pad256(iters * 4 * sizeof(int32_t));
-    plan.o_pts = plan.o_groups + pnp_pad256(groups * 2 * sizeof(int32_t));
-    plan.in_bytes = plan.o_pts + pnp_pad256(pts * sizeof(float));
-    plan.o_hyp = 0;
-    plan.o_masks = pnp_pad256(iters * sizeof(OrbxPnpHyp));
-    plan.o_counts = plan.o_masks + pnp_pad256(words * sizeof(uint64_t));
-    plan.out_bytes = plan.o_counts + pnp_pad256(iters * sizeof(int32_t));
+    plan = w.plan(nproblems, sizeof(DPnpProb), sizeof(OrbxPnpHyp));
     return ORBX_OK;
 }
 
@@ -76,25 +49,19 @@ static void pnp_planes(const orbx_pnp_problem &P, float *pl) {
 void orbx_pnp_pack(const orbx_pnp_problem *problems, const OrbxPnpPlan &plan, uint8_t *dst) {
     if (plan.nlaunch <= 0) return;
     DPnpProb *dp = (DPnpProb *)(dst + plan.o_prob);
-    int32_t *iter_prob = (int32_t *)(dst + plan.o_iter_prob);
     int32_t *sets = (int32_t *)(dst + plan.o_sets);
-    int32_t *groups = (int32_t *)(dst + plan.o_groups);
     float *pts = (float *)(dst + plan.o_pts);
-    int j = 0, g = 0;
-    size_t it = 0, po = 0, wo = 0;
+    OrbxRansacWalk w = pnp_walk((int32_t *)(dst + plan.o_hyp_prob), (int32_t *)(dst + plan.o_groups));
     for (int k = 0; k < plan.nproblems; ++k) {
         const orbx_pnp_problem &P = problems[k];
         if (!pnp_launches(P)) continue;
-        DPnpProb &D = dp[j];
-        D.n = P.n; D.iterations = P.iterations; D.nwords = (P.n + 63) / 64; D.pad = 0;
-        D.iter_off = (int32_t)it; D.pts_off = (int32_t)po; D.word_off = (int32_t)wo; D.pad2 = 0;
+        const OrbxRansacWalk::At at = pnp_add(w, P.n, P.iterations);
+        DPnpProb &D = dp[at.j];
+        D.n = P.n; D.iterations = P.iterations; D.nwords = at.nwords; D.pad = 0;
+        D.iter_off = at.hyp_off; D.pts_off = at.pts_off; D.word_off = at.word_off; D.pad2 = 0;
         memcpy(D.cam, P.camera, sizeof(D.cam));
-        for (int i = 0; i < P.iterations; ++i) iter_prob[it + i] = j;
-        memcpy(sets + it * 4, P.sets, (size_t)P.iterations * 4 * sizeof(int32_t));
-        for (int i = 0; i < P.iterations; i += ORBX_PNP_WAVES) { groups[2 * g] = j; groups[2 * g + 1] = i; ++g; }
-        pnp_planes(P, pts + po);
-        it += (size_t)P.iterations; po += (size_t)P.n * ORBX_PNP_PLANES; wo += (size_t)P.iterations * (size_t)D.nwords;
-        ++j;
+        memcpy(sets + at.set_off, P.sets, (size_t)P.iterations * 4 * sizeof(int32_t));
+        pnp_planes(P, pts + at.pts_off);
     }
 }
 
@@ -134,7 +101,7 @@ void orbx_pnp_host_run(const OrbxPnpPlan &plan, const uint8_t *in, uint8_t *out)
     const float *pts = (const float *)(in + plan.o_pts);
     OrbxPnpHyp *hyp = (OrbxPnpHyp *)(out + plan.o_hyp);
     uint64_t *masks = (uint64_t *)(out + plan.o_masks);
-    int32_t *counts = (int32_t *)(out + plan.o_counts);
+    int32_t *counts = (int32_t *)(out + plan.o_tally);
     std::vector<double> ws;
     for (int j = 0; j < plan.nlaunch; ++j) {
         const DPnpProb &D = dp[j];
@@ -165,22 +132,16 @@ orbx_pnp_batch *orbx_pnp_batch_new(const orbx_pnp_problem *problems, const OrbxP
 void orbx_pnp_batch_take(orbx_pnp_batch *b, const OrbxPnpPlan &plan, const uint8_t *out) {
     const OrbxPnpHyp *hyp = (const OrbxPnpHyp *)(out + plan.o_hyp);
     const uint64_t *masks = (const uint64_t *)(out + plan.o_masks);
-    const int32_t *counts = (const int32_t *)(out + plan.o_counts);
-    size_t it = 0, wo = 0;
+    const int32_t *counts = (const int32_t *)(out + plan.o_tally);
+    OrbxRansacWalk w = pnp_walk();
     for (OrbxPnpSolver &S : b->st) {
         if (!S.launches) continue;
+        const OrbxRansacWalk::At at = pnp_add(w, S.n, S.max_its);
         const size_t ni = (size_t)S.max_its, nw = ni * (size_t)S.nwords;
-        S.hyp.assign(hyp + it, hyp + it + ni);
-        S.counts.assign(counts + it, counts + it + ni);
-        S.masks.assign(masks + wo, masks + wo + nw);
-        it += ni; wo += nw;
+        S.hyp.assign(hyp + at.hyp_off, hyp + at.hyp_off + ni);
+        S.counts.assign(counts + at.hyp_off, counts + at.hyp_off + ni);
+        S.masks.assign(masks + at.word_off, masks + at.word_off + nw);
     }
-}
-
-static const OrbxPnpSolver *pnp_state(const orbx_pnp_batch *b, int k, const char **why) {
-    if (!b) { *why = "no batch"; return nullptr; }
-    if (k < 0 || (size_t)k >= b->st.size()) { *why = "problem outside the batch"; return nullptr; }
-    return &b->st[k];
 }
 
 // Refine (:386-438) of the best mask, computed when first asked for and kept while the best does not move
@@ -199,16 +160,12 @@ static const OrbxPnpRefined &pnp_refine(OrbxPnpSolver &S) {
     return R;
 }
 
-static void pnp_unpack(const uint64_t *mw, int n, uint8_t *inliers) {
-    for (int p = 0; p < n; ++p) inliers[p] = (uint8_t)((mw[p >> 6] >> (p & 63)) & 1u);
-}
-
 int32_t orbx_pnp_cursor_iterate(orbx_pnp_batch *b, int k, int n_iterations, int32_t *no_more, uint8_t *inliers, int32_t *ninliers,
                                 float *Tcw, const char **why) {
-    const OrbxPnpSolver *cs = pnp_state(b, k, why);
+    OrbxPnpSolver *cs = orbx_batch_state(b, k, why);
     if (!cs) return -1;
     if (!no_more || !ninliers || !Tcw || (cs->n > 0 && !inliers)) { *why = "null result pointer"; return -1; }
-    OrbxPnpSolver &S = b->st[k];
+    OrbxPnpSolver &S = *cs;
     *no_more = 0;                                              // bNoMore = false; vbInliers empty; nInliers = 0
     if (S.n > 0) memset(inliers, 0, (size_t)S.n);
     *ninliers = 0;
@@ -228,7 +185,7 @@ int32_t orbx_pnp_cursor_iterate(orbx_pnp_batch *b, int k, int n_iterations, int3
             const OrbxPnpRefined &R = pnp_refine(S);
             if (R.ok) {
                 *ninliers = R.count;
-                pnp_unpack(R.mask.data(), S.n, inliers);
+                orbx_unpack_mask(R.mask.data(), S.n, inliers);
                 memcpy(Tcw, R.hyp.Tcw, 16 * sizeof(float));
                 return 1;
             }
@@ -238,7 +195,7 @@ int32_t orbx_pnp_cursor_iterate(orbx_pnp_batch *b, int k, int n_iterations, int3
         *no_more = 1;
         if (S.best_inliers >= S.min_inliers) {
             *ninliers = S.best_inliers;
-            pnp_unpack(S.masks.data() + (size_t)S.best_it * S.nwords, S.n, inliers);
+            orbx_unpack_mask(S.masks.data() + (size_t)S.best_it * S.nwords, S.n, inliers);
             memcpy(Tcw, S.hyp[S.best_it].Tcw, 16 * sizeof(float));
             return 1;
         }
@@ -247,10 +204,10 @@ int32_t orbx_pnp_cursor_iterate(orbx_pnp_batch *b, int k, int n_iterations, int3
 }
 
 orbx_status orbx_pnp_cursor_append(orbx_pnp_batch *b, int k, int nsets, const int32_t *sets, const char **why) {
-    const OrbxPnpSolver *cs = pnp_state(b, k, why);
+    OrbxPnpSolver *cs = orbx_batch_state(b, k, why);
     if (!cs) return ORBX_BAD_ARGUMENT;
     if (nsets < 0 || (nsets > 0 && !sets)) { *why = "nsets < 0 or null sets"; return ORBX_BAD_ARGUMENT; }
-    OrbxPnpSolver &S = b->st[k];
+    OrbxPnpSolver &S = *cs;
     if (!S.launches) { *why = "a solver with n < min_inliers has no iterations"; return ORBX_BAD_ARGUMENT; }
     for (int i = 0; i < nsets; ++i)
         if (!pnp_set_ok(sets + 4 * (size_t)i, S.n)) { *why = "set index outside [0, n) or repeated within its set"; return ORBX_BAD_ARGUMENT; }
@@ -267,7 +224,7 @@ orbx_status orbx_pnp_cursor_append(orbx_pnp_batch *b, int k, int nsets, const in
 }
 
 orbx_status orbx_pnp_cursor_best(const orbx_pnp_batch *b, int k, float *Tcw, int32_t *ninliers, int32_t *iteration, const char **why) {
-    const OrbxPnpSolver *S = pnp_state(b, k, why);
+    const OrbxPnpSolver *S = orbx_batch_state(b, k, why);
     if (!S) return ORBX_BAD_ARGUMENT;
     if (S->best_it < 0) { *why = "no iteration of this solver has reached min_inliers"; return ORBX_BAD_ARGUMENT; }
     if (Tcw) memcpy(Tcw, S->hyp[S->best_it].Tcw, 16 * sizeof(float));
@@ -277,7 +234,7 @@ orbx_status orbx_pnp_cursor_best(const orbx_pnp_batch *b, int k, float *Tcw, int
 }
 
 orbx_status orbx_pnp_cursor_counts(const orbx_pnp_batch *b, int k, int32_t *counts, int32_t *niterations, const char **why) {
-    const OrbxPnpSolver *S = pnp_state(b, k, why);
+    const OrbxPnpSolver *S = orbx_batch_state(b, k, why);
     if (!S) return ORBX_BAD_ARGUMENT;
     if (counts && !S->counts.empty()) memcpy(counts, S->counts.data(), S->counts.size() * sizeof(int32_t));
     if (niterations) *niterations = (int32_t)S->counts.size();
@@ -286,7 +243,7 @@ orbx_status orbx_pnp_cursor_counts(const orbx_pnp_batch *b, int k, int32_t *coun
 
 orbx_status orbx_pnp_cursor_hypothesis(const orbx_pnp_batch *b, int k, int iteration, double *Rt12, float *Tcw, int32_t *N,
                                        uint64_t *mask_words, const char **why) {
-    const OrbxPnpSolver *S = pnp_state(b, k, why);
+    const OrbxPnpSolver *S = orbx_batch_state(b, k, why);
     if (!S) return ORBX_BAD_ARGUMENT;
     if (iteration < 0 || (size_t)iteration >= S->counts.size()) { *why = "iteration outside the solver's stored results"; return ORBX_BAD_ARGUMENT; }
     const OrbxPnpHyp &H = S->hyp[iteration];
@@ -298,21 +255,16 @@ orbx_status orbx_pnp_cursor_hypothesis(const orbx_pnp_batch *b, int k, int itera
     return ORBX_OK;
 }
 
-// the source converts a floating value to int as it is; outside int's range that conversion is undefined, so the library fixes
-// it as orbx_sim3_ransac_iterations does: NaN and anything at or beyond 2^31 count as the largest int, anything below -2^31 as
-// the lowest
-static int pnp_to_int(double v) { return !(v < 2147483648.0) ? 2147483647 : v < -2147483648.0 ? (-2147483647 - 1) : (int)v; }
-
 // PnPsolver::SetRansacParameters (:190-239): what mRansacMinInliers and mRansacMaxIts become for N = n
 extern "C" void orbx_pnp_ransac_parameters(int32_t n, double probability, int32_t min_inliers, int32_t max_iterations, int32_t min_set,
                                            float epsilon, int32_t *out_min_inliers, int32_t *out_iterations) {
-    int nMinInliers = pnp_to_int((double)((float)n * epsilon));           // int nMinInliers = N*mRansacEpsilon
+    int nMinInliers = orbx_to_int_clamped((double)((float)n * epsilon));           // int nMinInliers = N*mRansacEpsilon
     if (nMinInliers < min_inliers) nMinInliers = min_inliers;
     if (nMinInliers < min_set) nMinInliers = min_set;
     if (epsilon < (float)nMinInliers / n) epsilon = (float)nMinInliers / n;
     int nIterations;
     if (nMinInliers == n) nIterations = 1;
-    else nIterations = pnp_to_int(std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0))));
+    else nIterations = orbx_to_int_clamped(std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0))));
     if (out_min_inliers) *out_min_inliers = nMinInliers;
     if (out_iterations) *out_iterations = std::max(1, std::min(nIterations, max_iterations));
 }

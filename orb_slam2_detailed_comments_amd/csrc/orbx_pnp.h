@@ -17,6 +17,7 @@
 #pragma once
 #include <vector>
 #include "orbx_pose.h"
+#include "orbx_ransac.h"
 
 struct OrbxPnpHyp {          // one hypothesis as the kernels store it and the host cursor reads it
     double R[9], t[3];       // mRi, mti
@@ -57,22 +58,6 @@ struct OrbxPnpWs {
     int stride;
     ORBX_HD double &operator()(int e) const { return p[(long long)e * stride]; }
 };
-
-// A NaN's sign and payload differ between processors, so every stored NaN is the canonical quiet NaN
-ORBX_HD static inline float orbx_pnp_canonf(float x) {
-    uint32_t b;
-    __builtin_memcpy(&b, &x, 4);
-    if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;
-    __builtin_memcpy(&x, &b, 4);
-    return x;
-}
-ORBX_HD static inline double orbx_pnp_canond(double x) {
-    uint64_t b;
-    __builtin_memcpy(&b, &x, 8);
-    if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) b = 0x7ff8000000000000ull;
-    __builtin_memcpy(&x, &b, 8);
-    return x;
-}
 
 // cvSVD(CV_SVD_U_T) of a symmetric d x d double matrix (d = 3 or 12), as this library fixes it: cyclic Jacobi.  Only the upper
 // triangle of a (row stride d) is read and written.  A sweep visits (p, q), p < q, row by row; a pair with a_pq == 0 is skipped;
@@ -464,11 +449,11 @@ ORBX_UNROLL
 
 // what iterate() / Refine() keep of a pose: the doubles, eye(4) with their float conversions, the chosen N; NaNs canonical
 ORBX_HD static inline void orbx_pnp_store(const double *Rt, int N, OrbxPnpHyp &H) {
-    for (int i = 0; i < 9; ++i) H.R[i] = orbx_pnp_canond(Rt[i]);
-    for (int i = 0; i < 3; ++i) H.t[i] = orbx_pnp_canond(Rt[9 + i]);
+    for (int i = 0; i < 9; ++i) H.R[i] = orbx_canond(Rt[i]);
+    for (int i = 0; i < 3; ++i) H.t[i] = orbx_canond(Rt[9 + i]);
     for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) H.Tcw[4 * i + j] = orbx_pnp_canonf((float)Rt[3 * i + j]);
-        H.Tcw[4 * i + 3] = orbx_pnp_canonf((float)Rt[9 + i]);
+        for (int j = 0; j < 3; ++j) H.Tcw[4 * i + j] = orbx_canonf((float)Rt[3 * i + j]);
+        H.Tcw[4 * i + 3] = orbx_canonf((float)Rt[9 + i]);
         H.Tcw[12 + i] = 0.0f;
     }
     H.Tcw[15] = 1.0f;
@@ -505,24 +490,9 @@ struct DPnpProb {                   // one problem that launches, as the kernels
     double cam[4];                  // fu, fv, uc, vc
 };
 static_assert(sizeof(DPnpProb) == 64, "packed for the device");
-struct DPnpArgs {
-    const DPnpProb *prob;
-    const int32_t *iter_prob;       // [total_iters] the problem of a hypothesis
-    const int32_t *sets;            // [total_iters][4]
-    const int32_t *groups;          // [ngroups][2]: problem, first iteration of a workgroup of k_pnp_inliers
-    const float *pts;
-    int total_iters, ngroups;
-    OrbxPnpHyp *hyp;
-    int32_t *counts;
-    unsigned long long *masks;
-};
-// Uploaded block (one copy): DPnpProb[nlaunch] | iter_prob | sets | groups | pts.  Downloaded block: hyp | masks | counts.
-struct OrbxPnpPlan {
-    int nproblems = 0, nlaunch = 0, total_iters = 0, ngroups = 0;
-    size_t total_pts = 0, total_words = 0;
-    size_t o_prob = 0, o_iter_prob = 0, o_sets = 0, o_groups = 0, o_pts = 0, in_bytes = 0;
-    size_t o_hyp = 0, o_masks = 0, o_counts = 0, out_bytes = 0;
-};
+// sets: [total_hyps][4]; a group: ORBX_PNP_WAVES iterations of k_pnp_inliers; tally: the inlier counts
+using DPnpArgs = DRansacArgs<DPnpProb, OrbxPnpHyp, int32_t>;
+using OrbxPnpPlan = OrbxRansacPlan;
 orbx_status orbx_pnp_plan(int nproblems, const orbx_pnp_problem *problems, OrbxPnpPlan &plan, const char **why);
 void orbx_pnp_pack(const orbx_pnp_problem *problems, const OrbxPnpPlan &plan, uint8_t *dst);
 // the host path: reads the packed block, writes the downloaded block's layout (hyp | masks | counts) into out

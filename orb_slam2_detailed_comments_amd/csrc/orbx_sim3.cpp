@@ -7,15 +7,19 @@
 #include <algorithm>
 #include "orbx_sim3.h"
 
-static inline size_t sim3_pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline bool sim3_launches(const orbx_sim3_problem &P) { return P.n >= P.min_inliers; }
+static inline OrbxRansacWalk sim3_walk(int32_t *hyp_prob = nullptr, int32_t *groups = nullptr) {
+    return OrbxRansacWalk(0x3fffffff, SIZE_MAX, hyp_prob, groups);   // no limit on the set ints: no record stores an offset into them
+}
+static inline OrbxRansacWalk::At sim3_add(OrbxRansacWalk &w, const orbx_sim3_problem &P) {
+    return w.add(P.n, (size_t)P.iterations, (size_t)P.iterations * 3, ORBX_SIM3_PLANES, ORBX_SIM3_WAVES);
+}
 
 orbx_status orbx_sim3_plan(int nproblems, const orbx_sim3_problem *problems, OrbxSim3Plan &plan, const char **why) {
     plan = OrbxSim3Plan();
     if (nproblems < 0) { *why = "nproblems < 0"; return ORBX_BAD_ARGUMENT; }
     if (nproblems > 0 && !problems) { *why = "null problem array"; return ORBX_BAD_ARGUMENT; }
-    size_t iters = 0, pts = 0, words = 0, groups = 0;
-    int nlaunch = 0;
+    OrbxRansacWalk w = sim3_walk();
     for (int k = 0; k < nproblems; ++k) {
         const orbx_sim3_problem &P = problems[k];
         if (P.n < 0) { *why = "n < 0"; return ORBX_BAD_ARGUMENT; }
@@ -23,58 +27,31 @@ orbx_status orbx_sim3_plan(int nproblems, const orbx_sim3_problem *problems, Orb
         if (P.n > 0 && (!P.x1c || !P.x2c || !P.max_err1 || !P.max_err2)) { *why = "null correspondence array with n > 0"; return ORBX_BAD_ARGUMENT; }
         if (!sim3_launches(P)) continue;
         if (!P.sets) { *why = "null sets"; return ORBX_BAD_ARGUMENT; }
-        for (size_t i = 0; i < (size_t)P.iterations * 3; ++i)
-            if (P.sets[i] < 0 || P.sets[i] >= P.n) { *why = "set index outside [0, n)"; return ORBX_BAD_ARGUMENT; }
-        ++nlaunch;
-        iters += (size_t)P.iterations;
-        pts += (size_t)P.n * ORBX_SIM3_PLANES;
-        words += (size_t)P.iterations * (size_t)((P.n + 63) / 64);
-        groups += (size_t)((P.iterations + ORBX_SIM3_WAVES - 1) / ORBX_SIM3_WAVES);
-        if (iters > (size_t)0x3fffffff || pts > (size_t)0x3fffffff || words > (size_t)0x3fffffff) {
-            *why = "too many iterations or correspondences for 32-bit offsets";
-            return ORBX_UNSUPPORTED;
-        }
+        for (int i = 0; i < P.iterations; ++i)                 // a repeated index is a hypothesis like any other (the model pins it)
+            if (!orbx_set_ok<3>(P.sets + 3 * (size_t)i, P.n, false)) { *why = "set index outside [0, n)"; return ORBX_BAD_ARGUMENT; }
+        if (!sim3_add(w, P).ok) { *why = "too many iterations or correspondences for 32-bit offsets"; return ORBX_UNSUPPORTED; }
     }
-    plan.nproblems = nproblems;
-    plan.nlaunch = nlaunch;
-    plan.total_iters = (int)iters;
-    plan.ngroups = (int)groups;
-    plan.total_pts = pts;
-    plan.total_words = words;
-    plan.o_prob = 0;
-    plan.o_iter_prob = sim3_pad256((size_t)nlaunch * sizeof(DSim3Prob));
-    plan.o_sets = plan.o_iter_prob + sim3_pad256(iters * sizeof(int32_t));
-    plan.o_groups = plan.o_sets + sim3_pad256(iters * 3 * sizeof(int32_t));
-    plan.o_pts = plan.o_groups + sim3_pad256(groups * 2 * sizeof(int32_t));
-    plan.in_bytes = plan.o_pts + sim3_pad256(pts * sizeof(float));
-    plan.o_hyp = 0;
-    plan.o_masks = sim3_pad256(iters * sizeof(OrbxSim3Hyp));
-    plan.o_counts = plan.o_masks + sim3_pad256(words * sizeof(uint64_t));
-    plan.out_bytes = plan.o_counts + sim3_pad256(iters * sizeof(int32_t));
+    plan = w.plan(nproblems, sizeof(DSim3Prob), sizeof(OrbxSim3Hyp));
     return ORBX_OK;
 }
 
 void orbx_sim3_pack(const orbx_sim3_problem *problems, const OrbxSim3Plan &plan, uint8_t *dst) {
     if (plan.nlaunch <= 0) return;
     DSim3Prob *dp = (DSim3Prob *)(dst + plan.o_prob);
-    int32_t *iter_prob = (int32_t *)(dst + plan.o_iter_prob);
     int32_t *sets = (int32_t *)(dst + plan.o_sets);
-    int32_t *groups = (int32_t *)(dst + plan.o_groups);
     float *pts = (float *)(dst + plan.o_pts);
-    int j = 0, g = 0;
-    size_t it = 0, po = 0, wo = 0;
+    OrbxRansacWalk w = sim3_walk((int32_t *)(dst + plan.o_hyp_prob), (int32_t *)(dst + plan.o_groups));
     for (int k = 0; k < plan.nproblems; ++k) {
         const orbx_sim3_problem &P = problems[k];
         if (!sim3_launches(P)) continue;
-        DSim3Prob &D = dp[j];
-        D.n = P.n; D.iterations = P.iterations; D.fix_scale = P.fix_scale ? 1 : 0; D.nwords = (P.n + 63) / 64;
-        D.iter_off = (int32_t)it; D.pts_off = (int32_t)po; D.word_off = (int32_t)wo; D.pad = 0;
+        const OrbxRansacWalk::At at = sim3_add(w, P);
+        DSim3Prob &D = dp[at.j];
+        D.n = P.n; D.iterations = P.iterations; D.fix_scale = P.fix_scale ? 1 : 0; D.nwords = at.nwords;
+        D.iter_off = at.hyp_off; D.pts_off = at.pts_off; D.word_off = at.word_off; D.pad = 0;
         memcpy(D.K1, P.camera1, sizeof(D.K1));
         memcpy(D.K2, P.camera2, sizeof(D.K2));
-        for (int i = 0; i < P.iterations; ++i) iter_prob[it + i] = j;
-        memcpy(sets + it * 3, P.sets, (size_t)P.iterations * 3 * sizeof(int32_t));
-        for (int i = 0; i < P.iterations; i += ORBX_SIM3_WAVES) { groups[2 * g] = j; groups[2 * g + 1] = i; ++g; }
-        float *pl = pts + po;
+        memcpy(sets + 3 * (size_t)at.hyp_off, P.sets, (size_t)P.iterations * 3 * sizeof(int32_t));
+        float *pl = pts + at.pts_off;
         const size_t n = (size_t)P.n;
         for (size_t i = 0; i < n; ++i) {
             for (int c = 0; c < 3; ++c) { pl[c * n + i] = P.x1c[3 * i + c]; pl[(3 + c) * n + i] = P.x2c[3 * i + c]; }
@@ -84,8 +61,6 @@ void orbx_sim3_pack(const orbx_sim3_problem *problems, const OrbxSim3Plan &plan,
             orbx_sim3_to_image(P.x1c[3 * i], P.x1c[3 * i + 1], P.x1c[3 * i + 2], P.camera1, &pl[8 * n + i], &pl[9 * n + i]);
             orbx_sim3_to_image(P.x2c[3 * i], P.x2c[3 * i + 1], P.x2c[3 * i + 2], P.camera2, &pl[10 * n + i], &pl[11 * n + i]);
         }
-        it += (size_t)P.iterations; po += n * ORBX_SIM3_PLANES; wo += (size_t)P.iterations * (size_t)D.nwords;
-        ++j;
     }
 }
 
@@ -95,7 +70,7 @@ void orbx_sim3_host_run(const OrbxSim3Plan &plan, const uint8_t *in, uint8_t *ou
     const float *pts = (const float *)(in + plan.o_pts);
     OrbxSim3Hyp *hyp = (OrbxSim3Hyp *)(out + plan.o_hyp);
     uint64_t *masks = (uint64_t *)(out + plan.o_masks);
-    int32_t *counts = (int32_t *)(out + plan.o_counts);
+    int32_t *counts = (int32_t *)(out + plan.o_tally);
     for (int j = 0; j < plan.nlaunch; ++j) {
         const DSim3Prob &D = dp[j];
         const size_t n = (size_t)D.n;
@@ -131,32 +106,28 @@ void orbx_sim3_host_run(const OrbxSim3Plan &plan, const uint8_t *in, uint8_t *ou
 orbx_sim3_batch *orbx_sim3_batch_new(const orbx_sim3_problem *problems, const OrbxSim3Plan &plan) {
     orbx_sim3_batch *b = new orbx_sim3_batch();
     b->st.resize((size_t)plan.nproblems);
-    b->o_hyp = plan.o_hyp; b->o_masks = plan.o_masks; b->o_counts = plan.o_counts;
-    size_t it = 0, wo = 0;
+    b->o_hyp = plan.o_hyp; b->o_masks = plan.o_masks; b->o_counts = plan.o_tally;
+    OrbxRansacWalk w = sim3_walk();
     for (int k = 0; k < plan.nproblems; ++k) {
         const orbx_sim3_problem &P = problems[k];
         OrbxSim3State &S = b->st[k];
         S.n = P.n; S.min_inliers = P.min_inliers; S.iterations = P.iterations; S.nwords = (P.n + 63) / 64;
         if (!sim3_launches(P)) continue;
-        S.iter_off = (int32_t)it; S.word_off = wo;
-        it += (size_t)P.iterations; wo += (size_t)P.iterations * (size_t)S.nwords;
+        const OrbxRansacWalk::At at = sim3_add(w, P);
+        S.iter_off = at.hyp_off; S.word_off = (size_t)at.word_off;
     }
     b->out.assign(plan.nlaunch > 0 ? plan.out_bytes : 0, 0);
     return b;
 }
 
-static const OrbxSim3State *sim3_state(const orbx_sim3_batch *b, int k, const char **why) {
-    if (!b) { *why = "no batch"; return nullptr; }
-    if (k < 0 || (size_t)k >= b->st.size()) { *why = "problem outside the batch"; return nullptr; }
-    return &b->st[k];
-}
+void orbx_sim3_batch_take(orbx_sim3_batch *b, const OrbxSim3Plan &plan, const uint8_t *out) { memcpy(b->out.data(), out, plan.out_bytes); }
 
 int32_t orbx_sim3_cursor_iterate(orbx_sim3_batch *b, int k, int n_iterations, int32_t *no_more, uint8_t *inliers, int32_t *ninliers,
                                  float *T12, const char **why) {
-    const OrbxSim3State *cs = sim3_state(b, k, why);
+    OrbxSim3State *cs = orbx_batch_state(b, k, why);
     if (!cs) return -1;
     if (!no_more || !ninliers || !T12 || (cs->n > 0 && !inliers)) { *why = "null result pointer"; return -1; }
-    OrbxSim3State &S = b->st[k];
+    OrbxSim3State &S = *cs;
     *no_more = 0;                                              // bNoMore = false; vbInliers all false; nInliers = 0
     if (S.n > 0) memset(inliers, 0, (size_t)S.n);
     *ninliers = 0;
@@ -172,7 +143,7 @@ int32_t orbx_sim3_cursor_iterate(orbx_sim3_batch *b, int k, int n_iterations, in
             if (counts[i] > S.min_inliers) {
                 *ninliers = counts[i];
                 const uint64_t *mw = (const uint64_t *)(b->out.data() + b->o_masks) + S.word_off + (size_t)i * S.nwords;
-                for (int p = 0; p < S.n; ++p) inliers[p] = (uint8_t)((mw[p >> 6] >> (p & 63)) & 1u);
+                orbx_unpack_mask(mw, S.n, inliers);
                 memcpy(T12, ((const OrbxSim3Hyp *)(b->out.data() + b->o_hyp))[S.iter_off + i].T12, 16 * sizeof(float));
                 return 1;
             }
@@ -183,7 +154,7 @@ int32_t orbx_sim3_cursor_iterate(orbx_sim3_batch *b, int k, int n_iterations, in
 }
 
 orbx_status orbx_sim3_cursor_best(const orbx_sim3_batch *b, int k, float *R, float *t, float *s, const char **why) {
-    const OrbxSim3State *S = sim3_state(b, k, why);
+    const OrbxSim3State *S = orbx_batch_state(b, k, why);
     if (!S) return ORBX_BAD_ARGUMENT;
     if (!R || !t || !s) { *why = "null result pointer"; return ORBX_BAD_ARGUMENT; }
     if (S->best_it < 0) { *why = "no iteration of this solver has run"; return ORBX_BAD_ARGUMENT; }
@@ -195,7 +166,7 @@ orbx_status orbx_sim3_cursor_best(const orbx_sim3_batch *b, int k, float *R, flo
 }
 
 orbx_status orbx_sim3_cursor_counts(const orbx_sim3_batch *b, int k, int32_t *counts, int32_t *niterations, const char **why) {
-    const OrbxSim3State *S = sim3_state(b, k, why);
+    const OrbxSim3State *S = orbx_batch_state(b, k, why);
     if (!S) return ORBX_BAD_ARGUMENT;
     const int nit = S->iter_off < 0 ? 0 : S->iterations;
     if (nit > 0 && !counts) { *why = "null counts"; return ORBX_BAD_ARGUMENT; }
@@ -206,7 +177,7 @@ orbx_status orbx_sim3_cursor_counts(const orbx_sim3_batch *b, int k, int32_t *co
 
 orbx_status orbx_sim3_cursor_hypothesis(const orbx_sim3_batch *b, int k, int iteration, float *hyp48, uint64_t *mask_words,
                                         const char **why) {
-    const OrbxSim3State *S = sim3_state(b, k, why);
+    const OrbxSim3State *S = orbx_batch_state(b, k, why);
     if (!S) return ORBX_BAD_ARGUMENT;
     if (S->iter_off < 0 || iteration < 0 || iteration >= S->iterations) { *why = "iteration outside the solver's stored results"; return ORBX_BAD_ARGUMENT; }
     if (hyp48) memcpy(hyp48, (const OrbxSim3Hyp *)(b->out.data() + b->o_hyp) + S->iter_off + iteration, sizeof(OrbxSim3Hyp));
@@ -222,11 +193,8 @@ extern "C" int32_t orbx_sim3_ransac_iterations(int32_t n, double probability, in
     int nIterations;
     if (min_inliers == n) nIterations = 1;
     else {
-        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow(epsilon, 3)));
-        // the reference converts the double as it is; outside int's range (epsilon^3 rounds to 0 or exceeds 1) that conversion is
-        // undefined, so the library fixes it: NaN and anything beyond the int range count as "more than max_iterations" when
-        // positive or NaN, and as the lowest int when negative
-        nIterations = !(v < 2147483648.0) ? 2147483647 : v < -2147483648.0 ? (-2147483647 - 1) : (int)v;
+        // outside int's range when epsilon^3 rounds to 0 or exceeds 1: NaN and +inf then count as "more than max_iterations"
+        nIterations = orbx_to_int_clamped(std::ceil(std::log(1 - probability) / std::log(1 - std::pow(epsilon, 3))));
     }
     return std::max(1, std::min(nIterations, max_iterations));
 }

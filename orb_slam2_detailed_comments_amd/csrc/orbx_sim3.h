@@ -13,6 +13,7 @@
 #pragma once
 #include <vector>
 #include "orbx_pose.h"
+#include "orbx_ransac.h"
 
 struct OrbxSim3Hyp {         // one hypothesis as the kernels store it and the host cursor reads it
     float T12[16], T21[16];  // mT12i, mT21i, row major
@@ -135,16 +136,6 @@ ORBX_UNROLL
             R[3 * i + j] = (float)(((i == j ? cs : 0.0) + (c1 * u[i]) * u[j]) + sn * K[3 * i + j]);
 }
 
-// A NaN's sign and payload differ between processors (x86 makes 0xffc00000, gfx950 0x7fc00000), so every stored float of a
-// hypothesis that is a NaN is stored as 0x7fc00000: "bit for bit" then holds outside the contract too.
-ORBX_HD static inline float orbx_sim3_canon(float x) {
-    uint32_t b;
-    __builtin_memcpy(&b, &x, 4);
-    if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;
-    __builtin_memcpy(&x, &b, 4);
-    return x;
-}
-
 // Sim3Solver::ComputeSim3: P1, P2 are the three points of each set, point i at P[3 i .. 3 i + 2] (the columns of the source's
 // 3x3 matrices).  Every 3x3 float product sums k = 0, 1, 2 in order, each product and each sum rounded to float.
 ORBX_HD static inline void orbx_sim3_compute(const float *P1, const float *P2, int fix_scale, OrbxSim3Hyp &H) {
@@ -215,12 +206,12 @@ ORBX_UNROLL
     }
     H.T12[15] = 1.0f; H.T21[15] = 1.0f;
 ORBX_UNROLL
-    for (int i = 0; i < 12; ++i) { H.T12[i] = orbx_sim3_canon(H.T12[i]); H.T21[i] = orbx_sim3_canon(H.T21[i]); }
+    for (int i = 0; i < 12; ++i) { H.T12[i] = orbx_canonf(H.T12[i]); H.T21[i] = orbx_canonf(H.T21[i]); }
 ORBX_UNROLL
-    for (int i = 0; i < 9; ++i) H.R[i] = orbx_sim3_canon(H.R[i]);
+    for (int i = 0; i < 9; ++i) H.R[i] = orbx_canonf(H.R[i]);
 ORBX_UNROLL
-    for (int i = 0; i < 3; ++i) H.t[i] = orbx_sim3_canon(H.t[i]);
-    H.s = orbx_sim3_canon(H.s);
+    for (int i = 0; i < 3; ++i) H.t[i] = orbx_canonf(H.t[i]);
+    H.s = orbx_canonf(H.s);
     H.pad[0] = 0.0f; H.pad[1] = 0.0f; H.pad[2] = 0.0f;
 }
 
@@ -268,24 +259,9 @@ struct DSim3Prob {                  // one problem that launches, as the kernels
     float K1[4], K2[4];
 };
 static_assert(sizeof(DSim3Prob) == 64, "packed for the device");
-struct DSim3Args {
-    const DSim3Prob *prob;
-    const int32_t *iter_prob;       // [total_iters] the problem of a hypothesis
-    const int32_t *sets;            // [total_iters][3]
-    const int32_t *groups;          // [ngroups][2]: problem, first iteration of a workgroup of k_sim3_inliers
-    const float *pts;
-    int total_iters, ngroups;
-    OrbxSim3Hyp *hyp;
-    int32_t *counts;
-    unsigned long long *masks;
-};
-// Uploaded block (one copy): DSim3Prob[nlaunch] | iter_prob | sets | groups | pts.  Downloaded block: hyp | masks | counts.
-struct OrbxSim3Plan {
-    int nproblems = 0, nlaunch = 0, total_iters = 0, ngroups = 0;
-    size_t total_pts = 0, total_words = 0;
-    size_t o_prob = 0, o_iter_prob = 0, o_sets = 0, o_groups = 0, o_pts = 0, in_bytes = 0;
-    size_t o_hyp = 0, o_masks = 0, o_counts = 0, out_bytes = 0;
-};
+// sets: [total_hyps][3]; a group: ORBX_SIM3_WAVES iterations of k_sim3_inliers; tally: the inlier counts
+using DSim3Args = DRansacArgs<DSim3Prob, OrbxSim3Hyp, int32_t>;
+using OrbxSim3Plan = OrbxRansacPlan;
 orbx_status orbx_sim3_plan(int nproblems, const orbx_sim3_problem *problems, OrbxSim3Plan &plan, const char **why);
 void orbx_sim3_pack(const orbx_sim3_problem *problems, const OrbxSim3Plan &plan, uint8_t *dst);
 // the host path: reads the packed block, writes the downloaded block's layout (hyp | masks | counts) into out
@@ -303,6 +279,7 @@ struct orbx_sim3_batch {
     size_t o_hyp = 0, o_masks = 0, o_counts = 0;
 };
 orbx_sim3_batch *orbx_sim3_batch_new(const orbx_sim3_problem *problems, const OrbxSim3Plan &plan);   // out zeroed, states at start
+void orbx_sim3_batch_take(orbx_sim3_batch *b, const OrbxSim3Plan &plan, const uint8_t *out);         // the downloaded block, copied
 // The cursor behind orbx_sim3_batch_iterate / _best / _counts / _hypothesis; *why names what was wrong
 int32_t orbx_sim3_cursor_iterate(orbx_sim3_batch *b, int k, int n_iterations, int32_t *no_more, uint8_t *inliers, int32_t *ninliers,
                                  float *T12, const char **why);

@@ -10,17 +10,17 @@ import numpy as np
 
 from . import _capi
 from ._capi import INIT_F, INIT_H, INIT_NONE, check, ptr  # noqa: F401
+from ._ransac import RansacBatch, mask_bits
 
 
-class InitializerRansac:
+class InitializerRansac(RansacBatch):
     """problems: dicts with keys1 [n1, 2], keys2 [n2, 2] (float32, ALL keypoints of each frame), matches [n, 2] (int32: index in
     1, index in 2), sigma, iterations, sets [iterations, 8] (the draws in order; not read where n < 8) and models
     (INIT_H | INIT_F, the default)."""
+    _destroy = "orbx_init_batch_destroy"
 
     def __init__(self, extractor, problems):
-        self._L = _capi.lib()
-        self._b = C.c_void_p()
-        self.n = []
+        super().__init__()
         arr = (_capi.InitProblem * max(len(problems), 1))()
         keep = []
         for k, p in enumerate(problems):
@@ -43,9 +43,6 @@ class InitializerRansac:
             a.models = int(p.get("models", INIT_H | INIT_F))
             self.n.append(len(m))
         check(self._L.orbx_init_ransac_batch_create(extractor.handle, len(problems), C.cast(arr, C.c_void_p), C.byref(self._b)))
-
-    def __len__(self):
-        return len(self.n)
 
     def result(self, k):
         """dict: SH, SF, H21 and F21 (3x3 float32), inliersH and inliersF (bool [n]), itH and itF (-1: none), RH, model"""
@@ -73,21 +70,9 @@ class InitializerRansac:
         sc = np.zeros(1, np.float32)
         w = np.zeros(max((n + 63) // 64, 1), np.uint64)
         check(self._L.orbx_init_batch_hypothesis(self._b, int(k), int(model), int(it), ptr(M), ptr(Mi), ptr(sc), ptr(w)))
-        bits = np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
-        return M.reshape(3, 3), Mi.reshape(3, 3), sc[0], bits
+        return M.reshape(3, 3), Mi.reshape(3, 3), sc[0], mask_bits(w, n)
 
     def normalization(self, k):
         T1, T2 = np.zeros(9, np.float32), np.zeros(9, np.float32)
         check(self._L.orbx_init_batch_normalization(self._b, int(k), ptr(T1), ptr(T2)))
         return T1.reshape(3, 3), T2.reshape(3, 3)
-
-    def close(self):
-        if self._b:
-            self._L.orbx_init_batch_destroy(self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

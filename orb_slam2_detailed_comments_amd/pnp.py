@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import check, ptr
+from ._ransac import RansacBatch, mask_bits, round_robin
 
 
 def pnp_ransac_parameters(n, probability=0.99, min_inliers=8, max_iterations=300, min_set=4, epsilon=0.4):
@@ -20,14 +21,13 @@ def pnp_ransac_parameters(n, probability=0.99, min_inliers=8, max_iterations=300
     return int(mi.value), int(it.value)
 
 
-class PnPRansac:
+class PnPRansac(RansacBatch):
     """problems: dicts with p3dw [n, 3], p2d [n, 2], max_err [n] (float32), camera (fu, fv, uc, vc as doubles), min_inliers and
     iterations (both after SetRansacParameters) and sets [iterations, 4] (the draws in order; not read where n < min_inliers)."""
+    _destroy = "orbx_pnp_batch_destroy"
 
     def __init__(self, extractor, problems):
-        self._L = _capi.lib()
-        self._b = C.c_void_p()
-        self.n = []
+        super().__init__()
         arr = (_capi.PnpProblem * max(len(problems), 1))()
         keep = []
         for k, p in enumerate(problems):
@@ -50,9 +50,6 @@ class PnPRansac:
             a.sets = sets.ctypes.data if sets is not None and sets.size else None
             self.n.append(n)
         check(self._L.orbx_pnp_ransac_batch_create(extractor.handle, len(problems), C.cast(arr, C.c_void_p), C.byref(self._b)))
-
-    def __len__(self):
-        return len(self.n)
 
     def iterate(self, k, n_iterations, draw=None):
         """PnPsolver::iterate of solver k: (Tcw 4x4 float32 or None, no_more, inliers bool [n], ninliers).  When the replay needs
@@ -108,19 +105,7 @@ class PnPRansac:
         N = C.c_int32(0)
         w = np.zeros(max((n + 63) // 64, 1), np.uint64)
         check(self._L.orbx_pnp_batch_hypothesis(self._b, int(k), int(iteration), ptr(rt), ptr(T), C.byref(N), ptr(w)))
-        bits = np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
-        return rt, T, int(N.value), bits
-
-    def close(self):
-        if self._b:
-            self._L.orbx_pnp_batch_destroy(self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return rt, T, int(N.value), mask_bits(w, n)
 
 
 def relocalization_round_robin(ransac, accept, n_iterations=5, draw=None):
@@ -129,19 +114,4 @@ def relocalization_round_robin(ransac, accept, n_iterations=5, draw=None):
     that reports no_more is discarded; accept(k, Tcw, inliers, ninliers) -- PoseOptimization, the guided searches and the >= 50
     test in the reference -- ends the loop when it returns true.  Returns the accepted solver's index or -1, and the list of
     (k, returned, no_more, ninliers) calls made."""
-    K = len(ransac)
-    discarded = [False] * K
-    live = K
-    calls = []
-    while live > 0:
-        for k in range(K):
-            if discarded[k]:
-                continue
-            T, no_more, inl, nin = ransac.iterate(k, n_iterations, draw)
-            calls.append((k, T is not None, no_more, nin))
-            if no_more:
-                discarded[k] = True
-                live -= 1
-            if T is not None and accept(k, T, inl, nin):
-                return k, calls
-    return -1, calls
+    return round_robin(ransac, accept, n_iterations, draw)

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import check, ptr
+from ._ransac import RansacBatch, mask_bits, round_robin
 
 
 def ransac_iterations(n, probability=0.99, min_inliers=6, max_iterations=300):
@@ -17,15 +18,14 @@ def ransac_iterations(n, probability=0.99, min_inliers=6, max_iterations=300):
     return int(_capi.lib().orbx_sim3_ransac_iterations(int(n), float(probability), int(min_inliers), int(max_iterations)))
 
 
-class Sim3Ransac:
+class Sim3Ransac(RansacBatch):
     """problems: dicts with x1c, x2c [n, 3], max_err1, max_err2 [n], camera1, camera2 (fx, fy, cx, cy), fix_scale, min_inliers,
     iterations (mRansacMaxIts after SetRansacParameters) and sets [iterations, 3] (the draws in order; not read where
     n < min_inliers)."""
+    _destroy = "orbx_sim3_batch_destroy"
 
     def __init__(self, extractor, problems):
-        self._L = _capi.lib()
-        self._b = C.c_void_p()
-        self.n = []
+        super().__init__()
         arr = (_capi.Sim3Problem * max(len(problems), 1))()
         keep = []
         for k, p in enumerate(problems):
@@ -52,9 +52,6 @@ class Sim3Ransac:
             self.n.append(n)
         check(self._L.orbx_sim3_ransac_batch_create(extractor.handle, len(problems), C.cast(arr, C.c_void_p), C.byref(self._b)))
         self.iterations = [int(p["iterations"]) for p in problems]
-
-    def __len__(self):
-        return len(self.n)
 
     def iterate(self, k, n_iterations):
         """Sim3Solver::iterate of solver k: (T12 4x4 float32 or None, no_more, inliers bool [n], ninliers)"""
@@ -85,19 +82,7 @@ class Sim3Ransac:
         h = np.zeros(48, np.float32)
         w = np.zeros(max((n + 63) // 64, 1), np.uint64)
         check(self._L.orbx_sim3_batch_hypothesis(self._b, int(k), int(iteration), ptr(h), ptr(w)))
-        bits = np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
-        return h, bits
-
-    def close(self):
-        if self._b:
-            self._L.orbx_sim3_batch_destroy(self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return h, mask_bits(w, n)
 
 
 def compute_sim3_round_robin(ransac, accept, n_iterations=5):
@@ -105,19 +90,4 @@ def compute_sim3_round_robin(ransac, accept, n_iterations=5):
     __len__ and iterate(k, n)): every live solver gets iterate(n_iterations) in turn; a solver that reports no_more is
     discarded; accept(k, T12, inliers, ninliers) -- OptimizeSim3 and the >= 20 test in the reference -- ends the loop when it
     returns true.  Returns the accepted solver's index or -1, and the list of (k, returned, no_more, ninliers) calls made."""
-    K = len(ransac)
-    discarded = [False] * K
-    live = K
-    calls = []
-    while live > 0:
-        for k in range(K):
-            if discarded[k]:
-                continue
-            T, no_more, inl, nin = ransac.iterate(k, n_iterations)
-            calls.append((k, T is not None, no_more, nin))
-            if no_more:
-                discarded[k] = True
-                live -= 1
-            if T is not None and accept(k, T, inl, nin):
-                return k, calls
-    return -1, calls
+    return round_robin(ransac, accept, n_iterations)
