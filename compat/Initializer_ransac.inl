@@ -13,9 +13,12 @@
 // in place of those four statements.  The fragment is a block of statements.  It reads mvKeys1, mvKeys2, mvMatches12, mvSets,
 // mSigma and mMaxIterations and fills vbMatchesInliersH, SH, H, vbMatchesInliersF, SF, F exactly as the two threads do: the best
 // iteration of each model is the first strict maximum of its score from 0; when no iteration of a model scores above 0 its
-// matrix stays the empty cv::Mat it was, its mask is all false and its score 0.  What follows -- RH, ReconstructH,
-// ReconstructF, CheckRT, Triangulate -- stays the reference's.  FindHomography, FindFundamental, ComputeH21, ComputeF21,
-// CheckHomography, CheckFundamental and Normalize are no longer called from Initialize.
+// matrix stays the empty cv::Mat it was, its mask is all false and its score 0.  What follows in Initialize -- RH, the choice of
+// the model, the calls of ReconstructH / ReconstructF -- stays the reference's text; the BODIES of ReconstructH and
+// ReconstructF have a drop-in of their own, compat/Initializer_reconstruct.inl (with it DecomposeE, CheckRT and Triangulate are
+// no longer called either).  Pinned: the six variables equal tests/init_model.py bit for bit for the same draws.  Not pinned:
+// parity with an OpenCV build.  FindHomography, FindFundamental, ComputeH21, ComputeF21, CheckHomography, CheckFundamental and
+// Normalize are no longer called from Initialize.
 //
 // ONE call evaluates both models: every iteration of H and of F is a lane of the same launch (include/orbx.h,
 // orbx_init_ransac_batch_create).  The handle is thread_local, since a handle is not re-entrant, and is created on the current

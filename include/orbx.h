@@ -908,7 +908,8 @@ orbx_status orbx_pnp_batch_hypothesis(const orbx_pnp_batch *b, int k, int iterat
 void orbx_pnp_batch_destroy(orbx_pnp_batch *b);
 
 /* ---- Initializer (src/Initializer.cc), the H / F RANSAC of monocular initialisation: what Initializer::Initialize runs on its
- * two threads (:204-215) between SearchForInitialization and ReconstructH / ReconstructF, for any number of initialisation
+ * two threads (:204-215) between SearchForInitialization and ReconstructH / ReconstructF (which follow below:
+ * orbx_init_reconstruct_batch_create, and both in one round trip: orbx_initialize_batch_create), for any number of initialisation
  * attempts in one device round trip.  An iteration is an independent eight-point DLT followed by one pass over every match, so
  * every iteration of both models of every attempt is evaluated at once -- k_init_hypotheses: one lane per (problem, model,
  * iteration) builds A from the eight normalised matches, takes its null vector in a lane-interleaved LDS workspace, projects F
@@ -960,6 +961,74 @@ orbx_status orbx_init_batch_hypothesis(const orbx_init_batch *b, int k, int mode
 /* tests and tools: Normalize's T1 and T2 [9] each, row major */
 orbx_status orbx_init_batch_normalization(const orbx_init_batch *b, int k, float *T1, float *T2);
 void orbx_init_batch_destroy(orbx_init_batch *b);
+
+/* ---- Initializer, from the winning matrix to a map: ReconstructF (:963-1132) or ReconstructH (:1154-1462) with DecomposeE,
+ * CheckRT and Triangulate, for any number of attempts in one device round trip.  Any matrix and inlier mask go in (the result of
+ * orbx_init_batch_result, or anything else); R21, t21, the triangulated points and their flags come out.
+ * k_init_decompose: one lane per problem forms E21 = (K^T F21) K or A = (Kinv H21) K, takes the 3 x 3 SVD and stores the 4 (F) or
+ * 8 (H) pose hypotheses with P2 = K [R | t] and O2 = -R^T t.  k_init_check_rt: one wave per (problem, pose hypothesis), the
+ * lanes striding over the matches; per inlier match Triangulate (the 4 x 4 null vector in registers) and the tests of CheckRT,
+ * nGood as a ballot count, vCosParallax[min(50, size - 1)] as an exact selection by value (32 bisection steps on the integer key
+ * of the float: no sort, no atomics).  k_init_pick: one wave per problem copies the planes of the only hypothesis that can win
+ * -- F: the first i with nGood_i == maxGood; H: the first strict maximum -- into the block that is downloaded.  acos and the
+ * accept / reject arithmetic of both functions run on the host in double, once per hypothesis.
+ * CONTRACT: every R, t, n, nGood, cosine, parallax, status byte, point, the chosen hypothesis and ok of the device equal the
+ * library's host path (ORBX_RECON=host in the environment, read per call; host-only handles) and the numpy restatement
+ * tests/recon_model.py bit for bit, in both fp_modes.  Parity with an OpenCV build is NOT pinned: DESIGN.md section 2 (F15)
+ * lists what follows the reference's source and what this library fixes where the reference leaves it to OpenCV or libm (the
+ * 3 x 3 and 4 x 4 SVD, cv::determinant, cv::norm, Mat::dot, the products, Mat / scalar, the order statistic, acosf).
+ * Outputs are per MATCH, in match order, not per keypoint: status 0 -- skipped or rejected, 1 -- the point is not finite
+ * (vbGood[first] = false), 2 -- counted in nGood (the point is stored), 3 -- counted and vbGood[first] = true.  Scattering them
+ * to vP3D[first] / vbTriangulated[first] in match order reproduces the reference for repeated `first` indices too.
+ * A problem with n == 0 or an all-false mask launches nothing and reports failure with zero counts.
+ * Validated before any device work, ORBX_BAD_ARGUMENT: nproblems < 0, a negative count, a null array whose size is positive, a
+ * model that is neither ORBX_INIT_H nor ORBX_INIT_F, a match index outside its frame, sigma or an intrinsic that is not finite,
+ * sigma, fx or fy not > 0, min_parallax NaN.  nproblems == 0 gives an empty batch.
+ * OUTSIDE the contract (dist1 * dist2 == 0, non-finite keypoints or matrix): the same straight-line code runs, a NaN compares
+ * false wherever the source compares it, a stored NaN is the canonical quiet NaN and sorts after +infinity. */
+typedef struct orbx_recon_problem {
+    int32_t n1, n2;  const float *keys1, *keys2;   /* [n1][2], [n2][2]: mvKeys1 / mvKeys2 pt */
+    int32_t n;       const int32_t *matches;        /* [n][2] mvMatches12 in order (index in 1, index in 2) */
+    const uint8_t *inliers;                         /* [n] vbMatchesInliers, 0 = false */
+    int32_t model;                                  /* ORBX_INIT_H: M is H21 (ReconstructH); ORBX_INIT_F: M is F21 (ReconstructF) */
+    float M[9];                                     /* row major */
+    float K[4];                                     /* fx, fy, cx, cy */
+    float sigma;                                    /* mSigma */
+    float min_parallax;                             /* minParallax, 1.0 in Initialize */
+    int32_t min_triangulated;                       /* minTriangulated, 50 in Initialize */
+} orbx_recon_problem;
+typedef struct orbx_recon_batch orbx_recon_batch;
+/* One page-locked block up, three kernels, one block down; the batch owns copies of the results and needs neither the handle
+ * nor the caller's arrays afterwards.  On a host-only handle the library's host path runs. */
+orbx_status orbx_init_reconstruct_batch_create(orbx_handle *h, int nproblems, const orbx_recon_problem *problems,
+                                               orbx_recon_batch **out);
+/* Problem k: ok (the function's return value), R21 [9] and t21 [3] (zeros when not ok, where the reference leaves empty
+ * cv::Mat), the hypothesis the points belong to (-1: none -- nothing launched, ReconstructH returned early, or every count of
+ * ReconstructH was 0), its per-match status [n] and points [n][3] (zeros where nothing was stored; they are filled whether ok or
+ * not, the reference copies them only when ok), and N, the number of true mask entries.  Any pointer may be NULL. */
+orbx_status orbx_recon_batch_result(const orbx_recon_batch *b, int k, int32_t *ok, float *R21, float *t21, int32_t *chosen,
+                                    uint8_t *status, float *points, int32_t *N);
+/* tests and tools: pose hypothesis i of problem k (0..3 for F, 0..7 for H): R [9], t [3], n [3] (zeros for F), nGood, the
+ * selected cosine (0 when nGood == 0), parallax in degrees, valid (0: not evaluated); any pointer may be NULL */
+orbx_status orbx_recon_batch_hypothesis(const orbx_recon_batch *b, int k, int i, float *R9, float *t3, float *n3, int32_t *nGood,
+                                        float *cosine, float *parallax, int32_t *valid);
+void orbx_recon_batch_destroy(orbx_recon_batch *b);
+/* Initializer::Initialize from :204 to its return, for any number of attempts in ONE upload and ONE download: hypotheses, scores,
+ * k_init_select (one wave per problem: the first strict maximum of each model's scores from 0, RH and the model by the rule and
+ * with the bits of orbx_init_ransac_batch_create; it writes the winning matrix, the model and the winning mask as inlier bytes
+ * where the reconstruction kernels read them), decompose, check, pick.  cameras[k] goes with problems[k].
+ * CONTRACT: *ransac equals what orbx_init_ransac_batch_create gives for the same problems and *recon what
+ * orbx_init_reconstruct_batch_create gives when fed with that result (the chosen model's matrix and mask), bit for bit.  A problem
+ * whose model is ORBX_INIT_NONE reconstructs nothing and reports failure; it reads as an F problem with an all-false mask.
+ * The fused sequence runs on a device handle when neither ORBX_INIT nor ORBX_RECON is "host"; otherwise the two calls run one after
+ * the other, each by its own switch.  Validation is that of both calls, before any device work. */
+typedef struct orbx_init_camera {
+    float K[4];                                     /* fx, fy, cx, cy */
+    float min_parallax;                             /* 1.0 in Initialize */
+    int32_t min_triangulated;                       /* 50 in Initialize */
+} orbx_init_camera;
+orbx_status orbx_initialize_batch_create(orbx_handle *h, int nproblems, const orbx_init_problem *problems,
+                                         const orbx_init_camera *cameras, orbx_init_batch **ransac, orbx_recon_batch **recon);
 
 #ifdef __cplusplus
 }

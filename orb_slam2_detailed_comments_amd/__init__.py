@@ -14,4 +14,4 @@ from .mappoint import (distinctive_descriptors_batch, distinctive_descriptors_ba
 from .optimizer import pose_optimization, pose_optimization_batch  # noqa: F401
 from .sim3 import Sim3Ransac, compute_sim3_round_robin, ransac_iterations  # noqa: F401
 from .pnp import PnPRansac, relocalization_round_robin, pnp_ransac_parameters  # noqa: F401
-from .initializer import InitializerRansac, INIT_NONE, INIT_H, INIT_F  # noqa: F401
+from .initializer import InitializerRansac, InitializerReconstruct, initialize_batch, INIT_NONE, INIT_H, INIT_F  # noqa: F401

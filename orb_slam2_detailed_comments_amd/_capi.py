@@ -88,6 +88,16 @@ class InitProblem(C.Structure):   # orbx_init_problem
                 ("models", C.c_int32)]
 
 
+class ReconProblem(C.Structure):   # orbx_recon_problem
+    _fields_ = [("n1", C.c_int32), ("n2", C.c_int32), ("keys1", C.c_void_p), ("keys2", C.c_void_p), ("n", C.c_int32),
+                ("matches", C.c_void_p), ("inliers", C.c_void_p), ("model", C.c_int32), ("M", C.c_float * 9), ("K", C.c_float * 4),
+                ("sigma", C.c_float), ("min_parallax", C.c_float), ("min_triangulated", C.c_int32)]
+
+
+class InitCamera(C.Structure):   # orbx_init_camera
+    _fields_ = [("K", C.c_float * 4), ("min_parallax", C.c_float), ("min_triangulated", C.c_int32)]
+
+
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
 
 TRACK_STATE_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),
@@ -161,6 +171,8 @@ SYMBOLS = [
     "orbx_pnp_batch_best", "orbx_pnp_batch_counts", "orbx_pnp_batch_hypothesis", "orbx_pnp_batch_destroy",
     "orbx_init_ransac_batch_create", "orbx_init_batch_result", "orbx_init_batch_scores", "orbx_init_batch_hypothesis",
     "orbx_init_batch_normalization", "orbx_init_batch_destroy",
+    "orbx_init_reconstruct_batch_create", "orbx_recon_batch_result", "orbx_recon_batch_hypothesis", "orbx_recon_batch_destroy",
+    "orbx_initialize_batch_create",
 ]
 
 _lib = None
@@ -241,6 +253,14 @@ def lib():
         L.orbx_init_batch_hypothesis.restype = i32; L.orbx_init_batch_hypothesis.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
         L.orbx_init_batch_normalization.restype = i32; L.orbx_init_batch_normalization.argtypes = [vp, i32, vp, vp]
         L.orbx_init_batch_destroy.restype = None; L.orbx_init_batch_destroy.argtypes = [vp]
+    if hasattr(L, "orbx_init_reconstruct_batch_create"):
+        L.orbx_init_reconstruct_batch_create.restype = i32; L.orbx_init_reconstruct_batch_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+        L.orbx_recon_batch_result.restype = i32; L.orbx_recon_batch_result.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.orbx_recon_batch_hypothesis.restype = i32
+        L.orbx_recon_batch_hypothesis.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.orbx_recon_batch_destroy.restype = None; L.orbx_recon_batch_destroy.argtypes = [vp]
+        L.orbx_initialize_batch_create.restype = i32
+        L.orbx_initialize_batch_create.argtypes = [vp, i32, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     L.orbx_get_stream.restype = vp; L.orbx_get_stream.argtypes = [vp]
     L.orbx_set_stream.restype = i32; L.orbx_set_stream.argtypes = [vp, vp]
     L.orbx_synchronize.restype = i32; L.orbx_synchronize.argtypes = [vp]

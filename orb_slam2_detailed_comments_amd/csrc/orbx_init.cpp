@@ -8,7 +8,7 @@
 #include "orbx_init.h"
 
 static inline int init_nmodels(int32_t models) { return (models & 1) + ((models >> 1) & 1); }
-static inline bool init_launches(const orbx_init_problem &P) { return P.n >= 8 && P.models != 0; }
+static inline bool init_launches(const orbx_init_problem &P) { return orbx_init_launches(P); }
 static inline OrbxRansacWalk init_walk(int32_t *hyp_prob = nullptr, int32_t *groups = nullptr) {
     return OrbxRansacWalk(0x0fffffff, 0x3fffffff, hyp_prob, groups);
 }

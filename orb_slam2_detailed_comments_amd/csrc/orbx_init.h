@@ -271,6 +271,8 @@ ORBX_HD static inline int orbx_init_iteration(const DInitProb &D, int l) { retur
 // k_init_scores; tally: the scores
 using DInitArgs = DRansacArgs<DInitProb, OrbxInitHyp, float>;
 using OrbxInitPlan = OrbxRansacPlan;
+// a problem that has hypotheses to compute; any other launches nothing and reports ORBX_INIT_NONE
+static inline bool orbx_init_launches(const orbx_init_problem &P) { return P.n >= 8 && P.models != 0; }
 orbx_status orbx_init_plan(int nproblems, const orbx_init_problem *problems, OrbxInitPlan &plan, const char **why);
 void orbx_init_pack(const orbx_init_problem *problems, const OrbxInitPlan &plan, uint8_t *dst);
 // the host path: reads the packed block, writes the downloaded block's layout (hyp | masks | scores) into out

@@ -4775,6 +4775,149 @@ __global__ __launch_bounds__(ORBX_INIT_SCORE_LANES) void k_init_scores(const DIn
     if (active) A.tally[D.hyp_off + l] = orbx_canonf(score);
 }
 
+#include "orbx_recon.h"
+// ReconstructH / ReconstructF, batched (orbx_recon.h).  k_init_decompose: one lane per problem forms E21 or A, takes the 3 x 3
+// SVD -- its columns are picked at run time, so the matrix and its V live in the lane's slice of an LDS workspace, element e of
+// lane l at float index e * ORBX_RECON_LANES + l -- and stores the problem's 4 or 8 pose records.  The lanes share no data and
+// take no barrier.
+__global__ __launch_bounds__(ORBX_RECON_LANES) void k_init_decompose(const DReconArgs A) {
+    __shared__ float s_ws[ORBX_RECON_WS_FLOATS * ORBX_RECON_LANES];
+    const int j = blockIdx.x * ORBX_RECON_LANES + threadIdx.x;
+    if (j >= A.nlaunch) return;
+    const DReconProb &D = A.prob[j];
+    const OrbxInitWs W = {s_ws + threadIdx.x, ORBX_RECON_LANES};
+    float M[9], K[4];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M[k] = D.M[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) K[k] = D.K[k];
+    OrbxReconPose *out = A.pose + (long long)ORBX_RECON_MAX_HYP * j;
+    if (D.nhyp == 0) return;                                    // fused call: ORBX_INIT_NONE, nothing of this problem is read
+    if (D.is_h) orbx_recon_decompose_h(W, M, K, out);
+    else orbx_recon_decompose_f(W, M, K, out);
+}
+// k_init_check_rt: CheckRT with Triangulate.  One workgroup = one wave = one (problem, pose hypothesis); lane l takes the matches
+// l, l + 64, ...  Per match it writes the status byte, the point and the cosine into the hypothesis' planes (zeros where nothing
+// is stored); nGood is the sum of the ballot population counts, the same whatever the lane order.  The order statistic
+// vCosParallax[min(50, nGood - 1)] is selected by value: the largest key K with #{key < K} <= idx, built bit by bit from the top
+// in 32 steps, each a ballot count over the cosines -- every lane reads back only what it wrote itself.  No LDS, no atomics.
+__global__ __launch_bounds__(64) void k_init_check_rt(const DReconArgs A) {
+    const int h = blockIdx.x, j = h / ORBX_RECON_MAX_HYP, i = h % ORBX_RECON_MAX_HYP;
+    if (j >= A.nlaunch) return;
+    const DReconProb &D = A.prob[j];
+    if (i >= D.nhyp) return;                                    // slots 4 .. 7 of an F problem; every slot of a problem without a model
+    const int n = D.n, lane = threadIdx.x;
+    const OrbxReconPose P = A.pose[h];
+    float K[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) K[k] = D.K[k];
+    const float th2 = D.th2;
+    const long long plane = (long long)ORBX_RECON_MAX_HYP * D.m_off + (long long)i * n;
+    uint8_t *st = A.all_st + plane;
+    float *pts = A.all_pts + 3 * plane, *cs = A.all_cos + plane;
+    const float *pl = A.keys + D.key_off;
+    const uint8_t *inl = A.inl + D.m_off;
+    int nGood = 0;
+    for (int base = 0; base < n; base += 64) {
+        const int m = base + lane;
+        int s = 0;
+        float pt[3] = {0.0f, 0.0f, 0.0f}, c = 0.0f;
+        if (m < n && P.valid && inl[m])
+            s = orbx_recon_check_match(P, K, th2, pl[m], pl[(long long)n + m], pl[2 * (long long)n + m], pl[3 * (long long)n + m], pt, c);
+        const bool counted = s >= 2;
+        if (m < n) {
+            st[m] = (uint8_t)s;
+            pts[3 * (long long)m] = counted ? pt[0] : 0.0f;
+            pts[3 * (long long)m + 1] = counted ? pt[1] : 0.0f;
+            pts[3 * (long long)m + 2] = counted ? pt[2] : 0.0f;
+            cs[m] = counted ? c : 0.0f;
+        }
+        nGood += __popcll(__ballot(counted));
+    }
+    float cosine = 0.0f;
+    if (nGood > 0) {                                            // wave-uniform
+        const int idx = nGood - 1 < ORBX_RECON_IDX ? nGood - 1 : ORBX_RECON_IDX;
+        uint32_t key = 0;
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t trial = key | (1u << bit);
+            int below = 0;
+            for (int base = 0; base < n; base += 64) {
+                const int m = base + lane;
+                const bool lt = m < n && st[m] >= 2 && orbx_recon_key(cs[m]) < trial;
+                below += __popcll(__ballot(lt));
+            }
+            if (below <= idx) key = trial;
+        }
+        cosine = orbx_recon_unkey(key);
+    }
+    if (lane == 0) {
+        OrbxReconTally T;
+        T.nGood = nGood; T.cosine = cosine;
+        A.tally[h] = T;
+    }
+}
+// k_init_select (the fused call only): one wave per problem that launched its RANSAC.  Per requested model the first strict
+// maximum of the scores from 0 -- each lane keeps the first strict maximum of the iterations l, l + 64, ... it visits in
+// ascending order, the wave takes the largest of those and, among equal ones, the lowest iteration; a NaN never wins --, then RH
+// and the model (orbx_recon_choose), and the reconstruction's record: is_h, nhyp, the winning matrix, and the winning mask
+// unpacked into the problem's inlier bytes.  Without a model nhyp stays 0 and the inlier bytes are cleared.
+__global__ __launch_bounds__(64) void k_init_select(const DInitArgs I, const DReconArgs A) {
+    const int j = blockIdx.x;
+    if (j >= A.nlaunch) return;
+    const DInitProb &D = I.prob[j];
+    const int lane = threadIdx.x, n = D.n;
+    float S[2] = {0.0f, 0.0f};
+    int it[2] = {-1, -1};
+#pragma unroll
+    for (int mo = 0; mo < 2; ++mo) {
+        if (!(D.models & (1 << mo))) continue;
+        const float *sc = I.tally + D.hyp_off + ((mo == 1 && (D.models & 1)) ? D.iterations : 0);
+        float best = 0.0f;
+        int at = -1;
+        for (int l = lane; l < D.iterations; l += 64) {
+            const float s = sc[l];
+            if (s > best) { best = s; at = l; }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const float ob = __shfl_xor(best, d);
+            const int oa = __shfl_xor(at, d);
+            if (oa >= 0 && (at < 0 || ob > best || (ob == best && oa < at))) { best = ob; at = oa; }
+        }
+        S[mo] = best; it[mo] = at;
+    }
+    const int model = orbx_recon_choose(S[0], S[1], it[0], it[1]);
+    DReconProb &R = A.prob[j];
+    uint8_t *inl = A.inl + R.m_off;
+    if (model == ORBX_INIT_NONE) {
+        for (int m = lane; m < n; m += 64) inl[m] = 0;
+        return;
+    }
+    const bool is_h = model == ORBX_INIT_H;
+    const int l = (is_h || !(D.models & 1) ? 0 : D.iterations) + (is_h ? it[0] : it[1]);
+    const unsigned long long *mw = I.masks + D.word_off + (long long)l * D.nwords;
+    for (int m = lane; m < n; m += 64) inl[m] = (uint8_t)((mw[m >> 6] >> (m & 63)) & 1ull);
+    if (lane < 9) R.M[lane] = I.hyp[D.hyp_off + l].M[lane];
+    if (lane == 0) { R.is_h = is_h ? 1 : 0; R.nhyp = is_h ? 8 : 4; }
+}
+// k_init_pick: one wave per problem.  Which hypothesis can win depends on the counts alone (orbx_recon_candidate); only its status
+// and point planes go into the block that is downloaded, zeros when there is none.
+__global__ __launch_bounds__(64) void k_init_pick(const DReconArgs A) {
+    const int j = blockIdx.x;
+    if (j >= A.nlaunch) return;
+    const DReconProb &D = A.prob[j];
+    const int n = D.n, lane = threadIdx.x;
+    const int c = D.nhyp == 0 ? -1 : orbx_recon_candidate(D.is_h != 0, A.tally + (long long)ORBX_RECON_MAX_HYP * j);
+    if (lane == 0) A.chosen[j] = c;
+    const long long plane = (long long)ORBX_RECON_MAX_HYP * D.m_off + (long long)(c >= 0 ? c : 0) * n;
+    const uint8_t *st = A.all_st + plane;
+    const float *pts = A.all_pts + 3 * plane;
+    uint8_t *ost = A.st + D.m_off;
+    float *opts = A.pts + 3 * (long long)D.m_off;
+    for (int m = lane; m < n; m += 64) ost[m] = c >= 0 ? st[m] : (uint8_t)0;
+    for (int e = lane; e < 3 * n; e += 64) opts[e] = c >= 0 ? pts[e] : 0.0f;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from the C ABI units)
 // ------------------------------------------------------------------------------------------------
@@ -5232,4 +5375,14 @@ void orbx_launch_init(hipStream_t s, const DInitArgs &a) {
     hipLaunchKernelGGL(k_init_hypotheses, dim3((a.total_hyps + ORBX_INIT_HYP_LANES - 1) / ORBX_INIT_HYP_LANES),
                        dim3(ORBX_INIT_HYP_LANES), 0, s, a);
     hipLaunchKernelGGL(k_init_scores, dim3(a.ngroups), dim3(ORBX_INIT_SCORE_LANES), 0, s, a);
+}
+void orbx_launch_recon(hipStream_t s, const DReconArgs &a) {
+    if (a.nlaunch <= 0) return;
+    hipLaunchKernelGGL(k_init_decompose, dim3((a.nlaunch + ORBX_RECON_LANES - 1) / ORBX_RECON_LANES), dim3(ORBX_RECON_LANES), 0, s, a);
+    hipLaunchKernelGGL(k_init_check_rt, dim3(a.nlaunch * ORBX_RECON_MAX_HYP), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_init_pick, dim3(a.nlaunch), dim3(64), 0, s, a);
+}
+void orbx_launch_init_select(hipStream_t s, const DInitArgs &i, const DReconArgs &a) {
+    if (a.nlaunch <= 0) return;
+    hipLaunchKernelGGL(k_init_select, dim3(a.nlaunch), dim3(64), 0, s, i, a);
 }

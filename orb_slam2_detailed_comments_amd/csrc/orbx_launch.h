@@ -9,6 +9,7 @@
 #include "orbx_sim3.h"
 #include "orbx_pnp.h"
 #include "orbx_init.h"
+#include "orbx_recon.h"
 
 hipError_t orbx_upload_pattern();
 // the per-lane pattern tables orbx_upload_pattern uploads, 64 lanes x 16 coordinates each: c_pattern_lane and c_pattern_f32 (host only)
@@ -111,6 +112,10 @@ void orbx_launch_sim3(hipStream_t s, const DSim3Args &a);
 void orbx_launch_pnp(hipStream_t s, const DPnpArgs &a);
 // Initializer H / F RANSAC (orbx_init.h): k_init_hypotheses over all hypotheses, then k_init_scores over the workgroup table
 void orbx_launch_init(hipStream_t s, const DInitArgs &a);
+// ReconstructH / ReconstructF (orbx_recon.h): k_init_decompose over the problems, k_init_check_rt over the pose hypotheses, k_init_pick
+void orbx_launch_recon(hipStream_t s, const DReconArgs &a);
+// the fused call, between orbx_launch_init and orbx_launch_recon: k_init_select, one wave per problem of the RANSAC
+void orbx_launch_init_select(hipStream_t s, const DInitArgs &i, const DReconArgs &a);
 void orbx_launch_hamming_matrix(hipStream_t s, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *dist);
 
 void orbx_launch_stereo_batch(hipStream_t s, const OrbxStereoGeom &sg, int npairs, int cap, const orbx_keypoint *kL,

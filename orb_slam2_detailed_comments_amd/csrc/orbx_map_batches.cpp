@@ -1,7 +1,8 @@
-// orbx_map_batches.cpp -- the batched MapPoint refresh, Optimizer::PoseOptimization, the Sim3Solver RANSAC, the PnPsolver RANSAC
-// and the Initializer H / F RANSAC behind the C ABI: staging, launches and scatter.  Their HIP-free halves (validation, plans,
-// packing, the host solvers, the Sim3 and PnP cursors, the Initializer results) are orbx_mappoint.cpp, orbx_pose.cpp,
-// orbx_sim3.cpp, orbx_pnp.cpp and orbx_init.cpp; the three RANSACs go through one sequence, ransac_batch_create.
+// orbx_map_batches.cpp -- the batched MapPoint refresh, Optimizer::PoseOptimization, the Sim3Solver RANSAC, the PnPsolver RANSAC,
+// the Initializer H / F RANSAC and the Initializer's ReconstructH / ReconstructF behind the C ABI: staging, launches and scatter.
+// Their HIP-free halves (validation, plans, packing, the host solvers, the Sim3 and PnP cursors, the Initializer results) are
+// orbx_mappoint.cpp, orbx_pose.cpp, orbx_sim3.cpp, orbx_pnp.cpp, orbx_init.cpp and orbx_recon.cpp; the three RANSACs go through
+// one sequence, ransac_batch_create; the reconstruction has no draws and keeps its own.
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -83,7 +84,7 @@ extern "C" orbx_status orbx_update_normal_and_depth_batch(orbx_handle *h, int np
 // (ORBX_POSE=host, read per call; host-only handles, where the "d_" arguments are host arrays): the same header compiled by
 // the host compiler.  On a device handle it downloads the rows it needs, runs, and uploads the results -- a cross-check, not a
 // fast path.
-static bool host_selected(const char *var) {                  // ORBX_POSE / ORBX_SIM3 / ORBX_PNP / ORBX_INIT = host, read per call
+static bool host_selected(const char *var) {                  // ORBX_POSE / ORBX_SIM3 / ORBX_PNP / ORBX_INIT / ORBX_RECON = host, read per call
     const char *e = getenv(var);
     return e && strcmp(e, "host") == 0;
 }
@@ -349,3 +350,104 @@ extern "C" orbx_status orbx_init_batch_normalization(const orbx_init_batch *b, i
     return fail_why(orbx_init_get_normalization(b, k, T1, T2, &why), why);
 }
 extern "C" void orbx_init_batch_destroy(orbx_init_batch *b) { delete b; }
+
+// ---------------------------------------------------------------- Initializer ReconstructH / ReconstructF, batched (orbx_recon.h):
+// k_init_decompose, k_init_check_rt and k_init_pick; the batch keeps the results per problem and runs acos and the accept / reject
+// arithmetic on the host (orbx_recon_batch_take).  Not the RANSAC frame: this batch has no draws, no sets and no groups.
+// Device block: uploaded | downloaded | work (the per-hypothesis planes, never downloaded).
+extern "C" orbx_status orbx_init_reconstruct_batch_create(orbx_handle *h, int nproblems, const orbx_recon_problem *problems,
+                                                          orbx_recon_batch **out) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    if (!out) return orbx_fail(ORBX_BAD_ARGUMENT, "null batch pointer");
+    OrbxReconPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_recon_plan(nproblems, problems, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (plan.nlaunch == 0) {                                   // nothing to compute: the batch says so for every problem
+        *out = orbx_recon_batch_new(problems, plan);
+        return ORBX_OK;
+    }
+    if (h->host_only || host_selected("ORBX_RECON")) {
+        std::vector<uint8_t> in(plan.in_bytes), res(plan.out_bytes);
+        orbx_recon_pack(problems, plan, in.data());
+        orbx_recon_host_run(plan, in.data(), res.data());
+        *out = orbx_recon_batch_new(problems, plan);
+        orbx_recon_batch_take(*out, plan, res.data());
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), plan.in_bytes + plan.out_bytes + plan.work_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_recon_pack(problems, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    uint8_t *d_out = d + plan.in_bytes;
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_recon(h->stream, orbx_recon_args(plan, d, d_out + plan.out_bytes, d_out, nullptr)); }
+    st = stage_download_wait(h, pin, d_out, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    *out = orbx_recon_batch_new(problems, plan);
+    orbx_recon_batch_take(*out, plan, pin);
+    return ORBX_OK;
+}
+extern "C" orbx_status orbx_recon_batch_result(const orbx_recon_batch *b, int k, int32_t *ok, float *R21, float *t21, int32_t *chosen,
+                                               uint8_t *status, float *points, int32_t *N) {
+    const char *why = "";
+    return fail_why(orbx_recon_get_result(b, k, ok, R21, t21, chosen, status, points, N, &why), why);
+}
+extern "C" orbx_status orbx_recon_batch_hypothesis(const orbx_recon_batch *b, int k, int i, float *R9, float *t3, float *n3,
+                                                   int32_t *nGood, float *cosine, float *parallax, int32_t *valid) {
+    const char *why = "";
+    return fail_why(orbx_recon_get_hypothesis(b, k, i, R9, t3, n3, nGood, cosine, parallax, valid, &why), why);
+}
+extern "C" void orbx_recon_batch_destroy(orbx_recon_batch *b) { delete b; }
+
+// Initializer::Initialize from :204 to its return.  Fused: the RANSAC's block and the reconstruction's records go up in one copy,
+// k_init_hypotheses, k_init_scores, k_init_select, k_init_decompose, k_init_check_rt, k_init_pick run on the handle's stream, the
+// RANSAC's results and the reconstruction's come down in one copy.  Device block: RANSAC in | records | RANSAC out | recon out |
+// work.  With a host switch set, or on a host-only handle: the two calls, one after the other.
+extern "C" orbx_status orbx_initialize_batch_create(orbx_handle *h, int nproblems, const orbx_init_problem *problems,
+                                                    const orbx_init_camera *cameras, orbx_init_batch **ransac,
+                                                    orbx_recon_batch **recon) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    if (!ransac || !recon) return orbx_fail(ORBX_BAD_ARGUMENT, "null batch pointer");
+    OrbxInitPlan ip;
+    OrbxReconPlan rp;
+    const char *why = "";
+    orbx_status st = orbx_init_plan(nproblems, problems, ip, &why);
+    if (st == ORBX_OK) st = orbx_recon_fused_plan(nproblems, problems, cameras, rp, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (ip.nlaunch == 0 || h->host_only || host_selected("ORBX_INIT") || host_selected("ORBX_RECON")) {
+        st = orbx_init_ransac_batch_create(h, nproblems, problems, ransac);
+        if (st != ORBX_OK) return st;
+        std::vector<orbx_recon_problem> rprob;
+        std::vector<std::vector<uint8_t>> store;
+        orbx_recon_problems_from(problems, cameras, *ransac, rprob, store);
+        st = orbx_init_reconstruct_batch_create(h, nproblems, rprob.data(), recon);
+        if (st != ORBX_OK) { delete *ransac; *ransac = nullptr; }
+        return st;
+    }
+    const size_t init_in = pad256(ip.in_bytes), init_out = pad256(ip.out_bytes);
+    const size_t in_total = init_in + rp.in_bytes, out_total = init_out + rp.out_bytes;
+    uint8_t *pin = nullptr, *d = nullptr;
+    st = stage_begin(h, std::max(in_total, out_total), in_total + out_total + rp.work_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_init_pack(problems, ip, pin);
+    orbx_recon_fused_pack(problems, cameras, rp, pin + init_in);
+    st = stage_upload(h, pin, d, in_total);
+    if (st != ORBX_OK) return st;
+    uint8_t *d_out = d + in_total;
+    { ProfScope ps(h, ORBX_K_MISC);
+      const DInitArgs ia = orbx_ransac_args<DInitArgs>(ip, d, d_out);
+      const DReconArgs ra = orbx_recon_args(rp, d + init_in, d_out + out_total, d_out + init_out, ia.pts);
+      orbx_launch_init(h->stream, ia);
+      orbx_launch_init_select(h->stream, ia, ra);
+      orbx_launch_recon(h->stream, ra); }
+    st = stage_download_wait(h, pin, d_out, out_total);
+    if (st != ORBX_OK) return st;
+    *ransac = orbx_init_batch_new(problems, ip);
+    orbx_init_batch_take(*ransac, ip, pin);
+    *recon = orbx_recon_batch_new_fused(cameras, *ransac);
+    orbx_recon_batch_take(*recon, rp, pin + init_out);
+    return ORBX_OK;
+}
