@@ -20,24 +20,9 @@
 // Grid order: workgroups are dealt round-robin over the 8 XCDs (each with its own L2), so with the FRAME as the fastest grid
 // dimension (batch % 8 == 0) every block of one frame lands on the same XCD and the source lines two neighbouring blocks
 // both touch (strip seams, reflected rows, the border block's byte gathers) are fetched from HBM once instead of once per XCD.
-#ifndef L0_FF
-#define L0_FF 1
-#endif
-#ifndef RR_FF
-#define RR_FF 1
-#endif
-// k_quadtree: keys a thread may keep in registers (the register path covers QT_KPT * workgroup size keys), and the
-// barrier-stage reductions of section 5 of DESIGN.md as build switches for A/B variants (tools/build_variant.sh)
+// k_pyr_l0, the resize kernels and k_quadtree all take the frame from blockIdx.x for this reason.
+// k_quadtree: keys a thread may keep in registers (the register path covers QT_KPT * workgroup size keys)
 #define QT_KPT ORBX_QT_KPT
-#ifndef QT_DROP_STAGE_A
-#define QT_DROP_STAGE_A 1   // F bit set where a node is created; counters zeroed in stage E's interval: no stage A
-#endif
-#ifndef QT_ONE_SCAN
-#define QT_ONE_SCAN 1       // main pass: children, expandable children and survivors ranked by one two-word scan
-#endif
-#ifndef QT_REG_SIZE
-#define QT_REG_SIZE 1       // list size held by every thread, not passed through LDS
-#endif
 #ifndef QT_CENSUS_NODES
 #define QT_CENSUS_NODES 1   // register path: a list of at most this many nodes (and the root bins) is counted per wave with ballots;
                             // 0 = atomics per key.  Measured at 1 (107 us), 4 (116) and 0 (136 us per 1024 frames of 640x480)
@@ -47,22 +32,15 @@
 #endif
 static_assert(QT_KPT % QT_BGRP == 0, "QT_BGRP must divide QT_KPT");
 #define QT_SHARED_BYTES 144
-#ifndef QT_FF
-#define QT_FF 1
-#endif
 __global__ __launch_bounds__(256) void k_pyr_l0(DGeom g, const uint8_t *__restrict__ imgs, int W, int H, int stride,
                                                 long long frame_stride, uint8_t *__restrict__ pyr, int xe,
                                                 int *__restrict__ status, int *__restrict__ cand_cursor) {
-    // block = 64 x 4 threads, thread = L0_ROWS rows.  Blocks with blockIdx.x < gridDim.x - 1 copy the interior
+    // block = 64 x 4 threads, thread = L0_ROWS rows.  Blocks with bx < nbx - 1 copy the interior
     // columns [32, xe) with dword-aligned loads + funnel shifts (16 pixels per thread and row); the LAST block column
     // owns the two border strips [0, 32) and [xe, pitch) where reflect-101 reverses the byte order (byte gathers).
     // Keeping the two roles in different blocks keeps every wave free of divergence.
     const DLevel &L = g.lv[0];
-#if L0_FF
     const int f = blockIdx.x, bx = blockIdx.y, by = blockIdx.z, nbx = gridDim.y;
-#else
-    const int f = blockIdx.z, bx = blockIdx.x, by = blockIdx.y, nbx = gridDim.x;
-#endif
     // the per-frame status word (atomicMax'ed by the later kernels of the batch) is reset here: level 0 is the first kernel of
     // every batch, which saves a separate clearing launch in front of it
     if (bx == 0 && by == 0 && threadIdx.y == 0) {
@@ -312,9 +290,6 @@ __global__ __launch_bounds__(256) void k_pyr_resize(DGeom g, int level, const Or
 // the source rows of step k+1 are requested before step k is evaluated, and nothing in the loop waits on a table.
 // (A variant that lays (row pair, dword) items out linearly over the lanes to remove the idle lanes of odd level widths
 // measured 258 us against 207 us: vector tap loads, rows split across a wave.)
-#ifndef RR_REVERSE
-#define RR_REVERSE 1
-#endif
 #ifndef RR_WPB
 #define RR_WPB 1   // waves (column strips x row ranges) per block; nothing is shared between them, and one-wave blocks
                    // are placed as soon as any SIMD has room (201 us against 209 with 4)
@@ -447,14 +422,10 @@ __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows(DGeom g, int le
     const DLevel &L = g.lv[level];
     const DLevel &S = g.lv[level - 1];
     const int lane = threadIdx.x;
-#if RR_FF
     // Odd levels walk their row ranges bottom-up: with the frame as the fastest grid index the launch that wrote level l-1
     // finished with the bottom rows of every frame, and what the memory-side cache still holds of that level is those rows
     const int f = blockIdx.x, bx = blockIdx.y;
-    const int by = (RR_REVERSE && (level & 1)) ? (int)gridDim.z - 1 - (int)blockIdx.z : (int)blockIdx.z;
-#else
-    const int f = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
-#endif
+    const int by = (level & 1) ? (int)gridDim.z - 1 - (int)blockIdx.z : (int)blockIdx.z;
     const int X = (bx * 64 + lane) * 4;
     const int y_begin = __builtin_amdgcn_readfirstlane((by * RR_WPB + threadIdx.y) * rpw);
     if (y_begin >= L.ph) return;
@@ -530,14 +501,9 @@ __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows_l1(DGeom g, con
                                                             int *__restrict__ status, int *__restrict__ cand_cursor) {
     const DLevel &L = g.lv[1];
     const int lane = threadIdx.x;
-#if RR_FF
     const int f = blockIdx.x, bx = blockIdx.y;
-    const int by = RR_REVERSE ? (int)gridDim.z - 1 - (int)blockIdx.z : (int)blockIdx.z;
+    const int by = (int)gridDim.z - 1 - (int)blockIdx.z;   // level 1 is odd: bottom-up, as in k_pyr_resize_rows
     const bool first = blockIdx.y == 0 && blockIdx.z == 0;
-#else
-    const int f = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
-    const bool first = blockIdx.x == 0 && blockIdx.y == 0;
-#endif
     if (first && threadIdx.y == 0 && status) {   // one block per frame, as k_pyr_l0 does in the eager mode; null: the caller has reset them
         if (lane == 0) status[f] = 0;
         if (lane < g.nlevels) cand_cursor[f * g.nlevels + lane] = 0;
@@ -557,15 +523,6 @@ __global__ __launch_bounds__(64 * RR_WPB) void k_pyr_resize_rows_l1(DGeom g, con
 // K2: FAST-9/16 + score + 3x3 strict NMS per cell, with the per-cell threshold retry
 // (reference src/ORBextractor.cc:1465-1548; cv::FAST semantics SURVEY App. B.1): helpers, then k_fast_rows.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool orbx_arc9(uint32_t mask16) {
-    uint32_t m = mask16 | (mask16 << 16);
-    uint32_t a = m & (m >> 1);
-    a &= a >> 2;
-    a &= a >> 4;
-    a &= m >> 8;
-    return (a & 0xffffu) != 0;
-}
-
 // dynamic LDS: tile[rows*TP] | score[rows*TP] | list u16[lcap] (two-ended) | corn u16[lcap]; TP = tile pitch (%4 == 0)
 // ballot straight from the compare's lane mask (HIP's __ballot goes through an int and costs v_cndmask + v_cmp)
 __device__ __forceinline__ unsigned long long orbx_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
@@ -606,7 +563,7 @@ __device__ __forceinline__ void orbx_wave_sync() {
 #ifndef FR_CCAP
 #define FR_CCAP 512     // corner-list entries per group (see orbx_launch_fast_rows, which has the byte arithmetic)
 #endif
-#define FR_STACK 128    // re-run stack of fr_round, entries: the walk's 64 dummy dwords, between the work list and the corner list
+#define FR_STACK 128    // re-run stack of fr_round, entries: between the work list and the corner list
 #ifndef FR_GPW
 #define FR_GPW 2        // groups per wave
 #endif
@@ -616,12 +573,11 @@ typedef __attribute__((address_space(3))) uint16_t fr_lds_u16;
 __device__ __forceinline__ fr_u16 fr_max(fr_u16 a, fr_u16 b) { return a > b ? a : b; }
 __device__ __forceinline__ fr_u16 fr_min(fr_u16 a, fr_u16 b) { return a < b ? a : b; }
 __device__ __forceinline__ fr_i16 fr_smax(fr_i16 a, fr_i16 b) { return a > b ? a : b; }
-__device__ __forceinline__ fr_i16 fr_smin(fr_i16 a, fr_i16 b) { return a < b ? a : b; }
 
 static_assert(64 + ORBX_FAST_XCOLS + 6 + 3 <= FR_TP, "a cell pair's tile row must fit the LDS tile pitch");
 // The LDS of one wave, ONE definition for the kernel's pointers and the launcher's byte count:
-//   tile | score map (each map_bytes, 16-byte aligned: cleared with 16-byte stores) | work list u16[lcap] | stack u16[FR_STACK] (one
-//   private dummy dword per lane during the walk) | corner list of the group u16[ccap]
+//   tile | score map (each map_bytes, 16-byte aligned: cleared with 16-byte stores) | work list u16[lcap] | stack u16[FR_STACK] |
+//   corner list of the group u16[ccap]
 struct FrLds { int map_bytes, list_off, corn_off, bytes; };
 __host__ __device__ __forceinline__ FrLds fr_lds(int rows, int lcap, int ccap) {
     FrLds l;
@@ -631,7 +587,6 @@ __host__ __device__ __forceinline__ FrLds fr_lds(int rows, int lcap, int ccap) {
     l.bytes = l.corn_off + 2 * ccap;
     return l;
 }
-static_assert(2 * FR_STACK == 4 * 64, "the re-run stack is the 64 dummy dwords the walk's masked lanes write to");
 static_assert(FR_STACK >= 64 + 64, "a round pushes at most 64 entries on a stack that holds at most 64 before it");
 __device__ __forceinline__ bool colx_on_mask(unsigned act) { return (act & 2u) != 0; }   // columns >= 64 belong to the second cell
 struct FrCtx {
@@ -643,33 +598,31 @@ struct FrCtx {
     int lane;
 };
 
-#ifndef FR_UNIFIED
-#define FR_UNIFIED 1
-#endif
-#ifndef FR_NET
-#define FR_NET 1        // 1: the score network of orbx_fast_net.h; 0: the earlier doubling network (A/B builds)
-#endif
-#if FR_UNIFIED
 // Corner test and score of list[0..n) at threshold th in ONE pass per candidate; corners compacted IN PLACE to the front of the
 // list, their scores written to the score map; returns the number of corners.
 //   cv::FAST's test (9 contiguous ring pixels all brighter than v + th, or all darker than v - th) is "the largest over the 16
 // arcs of the smallest signed difference on the arc exceeds th" -- which is cv::cornerScore's own quantity (score + 1).  So the
-// min/max network of the score IS the test: 16-bit min / max issue at the full rate, where the ring masks of the separate test
-// (v_cmp + v_addc per ring pixel and polarity, fr_ring_and_score below) are all half-rate, and the second pass over the corners
-// (17 LDS reads per corner again) disappears.
+// min/max network of the score IS the test: 16-bit min / max issue at the full rate, where the ring masks of a separate test
+// (v_cmp + v_addc per ring pixel and polarity) are all half-rate, and the second pass over the corners (17 LDS reads per corner
+// again) disappears.  (The two-pass form with ring masks measured slower, profiles/r03_fast_onepass.md; the parent of this commit
+// has the code.)
 //   One polarity per candidate: the compass pixels (ring 0 / 4 / 8 / 12: the walk's pre-test) say which margin is the larger one,
 // and the network runs on the raw ring bytes, complemented for the darker polarity (one xor per ring pixel), in the prefix / suffix
-// form: 57 two-input operations, the centre subtracted once at the end (orbx_fast_net.h; the earlier doubling network on
-// d = +-(ring - v), 80 operations behind 16 multiply-adds, stays selectable as FR_NET=0).
+// form: 57 two-input operations, the centre subtracted once at the end (orbx_fast_net.h).  Two-input forms only: v_min3_i16 /
+// v_max3_i16 issue at a QUARTER of the rate of v_min_i16 on gfx950 (8.4 against 2.8 cycles per wave, tools/valu_rate6.hip).
+// (A doubling network on d = +-(ring - v), 80 operations behind 16 multiply-adds, measured slower, profiles/fast_net.md; the
+// parent of this commit has the code.)
 //   A candidate that passes BOTH pre-tests (a pixel half way
 // up a strong edge: < 1 % of the candidates) and fails its larger polarity may still be a corner of the other one: it is pushed on
-// a small stack (the 64 dummy dwords the walk's masked lanes write to, free during these rounds) and re-run with the polarity
+// a small stack (FR_STACK entries behind the work list) and re-run with the polarity
 // forced the other way in a later round; the stack is drained whenever it could not take another round's worth.
 // one round of up to 64 candidates.  FULL: 64 entries of the main list, every lane busy, nothing selected per lane.  Otherwise lanes
 // [0, cm) take main entries and lanes [cm, cm + cs) entries popped from the stack, which run with the polarity forced the other way.
 template <bool FULL>
 __device__ __forceinline__ void fr_round(const FrCtx &c, const uint16_t *src_main, int cm, const uint16_t *src_stack, int cs,
                                          int th, uint16_t *stack, int &ncorn, int &nredo) {
+    // offsets from the TOP-LEFT corner of the pixel's 7x7 window: none is negative, so every ring read is base + immediate (a DS
+    // offset is unsigned: the seven negative offsets of a centre-based table cost a v_add each, per round)
     const int rc = 3 * FR_TP + 3;
     const int ro[16] = {rc + 3 * FR_TP,      rc + 3 * FR_TP + 1,  rc + 2 * FR_TP + 2,  rc + FR_TP + 3, rc + 3,  rc - FR_TP + 3,
                         rc - 2 * FR_TP + 2, rc - 3 * FR_TP + 1, rc - 3 * FR_TP,     rc - 3 * FR_TP - 1, rc - 2 * FR_TP - 2,
@@ -689,7 +642,6 @@ __device__ __forceinline__ void fr_round(const FrCtx &c, const uint16_t *src_mai
     }
     const int off = ((code >> 8) - 3) * FR_TP + (code & 0xff);   // window corner: row - 3, column - 3 (rows start at 3)
     const uint8_t *ptr = c.tile + off;
-#if FR_NET
     // the network on the raw ring bytes, prefix / suffix form (orbx_fast_net.h); an entry from the stack takes the other polarity
     const fr_u16 v = ptr[rc];
     fr_u16 x[16];
@@ -698,81 +650,6 @@ __device__ __forceinline__ void fr_round(const FrCtx &c, const uint16_t *src_mai
     bool corner, both;
     uint8_t sc;
     orbx_fast_net(v, x, thl, !FULL && !is_main, corner, sc, both);
-#else
-    // the earlier network (A/B builds, tools/build_variant.sh NAME -DFR_NET=0): doubling on d = +-(ring - v).  FR_SGN and FR_NOMIN3
-    // describe this arm only.
-#ifndef FR_SGN
-#define FR_SGN 1
-#endif
-#if FR_SGN
-    // d = +-(ring - v) as ONE multiply-add per ring pixel (sgn * x - sgn * v), the sign from the four compass pixels first
-    const int v = ptr[rc];
-    int x[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) x[k] = ptr[ro[k]];
-    const fr_i16 c0 = (fr_i16)(x[0] - v), c4 = (fr_i16)(x[4] - v), c8 = (fr_i16)(x[8] - v), c12 = (fr_i16)(x[12] - v);
-    const fr_i16 s1 = fr_smin(fr_smax(c0, c8), fr_smax(c4, c12));
-    const fr_i16 s2 = fr_smax(fr_smin(c0, c8), fr_smin(c4, c12));
-    // both pre-tests pass (th < 256: no 16-bit overflow anywhere here)
-    const bool both = fr_smin(s1, (fr_i16)(-s2)) > thl;
-    // -1: the darker margin is the larger one; an entry from the stack takes the other polarity
-    int sgn = ((int)(fr_i16)(s1 + s2) >> 15) | 1;
-    if (!FULL) sgn = is_main ? sgn : -sgn;
-    const int cv = __mul24(-sgn, v);
-    fr_i16 d[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        int t;   // (as written in C the compiler factors the sign out again: a subtraction and a multiplication per pixel)
-        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(t) : "v"(x[k]), "v"(sgn), "v"(cv));
-        d[k] = (fr_i16)t;
-    }
-    const fr_i16 start = thl;
-    const fr_i16 f = 0;
-#else
-    const fr_i16 v = (fr_i16)ptr[rc];
-    fr_i16 d[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) d[k] = (fr_i16)((fr_i16)ptr[ro[k]] - v);
-    const fr_i16 s1 = fr_smin(fr_smax(d[0], d[8]), fr_smax(d[4], d[12]));
-    const fr_i16 s2 = fr_smax(fr_smin(d[0], d[8]), fr_smin(d[4], d[12]));
-    // both pre-tests pass (th < 256: no 16-bit overflow anywhere here)
-    const bool both = fr_smin(s1, (fr_i16)(-s2)) > thl;
-    // -1: the darker margin is the larger one; an entry from the stack takes the other polarity
-    uint32_t f32 = (uint32_t)(int)(fr_i16)((fr_i16)(s1 + s2) >> 15);
-    if (!FULL) f32 ^= is_main ? 0u : 0xffffffffu;
-    asm("" : "+v"(f32));   // ONE register: the 16 flips below stay plain v_xor (the compiler otherwise folds the terms into 16 three-input ops)
-    const fr_i16 f = (fr_i16)f32;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) d[k] = (fr_i16)(d[k] ^ f);
-    const fr_i16 start = (fr_i16)(thl + f);
-#endif
-    fr_i16 a0 = start;
-    fr_i16 m2[16], m4[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) m2[k] = fr_smin(d[k], d[(k + 1) & 15]);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) m4[k] = fr_smin(m2[k], m2[(k + 2) & 15]);
-#ifndef FR_NOMIN3
-#define FR_NOMIN3 1
-#endif
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-#if FR_NOMIN3
-        // two-input forms only: v_min3_i16 / v_max3_i16 issue at a QUARTER of the rate of v_min_i16 on gfx950 (8.4 against 2.8
-        // cycles per wave, tools/valu_rate6.hip) -- three two-input operations cost as much as one three-input one
-        fr_i16 m8 = fr_smin(m4[k], m4[(k + 4) & 15]);
-        asm("" : "+v"(m8));
-        fr_i16 w9 = fr_smin(m8, d[(k + 8) & 15]);
-        asm("" : "+v"(w9));
-        a0 = fr_smax(a0, w9);
-        asm("" : "+v"(a0));
-#else
-        a0 = fr_smax(a0, fr_smin(fr_smin(m4[k], m4[(k + 4) & 15]), d[(k + 8) & 15]));
-#endif
-    }
-    const bool corner = a0 > start;
-    const uint8_t sc = (uint8_t)(a0 - 1 - f);
-#endif
     const unsigned long long m = orbx_ballot(corner);
     if (corner) {
         c.list[ncorn + orbx_wave_rank(m)] = code;   // index < the entries already read: this round's are in registers
@@ -788,7 +665,7 @@ __device__ __forceinline__ void fr_round(const FrCtx &c, const uint16_t *src_mai
         nredo += __popcll(mr);
     }
 }
-__device__ __forceinline__ int fr_ring_and_score(const FrCtx &c, int n, int th, int dbg_stop) {
+__device__ __forceinline__ int fr_ring_and_score(const FrCtx &c, int n, int th) {
     uint16_t *const stack = c.list + c.lcap;   // FR_STACK entries
     int ncorn = 0, nredo = 0, e0 = 0;
     // full rounds of the main list (a round pushes at most 64 entries: with at most 64 on the stack before it, 128 hold them)
@@ -803,80 +680,8 @@ __device__ __forceinline__ int fr_ring_and_score(const FrCtx &c, int n, int th, 
         e0 += cm;
     }
     orbx_wave_sync();
-    (void)dbg_stop;
     return ncorn;
 }
-#else
-// full 16-ring test of list[0..n) at threshold th, corners compacted IN PLACE to the front of the list, their scores
-// written to the score map; returns the number of corners
-__device__ __forceinline__ int fr_ring_and_score(const FrCtx &c, int n, int th, int dbg_stop) {
-    // offsets from the TOP-LEFT corner of the pixel's 7x7 window: none is negative, so every ring read is base + immediate (a DS
-    // offset is unsigned: the seven negative offsets of a centre-based table cost a v_add each, per round)
-    const int rc = 3 * FR_TP + 3;
-    const int ro[16] = {rc + 3 * FR_TP,      rc + 3 * FR_TP + 1,  rc + 2 * FR_TP + 2,  rc + FR_TP + 3, rc + 3,  rc - FR_TP + 3,
-                        rc - 2 * FR_TP + 2, rc - 3 * FR_TP + 1, rc - 3 * FR_TP,     rc - 3 * FR_TP - 1, rc - 2 * FR_TP - 2,
-                        rc - FR_TP - 3,     rc - 3,             rc + FR_TP - 3,      rc + 2 * FR_TP - 2,  rc + 3 * FR_TP - 1};
-    int ncorn = 0;
-    for (int e0 = 0; e0 < n; e0 += 64) {
-        const int e = e0 + c.lane;
-        const bool valid = e < n;
-        const uint16_t code = valid ? c.list[e] : (uint16_t)(3 << 8);
-        const uint8_t *ptr = c.tile + ((code >> 8) - 3) * FR_TP + (code & 0xff);   // window corner: row - 3, column - 3 (rows start at 3)
-        const int v = ptr[rc];
-        const int hi = v + th, lo = v - th;
-        // ring masks by shift-in: mask = 2*mask + (compare) is one v_cmp + one v_addc per ring pixel and polarity
-        // (ring position k lands on bit 15-k; a circular run of 9 is a run of 9 in either direction)
-        uint32_t bright = 0, dark = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int x = ptr[ro[k]];
-            // (the compiler's own lowering is v_cmp -> SGPR, s_nop hazard padding, v_cndmask, v_or3, v_lshl)
-            asm("v_cmp_gt_i32 vcc, %2, %3\n\t"
-                "v_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
-                "v_cmp_lt_i32 vcc, %2, %4\n\t"
-                "v_addc_co_u32 %1, vcc, %1, %1, vcc"
-                : "+v"(bright), "+v"(dark)
-                : "v"(x), "v"(hi), "v"(lo)
-                : "vcc");
-        }
-        // (a pixel cannot have 9 brighter AND 9 darker ring pixels: the polarity of a corner is unique)
-        const bool cb = orbx_arc9(bright), cd = orbx_arc9(dark);
-        const bool corner = (int)valid & ((int)cb | (int)cd);
-        const unsigned long long m = orbx_ballot(corner);
-        // index <= e: this round's entries are already in registers.  Bit 15 = ring brighter than the centre.
-        if (corner) c.list[ncorn + orbx_wave_rank(m)] = (uint16_t)(code | (cb ? 0x8000u : 0u));
-        ncorn += __popcll(m);
-    }
-    orbx_wave_sync();
-    if (dbg_stop == 3) return ncorn;
-    // score = (largest t for which the corner test still passes) = max over the 16 arcs of the min over the arc of the
-    // signed difference, minus 1 (cv::cornerScore<16>).  The polarity that failed the test cannot exceed th, so only
-    // the corner's own polarity is evaluated: d = +-(v - ring), sliding 9-window minima by doubling (2, 4, 8, +1).
-    for (int e = c.lane; e < ncorn; e += 64) {
-        const uint16_t code = c.list[e];
-        const int off = ((code >> 8) & 0x7f) * FR_TP + 3 + (code & 0xff);
-        const uint8_t *ptr = c.tile + off - rc;
-        // darker ring: complement both sides (255 - x) - (255 - v) = v - x, so one instruction stream serves both cases
-        const fr_u16 flip = (code & 0x8000u) != 0 ? (fr_u16)0 : (fr_u16)0xff;
-        const fr_i16 v = (fr_i16)((fr_u16)ptr[rc] ^ flip);
-        fr_i16 d[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) d[k] = (fr_i16)((fr_i16)((fr_u16)ptr[ro[k]] ^ flip) - v);
-        fr_i16 a0 = (fr_i16)th;
-        fr_i16 m2[16], m4[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) m2[k] = fr_smin(d[k], d[(k + 1) & 15]);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) m4[k] = fr_smin(m2[k], m2[(k + 2) & 15]);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) a0 = fr_smax(a0, fr_smin(fr_smin(m4[k], m4[(k + 4) & 15]), d[(k + 8) & 15]));
-        c.score[off] = (uint8_t)(a0 - 1);
-    }
-    orbx_wave_sync();
-    return ncorn;
-}
-#endif
-
 
 // strict 3x3 NMS of list[0..n) among the corners of the SAME cell, survivors straight to the cell's slot range
 struct FrCells {
@@ -975,8 +780,8 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
     constexpr bool INPLACE = MODE != 0, L0ONLY = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) uint8_t fast_smem[];
     uint32_t *s_tile = (uint32_t *)fast_smem;
-    // tile | score map (16-byte aligned: cleared with 16-byte stores) | work list (lcap entries + one private dummy dword per
-    // lane) | corner list of the group (ccap entries: a group with more corners takes the dense NMS rescan)
+    // tile | score map (16-byte aligned: cleared with 16-byte stores) | work list (lcap entries + the re-run stack) |
+    // corner list of the group (ccap entries: a group with more corners takes the dense NMS rescan)
     const FrLds lds = fr_lds(rows, lcap, ccap);
     uint8_t *s_score = fast_smem + lds.map_bytes;
     uint16_t *s_list = (uint16_t *)(fast_smem + lds.list_off);
@@ -1152,37 +957,23 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
             // pair, so max(min(max(r0,r8),max(r4,r12)) - v, v - max(min(r0,r8),min(r4,r12))) > th is necessary.
             // The column window (rows y-3 .. y+3) rotates through seven registers: one new LDS byte per row.
             // Scalar instructions issue at the same rate as vector ones, so the step is written to need only two
-            // (popcount + list cursor): no per-row exit test, no exec masking (lanes without a candidate write to a
-            // private dummy slot), the lane mask folded into the threshold.
+            // (popcount + list cursor): no per-row exit test, the lane mask folded into the threshold; the list store is
+            // the step's one exec-masked instruction (the select of a dummy slot in its place takes one v_mov per row
+            // more, profiles/r03_fast_onepass.md).
             const uint8_t *pr = pc + y * FR_TP;
             fr_u16 w0 = pr[-3 * FR_TP], w1 = pr[-2 * FR_TP], w2 = pr[-FR_TP], w3 = pr[0], w4 = pr[FR_TP], w5 = pr[2 * FR_TP], w6;
             // list cursor as an LDS byte ADDRESS (scalar): a lane's slot is one v_lshl_add away
             const uint32_t list0 = (uint32_t)(uintptr_t)(fr_lds_u16 *)s_list;
             uint32_t nb = list0;
             uint32_t code = (uint32_t)((y << 8) | lane);
-            const uint32_t dummy = list0 + 2u * (uint32_t)lcap + 4u * (uint32_t)lane;
+            // (unused since the list store is exec-masked: the lane's dummy slot in the stack area.  The compiler schedules the
+            // walk differently without this dead value, and the change that retired the select form kept the code object byte
+            // for byte, profiles/knobs_retired.md: the next change to the walk can drop it.)
+            const uint32_t dummy = list0 + 2u * (uint32_t)lcap + 4u * (uint32_t)lane; (void)dummy;
             // software-pipelined: the three LDS bytes of row y+1 are requested before row y is evaluated (the list
             // store could alias them as far as the compiler knows, so it would not hoist them itself); the row after
             // the last one is read but never used (it is the first row of the score map)
             uint32_t nx0 = pr[3 * FR_TP], nx4 = pr[3], nx12 = pr[-3];   // (32-bit carriers: no re-extension in the loop)
-            uint32_t probe_s = 0, probe_v = 0; (void)probe_s; (void)probe_v;
-#ifndef FR_WALK_IF
-#define FR_WALK_IF 1
-#endif
-// issue-cost probes (measurement builds only; the result bits do not change): FR_PROBE_S = 4 scalar, FR_PROBE_V = 4 vector
-// filler instructions per walked row (profiles/r03_fast_issue_probe.md)
-#if defined(FR_PROBE_S)
-#define FR_PROBE() asm volatile("s_xor_b32 %0, %0, 1\n\ts_xor_b32 %0, %0, 1\n\ts_xor_b32 %0, %0, 1\n\ts_xor_b32 %0, %0, 1" : "+s"(probe_s));
-#elif defined(FR_PROBE_V)
-#define FR_PROBE() asm volatile("v_xor_b32 %0, 1, %0\n\tv_xor_b32 %0, 1, %0\n\tv_xor_b32 %0, 1, %0\n\tv_xor_b32 %0, 1, %0" : "+v"(probe_v));
-#else
-#define FR_PROBE()
-#endif
-#if FR_WALK_IF
-#define FR_STORE(cnd, m, nb, dummy, code) (void)(dummy); if (cnd) *(fr_lds_u16 *)(uintptr_t)((nb) + 2u * (uint32_t)orbx_wave_rank(m)) = (uint16_t)(code);
-#else
-#define FR_STORE(cnd, m, nb, dummy, code) *(fr_lds_u16 *)(uintptr_t)((cnd) ? (nb) + 2u * (uint32_t)orbx_wave_rank(m) : (dummy)) = (uint16_t)(code);
-#endif
 #define FR_STEP(R8, C, R0)                                                                                              \
             {                                                                                                           \
                 R0 = (fr_u16)nx0;                                                                                       \
@@ -1194,11 +985,10 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
                 const fr_u16 Bm = fr_max(fr_min(R0, R8), fr_min(r4, r12));                                              \
                 const bool cnd = fr_smax((fr_i16)(A - C), (fr_i16)(C - Bm)) > thv;                                      \
                 const unsigned long long m = orbx_ballot(cnd);                                                          \
-                FR_STORE(cnd, m, nb, dummy, code)                                                                       \
+                if (cnd) *(fr_lds_u16 *)(uintptr_t)(nb + 2u * (uint32_t)orbx_wave_rank(m)) = (uint16_t)code;           \
                 { const uint32_t pc_ = (uint32_t)__popcll(m);                                                           \
                   asm("s_lshl1_add_u32 %0, %1, %0" : "+s"(nb) : "s"(pc_) : "scc"); }   /* nb += 2 * popcount: ONE scalar instruction, ONE scalar cursor (a lane's slot stays mbcnt, mbcnt, v_lshl_add) */ \
                 code += 0x100u;                                                                                         \
-                FR_PROBE()                                                                                              \
             }
             // full chunks of 7 rows while the list is guaranteed to take them
             while (y + 7 <= yend && nb + 7u * 128u <= list0 + 2u * (uint32_t)lcap) {
@@ -1233,7 +1023,7 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
             const int n = (int)((nb - list0) >> 1);
             orbx_wave_sync();
             if (dbg_stop == 2) { if (n == 12345) cand_cursor[0] = n; continue; }
-            const int ncorn = fr_ring_and_score(cx, n, th, dbg_stop);
+            const int ncorn = fr_ring_and_score(cx, n, th);
             // keep the corners for the NMS walk while they fit
             if (!overflow && nctot + ncorn <= ccap) {
                 for (int e = lane; e < ncorn; e += 64) s_corn[nctot + e] = s_list[e];
@@ -1442,11 +1232,7 @@ __device__ __forceinline__ void qt_workgroup(const DGeom &g, const uint2 *__rest
     extern __shared__ __attribute__((aligned(16))) uint8_t qt_smem[];
     // grid: frame fastest, level 0 (the most keys) dispatched first.  With the level fastest, workgroup id % 8 = level for
     // the usual 8 levels: one XCD would get every level-0 workgroup and another every level-7 one.
-#if QT_FF
     const int level = level_begin + blockIdx.y, f = blockIdx.x, tid = threadIdx.x;
-#else
-    const int level = level_begin + blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
-#endif
     const DLevel &L = g.lv[level];
     const int N = L.nfeat;
     const uint2 *cand = dense_all + (long long)f * g.cand_total + L.cand_begin;
@@ -1531,7 +1317,7 @@ __device__ __forceinline__ void qt_workgroup(const DGeom &g, const uint2 *__rest
                 box0[n] = (uint32_t)(int)(hx * (float)i);                       // UL.x | UL.y(=0) << 16
                 box1[n] = (uint32_t)(int)(hx * (float)(i + 1)) | ((uint32_t)L.qt_h << 16);
                 cnt[n] = cc[i];
-                meta[n] = QT_DROP_STAGE_A ? (uint32_t)(cc[i] > 1) << 16 : 0u;   // F: splits in the first pass
+                meta[n] = (uint32_t)(cc[i] > 1) << 16;   // F: splits in the first pass
                 t0[i] = n++;
             } else t0[i] = 0xffff;
         }
@@ -1544,27 +1330,12 @@ __device__ __forceinline__ void qt_workgroup(const DGeom &g, const uint2 *__rest
     } else
     for (int k = tid; k < K; k += QT_THREADS) knode[k] = (uint16_t)t0[knode[k]];
     int size = sh->size;
-#if QT_DROP_STAGE_A
     // the root counts in cc are dead (thread 0 read them before the barrier above): zero the first pass's quadrant counters
     for (int p = tid; p < size; p += QT_THREADS) *(uint4 *)(cc + 4 * p) = make_uint4(0, 0, 0, 0);
-#endif
     __syncthreads();
 
     bool careful = false;
     while (size > 0) {
-#if !QT_REG_SIZE
-        size = sh->size;
-#endif
-#if !QT_DROP_STAGE_A
-        // ---- A: which nodes split in this pass; zero their quadrant counters
-        //      main pass: every node with more than one key; careful pass: nodes created by the last pass (F)
-        for (int p = tid; p < size; p += QT_THREADS) {
-            const bool ex = careful ? ((meta[p] >> 16) & 1) != 0 : cnt[p] > 1;
-            meta[p] = (meta[p] & 0xffffu) | ((uint32_t)ex << 16);
-            cc[4 * p] = cc[4 * p + 1] = cc[4 * p + 2] = cc[4 * p + 3] = 0;
-        }
-        __syncthreads();
-#endif
         // ---- B: quadrant census of the nodes that split in this pass (F).  F is what the pass that created the node wrote:
         //      a root or a child with more than one key; a survivor has at most one (main phase) or was not created by the
         //      last pass (careful phase), F = 0.  The counters were zeroed in the barrier interval of the previous stage E.
@@ -1602,31 +1373,11 @@ __device__ __forceinline__ void qt_workgroup(const DGeom &g, const uint2 *__rest
         // ---- C: creation ranks
         int ctot, nmtot, nexp_total = 0;
         if (!careful) {
-#if QT_ONE_SCAN
             uint32_t tot, nm;
             qt_scan_main<QT_THREADS>(meta, cc, t1, t2, size, sh, tot, nm);
             ctot = tot & 0xffff;
             nexp_total = tot >> 16;
             nmtot = (int)nm;
-#else
-            // pack: children (low 16) | expandable children (high 16)
-            for (int p = tid; p < size; p += QT_THREADS) {
-                uint32_t ne = 0, nx = 0;
-                if ((meta[p] >> 16) & 1)
-                    for (int q = 0; q < 4; ++q) { ne += cc[4 * p + q] > 0; nx += cc[4 * p + q] > 1; }
-                t0[p] = ne | (nx << 16);
-            }
-            __syncthreads();
-            const uint32_t tot = qt_block_scan<QT_THREADS>(t0, t1, size, sh);
-            ctot = tot & 0xffff;
-            nexp_total = tot >> 16;
-            for (int p = tid; p < size; p += QT_THREADS) {
-                t0[p] = ((meta[p] >> 16) & 1) ? 0 : 1;
-                t3[p] = 1;  // processed flag for expandable nodes: all of them
-            }
-            __syncthreads();
-            nmtot = (int)qt_block_scan<QT_THREADS>(t0, t2, size, sh);
-#endif
         } else {
             // careful phase: order candidates by descending (count, creation rank).  The candidate keys are first
             // compacted into a dense, 16-byte aligned LDS array (scratch = newpos, rewritten in phase D anyway); each
@@ -1722,18 +1473,12 @@ __device__ __forceinline__ void qt_workgroup(const DGeom &g, const uint2 *__rest
             const int q = ((meta[p] >> 16) & 1) ? qt_quadrant(QT_KPOS(k), box0[p], box1[p]) : 0;
             knode[k] = (uint16_t)newpos[4 * p + q];
         }
-#if QT_DROP_STAGE_A
         // stage E does not read the quadrant counters: zero them for the next pass here instead of in a stage of their own
         for (int p = tid; p < new_size; p += QT_THREADS) *(uint4 *)(cc + 4 * p) = make_uint4(0, 0, 0, 0);
-#endif
         __syncthreads();
         { uint32_t *t;
           t = box0; box0 = nbox0; nbox0 = t;  t = box1; box1 = nbox1; nbox1 = t;
           t = cnt; cnt = ncnt; ncnt = t;      t = meta; meta = nmeta; nmeta = t; }
-#if !QT_REG_SIZE
-        if (tid == 0) sh->size = new_size;
-        __syncthreads();
-#endif
         // ---- termination (:1260-1283, :1363-1372)
         const bool done = new_size >= N || new_size == size;
         if (!careful && new_size + 3 * nexp_total > N) careful = true;
@@ -1774,11 +1519,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : QT_THREADS == 5
                                                         uint32_t *__restrict__ lvl_kp, int *__restrict__ lvl_count,
                                                         int *__restrict__ status, uint16_t *__restrict__ knode_glob,
                                                         int ncap, int lds_keys, int reg_keys, int level_begin) {
-#if QT_FF
     const int level = level_begin + blockIdx.y, f = blockIdx.x;
-#else
-    const int level = level_begin + blockIdx.x, f = blockIdx.y;
-#endif
     const int K = min(cand_count[f * g.nlevels + level], g.lv[level].cand_cap);
     if (K <= reg_keys * QT_THREADS)   // workgroup-uniform
         qt_workgroup<QT_THREADS, true>(g, dense_all, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, level_begin);
@@ -1908,47 +1649,32 @@ __constant__ int4 c_pattern_lane[64];
 // row it covers, as byte weights for v_dot4_u32_u8: [0..4] = u + 16 inside the disc (|u| <= umax[|v|]) else 0, [5..9] = 1
 // inside the disc else 0.  m10 = sum(u * I) = dot(I, u + 16) - 16 * dot(I, 1), m01 = v * dot(I, 1): exact integers.
 __constant__ uint32_t c_orient_w[64][12];
-// B operands of the row pass on the matrix pipe (DS_MFMA): the banded 7-tap kernel, output column tile j of 16:
+// B operands of the row pass on the matrix pipe: the banded 7-tap kernel, output column tile j of 16:
 // entry [j][lane][.] = the 16 bytes B[k = 16 (lane >> 4) + s][n = lane & 15] = K7[k - (16 j + n)] (0 outside the band)
 __constant__ uint32_t c_blur_b[3][64][4];
-// c_pattern_lane's coordinates as exact floats (DS_PATTERN_F32): entry [l][r] = (x1, y1, x2, y2) of pair r*64 + l
-__constant__ float4 c_pattern_f32[64][4];
 
 // The 7x7 Gaussian (reference :2039-2047) is fused in: only a 43x43 neighbourhood of each keypoint is ever sampled
 // (|tap| <= 18, +3 px filter support), so each wave stages that patch of the UN-blurred level in LDS, runs the
 // fixed-point row pass over it (4 pixels per item, as k_blur does) and evaluates the column pass only at the 512 tap
 // positions.  The blurred image is never written: 2P bytes of HBM traffic per frame disappear.  Arithmetic is the
 // same as k_blur's (8-bit kernel, float column path for x < (w & ~3), integer tail), so descriptors are unchanged.
-#ifndef DS_ORDER
-#define DS_ORDER 1
-#endif
 #define DS_R 21                 // patch radius: 18 (taps) + 3 (filter support)
 #define DS_W (2 * DS_R + 1)     // 43
 #define DS_PP 44                // LDS patch pitch in bytes (11 dwords; rows start dword-aligned in LDS)
-#define DS_HC 40                // row-pass outputs per row (37 needed, computed in groups of 4)   [DS_COLFIRST == 0]
-#ifndef DS_COLFIRST
-#define DS_COLFIRST 1
-#endif
-// DS_COLFIRST: the separable Gaussian with the passes in the OTHER order.  The total I = sum_ij k_i k_j p[y+j][x+i] is one exact
-// integer whichever pass runs first (every partial sum <= 255 * 257 = 65535), so the result is the same bit for bit -- but with
-// the COLUMN pass done over the whole patch (v[r][c] = sum_j k_j p[r+j][c], u16), the seven values a tap needs are horizontal
-// neighbours: 14 contiguous bytes = two ds_read2_b32 from a dword-aligned address instead of seven ds_read_u16 at a 80-byte
-// stride, folded by four v_dot2_u32_u16 against weights chosen by the parity of the tap's column.  The tap reads are what the
-// LDS pipe of this kernel is busy with (56 per lane, 60 % of its active cycles bank conflicts).
-#ifndef DS_ALIAS
-#define DS_ALIAS 1
-#endif
-// DS_MFMA (with DS_COLFIRST's tap code): the first pass is the ROW pass again, but on the matrix pipe, which this kernel
-// leaves idle while its vector pipe is the busiest port: H = (P - 128) x B + 128 * 257 with P the patch rows as int8 (x ^ 0x80),
-// B the banded kernel (c_blur_b), as nine v_mfma_i32_16x16x64_i8 (3 row tiles x 3 column tiles, K = 64 patch columns at once),
-// exact in int32.  The accumulator layout hands every lane FOUR CONSECUTIVE ROWS of one column, so the results are stored
-// transposed for free -- HT[c][r], one ds_write_b64 per tile -- and the seven values a tap needs (vertical neighbours) are
-// contiguous again: the same 16-byte window + four v_dot2 as the column-first form.  ~45 vector instructions instead of ~150.
-#ifndef DS_MFMA
-#define DS_MFMA 1
-#endif
-#define DS_VC 44                // columns of v (43 needed: taps -18..18, +-3)
-#define DS_VR 40                // rows of v computed (37 needed: five lane groups of 8)
+// The Gaussian's first pass is the ROW pass on the matrix pipe, which this kernel leaves idle while its vector pipe is the
+// busiest port: H = (P - 128) x B + 128 * 257 with P the patch rows as int8 (x ^ 0x80), B the banded kernel (c_blur_b), as nine
+// v_mfma_i32_16x16x64_i8 (3 row tiles x 3 column tiles, K = 64 patch columns at once), exact in int32.  The accumulator layout
+// hands every lane FOUR CONSECUTIVE ROWS of one column, so the results are stored transposed for free -- HT[c][r], packed to u16
+// pairs by one v_perm_b32 each, one ds_write_b64 per tile -- and the seven values a tap needs (vertical neighbours) are
+// contiguous: 14 bytes inside one dword-aligned 16-byte window, folded by four v_dot2_u32_u16 against weights chosen by the
+// parity of the tap's row (orbx_ds_tap).  The total I = sum_ij k_i k_j p[y+j][x+i] is one exact integer whichever pass runs
+// first (every partial sum <= 255 * 257 = 65535), so the result is the same bit for bit.  The tap reads are what the LDS pipe
+// of this kernel is busy with.  ~45 vector instructions for the pass instead of ~150.
+// (The row pass on the vector pipe with seven ds_read_u16 per tap at an 80-byte stride, and the column pass over the whole
+// patch in front of horizontal windows, came before this form: DESIGN.md, "the Gaussian's row pass on the matrix pipe"; the
+// parent of this commit has the code.)
+#define DS_VC 44                // pitch of HT in u16: the rows r of one column c (43 patch rows)
+#define DS_VR 40                // columns c of HT the buffer holds (37 needed: taps -18..18)
 #ifndef DS_WPB
 #define DS_WPB 1   // waves (= keypoints) per block.  Nothing is shared between the waves of a block; one-wave blocks let the
                    // dispatcher place every wave as soon as any SIMD has room: 282 us against 299 (4 waves) and 372 (8)
@@ -1968,64 +1694,34 @@ __constant__ float4 c_pattern_f32[64][4];
 // (Several keypoints per wave with register prefetch of the next patch was measured: 430-440 us at the 4-5 waves per
 // SIMD its registers allow against 375 us for one keypoint per wave -- every phase of this kernel is a dependent chain of
 // LDS round trips, and resident waves are what hides them.)
-// The length of one wave's dependent chain (profiles/describe_chain.md); every item is a build switch, 0 = the earlier form:
-// DS_SLOT: waves indexed by the SLOT of the per-frame level-keypoint table instead of by output position.  The level of a slot
+// The length of one wave's dependent chain (profiles/describe_chain.md):
+// Waves are indexed by the SLOT of the per-frame level-keypoint table, not by output position.  The level of a slot
 //   follows from the kp_begin values (kernel arguments) alone, so the level's table entry, the eight counts and the slot's
 //   position word are requested together, in front of one wait: kernel arguments, {level entry, counts, position}, patch -- three
-//   memory round trips in front of the first LDS write where the output-indexed form has eight.  A slot beyond its level's count
+//   memory round trips in front of the first LDS write where an output-indexed wave has eight.  A slot beyond its level's count
 //   is a dead wave; the output position is the sum of the counts below the level + the index in the level.  Slot order is
 //   level-major like the output order, so the order of the workgroups of a frame on its XCD is the same.
-// DS_EARLY_TABLES (bit 0: pattern, bit 1: c_orient_w, bit 2: c_blur_b): the constant tables are requested right behind the patch
-//   loads, before the first LDS write, instead of in front of their first use.
-// DS_TAP_BATCH (1 / 2 / 4 / 8): taps per batch; a batch forms all its addresses, issues all its LDS reads, then runs the dot
-//   products as independent chains.
-// DS_PATTERN_F32: the pattern coordinates come as floats (c_pattern_f32) instead of 16 int8 -> float conversions per lane.
-// DS_PACK_PERM: the MFMA accumulators are packed to u16 pairs by one v_perm_b32 instead of a shift and an or.
-#ifndef DS_SLOT
-#define DS_SLOT 1
-#endif
-#ifndef DS_EARLY_TABLES
-#define DS_EARLY_TABLES 7
-#endif
-#ifndef DS_TAP_BATCH
-#define DS_TAP_BATCH 1   // 2 / 4 / 8 measured slower or equal (profiles/describe_chain.md)
-#endif
-#ifndef DS_PATTERN_F32
-#define DS_PATTERN_F32 0   // measured slower: four 16-byte loads per lane in place of one cost more than 16 conversions
-#endif
-#ifndef DS_PACK_PERM
-#define DS_PACK_PERM 1
-#endif
+// The constant tables (pattern, c_orient_w, c_blur_b) are requested right behind the patch loads, before the first LDS write,
+//   not in front of their first use.
+// The taps run one after the other: batches of 2 / 4 / 8 (all addresses, all LDS reads, then independent dot-product chains)
+//   measured slower or equal.  The pattern coordinates are 16 int8 -> float conversions per lane: as a float table, four
+//   16-byte loads per lane in place of one cost more.  (Both in profiles/describe_chain.md; the parent of this commit has the code.)
 // FPM (fp_mode) is a template constant: as a run-time value it costs a scalar branch and both code paths in each of the 8 taps
 typedef const __attribute__((address_space(3))) uint16_t *orbx_lds_u16p;
 typedef const __attribute__((address_space(3))) uint32_t *orbx_lds_u32p;
-// I = sum_i k_i v[r][c + i], i = 0..6, for the u16 element at LDS byte address `adr` (DS_COLFIRST): the 8 elements of the
-// dword-aligned 16-byte window around them, against the weights shifted by the parity of c; I < 2^24.01.
-// N taps at once (DS_TAP_BATCH): every window read is issued before the first weight is formed, and the N dot-product chains are
-// independent of one another -- one LDS round trip per batch where tap after tap pays one each
-template <int N>
-__device__ __forceinline__ void orbx_ds_taps(const uint32_t (&adr)[N], uint32_t (&I)[N]) {
+// I = sum_i k_i HT[c][r + i], i = 0..6, for the u16 element at LDS byte address `adr`: the 8 elements of the dword-aligned
+// 16-byte window around them, against the weights shifted by the parity of r; I < 2^24.01.
+__device__ __forceinline__ uint32_t orbx_ds_tap(uint32_t adr) {
     typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    uint32_t d[N][4];
+    const orbx_lds_u32p wp = (orbx_lds_u32p)(uintptr_t)(adr & ~3u);
+    const uint32_t d[4] = {wp[0], wp[1], wp[2], wp[3]};
+    const bool odd = (adr & 2u) != 0;
+    const uint32_t w[4] = {odd ? (18u << 16) : (18u | (34u << 16)), odd ? (34u | (49u << 16)) : (49u | (55u << 16)),
+                           odd ? (55u | (49u << 16)) : (49u | (34u << 16)), odd ? (34u | (18u << 16)) : 18u};
+    uint32_t I = 0u;
 #pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const orbx_lds_u32p wp = (orbx_lds_u32p)(uintptr_t)(adr[k] & ~3u);
-        d[k][0] = wp[0]; d[k][1] = wp[1]; d[k][2] = wp[2]; d[k][3] = wp[3];
-    }
-    uint32_t w[N][4];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const bool odd = (adr[k] & 2u) != 0;
-        w[k][0] = odd ? (18u << 16) : (18u | (34u << 16)); w[k][1] = odd ? (34u | (49u << 16)) : (49u | (55u << 16));
-        w[k][2] = odd ? (55u | (49u << 16)) : (49u | (34u << 16)); w[k][3] = odd ? (34u | (18u << 16)) : 18u;
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) I[k] = 0u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int k = 0; k < N; ++k)
-            I[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, d[k][i]), __builtin_bit_cast(u16x2, w[k][i]), I[k], false);
+    for (int i = 0; i < 4; ++i) I = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, d[i]), __builtin_bit_cast(u16x2, w[i]), I, false);
+    return I;
 }
 // INPLACE: level-0 keypoints stage their patch from the caller's grey image (`raw`), which holds no border: interior
 // keypoints run the slab path's code on it; a patch that leaves the raw image (about 15 % of the level-0 keypoints: the 19-pixel
@@ -2044,17 +1740,11 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
 #ifndef ORBX_TIMING_KNOBS
     dbg_stop = 0;
 #endif
-#if DS_COLFIRST && DS_ALIAS
-    // v OVER the patch: the column pass holds every patch row it needs in registers before its first store (a wave's LDS
+    // HT OVER the patch: the row pass holds every patch row it needs in registers before its first store (a wave's LDS
     // instructions execute in order, and one wave owns the buffers), and nothing reads the patch afterwards -- 3.5 KB of LDS per
     // wave instead of 5.4
     __shared__ __attribute__((aligned(16))) uint16_t s_h[DS_WPB][DS_VR * DS_VC];
-#else
-    __shared__ uint32_t s_patch[DS_WPB][DS_W * DS_PP / 4 + 4];
-    __shared__ __attribute__((aligned(16))) uint16_t s_h[DS_WPB][DS_COLFIRST ? DS_VR * DS_VC : DS_W * DS_HC];
-#endif
-    // one wave per keypoint, waves indexed by dense OUTPUT position (level-major order of operator(), :2066-2082).
-    // The wave index is wave-uniform (which the compiler cannot see): with it scalar, the level search and the position
+    // one wave per keypoint slot.  The wave index is wave-uniform (which the compiler cannot see): with it scalar, the level search and the position
     // load run on the scalar unit.
     const int lane = threadIdx.x & 63, wv_id = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // Workgroup order (x fastest): frame mod 8, then keypoint, then frame / 8.  Workgroups are dealt round-robin over the 8
@@ -2062,7 +1752,6 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
     // own 4 MB L2, and the chip holds 8 frames at a time.  (With the frame as the fastest index -- the order of the first
     // version -- every frame of the batch has a few keypoints in flight at once: at 1024 frames per launch no cache holds that,
     // and every patch came from HBM, 3.1 MB per frame.)
-#if DS_SLOT
     // every kernel argument the path to the first patch load reads, requested in front of ONE wait (left alone, each is loaded
     // in front of its first use: one round trip per basic block of the prologue)
     // (the empty asm only fixes the point by which all of them have arrived.  Not volatile, and with results that are used: a
@@ -2072,25 +1761,15 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
     for (int l = 0; l < 8; ++l) kbv[l] = g.lv[l].kp_begin;
     asm("" : "+s"(nframes), "+s"(cap), "+s"(kbv[0]), "+s"(kbv[1]), "+s"(kbv[2]), "+s"(kbv[3]), "+s"(kbv[4]), "+s"(kbv[5]), "+s"(kbv[6]), "+s"(kbv[7])
            : "s"(g.nlevels), "s"(g.kp_total), "s"(g.pyr_bytes), "s"(lvl_kp), "s"(lvl_count), "s"(pyr));
-#endif
-#if DS_ORDER == 1
     const int f = blockIdx.y * 8 + (blockIdx.x & 7);
     const int wi = (blockIdx.x >> 3) * DS_WPB + wv_id;
     if (f >= nframes) return;
-#else
-    const int f = blockIdx.x;   // frame fastest: one frame's patches stay in one XCD's L2
-    const int wi = blockIdx.y * DS_WPB + wv_id;
-#endif
     const int *lc = lvl_count + f * g.nlevels;
     int total = 0, level = 0;
-#ifndef DS_LEVELS8
-#define DS_LEVELS8 1
-#endif
-#if DS_SLOT
     // wave = slot.  (First round trip: the kernel arguments, pinned at the top of the kernel.)
     const int slot = wi;
     if (DS_WPB > 1 && slot >= g.kp_total) return;
-    const bool all8 = DS_LEVELS8 && g.nlevels == 8;   // every ORB-SLAM2 configuration
+    const bool all8 = g.nlevels == 8;   // every ORB-SLAM2 configuration
     int kb = kbv[0];
     if (all8) {
 #pragma unroll
@@ -2136,65 +1815,19 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
         if (total > cap) atomicMax(&status[f], (int)ORBX_CAPACITY);
     }
     if (slot - kb >= mine || oi >= min(total, cap) || dbg_stop == 4) return;
-#else
-    const int oi = wi;
-    int slot = oi;
-    if (DS_LEVELS8 && g.nlevels == 8) {
-        // every ORB-SLAM2 configuration: the eight counts in one scalar load, then compares and selects only, and ONE table
-        // load for the level found (the general loop below pays two dependent scalar loads and two branches per level:
-        // ~120 scalar instructions and eight memory round trips in front of every keypoint)
-        const int4 ca = *(const int4 *)lc, cb = *(const int4 *)(lc + 4);
-        const int cnt[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
-        int base = 0;
-#pragma unroll
-        for (int l = 0; l < 8; ++l) {
-            if (oi >= total) { level = l; base = total; }
-            total += cnt[l];
-        }
-        slot = g.lv[level].kp_begin + (oi - base);
-    } else {
-#pragma unroll
-    for (int l = 0; l < ORBX_MAX_LEVELS; ++l) {
-        if (l < g.nlevels) {
-            if (oi >= total) { level = l; slot = g.lv[l].kp_begin + (oi - total); }
-            total += lc[l];
-        }
-    }
-    }
-    if (oi == 0 && lane == 0) {
-        counts[f] = min(total, cap);
-        if (total > cap) atomicMax(&status[f], (int)ORBX_CAPACITY);
-    }
-    if (oi >= min(total, cap) || dbg_stop == 4) return;
-    const uint32_t pos = lvl_kp[(long long)f * g.kp_total + slot];
-    const DLevel &L = g.lv[level];
-#endif
-#if DS_COLFIRST && DS_ALIAS
     uint32_t *patch = (uint32_t *)s_h[wv_id];
-#else
-    uint32_t *patch = s_patch[wv_id];
-#endif
     uint16_t *hrow = s_h[wv_id];
-    // the constant tables: requested behind the patch loads (DS_EARLY_TABLES) or in front of their first use
-#if DS_PATTERN_F32
-    float4 patf[4];
-#define DS_LOAD_PATTERN() do { _Pragma("unroll") for (int r = 0; r < 4; ++r) patf[r] = c_pattern_f32[lane][r]; } while (0)
-#else
+    // the constant tables, requested right behind the patch loads (the scheduling barrier keeps every patch load in front of
+    // them: loads return in order, and the first LDS write waits for the patch alone)
     int4 pat;
-#define DS_LOAD_PATTERN() do { pat = c_pattern_lane[lane]; } while (0)
-#endif
     uint4 wa, wb, wc;
-#define DS_LOAD_ORIENT_W() do { wa = *(const uint4 *)&c_orient_w[lane][0]; wb = *(const uint4 *)&c_orient_w[lane][4]; wc = *(const uint4 *)&c_orient_w[lane][8]; } while (0)
-#if DS_COLFIRST && DS_MFMA
     uint4 b4[3];
-#define DS_LOAD_BLUR_B() do { _Pragma("unroll") for (int j = 0; j < 3; ++j) b4[j] = *(const uint4 *)&c_blur_b[j][lane][0]; } while (0)
-#else
-#define DS_LOAD_BLUR_B() do { } while (0)
-#endif
-    // (the scheduling barrier keeps every patch load in front of the table loads: loads return in order, and the first LDS write
-    // waits for the patch alone)
-#define DS_LOAD_EARLY() do { if (DS_EARLY_TABLES) __builtin_amdgcn_sched_barrier(0); if (DS_EARLY_TABLES & 1) DS_LOAD_PATTERN(); if (DS_EARLY_TABLES & 2) DS_LOAD_ORIENT_W(); if (DS_EARLY_TABLES & 4) DS_LOAD_BLUR_B(); } while (0)
-    if (!(DS_EARLY_TABLES & 1)) DS_LOAD_PATTERN();
+#define DS_LOAD_EARLY() do {                                                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                                   \
+        pat = c_pattern_lane[lane];                                                                                          \
+        wa = *(const uint4 *)&c_orient_w[lane][0]; wb = *(const uint4 *)&c_orient_w[lane][4]; wc = *(const uint4 *)&c_orient_w[lane][8]; \
+        _Pragma("unroll") for (int j = 0; j < 3; ++j) b4[j] = *(const uint4 *)&c_blur_b[j][lane][0];                         \
+    } while (0)
     const int x = (int)(pos & 0xfff) + (ORBX_EDGE - 3), y = (int)((pos >> 12) & 0xfff) + (ORBX_EDGE - 3);
     const bool ip0 = INPLACE && level == 0;   // wave-uniform
     const uint8_t *img = ip0 ? raw.img + (long long)f * raw.frame_stride : pyr + (long long)f * g.pyr_bytes + L.off;
@@ -2297,7 +1930,6 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
             // lane = (row, half): 5 aligned dwords of patch row 21 + v, two v_dot4_u32_u8 each against the constant weights
             const int row = lane >> 1, half = lane & 1;                 // row = v + 15 (lanes 62, 63 carry zero weights)
             const uint32_t *pr = patch + min(row + (DS_R - ORBX_HALF_PATCH), DS_W - 1) * (DS_PP / 4) + 1 + 5 * half;
-            if (!(DS_EARLY_TABLES & 2)) DS_LOAD_ORIENT_W();
             const uint32_t p0 = pr[0], p1 = pr[1], p2 = pr[2], p3 = pr[3], p4 = pr[4];
             uint32_t A = __builtin_amdgcn_udot4(p0, wa.x, 0u, false), S = __builtin_amdgcn_udot4(p0, wb.y, 0u, false);
             A = __builtin_amdgcn_udot4(p1, wa.y, A, false); S = __builtin_amdgcn_udot4(p1, wb.z, S, false);
@@ -2312,9 +1944,7 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
             if (lane == 0) lvl_angle[(long long)f * g.kp_total + slot] = angle_deg;
         }
         if (dbg_stop == 2) return;
-        // ---- row pass: h[r][c] for patch columns c+3 (c = 0..36 used); 4 outputs per item from 3 aligned dwords via
-        // v_alignbyte + v_dot4_u32_u8 with the packed 8-bit kernel {18,34,49,55 | 49,34,18,0}
-#if DS_COLFIRST && DS_MFMA
+        // ---- row pass: h[r][c] for patch columns c+3 (c = 0..36 used), on the matrix pipe, stored transposed (HT[c][r]) over the patch
         {
             typedef int i32x4 __attribute__((ext_vector_type(4)));
             const int m = lane & 15, gq = lane >> 4;
@@ -2325,7 +1955,6 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
                 A[t][0] = (int)(ap[0] ^ 0x80808080u); A[t][1] = (int)(ap[1] ^ 0x80808080u);
                 A[t][2] = (int)(ap[2] ^ 0x80808080u); A[t][3] = (int)(ap[3] ^ 0x80808080u);
             }
-            if (!(DS_EARLY_TABLES & 4)) DS_LOAD_BLUR_B();
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 Bm[j][0] = (int)b4[j].x; Bm[j][1] = (int)b4[j].y; Bm[j][2] = (int)b4[j].z; Bm[j][3] = (int)b4[j].w;
@@ -2339,72 +1968,14 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
                     const i32x4 acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t], Bm[j], c0, 0, 0, 0);
                     // columns c < 37 and rows r < 44 exist in HT
                     if ((j < 2 || m < DS_W - 6 - 32) && (t < 2 || gq < 3))
-#if DS_PACK_PERM
                         // every accumulator is a sum of bytes x the 8-bit kernel (<= 255 * 257, whatever bytes the don't-care rows
                         // hold): its two low bytes are the whole value
                         *(uint2 *)(vo + (16 * j) * (DS_VC / 2) + 8 * t) =
                             make_uint2(__builtin_amdgcn_perm((uint32_t)acc[1], (uint32_t)acc[0], 0x05040100u),
                                        __builtin_amdgcn_perm((uint32_t)acc[3], (uint32_t)acc[2], 0x05040100u));
-#else
-                        *(uint2 *)(vo + (16 * j) * (DS_VC / 2) + 8 * t) =
-                            make_uint2((uint32_t)acc[0] | ((uint32_t)acc[1] << 16), (uint32_t)acc[2] | ((uint32_t)acc[3] << 16));
-#endif
                 }
             }
         }
-#elif DS_COLFIRST
-        // ---- column pass over the whole patch: lane = (dword column cg of 11, row group seg of 5), 8 output rows from 14 patch
-        // rows held in registers as u16 pairs (v_perm), the filter as packed 16-bit multiply-adds (sums <= 65535)
-        {
-            typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-            const int seg = (lane * 373) >> 12, cg = lane - 11 * seg;   // lane / 11, lane % 11
-            if (seg < 5) {
-                // (the symmetric sums and the centre product as plain 32-bit operations on the pair -- no carry crosses the halves:
-                // <= 510 and <= 14025 -- which issue at the full rate; the three multiply-adds of the sums are packed 16-bit ones)
-                uint32_t pa[14], pb[14];
-#pragma unroll
-                for (int j = 0; j < 14; ++j) {
-                    const uint32_t d = patch[min(8 * seg + j, DS_W - 1) * (DS_PP / 4) + cg];
-                    pa[j] = __builtin_amdgcn_perm(0u, d, 0x0c010c00u);   // columns 4cg, 4cg+1 as u16 pair
-                    pb[j] = __builtin_amdgcn_perm(0u, d, 0x0c030c02u);   // columns 4cg+2, 4cg+3
-                }
-                const u16x2 k1 = {49, 49}, k2 = {34, 34}, k3 = {18, 18};
-                uint32_t *vo = (uint32_t *)hrow + (8 * seg) * (DS_VC / 2) + 2 * cg;
-#define DS_CP(P, r)                                                                                                          \
-    __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, P[r + 2] + P[r + 4]) * k1 +                                       \
-                                     (__builtin_bit_cast(u16x2, P[r + 1] + P[r + 5]) * k2 +                                  \
-                                      (__builtin_bit_cast(u16x2, P[r] + P[r + 6]) * k3 + __builtin_bit_cast(u16x2, __umul24(P[r + 3], 55u)))))
-#pragma unroll
-                for (int r = 0; r < 8; ++r) *(uint2 *)(vo + r * (DS_VC / 2)) = make_uint2(DS_CP(pa, r), DS_CP(pb, r));
-#undef DS_CP
-            }
-        }
-#else
-        for (int i = lane; i < DS_W * (DS_HC / 8); i += 64) {
-            // item = 8 consecutive outputs of one row from 4 aligned dwords: the byte-shifted middle dwords are shared
-            // between the two groups of four (9 v_alignbyte + 16 v_dot4 per 8 outputs)
-            const int r = __mul24(i, 13108) >> 16, q8 = i - r * (DS_HC / 8);   // i / 5 for i < 16384
-            const uint32_t *w = patch + r * (DS_PP / 4) + 2 * q8;
-            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
-            const uint32_t KLO = 18u | (34u << 8) | (49u << 16) | (55u << 24), KHI = 49u | (34u << 8) | (18u << 16);
-            uint32_t hv[8];
-            hv[0] = __builtin_amdgcn_udot4(w0, KLO, __builtin_amdgcn_udot4(w1, KHI, 0u, false), false);
-            hv[4] = __builtin_amdgcn_udot4(w1, KLO, __builtin_amdgcn_udot4(w2, KHI, 0u, false), false);
-#pragma unroll
-            for (int j = 1; j < 4; ++j) {
-                const uint32_t a01 = __builtin_amdgcn_alignbyte(w1, w0, j), a12 = __builtin_amdgcn_alignbyte(w2, w1, j),
-                               a23 = __builtin_amdgcn_alignbyte(w3, w2, j);
-                hv[j] = __builtin_amdgcn_udot4(a01, KLO, __builtin_amdgcn_udot4(a12, KHI, 0u, false), false);
-                hv[4 + j] = __builtin_amdgcn_udot4(a12, KLO, __builtin_amdgcn_udot4(a23, KHI, 0u, false), false);
-            }
-            uint4 o;
-            o.x = hv[0] | (hv[1] << 16);   // each <= 255 * 257 = 65535
-            o.y = hv[2] | (hv[3] << 16);
-            o.z = hv[4] | (hv[5] << 16);
-            o.w = hv[6] | (hv[7] << 16);
-            *(uint4 *)(hrow + r * DS_HC + 8 * q8) = o;
-        }
-#endif
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -2421,122 +1992,57 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
         // with I = 55 r0 + 49 r1 + 34 r2 + 18 r3: one integer formula serves both, the tail only changes the tie rule.
         const int wvec = (L.pw - 2 * L.org) & ~3;   // of the image GaussianBlur is given (fork: the padded level; upstream: the view)
         // tap t = 2 r + s2: point s2 of the lane's pair of round r
-#if DS_PATTERN_F32
-#define DS_PX(t) (((t) & 1) ? patf[(t) >> 1].z : patf[(t) >> 1].x)
-#define DS_PY(t) (((t) & 1) ? patf[(t) >> 1].w : patf[(t) >> 1].y)
-#else
         const int pw4[4] = {pat.x, pat.y, pat.z, pat.w};
 #define DS_PX(t) ((float)(signed char)((pw4[(t) >> 1] >> (16 * ((t) & 1))) & 0xff))
 #define DS_PY(t) ((float)(signed char)((pw4[(t) >> 1] >> (16 * ((t) & 1) + 8)) & 0xff))
-#endif
         unsigned long long words[4];
         if (x + (DS_R - 3) < wvec) {
             // No tap of this keypoint reaches the tail columns (all but keypoints within 18 px of the right edge): the
             // float form of round-half-even is the shortest.  cvRound of the rotated coordinates = adding 1.5 * 2^23
             // (round-to-nearest-even in the add, the integer lands in the low mantissa bits); the 24-bit multiply-add
             // takes those low bits as they are, the exponent bits of the column term cancel in the constant.
-#if DS_COLFIRST
             const uint32_t cbias = (uint32_t)(2 * ((DS_R - 3) * DS_VC + (DS_R - 3))) - 0x400000u * (2u * DS_VC) - (0x4B400000u << 1);
-#else
-            const uint32_t cbias = (uint32_t)(2 * ((DS_R - 3) * DS_HC + (DS_R - 3))) - 0x400000u * (2u * DS_HC) - (0x4B400000u << 1);
-#endif
             const uint32_t hbase = (uint32_t)(uintptr_t)(orbx_lds_u16p)hrow + cbias;
             float tv[8];
             float nb = -b;
             asm("" : "+v"(nb));   // a register of its own (the compiler would fold the negation back into every product)
 #pragma unroll
-            for (int t0 = 0; t0 < 8; t0 += DS_TAP_BATCH) {
-                uint32_t adr[DS_TAP_BATCH], I[DS_TAP_BATCH];
-#pragma unroll
-                for (int k = 0; k < DS_TAP_BATCH; ++k) {
-                    const float px = DS_PX(t0 + k), py = DS_PY(t0 + k);
-                    float fy, fx;
-                    if (FPM == ORBX_FP_GCC_FMA) {
-                        fy = __builtin_fmaf(px, b, py * a);     // vfmadd132ss: x*b + rn(y*a)
-                        fx = __builtin_fmaf(px, a, py * nb);    // vfmsub132ss: x*a - rn(y*b); -(y*b) = y*(-b) exactly, and a
-                                                                // product by a NEGATED REGISTER is a VOP3 encoding (half rate)
-                    } else {
-                        fy = px * b + py * a;
-                        fx = px * a + py * nb;
-                    }
-                    const uint32_t uy = __float_as_uint(fy + 12582912.0f), ux = __float_as_uint(fx + 12582912.0f);
-#if DS_COLFIRST
-#if DS_MFMA
-                    // LDS byte address of HT[ix+18][iy+18]: the tap's window starts here (two instructions: v_lshl_add + v_mad_u32_u24)
-                    uint32_t ay = (uy << 1) + hbase;
-                    asm("" : "+v"(ay));
-                    adr[k] = __umul24(ux, 2u * DS_VC) + ay;
-#else
-                    adr[k] = __umul24(uy, 2u * DS_VC) + ((ux << 1) + hbase);   // LDS byte address of v[iy+18][ix+18]: the tap's window starts here
-#endif
-#else
-                    adr[k] = __umul24(uy, 2u * DS_HC) + ((ux << 1) + hbase);   // LDS byte address of h[iy+18][ix+18]
-                    asm("" : "+v"(adr[k]));   // a plain address from here on: the row offsets fold into the ds_read immediates
-#endif
-                }
-#if DS_COLFIRST
-                orbx_ds_taps<DS_TAP_BATCH>(adr, I);
-#else
-#pragma unroll
-                for (int k = 0; k < DS_TAP_BATCH; ++k) {
-                    const orbx_lds_u16p hp = (orbx_lds_u16p)(uintptr_t)adr[k];
-                    const uint32_t r0 = hp[3 * DS_HC], r1 = (uint32_t)hp[2 * DS_HC] + hp[4 * DS_HC],
-                                   r2 = (uint32_t)hp[1 * DS_HC] + hp[5 * DS_HC], r3 = (uint32_t)hp[0] + hp[6 * DS_HC];
-                    I[k] = __umul24(55u, r0) + __umul24(49u, r1) + __umul24(34u, r2) + __umul24(18u, r3);   // < 2^24.01
-                }
-#endif
+            for (int t = 0; t < 8; ++t) {
+                const float px = DS_PX(t), py = DS_PY(t);
+                // fy = x*b + rn(y*a) (vfmadd132ss), fx = x*a - rn(y*b) (vfmsub132ss); -(y*b) = y*(-b) exactly, and a product by a
+                // NEGATED REGISTER is a VOP3 encoding (half rate).  fx is formed behind the pin of the row address: where the
+                // compiler's schedule of the eight taps wants it
+                const float fy = FPM == ORBX_FP_GCC_FMA ? __builtin_fmaf(px, b, py * a) : px * b + py * a;
+                const uint32_t uy = __float_as_uint(fy + 12582912.0f);
+                // LDS byte address of HT[ix+18][iy+18]: the tap's window starts here (two instructions: v_lshl_add + v_mad_u32_u24)
+                uint32_t ay = (uy << 1) + hbase;
+                asm("" : "+v"(ay));
+                const float fx = FPM == ORBX_FP_GCC_FMA ? __builtin_fmaf(px, a, py * nb) : px * a + py * nb;
+                const uint32_t ux = __float_as_uint(fx + 12582912.0f);
+                const uint32_t I = orbx_ds_tap(__umul24(ux, 2u * DS_VC) + ay);
                 // I <= 2^24 converts exactly and I * 2^-16 is exact; above, the conversion's own rounding keeps it >= 256
-#pragma unroll
-                for (int k = 0; k < DS_TAP_BATCH; ++k) tv[t0 + k] = __builtin_fminf(__builtin_rintf((float)I[k] * (1.f / 65536.f)), 255.f);
+                tv[t] = __builtin_fminf(__builtin_rintf((float)I * (1.f / 65536.f)), 255.f);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) words[r] = orbx_ballot(tv[2 * r] < tv[2 * r + 1]);
         } else {
             int tval[8];
 #pragma unroll
-            for (int t0 = 0; t0 < 8; t0 += DS_TAP_BATCH) {
-                uint32_t adr[DS_TAP_BATCH], I[DS_TAP_BATCH];
-                int ixs[DS_TAP_BATCH];
-#pragma unroll
-                for (int k = 0; k < DS_TAP_BATCH; ++k) {
-                    const float px = DS_PX(t0 + k), py = DS_PY(t0 + k);
-                    float fy, fx;
-                    if (FPM == ORBX_FP_GCC_FMA) {
-                        fy = __builtin_fmaf(px, b, py * a);
-                        fx = __builtin_fmaf(px, a, -(py * b));
-                    } else {
-                        fy = px * b + py * a;
-                        fx = px * a - py * b;
-                    }
-                    const int iy = (int)__builtin_rintf(fy), ix = (int)__builtin_rintf(fx);
-                    ixs[k] = ix;
-                    // blurred pixel (x+ix, y+iy): column pass over h rows (iy+21-3 .. iy+21+3), h column ix+18
-#if DS_COLFIRST
-#if DS_MFMA
-                    adr[k] = (uint32_t)(uintptr_t)(orbx_lds_u16p)hrow + 2u * (uint32_t)(__mul24(ix + DS_R - 3, DS_VC) + (iy + DS_R - 3));
-#else
-                    adr[k] = (uint32_t)(uintptr_t)(orbx_lds_u16p)hrow + 2u * (uint32_t)(__mul24(iy + DS_R - 3, DS_VC) + (ix + DS_R - 3));
-#endif
-#else
-                    adr[k] = (uint32_t)(__mul24(iy + DS_R - 3, DS_HC) + (ix + DS_R - 3));   // element index in h
-#endif
+            for (int t = 0; t < 8; ++t) {
+                const float px = DS_PX(t), py = DS_PY(t);
+                float fy, fx;
+                if (FPM == ORBX_FP_GCC_FMA) {
+                    fy = __builtin_fmaf(px, b, py * a);
+                    fx = __builtin_fmaf(px, a, -(py * b));
+                } else {
+                    fy = px * b + py * a;
+                    fx = px * a - py * b;
                 }
-#if DS_COLFIRST
-                orbx_ds_taps<DS_TAP_BATCH>(adr, I);
-#else
-#pragma unroll
-                for (int k = 0; k < DS_TAP_BATCH; ++k) {
-                    const uint16_t *hp = hrow + adr[k];
-                    const uint32_t r0 = hp[3 * DS_HC], r1 = (uint32_t)hp[2 * DS_HC] + hp[4 * DS_HC],
-                                   r2 = (uint32_t)hp[1 * DS_HC] + hp[5 * DS_HC], r3 = (uint32_t)hp[0] + hp[6 * DS_HC];
-                    I[k] = __umul24(55u, r0) + __umul24(49u, r1) + __umul24(34u, r2) + __umul24(18u, r3);
-                }
-#endif
-#pragma unroll
-                for (int k = 0; k < DS_TAP_BATCH; ++k) {
-                    const uint32_t tie = x + ixs[k] >= wvec ? 1u : ((I[k] >> 16) & 1u);   // half-up in the tail, half-even elsewhere
-                    tval[t0 + k] = (int)min((I[k] + 0x7fffu + tie) >> 16, 255u);
-                }
+                const int iy = (int)__builtin_rintf(fy), ix = (int)__builtin_rintf(fx);
+                // blurred pixel (x+ix, y+iy): column pass over h rows (iy+21-3 .. iy+21+3), h column ix+18
+                const uint32_t I = orbx_ds_tap((uint32_t)(uintptr_t)(orbx_lds_u16p)hrow + 2u * (uint32_t)(__mul24(ix + DS_R - 3, DS_VC) + (iy + DS_R - 3)));
+                const uint32_t tie = x + ix >= wvec ? 1u : ((I >> 16) & 1u);   // half-up in the tail, half-even elsewhere
+                tval[t] = (int)min((I + 0x7fffu + tie) >> 16, 255u);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) words[r] = orbx_ballot(tval[2 * r] < tval[2 * r + 1]);
@@ -2755,9 +2261,6 @@ typedef float mt_v16f __attribute__((ext_vector_type(16)));
 #endif
 #ifndef MT_F4_LB4
 #define MT_F4_LB4 2
-#endif
-#ifndef MT_F4_USE4
-#define MT_F4_USE4 1
 #endif
 template <int QT>
 __global__ __launch_bounds__(64 * MT_WAVES, QT == 2 ? MT_F4_LB2 : MT_F4_LB4) void k_match_f4(const uint8_t *__restrict__ q, const int *__restrict__ nq,
@@ -4935,11 +4438,9 @@ void orbx_pattern_lane_tables(signed char *i8, float *f32) {
 }
 hipError_t orbx_upload_pattern() {
     signed char t[64 * 16];
-    static float tf[64 * 16];
+    static float tf[64 * 16];   // (orbx_pattern_lane_tables fills both forms; the device reads the int8 one alone)
     orbx_pattern_lane_tables(t, tf);
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_pattern_lane), t, sizeof(t));
-    if (e != hipSuccess) return e;
-    e = hipMemcpyToSymbol(HIP_SYMBOL(c_pattern_f32), tf, sizeof(tf));
     if (e != hipSuccess) return e;
     // IC_Angle weight table: umax of the reference's constructor (src/ORBextractor.cc:866-910) for HALF_PATCH_SIZE = 15
     orbx_params p;
@@ -4990,11 +4491,7 @@ void orbx_launch_pyr_l0(hipStream_t s, const DGeom &g, int B, const uint8_t *img
     int xe = 32;
     while (xe + 1 <= W) xe += 16;           // chunk at X reads source bytes [X - 22, X + 1): must end inside the row
     const int icols = (xe - 32 + 1023) / 1024;
-#if L0_FF
     dim3 grid(B, icols + 1, (L.ph + 4 * L0_ROWS - 1) / (4 * L0_ROWS));
-#else
-    dim3 grid(icols + 1, (L.ph + 4 * L0_ROWS - 1) / (4 * L0_ROWS), B);
-#endif
     hipLaunchKernelGGL(k_pyr_l0, grid, dim3(64, 4), 0, s, g, imgs, W, H, stride, frame_stride, pyr, xe, status, cand_cursor);
 }
 void orbx_launch_pyr_l0_color(hipStream_t s, const DGeom &g, int B, const uint8_t *imgs, int W, int H, int stride,
@@ -5023,11 +4520,7 @@ void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, con
     const DLevel &L = g.lv[level];
     if (narrow) {
         const int rpw = rr_rows_per_wave(L, B, rpw_forced);
-#if RR_FF
         dim3 grid(B, (L.pw + 255) / 256, (L.ph + RR_WPB * rpw - 1) / (RR_WPB * rpw));
-#else
-        dim3 grid((L.pw + 255) / 256, (L.ph + RR_WPB * rpw - 1) / (RR_WPB * rpw), B);
-#endif
         hipLaunchKernelGGL(k_pyr_resize_rows, grid, dim3(64, RR_WPB), 0, s, g, level, taps, pyr, rpw);
         return;
     }
@@ -5038,11 +4531,7 @@ void orbx_launch_pyr_resize_l1(hipStream_t s, const DGeom &g, int B, const OrbxT
                                int tail_bx, int *status, int *cand_cursor, int rpw_forced) {
     const DLevel &L = g.lv[1];
     const int rpw = rr_rows_per_wave(L, B, rpw_forced);
-#if RR_FF
     dim3 grid(B, (L.pw + 255) / 256, (L.ph + RR_WPB * rpw - 1) / (RR_WPB * rpw));
-#else
-    dim3 grid((L.pw + 255) / 256, (L.ph + RR_WPB * rpw - 1) / (RR_WPB * rpw), B);
-#endif
     hipLaunchKernelGGL(k_pyr_resize_rows_l1, grid, dim3(64, RR_WPB), 0, s, g, taps_l1, raw, pyr, rpw, tail_bx, status, cand_cursor);
 }
 void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell *cells, const OrbxFastGroup *groups,
@@ -5125,7 +4614,7 @@ void orbx_launch_quadtree(hipStream_t s, const DGeom &g, int B, const uint2 *den
     for (int l = 0; l < g.nlevels; ++l) nfeat += g.lv[l].nfeat;   // (1241x376 / 2000, 128 frames: 77 / 63 / 99 us with 256 / 512 / 1024)
     int threads = wgs >= 4 * cus && nfeat <= 1600 ? 256 : wgs >= 2 * cus ? 512 : 1024;
     if (forced == 256 || forced == 512 || forced == 1024) threads = forced;
-    const dim3 grid = QT_FF ? dim3(B, level_count) : dim3(level_count, B);
+    const dim3 grid(B, level_count);   // frame fastest (see qt_workgroup)
     if (threads == 256)
         hipLaunchKernelGGL(k_quadtree<256>, grid, dim3(256), smem, s, g, dense, cand_count, lvl_kp, lvl_count, status, knode_glob, ncap, lds_keys, reg_keys, level_begin);
     else if (threads == 512)
@@ -5162,11 +4651,7 @@ void orbx_launch_describe(hipStream_t s, const DGeom &g, int B, const uint8_t *p
 #else
     const int dbg_stop = 0;
 #endif
-#if DS_ORDER == 1
     const dim3 grid(8 * ((g.kp_total + DS_WPB - 1) / DS_WPB), (B + 7) / 8);
-#else
-    const dim3 grid(B, (g.kp_total + DS_WPB - 1) / DS_WPB);
-#endif
     const OrbxRaw0 none{nullptr, 0, 0, 0, 0};
     if (raw && g.fp_mode == ORBX_FP_GCC_FMA)
         hipLaunchKernelGGL((k_describe<ORBX_FP_GCC_FMA, true>), grid, dim3(64 * DS_WPB), 0, s, g, pyr, lvl_kp, lvl_count, lvl_angle, kps, desc, counts, status, cap, dbg_stop, B, *raw);
@@ -5261,7 +4746,7 @@ void orbx_launch_match(hipStream_t s, int npairs, int max_nq, const uint8_t *q, 
     // 512 queries per block (QT = 4, two waves per SIMD: the chip holds 2048 such waves) when the launch fills the chip that
     // way without splitting the train set; otherwise 256 per block and the train split that reaches ~4096 waves
     const long long waves4 = (long long)((max_nq + MT_QPW(4) - 1) / MT_QPW(4)) * npairs;
-    if (waves4 >= 2048 && (!f4 || MT_F4_USE4)) {
+    if (waves4 >= 2048) {
         hipLaunchKernelGGL(f4 ? k_match_f4<4> : k_match<4>, dim3((max_nq + MT_QPB(4) - 1) / MT_QPB(4), 1, npairs), dim3(64 * MT_WAVES), 0, s, q, nq,
                            q_stride, t, nt, t_stride, (uint2 *)workspace, best_idx, best_dist, second_dist, out_stride, 1);
         return;

@@ -12,7 +12,8 @@
 #include "orbx_recon.h"
 
 hipError_t orbx_upload_pattern();
-// the per-lane pattern tables orbx_upload_pattern uploads, 64 lanes x 16 coordinates each: c_pattern_lane and c_pattern_f32 (host only)
+// the per-lane pattern tables, 64 lanes x 16 coordinates each (host only): orbx_upload_pattern uploads the int8 one (c_pattern_lane);
+// the same coordinates as floats serve the debug entry orbx_debug_describe_pattern
 void orbx_pattern_lane_tables(signed char *i8, float *f32);
 size_t orbx_quadtree_smem(int ncap, int lds_keys);
 hipError_t orbx_quadtree_prepare(size_t smem);

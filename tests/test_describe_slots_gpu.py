@@ -1,4 +1,4 @@
-"""k_describe indexes its waves by slot of the per-frame level-keypoint table (DS_SLOT): the level of a slot comes from the
+"""k_describe indexes its waves by slot of the per-frame level-keypoint table: the level of a slot comes from the
 kp_begin values, a slot beyond its level's count is a dead wave, the output position is the sum of the counts below + the index.
 Everything that prologue can get wrong shows in the output rows, so every case below compares keypoints, descriptors, counts and
 status of every frame with the CPU oracle, at the smallest shapes where the condition occurs -- and asserts that it does occur."""
