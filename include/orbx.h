@@ -155,7 +155,9 @@ orbx_status orbx_pyramid_level_copy(orbx_handle *h, int frame, int level, uint8_
  *      npairs independent problems: pair p uses query rows d_q + p*q_stride (nq[p] rows) and train
  *      rows d_t + p*t_stride (nt[p] rows); outputs [npairs][out_stride].  Contract: out_stride is the
  *      query capacity -- queries beyond it are ignored (nq[p] is clamped to out_stride on the device,
- *      nothing is written outside row p of the outputs). --------------------------------------------- */
+ *      nothing is written outside row p of the outputs).  Train rows: at most 2^20 = 1 048 576 per pair
+ *      -- nt[p] is clamped to that on the device and rows beyond it are ignored (a result packs the
+ *      train index into 20 bits below the distance), so best_idx never exceeds 2^20 - 1. -------------- */
 orbx_status orbx_match_bruteforce_device(orbx_handle *h, int npairs, const uint8_t *d_q,
                                          const int32_t *d_nq, int64_t q_stride, const uint8_t *d_t,
                                          const int32_t *d_nt, int64_t t_stride, int32_t *d_best_idx,
@@ -724,6 +726,16 @@ orbx_status orbx_debug_level_keypoints(orbx_handle *h, int frame, int level, orb
 orbx_status orbx_debug_blur_copy(orbx_handle *h, int frame, int level, uint8_t *dst, int dst_stride);
 /* FAST groups (waves' work items of k_fast_rows) per frame of the configured geometry: those of level 0, and all of them */
 orbx_status orbx_debug_fast_groups(orbx_handle *h, int *level0, int *total);
+/* The regime a launcher picks from the size of a launch alone, as it would on this handle (tests assert the regime they mean to
+ * run in).  Pure arithmetic: no device work, host-only handles answer too.
+ * orbx_debug_match_plan: orbx_match_bruteforce_device(npairs, ..., out_stride) with the handle's ORBX_MATCH_KERNEL -- qt = query
+ * tiles of 32 per wave of the matrix-pipe kernels (4 or 2; 0 = the vector-pipe kernel), nsplit = blocks a pair's train set is
+ * split over (1..16; 1 on the matrix pipe = direct output, no merge kernel).
+ * orbx_debug_fast_gpw: groups per wave (1 or 2) of a k_fast_rows launch over `nframes` frames x `ngroups` groups -- the forced
+ * value when ORBX_FAST_GPW=1|2 is set (read when the handle is configured; any other value is ORBX_BAD_ARGUMENT), else the size
+ * rule. */
+orbx_status orbx_debug_match_plan(orbx_handle *h, int npairs, int out_stride, int *qt, int *nsplit);
+orbx_status orbx_debug_fast_gpw(orbx_handle *h, int nframes, int ngroups, int *gpw);
 /* the two per-lane forms of the BRIEF pattern k_describe reads, as uploaded: 64 lanes x 16 coordinates (round r of lane l =
  * pair r*64 + l as x1, y1, x2, y2), int8 and float.  Host only: needs no handle and no device. */
 orbx_status orbx_debug_describe_pattern(int8_t *lane_i8_1024, float *lane_f32_1024);

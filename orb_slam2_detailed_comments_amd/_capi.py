@@ -147,7 +147,7 @@ SYMBOLS = [
     "orbx_pyramid_level_copy", "orbx_match_bruteforce_device", "orbx_match_bruteforce", "orbx_hamming_matrix",
     "orbx_get_stream", "orbx_set_stream", "orbx_synchronize", "orbx_profile_enable", "orbx_profile_read",
     "orbx_kernel_name", "orbx_debug_candidates", "orbx_debug_level_keypoints", "orbx_debug_blur_copy", "orbx_debug_fast_groups",
-    "orbx_debug_describe_pattern",
+    "orbx_debug_describe_pattern", "orbx_debug_match_plan", "orbx_debug_fast_gpw",
     "orbx_grid_create", "orbx_grid_destroy", "orbx_grid_query", "orbx_three_maxima",
     "orbx_search_for_initialization", "orbx_stereo_match", "orbx_search_by_projection_frame",
     "orbx_search_by_projection_mappoints", "orbx_search_by_projection_frame_batch_device",
@@ -274,6 +274,9 @@ def lib():
     L.orbx_debug_fast_groups.restype = i32; L.orbx_debug_fast_groups.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     if hasattr(L, "orbx_debug_describe_pattern"):   # (absent from an ORBX_LIB build older than the symbol: A/B runs against it)
         L.orbx_debug_describe_pattern.restype = i32; L.orbx_debug_describe_pattern.argtypes = [vp, vp]
+    if hasattr(L, "orbx_debug_match_plan"):   # (absent from an ORBX_LIB build older than the symbols: A/B runs against it)
+        L.orbx_debug_match_plan.restype = i32; L.orbx_debug_match_plan.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+        L.orbx_debug_fast_gpw.restype = i32; L.orbx_debug_fast_gpw.argtypes = [vp, i32, i32, C.POINTER(i32)]
     L.orbx_grid_create.restype = vp; L.orbx_grid_create.argtypes = [vp, i32, f32, f32, f32, f32]
     L.orbx_grid_destroy.restype = None; L.orbx_grid_destroy.argtypes = [vp]
     L.orbx_grid_query.restype = i32; L.orbx_grid_query.argtypes = [vp, f32, f32, f32, i32, i32, vp, i32]

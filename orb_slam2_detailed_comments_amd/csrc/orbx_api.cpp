@@ -90,6 +90,15 @@ static void free_geometry_buffers(orbx_handle *h) {
     h->configured = false;
 }
 
+orbx_status read_fast_gpw(orbx_handle *h) {
+    h->fast_gpw = 0;
+    if (const char *e = getenv("ORBX_FAST_GPW")) {   // tests run two planted groups per wave at a batch of 16 frames with it
+        if (strcmp(e, "1") == 0 || strcmp(e, "2") == 0) h->fast_gpw = e[0] - '0';
+        else return orbx_fail(ORBX_BAD_ARGUMENT, "ORBX_FAST_GPW must be 1 or 2");
+    }
+    return ORBX_OK;
+}
+
 orbx_status configure(orbx_handle *h, int width, int height) {
     if (h->configured && h->geom.width == width && h->geom.height == height) return ORBX_OK;
     if (h->host_only) return orbx_fail(ORBX_NO_DEVICE, "host-only handle (device = -2) cannot extract");
@@ -191,6 +200,8 @@ orbx_status configure(orbx_handle *h, int width, int height) {
     if (const char *e = getenv("ORBX_FAST_STOP")) h->fast_stop = atoi(e);
 #endif
     if (const char *e = getenv("ORBX_FAST_LCAP")) h->fast_lcap = std::max(64, atoi(e));
+    { const orbx_status gs = read_fast_gpw(h);
+      if (gs != ORBX_OK) return gs; }
     const OrbxGeom &hg = h->geom;
     hipStream_t s = h->stream;
     // Optional fork of the batched launch sequence (run_chunk): ORBX_FORK_LEVEL = l > 0 resizes levels >= l and runs their

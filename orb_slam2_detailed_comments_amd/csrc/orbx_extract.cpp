@@ -117,7 +117,8 @@ static orbx_status run_chunk(orbx_handle *h, int B, const uint8_t *d_imgs, int W
         orbx_launch_fast_rows(st, g, b, h->d_cells, h->d_groups + g0, ng, h->d_pyr + (size_t)f0 * h->geom.pyr_bytes,
                               h->d_dense + (size_t)f0 * g.cand_total, h->d_cand_count + (size_t)f0 * NL, d_status + f0,
                               part == 1 ? h->max_ch_l0 : part == 2 ? h->max_ch_rest : h->max_ch,
-                              h->fast_lcap, h->fast_stop, lds_floor, inplace && part != 2 ? &raw : nullptr, part == 1);
+                              h->fast_lcap, h->fast_stop, lds_floor, inplace && part != 2 ? &raw : nullptr, part == 1,
+                              h->fast_gpw);
     };
     auto finish = [&](int f0, int b) {
         { ProfScope ps(h, ORBX_K_QUADTREE);

@@ -58,6 +58,7 @@ struct orbx_handle {
     int match_kernel = 0;        // ORBX_MATCH_KERNEL, read ONCE when the handle is created: 0 = matrix pipe with FP4 operands (default), 1 = "valu" (vector pipe), 2 = "i8" (matrix pipe, int8 operands) -- A/B runs, parity tests
     int fast_stop = 0;      // ORBX_FAST_STOP: only read in -DORBX_TIMING_KNOBS builds
     int fast_lcap = 640;    // LDS work-list entries of k_fast_rows (ORBX_FAST_LCAP; tests shrink it to force the flush paths)
+    int fast_gpw = 0;       // ORBX_FAST_GPW: groups per wave of k_fast_rows forced to 1 or 2 (tests pair planted groups at small batches); 0 = the launcher's size rule
     OrbxTap *d_taps = nullptr;
     uint2 *d_dense = nullptr;   // dense per-(frame, level) key arrays, appended to by k_fast_rows (fill counts in d_cand_count)
     int *d_cand_count = nullptr, *d_lvl_count = nullptr, *d_status = nullptr;
@@ -136,6 +137,9 @@ struct ProfScope {
 #pragma GCC visibility push(hidden)   // what follows is shared between the library's own units only: not exported
 void prof_drain(orbx_handle *h);
 orbx_status configure(orbx_handle *h, int width, int height);   // orbx_api.cpp: the handle's geometry and device buffers for one image size
+// ORBX_FAST_GPW into h->fast_gpw (0 when unset; anything but 1 or 2 is ORBX_BAD_ARGUMENT): configure(), and orbx_debug_fast_gpw on
+// a handle that has not been configured (a host-only one never is)
+orbx_status read_fast_gpw(orbx_handle *h);
 // ---------------------------------------------------------------- staging (orbx_api.cpp)
 // A grow-only device buffer: *cap < need frees it behind a wait for the handle's stream and allocates `want` elements (contents go).
 orbx_status dev_grow(orbx_handle *h, void **p, size_t *cap, size_t need, size_t want, size_t elem = 1);

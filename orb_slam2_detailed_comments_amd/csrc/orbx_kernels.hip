@@ -10,6 +10,7 @@
 #include "orbx_inplace.h"
 #include "orbx_fast_net.h"
 #include "orbx_track.h"
+#include "orbx_launch.h"   // the launch regimes (MT_SPLIT, MT_QPW, FR_GPW and the plan functions) ahead of the kernels
 #include "../../include/orbx_pattern_data.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -564,9 +565,7 @@ __device__ __forceinline__ void orbx_wave_sync() {
 #define FR_CCAP 512     // corner-list entries per group (see orbx_launch_fast_rows, which has the byte arithmetic)
 #endif
 #define FR_STACK 128    // re-run stack of fr_round, entries: between the work list and the corner list
-#ifndef FR_GPW
-#define FR_GPW 2        // groups per wave
-#endif
+// (FR_GPW, the groups per wave of a large launch: orbx_launch.h)
 typedef unsigned short fr_u16;
 typedef short fr_i16;
 typedef __attribute__((address_space(3))) uint16_t fr_lds_u16;
@@ -2092,16 +2091,13 @@ __global__ __launch_bounds__(64 * DS_WPB, DS_WPS) void k_describe(DGeom g, const
 // -- the result is the same integer, bit for bit -- so the MFMA kernel is the default and the vector-pipe kernel stays
 // selectable (ORBX_MATCH_KERNEL=valu) and parity-tested, for A/B runs and for readers who want the path as specified.
 // ------------------------------------------------------------------------------------------------
-#define MT_SPLIT 16     // most ways the train set is split over blockIdx.y; partials merged by k_match_merge.  The launcher picks
-                        // the smallest split that still fills the chip (every extra split repeats the query expansion and
-                        // one partial record per query)
+// (MT_SPLIT, the most ways the train set is split over blockIdx.y, and MT_QPW: orbx_launch.h, beside the launcher's rule)
 #define MT_WAVES 4      // waves per block; they share the train key table
 // Query column tiles (of 32) per wave, QT: the expanded train tile (A operand: 32 shift-and pairs) and its key registers serve QT
 // MFMA chains.  QT = 2: 64 B-operand registers, three waves per SIMD without a spill (round 2 capped the registers for four
 // and spilled 11 of them inside the MFMA loop).  QT = 4: a block walks its train tiles ONCE for 512 queries -- half the train
 // loads, half the expansions and half the key-table reads per distance -- with 128 B-operand + 64 accumulator registers, two
 // waves per SIMD; the launcher takes it when the launch still fills the chip that way.
-#define MT_QPW(QT) (32 * (QT))
 #define MT_QPB(QT) (MT_WAVES * MT_QPW(QT))
 #define MT_CHUNK 4096   // train descriptors per key table (12 index bits in the key)
 typedef int mt_v4i __attribute__((ext_vector_type(4)));
@@ -4536,7 +4532,7 @@ void orbx_launch_pyr_resize_l1(hipStream_t s, const DGeom &g, int B, const OrbxT
 }
 void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell *cells, const OrbxFastGroup *groups,
                            int ngroups, const uint8_t *pyr, uint2 *cand, int *cand_cursor, int *status, int max_ch, int lcap,
-                           int dbg_stop, int lds_floor, const OrbxRaw0 *raw, bool l0_only) {
+                           int dbg_stop, int lds_floor, const OrbxRaw0 *raw, bool l0_only, int gpw_forced) {
     if (ngroups <= 0) return;
     lcap = (max(lcap, 64) + 1) & ~1;
     // LDS per wave decides how many waves a CU holds: the corner list of a group is sized for its usual load, FR_CCAP entries (the
@@ -4552,9 +4548,7 @@ void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell 
     // kernels of the other stream; the kernel uses no more than it did
     const size_t need = (size_t)lds.bytes;
     const size_t smem = lds_floor > 0 && (size_t)lds_floor > need ? (size_t)lds_floor : need;
-    // groups per wave: FR_GPW when the launch has waves to spare (the second group's tile is prefetched while the first
-    // is processed); one per wave for small batches, where the serial length of a wave is what the caller waits for
-    const int gpw = (long long)B * ngroups >= 16384 ? FR_GPW : 1;
+    const int gpw = orbx_fast_gpw(B, ngroups, gpw_forced);   // groups per wave (orbx_launch.h)
     if (raw && l0_only)
         hipLaunchKernelGGL(k_fast_rows_l0, dim3(B, (ngroups + gpw - 1) / gpw), dim3(64), smem, s, g, cells, groups, cand,
                            cand_cursor, status, max_ch, lcap, ngroups, gpw, dbg_stop, ccap, *raw);
@@ -4731,29 +4725,24 @@ void orbx_launch_match(hipStream_t s, int npairs, int max_nq, const uint8_t *q, 
                        const uint8_t *t, const int *nt, long long t_stride, int *best_idx, int *best_dist,
                        int *second_dist, int out_stride, void *workspace, int kernel) {
     // kernel: 0 = matrix pipe, FP4 operands (default); 1 = vector pipe (ORBX_MATCH_KERNEL=valu); 2 = matrix pipe, int8 operands (=i8)
-    const bool use_valu = kernel == 1, f4 = kernel == 0;
+    const bool f4 = kernel == 0;
     if (npairs <= 0 || max_nq <= 0) return;
-    if (use_valu) {   // the vector-pipe kernel (orbx_params-free A/B switch ORBX_MATCH_KERNEL=valu, read once per handle)
+    const OrbxMatchPlan plan = orbx_match_plan(npairs, max_nq, kernel);   // QT and the train split (orbx_launch.h)
+    const int nsplit = plan.nsplit;
+    if (plan.qt == 0) {   // the vector-pipe kernel (orbx_params-free A/B switch ORBX_MATCH_KERNEL=valu, read once per handle)
         const int qblocks = (max_nq + 127) / 128;
-        const long long base = (long long)qblocks * npairs;
-        const int nsplit = (int)std::min<long long>(MT_SPLIT, std::max<long long>(1, (16384 + base - 1) / base));
         hipLaunchKernelGGL(k_match_valu, dim3(qblocks, nsplit, npairs), dim3(64), 0, s, q, nq, q_stride, t, nt, t_stride,
                            (uint2 *)workspace, out_stride, nsplit);
         hipLaunchKernelGGL(k_match_merge, dim3((max_nq + 255) / 256, npairs), dim3(256), 0, s, nq, (const uint2 *)workspace,
                            best_idx, best_dist, second_dist, out_stride, nsplit);
         return;
     }
-    // 512 queries per block (QT = 4, two waves per SIMD: the chip holds 2048 such waves) when the launch fills the chip that
-    // way without splitting the train set; otherwise 256 per block and the train split that reaches ~4096 waves
-    const long long waves4 = (long long)((max_nq + MT_QPW(4) - 1) / MT_QPW(4)) * npairs;
-    if (waves4 >= 2048) {
+    if (plan.qt == 4) {
         hipLaunchKernelGGL(f4 ? k_match_f4<4> : k_match<4>, dim3((max_nq + MT_QPB(4) - 1) / MT_QPB(4), 1, npairs), dim3(64 * MT_WAVES), 0, s, q, nq,
                            q_stride, t, nt, t_stride, (uint2 *)workspace, best_idx, best_dist, second_dist, out_stride, 1);
         return;
     }
     const int qblocks = (max_nq + MT_QPB(2) - 1) / MT_QPB(2);
-    const long long base = (long long)((max_nq + MT_QPW(2) - 1) / MT_QPW(2)) * npairs;
-    const int nsplit = (int)std::min<long long>(MT_SPLIT, std::max<long long>(1, 4096 / base));
     hipLaunchKernelGGL(f4 ? k_match_f4<2> : k_match<2>, dim3(qblocks, nsplit, npairs), dim3(64 * MT_WAVES), 0, s, q, nq,
                        q_stride, t, nt, t_stride, (uint2 *)workspace, best_idx, best_dist, second_dist, out_stride, nsplit);
     if (nsplit > 1)

@@ -11,6 +11,41 @@
 #include "orbx_init.h"
 #include "orbx_recon.h"
 
+// ---- launch regimes chosen from the size of a launch alone: ONE definition, used by the launchers (orbx_kernels.hip) and
+// reported by orbx_debug_match_plan / orbx_debug_fast_gpw, so that a test can assert the regime it is running in
+#define MT_SPLIT 16     // most ways the train set is split over blockIdx.y; partials merged by k_match_merge.  The launcher picks
+                        // the smallest split that still fills the chip (every extra split repeats the query expansion and
+                        // one partial record per query)
+#define MT_QPW(QT) (32 * (QT))   // queries per wave of k_match / k_match_f4: QT column tiles of 32
+#ifndef FR_GPW
+#define FR_GPW 2        // groups per wave of k_fast_rows in a launch with waves to spare
+#endif
+// orbx_launch_match.  kernel: 0 = matrix pipe, FP4 operands (default); 1 = vector pipe (ORBX_MATCH_KERNEL=valu); 2 = matrix pipe,
+// int8 operands (=i8).  qt = query tiles per wave of the matrix-pipe kernels (0: the vector-pipe kernel); nsplit = blocks the
+// train set of a pair is split over (nsplit == 1 on the matrix pipe: direct output, no k_match_merge)
+struct OrbxMatchPlan { int qt, nsplit; };
+static inline OrbxMatchPlan orbx_match_plan(int npairs, int max_nq, int kernel) {
+    auto split = [](long long waves, long long base) {
+        const long long n = waves / base;
+        return (int)(n < 1 ? 1 : n > MT_SPLIT ? MT_SPLIT : n);
+    };
+    if (kernel == 1) {   // 128 queries per wave; the split that reaches ~16384 waves
+        const long long base = (long long)((max_nq + 127) / 128) * npairs;
+        return {0, split(16384 + base - 1, base)};
+    }
+    // 512 queries per block (QT = 4, two waves per SIMD: the chip holds 2048 such waves) when the launch fills the chip that
+    // way without splitting the train set; otherwise 256 per block and the train split that reaches ~4096 waves
+    const long long waves4 = (long long)((max_nq + MT_QPW(4) - 1) / MT_QPW(4)) * npairs;
+    if (waves4 >= 2048) return {4, 1};
+    return {2, split(4096, (long long)((max_nq + MT_QPW(2) - 1) / MT_QPW(2)) * npairs)};
+}
+// orbx_launch_fast_rows, groups per wave: FR_GPW when the launch has waves to spare (the second group's tile is prefetched while
+// the first is processed); one per wave for small batches, where the serial length of a wave is what the caller waits for.
+// forced = 1 or 2 (ORBX_FAST_GPW, tests) overrides the size rule; 0 = the size rule.
+static inline int orbx_fast_gpw(int B, int ngroups, int forced) {
+    return forced > 0 ? forced : (long long)B * ngroups >= 16384 ? FR_GPW : 1;
+}
+
 hipError_t orbx_upload_pattern();
 // the per-lane pattern tables, 64 lanes x 16 coordinates each (host only): orbx_upload_pattern uploads the int8 one (c_pattern_lane);
 // the same coordinates as floats serve the debug entry orbx_debug_describe_pattern
@@ -29,9 +64,10 @@ void orbx_launch_pyr_resize(hipStream_t s, const DGeom &g, int B, int level, con
 // (rpw_forced > 0: destination rows per wave of the row-walking kernel, a power of two in 2..64 -- ORBX_RR_RPW; 0: the launcher's choice)
 void orbx_launch_fast_rows(hipStream_t s, const DGeom &g, int B, const OrbxCell *cells, const OrbxFastGroup *groups,
                            int ngroups, const uint8_t *pyr, uint2 *cand, int *cand_cursor, int *status, int max_ch, int lcap,
-                           int dbg_stop, int lds_floor = 0, const OrbxRaw0 *raw = nullptr, bool l0_only = false);
+                           int dbg_stop, int lds_floor = 0, const OrbxRaw0 *raw = nullptr, bool l0_only = false,
+                           int gpw_forced = 0);
 // (raw: the level-0 groups read the caller's image; l0_only with raw: every group of the launch is a level-0 group.  max_ch is
-// the tallest cell of the groups of THIS launch: it sizes the LDS tile and score map.)
+// the tallest cell of the groups of THIS launch: it sizes the LDS tile and score map.  gpw_forced: orbx_fast_gpw above.)
 // in-place mode (orbx_inplace.h): level 1 from the caller's grey image `raw`; also resets status[f] and cand_cursor[f][*] as
 // k_pyr_l0 does, unless `status` is null (the FAST-first plan resets them before its first FAST launch).  taps_l1 = the level's raw-coordinate tap table (pw horizontal records, then ph vertical ones).
 void orbx_launch_pyr_resize_l1(hipStream_t s, const DGeom &g, int B, const OrbxTap *taps_l1, const OrbxRaw0 &raw, uint8_t *pyr,

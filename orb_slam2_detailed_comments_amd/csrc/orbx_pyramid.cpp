@@ -139,6 +139,23 @@ extern "C" orbx_status orbx_debug_fast_groups(orbx_handle *h, int *level0, int *
     if (total) *total = (int)h->geom.fast_groups.size();
     return ORBX_OK;
 }
+// the launchers' size rules (orbx_launch.h), pure arithmetic: host-only handles answer too
+extern "C" orbx_status orbx_debug_match_plan(orbx_handle *h, int npairs, int out_stride, int *qt, int *nsplit) {
+    if (!h || npairs <= 0 || out_stride <= 0) return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
+    const OrbxMatchPlan plan = orbx_match_plan(npairs, out_stride, h->match_kernel);
+    if (qt) *qt = plan.qt;
+    if (nsplit) *nsplit = plan.nsplit;
+    return ORBX_OK;
+}
+extern "C" orbx_status orbx_debug_fast_gpw(orbx_handle *h, int nframes, int ngroups, int *gpw) {
+    if (!h || nframes <= 0 || ngroups <= 0) return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
+    if (!h->configured) {   // what configure() would store
+        const orbx_status st = read_fast_gpw(h);
+        if (st != ORBX_OK) return st;
+    }
+    if (gpw) *gpw = orbx_fast_gpw(nframes, ngroups, h->fast_gpw);
+    return ORBX_OK;
+}
 extern "C" orbx_status orbx_debug_describe_pattern(int8_t *lane_i8_1024, float *lane_f32_1024) {
     if (!lane_i8_1024 || !lane_f32_1024) return orbx_fail(ORBX_BAD_ARGUMENT, "null table");
     orbx_pattern_lane_tables((signed char *)lane_i8_1024, lane_f32_1024);

@@ -311,7 +311,9 @@ def test_match_bruteforce_random_ties_empty(match_kernel):
     rng = np.random.default_rng(3)
     ex = ORBextractor(300)
     m = ORBmatcher(0.9, True, extractor=ex)
-    # (5, 4097) / (257, 8200): more train descriptors than one key table of the kernel holds (4096)
+    # (5, 4097) / (257, 8200): more train rows than one key table of the kernel holds (4096) -- but every call here is one small
+    # pair, which the launcher splits 16 ways: no block gets more than 544 rows, so the loop over key tables does not run here.
+    # tests/test_match_regimes_gpu.py runs it (and every other launch regime)
     for nq, nt in [(1, 1), (63, 64), (64, 257), (65, 255), (1000, 1003), (300, 0), (5, 4097), (257, 8200), (33, 31)]:
         q = rng.integers(0, 256, (nq, 32)).astype(np.uint8)
         t = rng.integers(0, 256, (nt, 32)).astype(np.uint8)
