@@ -858,6 +858,55 @@ void orbx_sim3_batch_destroy(orbx_sim3_batch *b);
  * tests/sim3_model.py, which takes this primitive and orbx_pose_sin_cos from the library. */
 double orbx_sim3_atan2(double y, double x);
 
+/* ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:1383-1615), the link after SearchBySim3 in LoopClosing::ComputeSim3, for every
+ * candidate that returned a Sim3 in one round (and for many streams) in one call.  All VertexSBAPointXYZ are fixed, so the
+ * system is ONE dense 7x7 around a VertexSim3Expmap; g2o takes the Jacobians of EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ
+ * numerically (central differences, delta = 1e-9), so an edge costs 1 + 14 map-and-project evaluations under 14 perturbed
+ * Sim3 that are the same for every edge.  optimize(5), the chi2 test, return 0 below 10 survivors, optimize(5 or 10), the
+ * chi2 test (k_sim3_opt: one wave per problem, one problem per workgroup).
+ * CONTRACT: results and keep rows of the device equal the library's host path (ORBX_SIM3OPT=host in the environment, read per
+ * call; host-only handles) and the numpy restatement tests/sim3opt_model.py bit for bit, in both fp_modes.  Parity with a g2o +
+ * Eigen build is NOT pinned: DESIGN.md section 2 (F16) lists what follows the reference's source and what this library fixes
+ * where the reference leaves it to Eigen (product and summation orders, the dense solve) or to libm (exp, sin, cos).
+ * The caller runs the pointer-chasing filters (pMP1 && pMP2, isBad, GetIndexInKeyFrame >= 0) and the float products
+ * R1w * P3D1w + t1w; a problem lists the correspondences that passed, in order of i.
+ * Results: keep[i] = 1 where vpMatches1[idx_i] survives, 0 where the reference nulls it (the first test's nulls are present
+ * also when the call then returns 0); written = 1 iff the reference assigns g2oS12, r / t / s are then the optimised Sim3,
+ * otherwise the input as g2o::Sim3(R, t, s) holds it; ninliers is the return value; nbad the first test's count.
+ * Validated before any device work, ORBX_BAD_ARGUMENT: nproblems < 0, a null array whose size is positive, n < 0.
+ * nproblems == 0 launches nothing.  n == 0 gives ninliers = 0, written = 0 and reads no array of the problem.
+ * OUTSIDE the contract (z == 0 after a map, s == 0, non-finite input): the same straight-line code runs, every loop is
+ * bounded, a NaN chi2 compares as "not greater" (an inlier, as in the reference) and every stored NaN is the canonical one.
+ * MEASURED on an MI355X (tools/sim3opt_rate.py, profiles/sim3opt_batch.md; n = 30 / 100 / 300 correspondences, against the
+ * library's own host path on one core, which is neither g2o nor the reference): ONE problem per call loses on the device,
+ * 188 / 357 / 776 us against 36 / 91 / 263 us; 16 per call 14 / 26 / 57 us each against 32 / 94 / 279 us; 256 per call
+ * 1.0 / 2.0 / 4.7 us each.  A caller with one candidate at a time uses a host-only handle (compat/Optimizer_sim3.inl does). */
+typedef struct orbx_sim3opt_problem {
+    int32_t n;                         /* correspondences that passed OptimizeSim3's own filters, in order of i */
+    const float *x1c, *x2c;            /* [n][3] P3D1c, P3D2c */
+    const float *obs1, *obs2;          /* [n][2] kpUn1.pt, kpUn2.pt */
+    const float *inv_sigma2_1, *inv_sigma2_2;   /* [n] */
+    float camera1[4], camera2[4];      /* fx, fy, cx, cy */
+    float R[9], t[3], s;               /* the solver's estimate (orbx_sim3_batch_best) */
+    float th2; int32_t fix_scale;
+    uint8_t *keep;                     /* [n] out: 1 = vpMatches1[idx] survives */
+} orbx_sim3opt_problem;
+typedef struct orbx_sim3opt_result {
+    double r[4], t[3], s;              /* g2oS12 on return: quaternion x, y, z, w; the input when written == 0 */
+    float T12[16];                     /* Converter::toCvMat(g2oS12): [sR | t] */
+    int32_t ninliers, nbad, ncorr, written;
+} orbx_sim3opt_result;
+/* One page-locked block up, k_sim3_opt, one block down, the wait.  On a host-only handle the library's host path runs. */
+orbx_status orbx_optimize_sim3_batch(orbx_handle *h, int nproblems, const orbx_sim3opt_problem *problems, orbx_sim3opt_result *results);
+/* parity tests only: the chi2 test alone on all n correspondences of each problem, with the Sim3 at which computeActiveErrors
+ * ran last given explicitly (S_last [nproblems][8]: r x y z w, t, s); keep as after the first test, nbad = its count,
+ * ninliers = n - nbad, written = 0, r / t / s = the input.  Device path, ORBX_SIM3OPT=host and host-only handles. */
+orbx_status orbx_debug_sim3opt_inlier_test(orbx_handle *h, int nproblems, const orbx_sim3opt_problem *problems, const double *S_last,
+                                           orbx_sim3opt_result *results);
+/* exp as Sim3(Vector7d) gets it in both paths (csrc/orbx_sim3opt.h: *, +, fma only).  Exported for tests/sim3opt_model.py,
+ * which takes this primitive and orbx_pose_sin_cos from the library. */
+double orbx_sim3opt_exp(double sigma);
+
 /* ---- PnPsolver (src/PnPsolver.cc), the EPnP RANSAC between SearchByBoW and PoseOptimization in Tracking::Relocalization
  * (src/Tracking.cc:2336-2366), for all candidate keyframes in one device round trip.  An iteration is an independent 4-point
  * EPnP followed by one projection of every correspondence, so every iteration of every candidate is evaluated ahead of time --

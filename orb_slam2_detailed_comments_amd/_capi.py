@@ -77,6 +77,18 @@ class Sim3Problem(C.Structure):   # orbx_sim3_problem
                 ("iterations", C.c_int32), ("sets", C.c_void_p)]
 
 
+class Sim3OptProblem(C.Structure):   # orbx_sim3opt_problem
+    _fields_ = [("n", C.c_int32), ("x1c", C.c_void_p), ("x2c", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p),
+                ("inv_sigma2_1", C.c_void_p), ("inv_sigma2_2", C.c_void_p), ("camera1", C.c_float * 4), ("camera2", C.c_float * 4),
+                ("R", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float), ("th2", C.c_float), ("fix_scale", C.c_int32),
+                ("keep", C.c_void_p)]
+
+
+SIM3OPT_RESULT_DTYPE = np.dtype([("r", "<f8", 4), ("t", "<f8", 3), ("s", "<f8"), ("T12", "<f4", 16), ("ninliers", "<i4"),
+                                 ("nbad", "<i4"), ("ncorr", "<i4"), ("written", "<i4")])   # orbx_sim3opt_result
+assert SIM3OPT_RESULT_DTYPE.itemsize == 144
+
+
 class PnpProblem(C.Structure):   # orbx_pnp_problem
     _fields_ = [("n", C.c_int32), ("p3dw", C.c_void_p), ("p2d", C.c_void_p), ("max_err", C.c_void_p), ("camera", C.c_double * 4),
                 ("min_inliers", C.c_int32), ("iterations", C.c_int32), ("sets", C.c_void_p)]
@@ -167,6 +179,7 @@ SYMBOLS = [
     "orbx_debug_pose_inlier_test",
     "orbx_sim3_ransac_iterations", "orbx_sim3_ransac_batch_create", "orbx_sim3_batch_iterate", "orbx_sim3_batch_best",
     "orbx_sim3_batch_counts", "orbx_sim3_batch_hypothesis", "orbx_sim3_batch_destroy", "orbx_sim3_atan2",
+    "orbx_optimize_sim3_batch", "orbx_debug_sim3opt_inlier_test", "orbx_sim3opt_exp",
     "orbx_pnp_ransac_parameters", "orbx_pnp_ransac_batch_create", "orbx_pnp_batch_iterate", "orbx_pnp_batch_append",
     "orbx_pnp_batch_best", "orbx_pnp_batch_counts", "orbx_pnp_batch_hypothesis", "orbx_pnp_batch_destroy",
     "orbx_init_ransac_batch_create", "orbx_init_batch_result", "orbx_init_batch_scores", "orbx_init_batch_hypothesis",
@@ -235,6 +248,10 @@ def lib():
     L.orbx_sim3_batch_hypothesis.restype = i32; L.orbx_sim3_batch_hypothesis.argtypes = [vp, i32, i32, vp, vp]
     L.orbx_sim3_batch_destroy.restype = None; L.orbx_sim3_batch_destroy.argtypes = [vp]
     L.orbx_sim3_atan2.restype = C.c_double; L.orbx_sim3_atan2.argtypes = [C.c_double, C.c_double]
+    if hasattr(L, "orbx_optimize_sim3_batch"):   # (absent from an ORBX_LIB build older than the symbols: A/B runs against it)
+        L.orbx_optimize_sim3_batch.restype = i32; L.orbx_optimize_sim3_batch.argtypes = [vp, i32, vp, vp]
+        L.orbx_debug_sim3opt_inlier_test.restype = i32; L.orbx_debug_sim3opt_inlier_test.argtypes = [vp, i32, vp, vp, vp]
+        L.orbx_sim3opt_exp.restype = C.c_double; L.orbx_sim3opt_exp.argtypes = [C.c_double]
     L.orbx_pnp_ransac_parameters.restype = None
     L.orbx_pnp_ransac_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
     L.orbx_pnp_ransac_batch_create.restype = i32; L.orbx_pnp_ransac_batch_create.argtypes = [vp, i32, vp, C.POINTER(vp)]

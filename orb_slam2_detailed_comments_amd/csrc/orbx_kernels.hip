@@ -4064,6 +4064,166 @@ __global__ __launch_bounds__(64) void k_pose_opt(const DPoseArgs A) {
     }
 }
 
+#include "orbx_sim3opt.h"
+// Optimizer::OptimizeSim3, batched (orbx_sim3opt.h): one wave per problem, one problem per workgroup, in the anatomy of
+// k_pose_opt.  Per linearisation lanes 0..14 build the estimate's and the 14 perturbed Sim3 with their inverses into LDS (the
+// same for every edge; every lane then reads them by broadcast).  The lanes take the correspondences 64 at a time; a lane
+// whose correspondence is live computes the 36 terms of e12 and of e21, and the chunk goes through the [36][65] term array in
+// two halves of 32 correspondences -- column 2 c = e12, column 2 c + 1 = e21 -- so that lane t < 36 adds term t in the
+// reference's edge order, e12_i before e21_i, i ascending: 36 chains side by side, no atomics.  The 7x7 solve, exp, the update
+// and the Levenberg-Marquardt bookkeeping (orbx_sim3opt_run) run redundantly in every lane on the broadcast sums, so every
+// branch around a barrier is uniform.  The live flags are the output keep row (each lane re-reads what it wrote itself).
+// Every loop is bounded ((5 + 10) x 10 passes over n correspondences) and nothing waits on another wave.
+struct Sim3OptEvDev {
+    OrbxSim3OptView v;
+    OrbxSim3OptCam K1, K2;
+    double th2, delta;
+    bool fix_scale;
+    uint8_t *keep;
+    double *s_term;     // [36][65]: term t of column k at t * 65 + k
+    double *s_acc;      // [36]
+    double *s_tab;      // [15][16]
+    int lane;
+    __device__ void system(const OrbxSim3 &S, double *acc) {
+        if (lane < ORBX_SIM3OPT_NSIM) orbx_sim3opt_table_entry(S, lane, fix_scale, s_tab + lane * ORBX_SIM3OPT_SIM);
+        __syncthreads();
+        double a = 0.0;
+        for (int base = 0; base < v.n; base += 64) {
+            const int i = base + lane;
+            const bool act = i < v.n && keep[i];
+            const unsigned long long mask = orbx_ballot(act);
+            if (mask == 0ull) continue;
+            double t12[ORBX_SIM3OPT_TERMS], t21[ORBX_SIM3OPT_TERMS];
+            if (act) {
+                OrbxSim3OptEdge e12, e21;
+                orbx_sim3opt_load(v, i, e12, e21);
+                orbx_sim3opt_terms(s_tab, 0, K1, e12, delta, t12);
+                orbx_sim3opt_terms(s_tab, 8, K2, e21, delta, t21);
+            }
+#pragma unroll 1
+            for (int half = 0; half < 2; ++half) {
+                const unsigned long long hm = (mask >> (32 * half)) & 0xffffffffull;
+                if (hm == 0ull) continue;
+                if (act && (lane >> 5) == half) {
+                    const int c = 2 * (lane & 31);
+#pragma unroll
+                    for (int k = 0; k < ORBX_SIM3OPT_TERMS; ++k) { s_term[k * 65 + c] = t12[k]; s_term[k * 65 + c + 1] = t21[k]; }
+                }
+                __syncthreads();
+                if (lane < ORBX_SIM3OPT_TERMS) {
+                    unsigned long long m = hm;
+                    while (m) {
+                        const int c = 2 * __builtin_ctzll(m);
+                        m &= m - 1;
+                        a = orbx_sim3opt_accumulate(lane, a, s_term[lane * 65 + c]);
+                        a = orbx_sim3opt_accumulate(lane, a, s_term[lane * 65 + c + 1]);
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        if (lane < ORBX_SIM3OPT_TERMS) s_acc[lane] = a;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < ORBX_SIM3OPT_TERMS; ++k) acc[k] = s_acc[k];
+        __syncthreads();
+    }
+    // the table's entry 0 (S and its inverse), the same in every lane
+    __device__ void entry0(const OrbxSim3 &S) {
+        if (lane == 0) orbx_sim3opt_table_entry(S, 0, fix_scale, s_tab);
+        __syncthreads();
+    }
+    __device__ double chi(const OrbxSim3 &S) {
+        entry0(S);
+        double a = 0.0;
+        for (int base = 0; base < v.n; base += 64) {
+            const int i = base + lane;
+            const bool act = i < v.n && keep[i];
+            const unsigned long long mask = orbx_ballot(act);
+            if (mask == 0ull) continue;
+            if (act) {
+                OrbxSim3OptEdge e12, e21;
+                double err[2], rho1;
+                orbx_sim3opt_load(v, i, e12, e21);
+                s_term[2 * lane] = orbx_sim3opt_huber(orbx_sim3opt_error(s_tab, K1, e12, err), delta, &rho1);
+                s_term[2 * lane + 1] = orbx_sim3opt_huber(orbx_sim3opt_error(s_tab + 8, K2, e21, err), delta, &rho1);
+            }
+            __syncthreads();
+            if (lane == 0) {
+                unsigned long long m = mask;
+                while (m) {
+                    const int k = __builtin_ctzll(m);
+                    m &= m - 1;
+                    a = a + s_term[2 * k];
+                    a = a + s_term[2 * k + 1];
+                }
+            }
+            __syncthreads();
+        }
+        if (lane == 0) s_acc[0] = a;
+        __syncthreads();
+        const double r = s_acc[0];
+        __syncthreads();
+        return r;
+    }
+    __device__ int classify(const OrbxSim3 &Slast) {
+        entry0(Slast);
+        int nbad = 0;
+        for (int base = 0; base < v.n; base += 64) {
+            const int i = base + lane;
+            const bool act = i < v.n && keep[i];
+            bool bad = false;
+            if (act) {
+                OrbxSim3OptEdge e12, e21;
+                double err[2];
+                orbx_sim3opt_load(v, i, e12, e21);
+                bad = orbx_sim3opt_error(s_tab, K1, e12, err) > th2 || orbx_sim3opt_error(s_tab + 8, K2, e21, err) > th2;
+                if (bad) keep[i] = 0;
+            }
+            nbad += __popcll(orbx_ballot(bad));
+        }
+        __syncthreads();                                       // the table is free again
+        return nbad;
+    }
+};
+__global__ __launch_bounds__(64) void k_sim3_opt(const DSim3OptArgs A) {
+    __shared__ double s_mem[ORBX_SIM3OPT_LDS_DOUBLES];
+    const int p = blockIdx.x;
+    if (p >= A.nproblems) return;
+    const DSim3OptProb &P = A.prob[p];
+    Sim3OptEvDev ev;
+    ev.lane = threadIdx.x;
+    ev.s_term = s_mem;
+    ev.s_acc = s_mem + ORBX_SIM3OPT_TERMS * 65;
+    ev.s_tab = ev.s_acc + ORBX_SIM3OPT_TERMS;
+    ev.v.n = P.n < 0 ? 0 : P.n;
+    ev.v.pl = A.pts + ORBX_SIM3OPT_PLANES * P.off;
+    ev.K1.fx = (double)P.cam1[0]; ev.K1.fy = (double)P.cam1[1]; ev.K1.cx = (double)P.cam1[2]; ev.K1.cy = (double)P.cam1[3];
+    ev.K2.fx = (double)P.cam2[0]; ev.K2.fy = (double)P.cam2[1]; ev.K2.cx = (double)P.cam2[2]; ev.K2.cy = (double)P.cam2[3];
+    ev.th2 = (double)P.th2;
+    ev.delta = (double)(float)sqrt((double)P.th2);
+    ev.fix_scale = P.fix_scale != 0;
+    ev.keep = A.keep + P.off;
+    for (int i = ev.lane; i < ev.v.n; i += 64) ev.keep[i] = 1;
+    float R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = P.R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = P.t[k];
+    const OrbxSim3 init = orbx_sim3opt_from_input(R, t, P.s);
+    orbx_sim3opt_result out;
+    if (A.inlier_test_only) {                                  // orbx_debug_sim3opt_inlier_test (uniform)
+        double l8[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) l8[k] = P.last[k];
+        const int nbad = ev.classify(orbx_sim3opt_fetch(l8));
+        orbx_sim3opt_store_result(init, ev.v.n - nbad, nbad, ev.v.n, 0, &out);
+    } else {
+        orbx_sim3opt_run(ev, init, ev.v.n, ev.fix_scale, &out);
+    }
+    if (ev.lane == 0) A.res[p] = out;
+}
+
 #include "orbx_sim3.h"
 // CheckInliers of the batched RANSACs (k_sim3_inliers, k_pnp_inliers): one workgroup = WAVES consecutive hypotheses of ONE
 // problem, one wave each.  The problem's points are staged in LDS once per workgroup, CHUNK at a time as PLANES planes (lane i
@@ -4832,6 +4992,10 @@ void orbx_launch_mp_normal_depth(hipStream_t s, const int32_t *obs_begin, const 
 void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a) {
     if (a.nproblems <= 0) return;
     hipLaunchKernelGGL(k_pose_opt, dim3(a.nproblems), dim3(64), 0, s, a);
+}
+void orbx_launch_sim3_opt(hipStream_t s, const DSim3OptArgs &a) {
+    if (a.nproblems <= 0) return;
+    hipLaunchKernelGGL(k_sim3_opt, dim3(a.nproblems), dim3(64), 0, s, a);
 }
 void orbx_launch_sim3(hipStream_t s, const DSim3Args &a) {
     if (a.total_hyps <= 0 || a.ngroups <= 0) return;

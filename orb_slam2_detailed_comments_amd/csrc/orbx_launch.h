@@ -6,6 +6,7 @@
 #include "orbx_track.h"
 #include "orbx_mappoint.h"
 #include "orbx_pose.h"
+#include "orbx_sim3opt.h"
 #include "orbx_sim3.h"
 #include "orbx_pnp.h"
 #include "orbx_init.h"
@@ -143,6 +144,8 @@ void orbx_launch_mp_distinct(hipStream_t s, const int32_t *obs_begin, const uint
 void orbx_launch_mp_normal_depth(hipStream_t s, const int32_t *obs_begin, const DMpPoint *pts, const float *centers, int npoints,
                                  float scale_last, float *out);
 void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a);
+// Optimizer::OptimizeSim3 (orbx_sim3opt.h): k_sim3_opt, one wave per problem
+void orbx_launch_sim3_opt(hipStream_t s, const DSim3OptArgs &a);
 // Sim3Solver RANSAC (orbx_sim3.h): k_sim3_hypotheses over all iterations, then k_sim3_inliers over the workgroup table
 void orbx_launch_sim3(hipStream_t s, const DSim3Args &a);
 // PnPsolver RANSAC (orbx_pnp.h): k_pnp_hypotheses over all iterations, then k_pnp_inliers over the workgroup table

@@ -198,6 +198,54 @@ extern "C" orbx_status orbx_pose_optimization(orbx_handle *h, float *Tcw, int n,
     return ORBX_OK;
 }
 
+// ---------------------------------------------------------------- Optimizer::OptimizeSim3, batched (orbx_sim3opt.h).
+// Device path: validation and layout (orbx_sim3opt.cpp), all problems packed into the page-locked block, ONE upload, k_sim3_opt
+// on the handle's stream, ONE download of results | keep, the wait, the scatter.  Host path (ORBX_SIM3OPT=host, read per call;
+// host-only handles): the same header compiled by the host compiler over the same packed block.
+static orbx_status sim3opt_batch(orbx_handle *h, int nproblems, const orbx_sim3opt_problem *problems, const double *last,
+                                 bool inlier_test, orbx_sim3opt_result *results) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxSim3OptPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_sim3opt_plan(nproblems, problems, results, last, inlier_test, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (nproblems == 0) return ORBX_OK;
+    if (h->host_only || host_selected("ORBX_SIM3OPT")) {
+        std::vector<uint8_t> in(plan.in_bytes), out(plan.out_bytes);
+        orbx_sim3opt_pack(problems, last, plan, in.data());
+        orbx_sim3opt_host_run(plan, in.data(), inlier_test, out.data());
+        orbx_sim3opt_unpack(problems, plan, out.data(), results);
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    const size_t dev_in = pad256(plan.in_bytes);
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + plan.out_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_sim3opt_pack(problems, last, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    DSim3OptArgs a;
+    a.prob = (const DSim3OptProb *)(d + plan.o_prob);
+    a.pts = (const float *)(d + plan.o_pts);
+    a.res = (orbx_sim3opt_result *)(d + dev_in + plan.o_res);
+    a.keep = d + dev_in + plan.o_keep;
+    a.nproblems = nproblems; a.inlier_test_only = inlier_test ? 1 : 0;
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_sim3_opt(h->stream, a); }
+    st = stage_download_wait(h, pin, d + dev_in, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    orbx_sim3opt_unpack(problems, plan, pin, results);
+    return ORBX_OK;
+}
+extern "C" orbx_status orbx_optimize_sim3_batch(orbx_handle *h, int nproblems, const orbx_sim3opt_problem *problems,
+                                                orbx_sim3opt_result *results) {
+    return sim3opt_batch(h, nproblems, problems, nullptr, false, results);
+}
+extern "C" orbx_status orbx_debug_sim3opt_inlier_test(orbx_handle *h, int nproblems, const orbx_sim3opt_problem *problems,
+                                                      const double *S_last, orbx_sim3opt_result *results) {
+    return sim3opt_batch(h, nproblems, problems, S_last, true, results);
+}
+
 // ---------------------------------------------------------------- the batched RANSACs (orbx_ransac.h): one sequence for all.
 // Device path: validation and layout (S::plan), all problems packed into the page-locked block, ONE upload, the solver's two
 // kernels on the handle's stream (S::launch), ONE download of hypotheses | masks | tally, the wait; the batch keeps a host copy

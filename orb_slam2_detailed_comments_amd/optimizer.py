@@ -1,5 +1,5 @@
 """Optimizer::PoseOptimization(Frame*) for tracked frames (include/orbx.h: orbx_pose_optimization_batch_device,
-orbx_pose_optimization).  ctypes marshalling only; `extractor` is the ORBextractor whose handle (stream, staging block) the
+orbx_pose_optimization) and Optimizer::OptimizeSim3 for loop-closure candidates (orbx_optimize_sim3_batch).  ctypes marshalling only; `extractor` is the ORBextractor whose handle (stream, staging block) the
 calls run on.  The batch reads the frames where the device batch left them and writes poses, outlier rows and inlier counts on
 the device; nothing is downloaded.  On a host-only extractor (device=-2) every device argument is a numpy array and the
 library's host path runs."""
@@ -59,3 +59,62 @@ def pose_optimization(extractor, Tcw, keys_un, u_right, point, world_pos, camera
                                              ptr(world) if world.size else None, ptr(cam), float(mbf), ptr(sig), len(sig),
                                              ptr(outlier), C.byref(nin)))
     return T, outlier, int(nin.value)
+
+
+def _sim3opt_marshal(problems):
+    arr = (_capi.Sim3OptProblem * max(len(problems), 1))()
+    hold, keeps = [], []
+    for k, p in enumerate(problems):
+        x1 = np.ascontiguousarray(p["x1c"], np.float32).reshape(-1, 3)
+        x2 = np.ascontiguousarray(p["x2c"], np.float32).reshape(-1, 3)
+        o1 = np.ascontiguousarray(p["obs1"], np.float32).reshape(-1, 2)
+        o2 = np.ascontiguousarray(p["obs2"], np.float32).reshape(-1, 2)
+        w1 = np.ascontiguousarray(p["inv_sigma2_1"], np.float32).reshape(-1)
+        w2 = np.ascontiguousarray(p["inv_sigma2_2"], np.float32).reshape(-1)
+        n = len(x1)
+        assert len(x2) == n and len(o1) == n and len(o2) == n and len(w1) == n and len(w2) == n
+        keep = p.get("keep")
+        if keep is None:
+            keep = np.zeros(n, np.uint8)
+        assert keep.dtype == np.uint8 and keep.flags.c_contiguous and len(keep) >= n
+        hold += [x1, x2, o1, o2, w1, w2]
+        keeps.append(keep)
+        a = arr[k]
+        a.n = n
+        a.x1c, a.x2c, a.obs1, a.obs2, a.inv_sigma2_1, a.inv_sigma2_2 = (v.ctypes.data if n else None for v in (x1, x2, o1, o2, w1, w2))
+        a.keep = keep.ctypes.data if n else None
+        a.camera1[:] = np.asarray(p["camera1"], np.float32).tolist()
+        a.camera2[:] = np.asarray(p["camera2"], np.float32).tolist()
+        a.R[:] = np.asarray(p["R"], np.float32).reshape(9).tolist()
+        a.t[:] = np.asarray(p["t"], np.float32).reshape(3).tolist()
+        a.s = float(np.float32(p["s"]))
+        a.th2 = float(np.float32(p["th2"]))
+        a.fix_scale = int(bool(p["fix_scale"]))
+    return arr, hold, keeps
+
+
+def optimize_sim3_batch(extractor, problems, results=None):
+    """Optimizer::OptimizeSim3 for many (candidate, matches, Sim3) problems in one call.  problems: dicts with x1c, x2c [n, 3]
+    (P3D1c, P3D2c of the correspondences that passed OptimizeSim3's own filters, in order of i), obs1, obs2 [n, 2], inv_sigma2_1,
+    inv_sigma2_2 [n], camera1, camera2 (fx, fy, cx, cy), R [3, 3], t [3], s (the solver's estimate), th2, fix_scale and optionally
+    keep (uint8, at least n entries, written in place).  Returns (results, keeps): results a record array of
+    _capi.SIM3OPT_RESULT_DTYPE (r, t, s = g2oS12 on return, T12, ninliers, nbad, ncorr, written), keeps[k] uint8 with 1 where
+    vpMatches1[idx] survives.  On a host-only extractor the library's host path runs."""
+    arr, hold, keeps = _sim3opt_marshal(problems)
+    if results is None:
+        results = np.zeros(len(problems), _capi.SIM3OPT_RESULT_DTYPE)
+    assert results.dtype == _capi.SIM3OPT_RESULT_DTYPE and results.flags.c_contiguous and len(results) >= len(problems)
+    check(_capi.lib().orbx_optimize_sim3_batch(extractor.handle, len(problems), C.cast(arr, C.c_void_p),
+                                               ptr(results) if len(problems) else None))
+    return results, keeps
+
+
+def debug_sim3opt_inlier_test(extractor, problems, S_last):
+    """parity tests only (orbx_debug_sim3opt_inlier_test): S_last [nproblems, 8] float64 = r x y z w, t, s"""
+    arr, hold, keeps = _sim3opt_marshal(problems)
+    last = np.ascontiguousarray(S_last, np.float64).reshape(-1, 8)
+    assert len(last) == len(problems)
+    results = np.zeros(len(problems), _capi.SIM3OPT_RESULT_DTYPE)
+    check(_capi.lib().orbx_debug_sim3opt_inlier_test(extractor.handle, len(problems), C.cast(arr, C.c_void_p), ptr(last),
+                                                     ptr(results)))
+    return results, keeps

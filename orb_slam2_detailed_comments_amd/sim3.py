@@ -26,6 +26,7 @@ class Sim3Ransac(RansacBatch):
 
     def __init__(self, extractor, problems):
         super().__init__()
+        self.extractor = extractor   # compute_sim3_rounds_batched runs OptimizeSim3 on the same handle
         arr = (_capi.Sim3Problem * max(len(problems), 1))()
         keep = []
         for k, p in enumerate(problems):
@@ -91,3 +92,40 @@ def compute_sim3_round_robin(ransac, accept, n_iterations=5):
     discarded; accept(k, T12, inliers, ninliers) -- OptimizeSim3 and the >= 20 test in the reference -- ends the loop when it
     returns true.  Returns the accepted solver's index or -1, and the list of (k, returned, no_more, ninliers) calls made."""
     return round_robin(ransac, accept, n_iterations)
+
+
+def compute_sim3_rounds_batched(ransac, prepare, n_iterations=5, min_inliers=20, extractor=None):
+    """The candidate loop of LoopClosing::ComputeSim3 with OptimizeSim3 batched per round: every live solver gets
+    iterate(n_iterations); prepare(k, T12, inliers) -- the caller's SearchBySim3 -- gives an optimize_sim3_batch problem (or None)
+    for each solver that returned a Sim3; ONE optimize_sim3_batch call serves the round, and the lowest k with
+    ninliers >= min_inliers is accepted.  Returns (k or -1, calls, result record or None, keep or None); calls as
+    compute_sim3_round_robin lists them.  The one difference from compute_sim3_round_robin: solvers after the accepted one have
+    been iterated in the final round (the reference destroys them at that point anyway).  extractor: the ORBextractor whose handle
+    the batch runs on (default: ransac.extractor)."""
+    from .optimizer import optimize_sim3_batch
+    ex = extractor if extractor is not None else ransac.extractor
+    K = len(ransac)
+    discarded = [False] * K
+    live = K
+    calls = []
+    while live > 0:
+        ks, problems = [], []
+        for k in range(K):
+            if discarded[k]:
+                continue
+            T, no_more, inl, nin = ransac.iterate(k, n_iterations)
+            calls.append((k, T is not None, no_more, nin))
+            if no_more:
+                discarded[k] = True
+                live -= 1
+            if T is not None:
+                p = prepare(k, T, inl)
+                if p is not None:
+                    ks.append(k)
+                    problems.append(p)
+        if problems:
+            results, keeps = optimize_sim3_batch(ex, problems)
+            for j, k in enumerate(ks):
+                if results[j]["ninliers"] >= min_inliers:
+                    return k, calls, results[j].copy(), keeps[j]
+    return -1, calls, None, None
