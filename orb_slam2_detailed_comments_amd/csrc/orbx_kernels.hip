@@ -3907,6 +3907,33 @@ __global__ __launch_bounds__(256) void k_mp_normal_depth(const int32_t *__restri
 }
 
 #include "orbx_pose.h"
+// The ordered term sums of k_pose_opt and k_sim3_opt over one wave's LDS term array (row t at s_term + 65 * t; 65: the summing
+// lanes hit different banks) for N unknowns.  Bit k of m stands for COLS consecutive columns from COLS * k on, one edge each.
+// add: lane t < TERMS adds its row's columns of the set bits to a, bits and columns ascending -- the reference's edge order, one
+// chain per term, no atomics.  share: every lane gets the TERMS sums through s_acc.  The caller's barriers stand between the
+// lanes' writes to s_term and add, and after add; m is wave-uniform.  (The one-lane rho0 sums of the chi passes stay in the
+// evaluators: routed through here, k_sim3_opt comes out of the compiler with other registers throughout.)
+template <int N, int COLS> struct LmSum {
+    enum { TERMS = OrbxLm<N>::TERMS };
+    static __device__ __forceinline__ double add(const double *s_term, int lane, unsigned long long m, double a) {
+        if (lane < TERMS) {
+            while (m) {
+                const int c = COLS * __builtin_ctzll(m);
+                m &= m - 1;
+#pragma unroll
+                for (int j = 0; j < COLS; ++j) a = orbx_lm_accumulate<N>(lane, a, s_term[lane * 65 + c + j]);
+            }
+        }
+        return a;
+    }
+    static __device__ __forceinline__ void share(double *s_acc, int lane, double a, double *acc) {
+        if (lane < TERMS) s_acc[lane] = a;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < TERMS; ++k) acc[k] = s_acc[k];
+        __syncthreads();
+    }
+};
 // Optimizer::PoseOptimization, batched (orbx_pose.h): one wave per problem, one problem per workgroup (problems share
 // nothing).  The lanes take the frame's features 64 at a time; a lane whose feature carries an active edge computes the edge's
 // 28 terms (21 of H, 6 of b, rho0) into LDS, then lane t < 28 adds term t of the chunk's active edges to its accumulator in
@@ -3919,7 +3946,7 @@ struct PoseEvDev {
     OrbxPoseView v;
     OrbxPoseCam K;
     uint8_t *outlier;
-    double *s_term;     // [28][65]: term t of lane k at t * 65 + k (65: the summing lanes hit different banks)
+    double *s_term;     // [28][65]: term t of lane k at t * 65 + k
     double *s_acc;      // [28]
     int lane, nactive;
     __device__ int active() const { return nactive; }
@@ -3938,21 +3965,10 @@ struct PoseEvDev {
                 for (int k = 0; k < ORBX_POSE_TERMS; ++k) s_term[k * 65 + lane] = t[k];
             }
             __syncthreads();
-            if (lane < ORBX_POSE_TERMS) {
-                unsigned long long m = mask;
-                while (m) {
-                    const int k = __builtin_ctzll(m);
-                    m &= m - 1;
-                    a = orbx_pose_accumulate(lane, a, s_term[lane * 65 + k]);
-                }
-            }
+            a = LmSum<6, 1>::add(s_term, lane, mask, a);
             __syncthreads();
         }
-        if (lane < ORBX_POSE_TERMS) s_acc[lane] = a;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < ORBX_POSE_TERMS; ++k) acc[k] = s_acc[k];
-        __syncthreads();
+        LmSum<6, 1>::share(s_acc, lane, a, acc);
     }
     __device__ double chi(const OrbxPoseSE3 &T, bool robust) {
         double a = 0.0;
@@ -4110,23 +4126,11 @@ struct Sim3OptEvDev {
                     for (int k = 0; k < ORBX_SIM3OPT_TERMS; ++k) { s_term[k * 65 + c] = t12[k]; s_term[k * 65 + c + 1] = t21[k]; }
                 }
                 __syncthreads();
-                if (lane < ORBX_SIM3OPT_TERMS) {
-                    unsigned long long m = hm;
-                    while (m) {
-                        const int c = 2 * __builtin_ctzll(m);
-                        m &= m - 1;
-                        a = orbx_sim3opt_accumulate(lane, a, s_term[lane * 65 + c]);
-                        a = orbx_sim3opt_accumulate(lane, a, s_term[lane * 65 + c + 1]);
-                    }
-                }
+                a = LmSum<7, 2>::add(s_term, lane, hm, a);
                 __syncthreads();
             }
         }
-        if (lane < ORBX_SIM3OPT_TERMS) s_acc[lane] = a;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < ORBX_SIM3OPT_TERMS; ++k) acc[k] = s_acc[k];
-        __syncthreads();
+        LmSum<7, 2>::share(s_acc, lane, a, acc);
     }
     // the table's entry 0 (S and its inverse), the same in every lane
     __device__ void entry0(const OrbxSim3 &S) {
@@ -4145,8 +4149,8 @@ struct Sim3OptEvDev {
                 OrbxSim3OptEdge e12, e21;
                 double err[2], rho1;
                 orbx_sim3opt_load(v, i, e12, e21);
-                s_term[2 * lane] = orbx_sim3opt_huber(orbx_sim3opt_error(s_tab, K1, e12, err), delta, &rho1);
-                s_term[2 * lane + 1] = orbx_sim3opt_huber(orbx_sim3opt_error(s_tab + 8, K2, e21, err), delta, &rho1);
+                s_term[2 * lane] = orbx_lm_huber(orbx_sim3opt_error(s_tab, K1, e12, err), delta, &rho1);
+                s_term[2 * lane + 1] = orbx_lm_huber(orbx_sim3opt_error(s_tab + 8, K2, e21, err), delta, &rho1);
             }
             __syncthreads();
             if (lane == 0) {
@@ -4166,6 +4170,7 @@ struct Sim3OptEvDev {
         __syncthreads();
         return r;
     }
+    __device__ OrbxSim3 oplus(const OrbxSim3 &S, double *x) const { return orbx_sim3opt_oplus(S, x, fix_scale); }
     __device__ int classify(const OrbxSim3 &Slast) {
         entry0(Slast);
         int nbad = 0;
@@ -4219,7 +4224,7 @@ __global__ __launch_bounds__(64) void k_sim3_opt(const DSim3OptArgs A) {
         const int nbad = ev.classify(orbx_sim3opt_fetch(l8));
         orbx_sim3opt_store_result(init, ev.v.n - nbad, nbad, ev.v.n, 0, &out);
     } else {
-        orbx_sim3opt_run(ev, init, ev.v.n, ev.fix_scale, &out);
+        orbx_sim3opt_run(ev, init, ev.v.n, &out);
     }
     if (ev.lane == 0) A.res[p] = out;
 }

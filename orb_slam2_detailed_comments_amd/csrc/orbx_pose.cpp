@@ -5,8 +5,7 @@
 // arena and the launch.
 #include <cstring>
 #include "orbx_pose.h"
-
-static inline size_t pose_pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+#include "orbx_ransac.h"   // orbx_pad256
 
 orbx_status orbx_pose_plan(int nproblems, const orbx_pose_problem *problems, const OrbxPoseCall &c, OrbxPosePlan &plan, const char **why) {
     plan = OrbxPosePlan();
@@ -40,11 +39,11 @@ orbx_status orbx_pose_plan(int nproblems, const orbx_pose_problem *problems, con
     plan.nproblems = nproblems;
     plan.nindex = nindex;
     plan.o_prob = 0;
-    plan.o_index = pose_pad256((size_t)nproblems * sizeof(DPoseProb));
-    plan.o_world = plan.o_index + pose_pad256(nindex * sizeof(int32_t));
-    plan.o_sig = plan.o_world + pose_pad256((size_t)c.npool * 3 * sizeof(float));
-    plan.o_dbg = plan.o_sig + pose_pad256((size_t)c.nlevels * sizeof(float));
-    plan.in_bytes = plan.o_dbg + (c.dbg_est ? pose_pad256((size_t)nproblems * 32 * sizeof(float)) : 0);
+    plan.o_index = orbx_pad256((size_t)nproblems * sizeof(DPoseProb));
+    plan.o_world = plan.o_index + orbx_pad256(nindex * sizeof(int32_t));
+    plan.o_sig = plan.o_world + orbx_pad256((size_t)c.npool * 3 * sizeof(float));
+    plan.o_dbg = plan.o_sig + orbx_pad256((size_t)c.nlevels * sizeof(float));
+    plan.in_bytes = plan.o_dbg + (c.dbg_est ? orbx_pad256((size_t)nproblems * 32 * sizeof(float)) : 0);
     return ORBX_OK;
 }
 
@@ -108,7 +107,7 @@ struct PoseEvHost {
         for (int i = 0; i < v.n; ++i) {
             if (!orbx_pose_load(v, i, e) || outlier[i]) continue;
             orbx_pose_terms(T, K, e, robust, term);
-            for (int t = 0; t < ORBX_POSE_TERMS; ++t) acc[t] = orbx_pose_accumulate(t, acc[t], term[t]);
+            for (int t = 0; t < ORBX_POSE_TERMS; ++t) acc[t] = orbx_lm_accumulate<6>(t, acc[t], term[t]);
         }
     }
     double chi(const OrbxPoseSE3 &T, bool robust) const {

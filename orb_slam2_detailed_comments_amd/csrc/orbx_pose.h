@@ -9,30 +9,12 @@
 // and ORBX_FP_STRICT handles therefore give the same bits, on the host and on the device.  Division and square root are the
 // correctly rounded IEEE double operations on both sides.  No pow, sin or cos of any math library is called.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#include "../../include/orbx.h"
-#if defined(__HIPCC__)
-#ifndef ORBX_HD
-#define ORBX_HD __host__ __device__
-#endif
-#else
-#ifndef ORBX_HD
-#define ORBX_HD
-#endif
-#endif
+#include "orbx_lm.h"   // ORBX_HD, ORBX_UNROLL, the Huber kernel, the 6 x 6 solve and the Levenberg-Marquardt loop
 
-#if defined(__clang__)
-#define ORBX_UNROLL _Pragma("unroll")
-#else
-#define ORBX_UNROLL
-#endif
-
-enum { ORBX_POSE_ROUNDS = 4, ORBX_POSE_ITERS = 10, ORBX_POSE_TRIALS = 10, ORBX_POSE_TERMS = 28 };
+enum { ORBX_POSE_ROUNDS = 4, ORBX_POSE_ITERS = 10, ORBX_POSE_TERMS = OrbxLm<6>::TERMS };   // 21 of H, 6 of b, rho0
 // (float)sqrt(5.991), (float)sqrt(7.815) widened: RobustKernelHuber::setDelta(deltaMono / deltaStereo), src/Optimizer.cc:407-409
 #define ORBX_POSE_DELTA_MONO 0x1.394ca8p+1
 #define ORBX_POSE_DELTA_STEREO 0x1.65d4p+1
-#define ORBX_POSE_DBL_MAX 0x1.fffffffffffffp+1023
 
 struct OrbxPoseSE3 { double qx, qy, qz, qw, tx, ty, tz; };   // g2o::SE3Quat: _r (x, y, z, w), _t
 struct OrbxPoseCam { double fx, fy, cx, cy, bf; };
@@ -48,8 +30,6 @@ struct OrbxPoseView {
     const float *sig;           // mvInvLevelSigma2
     int nlevels, npoints, n;    // n = min(count of the frame, cap)
 };
-
-ORBX_HD static inline bool orbx_pose_finite(double v) { return __builtin_fabs(v) <= ORBX_POSE_DBL_MAX; }
 
 // sin and cos of theta >= 0 for SE3Quat::exp.  Only *, +, fma and int conversion: pi/2 reduction in three parts, then the
 // fdlibm kernel polynomials on [-pi/4, pi/4].  theta >= 2^30 or NaN (no tracking update) is defined as sin = 0, cos = 1.
@@ -234,16 +214,10 @@ ORBX_HD static inline double orbx_pose_error(const OrbxPoseSE3 &T, const OrbxPos
     err[2] = 0.0;
     return err[0] * (e.w * err[0]) + err[1] * (e.w * err[1]);
 }
-// RobustKernelHuber::robustify; without the kernel rho = (chi2, 1)
+// RobustKernelHuber::robustify with the edge kind's delta; without the kernel rho = (chi2, 1)
 ORBX_HD static inline double orbx_pose_huber(double chi2, int stereo, bool robust, double *rho1) {
     *rho1 = 1.0;
-    if (!robust) return chi2;
-    const double delta = stereo ? ORBX_POSE_DELTA_STEREO : ORBX_POSE_DELTA_MONO;
-    const double dsqr = delta * delta;
-    if (chi2 <= dsqr) return chi2;
-    const double sq = sqrt(chi2);
-    *rho1 = delta / sq;
-    return 2.0 * sq * delta - dsqr;
+    return robust ? orbx_lm_huber(chi2, stereo ? ORBX_POSE_DELTA_STEREO : ORBX_POSE_DELTA_MONO, rho1) : chi2;
 }
 // One edge's 28 terms at pose T: t[0..20] = A^T (rho1 Omega) A, upper triangle row by row; t[21..26] = rho1 (A^T Omega e);
 // t[27] = rho0.  Per entry the rows are summed in order r = 0, 1[, 2]; a product is (A_rj * W) * A_rk with W = rho1 * w,
@@ -292,59 +266,11 @@ ORBX_UNROLL
         t[21 + j] = rho1 * s;
     }
 }
-// acc = acc (+) t for one edge, in the order every caller adds edges: H and chi by addition, b by subtraction (b -= ...)
-ORBX_HD static inline double orbx_pose_accumulate(int term, double acc, double t) { return term >= 21 && term < 27 ? acc - t : acc + t; }
 
-// (H + lambda I) x = b by an unpivoted L D L^T (H: upper triangle row by row).  The system counts as positive, and is solved,
-// when every pivot d_j is > 0 and finite; otherwise the solve fails and x = 0.
-ORBX_HD static inline bool orbx_pose_solve6(const double *H, double lambda, const double *b, double *x) {
-    double A[36], L[36], d[6], w[6], y[6];
-    {
-        int n = 0;
-ORBX_UNROLL
-        for (int j = 0; j < 6; ++j)
-ORBX_UNROLL
-            for (int k = j; k < 6; ++k) { const double v = j == k ? H[n] + lambda : H[n]; A[6 * j + k] = v; A[6 * k + j] = v; ++n; }
-    }
-    bool ok = true;
-ORBX_UNROLL
-    for (int j = 0; j < 6; ++j) {
-        double s = A[6 * j + j];
-ORBX_UNROLL
-        for (int k = 0; k < j; ++k) { w[k] = L[6 * j + k] * d[k]; s = s - L[6 * j + k] * w[k]; }
-        d[j] = s;
-        if (!(s > 0 && s <= ORBX_POSE_DBL_MAX)) ok = false;
-ORBX_UNROLL
-        for (int i = j + 1; i < 6; ++i) {
-            double t = A[6 * i + j];
-ORBX_UNROLL
-            for (int k = 0; k < j; ++k) t = t - L[6 * i + k] * w[k];
-            L[6 * i + j] = t / s;
-        }
-    }
-    if (!ok) {
-ORBX_UNROLL
-        for (int i = 0; i < 6; ++i) x[i] = 0.0;
-        return false;
-    }
-ORBX_UNROLL
-    for (int i = 0; i < 6; ++i) {
-        double s = b[i];
-ORBX_UNROLL
-        for (int k = 0; k < i; ++k) s = s - L[6 * i + k] * y[k];
-        y[i] = s;
-    }
-ORBX_UNROLL
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i] / d[i];
-ORBX_UNROLL
-        for (int k = i + 1; k < 6; ++k) s = s - L[6 * k + i] * x[k];
-        x[i] = s;
-    }
-    return true;
-}
-
-// The four rounds (src/Optimizer.cc:523-596) around SparseOptimizer::optimize(10) and OptimizationAlgorithmLevenberg::solve.
+// The four rounds (src/Optimizer.cc:523-596) around SparseOptimizer::optimize(10).  The Levenberg loop stands HERE, word for word
+// orbx_lm_optimize<6> of orbx_lm.h with system / chi taking the round's `robust` (tests/test_lm_parent_pin.py holds both to the
+// same recorded results): behind any function boundary, forced inline included, the compilers lay out k_pose_opt and the host
+// path differently, and both lose speed to it (profiles/lm_shared.md).
 // Ev supplies the three passes over the edges; everything here is uniform over the lanes of a wave that run it side by side:
 //   int  active()                                   number of edges of level 0
 //   void system(T, robust, acc[28])                 computeActiveErrors + activeRobustChi2 + buildSystem at T, edge order
@@ -368,13 +294,13 @@ ORBX_HD static inline int orbx_pose_rounds(Ev &ev, const float *Tcw, int nedges,
                 double acc[ORBX_POSE_TERMS], x[6];
                 ev.system(est, robust, acc);
                 last = est;
-                double cur = acc[27];
+                double cur = acc[OrbxLm<6>::CHI];
                 const double ini = cur;
                 if (it == 0) {                                 // computeLambdaInit: tau * max |H_jj|, std::max as written
                     double m = 0.0;
-                    const int dg[6] = {0, 6, 11, 15, 18, 20};
+                    int dg = 0;                                // H_jj sits 6 - j terms after H_(j-1)(j-1)
 ORBX_UNROLL
-                    for (int j = 0; j < 6; ++j) { const double a = __builtin_fabs(acc[dg[j]]); m = a < m ? m : a; }
+                    for (int j = 0; j < 6; ++j) { const double a = __builtin_fabs(acc[dg]); m = a < m ? m : a; dg += 6 - j; }
                     lambda = 1e-5 * m;
                     nu = 2.0;
                     stall = 0;
@@ -383,18 +309,18 @@ ORBX_UNROLL
                 int q = 0;
                 do {
                     const OrbxPoseSE3 backup = est;
-                    const bool ok = orbx_pose_solve6(acc, lambda, acc + 21, x);
+                    const bool ok = orbx_lm_solve<6>(acc, lambda, acc + OrbxLm<6>::B, x);
                     est = orbx_pose_mul(orbx_pose_exp(x), est);
                     double tmp = ev.chi(est, robust);
                     last = est;
-                    if (!ok) tmp = ORBX_POSE_DBL_MAX;
+                    if (!ok) tmp = ORBX_DBL_MAX;
                     rho = cur - tmp;
                     double scale = 0.0;
 ORBX_UNROLL
-                    for (int j = 0; j < 6; ++j) scale = scale + x[j] * (lambda * x[j] + acc[21 + j]);
+                    for (int j = 0; j < 6; ++j) scale = scale + x[j] * (lambda * x[j] + acc[OrbxLm<6>::B + j]);
                     scale = scale + 1e-3;
                     rho = rho / scale;
-                    if (rho > 0 && orbx_pose_finite(tmp)) {
+                    if (rho > 0 && orbx_finite(tmp)) {
                         const double r2 = 2.0 * rho - 1.0;
                         double alpha = 1.0 - (r2 * r2) * r2;
                         alpha = (2.0 / 3.0) < alpha ? (2.0 / 3.0) : alpha;
@@ -408,8 +334,8 @@ ORBX_UNROLL
                         est = backup;
                     }
                     ++q;
-                } while (rho < 0 && q < ORBX_POSE_TRIALS);
-                if (q == ORBX_POSE_TRIALS || rho == 0) break;   // Terminate
+                } while (rho < 0 && q < ORBX_LM_TRIALS);
+                if (q == ORBX_LM_TRIALS || rho == 0) break;   // Terminate
                 if ((ini - cur) * 1e3 < ini) ++stall; else stall = 0;
                 if (stall >= 3) break;                          // Stop criterium (Raul)
             }

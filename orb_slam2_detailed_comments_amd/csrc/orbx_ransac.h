@@ -8,7 +8,7 @@
 #pragma once
 #include <limits.h>
 #include <stddef.h>
-#include "orbx_pose.h"   // ORBX_HD, include/orbx.h
+#include "orbx_lm.h"   // ORBX_HD, ORBX_UNROLL, include/orbx.h
 
 // A NaN's sign and payload differ between processors (x86 makes 0xffc00000, gfx950 0x7fc00000), so every stored value that is
 // a NaN is stored as the canonical quiet NaN: "bit for bit" then holds outside the contract too.

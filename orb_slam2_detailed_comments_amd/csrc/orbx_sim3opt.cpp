@@ -77,9 +77,9 @@ struct Sim3OptEvHost {
             if (!keep[i]) continue;
             orbx_sim3opt_load(v, i, e12, e21);
             orbx_sim3opt_terms(tab, 0, K1, e12, delta, term);
-            for (int t = 0; t < ORBX_SIM3OPT_TERMS; ++t) acc[t] = orbx_sim3opt_accumulate(t, acc[t], term[t]);
+            for (int t = 0; t < ORBX_SIM3OPT_TERMS; ++t) acc[t] = orbx_lm_accumulate<7>(t, acc[t], term[t]);
             orbx_sim3opt_terms(tab, 8, K2, e21, delta, term);
-            for (int t = 0; t < ORBX_SIM3OPT_TERMS; ++t) acc[t] = orbx_sim3opt_accumulate(t, acc[t], term[t]);
+            for (int t = 0; t < ORBX_SIM3OPT_TERMS; ++t) acc[t] = orbx_lm_accumulate<7>(t, acc[t], term[t]);
         }
     }
     double chi(const OrbxSim3 &S) const {
@@ -89,11 +89,12 @@ struct Sim3OptEvHost {
         for (int i = 0; i < v.n; ++i) {
             if (!keep[i]) continue;
             orbx_sim3opt_load(v, i, e12, e21);
-            s = s + orbx_sim3opt_huber(orbx_sim3opt_error(tab, K1, e12, err), delta, &rho1);
-            s = s + orbx_sim3opt_huber(orbx_sim3opt_error(tab + 8, K2, e21, err), delta, &rho1);
+            s = s + orbx_lm_huber(orbx_sim3opt_error(tab, K1, e12, err), delta, &rho1);
+            s = s + orbx_lm_huber(orbx_sim3opt_error(tab + 8, K2, e21, err), delta, &rho1);
         }
         return s;
     }
+    OrbxSim3 oplus(const OrbxSim3 &S, double *x) const { return orbx_sim3opt_oplus(S, x, fix_scale); }
     int classify(const OrbxSim3 &Slast) {
         double tab[ORBX_SIM3OPT_SIM], err[2];
         orbx_sim3opt_table_entry(Slast, 0, fix_scale, tab);
@@ -133,7 +134,7 @@ void orbx_sim3opt_host_run(const OrbxSim3OptPlan &plan, const uint8_t *in, bool 
             orbx_sim3opt_store_result(init, D.n - nbad, nbad, D.n, 0, &res[k]);
             continue;
         }
-        orbx_sim3opt_run(ev, init, D.n, ev.fix_scale, &res[k]);
+        orbx_sim3opt_run(ev, init, D.n, &res[k]);
     }
 }
 

@@ -9,17 +9,18 @@
 // -ffp-contract=off; the only fused operations are the explicit ones inside orbx_pose_sincos and orbx_sim3opt_expd.  No exp, sin
 // or cos of any math library is called.
 #pragma once
-#include "orbx_ransac.h"   // orbx_pose.h (ORBX_HD, the quaternion helpers), orbx_canonf / orbx_canond, orbx_pad256
+#include "orbx_pose.h"     // orbx_lm.h, the quaternion helpers, orbx_pose_sincos
+#include "orbx_ransac.h"   // orbx_canonf / orbx_canond, orbx_pad256
 
 enum {
     ORBX_SIM3OPT_TERMS = 36,      // 28 of H (upper triangle row by row), 7 of b, rho0
     ORBX_SIM3OPT_NSIM = 15,       // the estimate and its 14 perturbations Sim3(+-delta e_d) * estimate
     ORBX_SIM3OPT_SIM = 16,        // doubles per entry of the table: the Sim3 (8) and its inverse (8)
-    ORBX_SIM3OPT_TRIALS = 10,
     ORBX_SIM3OPT_PLANES = 12,     // x1c xyz, x2c xyz, obs1 uv, obs2 uv, invSigma2 1, invSigma2 2
     // k_sim3_opt's LDS in doubles: the [36][65] term array, the 36 broadcast sums and the table of the 15 Sim3
     ORBX_SIM3OPT_LDS_DOUBLES = ORBX_SIM3OPT_TERMS * 65 + ORBX_SIM3OPT_TERMS + ORBX_SIM3OPT_NSIM * ORBX_SIM3OPT_SIM
 };
+static_assert(ORBX_SIM3OPT_TERMS == OrbxLm<7>::TERMS, "the term layout of orbx_lm.h for 7 unknowns");
 #define ORBX_SIM3OPT_DELTA 1e-9   // base_binary_edge.hpp:147
 
 // g2o::Sim3: r (x, y, z, w) and t in q (never normalised), s
@@ -198,15 +199,6 @@ ORBX_HD static inline double orbx_sim3opt_error(const double *s8, const OrbxSim3
     err[1] = e.oy - ((p[1] / p[2]) * K.fy + K.cy);
     return err[0] * (e.w * err[0]) + err[1] * (e.w * err[1]);
 }
-// RobustKernelHuber::robustify
-ORBX_HD static inline double orbx_sim3opt_huber(double chi2, double delta, double *rho1) {
-    *rho1 = 1.0;
-    const double dsqr = delta * delta;
-    if (chi2 <= dsqr) return chi2;
-    const double sq = sqrt(chi2);
-    *rho1 = delta / sq;
-    return 2.0 * sq * delta - dsqr;
-}
 // One edge's 36 terms.  tab: the table of orbx_sim3opt_table_entry; inv = 0 for e12 (the Sim3), 8 for e21 (its inverse).
 // Column d of the Jacobian = (1 / (2 delta)) * (err(+delta e_d) - err(-delta e_d)), as linearizeOplus() computes it.
 // t[0..27] = A^T (rho1 Omega) A, upper triangle row by row; t[28..34] = A^T (rho1 (Omega e)); t[35] = rho0.  Per entry the rows
@@ -215,7 +207,7 @@ ORBX_HD static inline void orbx_sim3opt_terms(const double *tab, int inv, const 
                                               double *t) {
     double err[2], ep[2], em[2], J0[7], J1[7], rho1;
     const double chi2 = orbx_sim3opt_error(tab + inv, K, e, err);
-    t[35] = orbx_sim3opt_huber(chi2, delta, &rho1);
+    t[35] = orbx_lm_huber(chi2, delta, &rho1);
     const double scalar = 1.0 / (2 * ORBX_SIM3OPT_DELTA);
 ORBX_UNROLL
     for (int d = 0; d < 7; ++d) {
@@ -234,115 +226,6 @@ ORBX_UNROLL
 ORBX_UNROLL
     for (int j = 0; j < 7; ++j) t[28 + j] = J0[j] * we0 + J1[j] * we1;
 }
-// acc = acc (+) t for one edge: H and chi by addition, b by subtraction (b += A^T (-(rho1 Omega e)))
-ORBX_HD static inline double orbx_sim3opt_accumulate(int term, double acc, double t) { return term >= 28 && term < 35 ? acc - t : acc + t; }
-
-// (H + lambda I) x = b: orbx_pose_solve6 grown to 7.  Unpivoted L D L^T (H: upper triangle row by row); solved when every
-// pivot d_j is > 0 and finite; otherwise the solve fails and x = 0.
-ORBX_HD static inline bool orbx_sim3opt_solve7(const double *H, double lambda, const double *b, double *x) {
-    double A[49], L[49], d[7], w[7], y[7];
-    {
-        int n = 0;
-ORBX_UNROLL
-        for (int j = 0; j < 7; ++j)
-ORBX_UNROLL
-            for (int k = j; k < 7; ++k) { const double v = j == k ? H[n] + lambda : H[n]; A[7 * j + k] = v; A[7 * k + j] = v; ++n; }
-    }
-    bool ok = true;
-ORBX_UNROLL
-    for (int j = 0; j < 7; ++j) {
-        double s = A[7 * j + j];
-ORBX_UNROLL
-        for (int k = 0; k < j; ++k) { w[k] = L[7 * j + k] * d[k]; s = s - L[7 * j + k] * w[k]; }
-        d[j] = s;
-        if (!(s > 0 && s <= ORBX_POSE_DBL_MAX)) ok = false;
-ORBX_UNROLL
-        for (int i = j + 1; i < 7; ++i) {
-            double t = A[7 * i + j];
-ORBX_UNROLL
-            for (int k = 0; k < j; ++k) t = t - L[7 * i + k] * w[k];
-            L[7 * i + j] = t / s;
-        }
-    }
-    if (!ok) {
-ORBX_UNROLL
-        for (int i = 0; i < 7; ++i) x[i] = 0.0;
-        return false;
-    }
-ORBX_UNROLL
-    for (int i = 0; i < 7; ++i) {
-        double s = b[i];
-ORBX_UNROLL
-        for (int k = 0; k < i; ++k) s = s - L[7 * i + k] * y[k];
-        y[i] = s;
-    }
-ORBX_UNROLL
-    for (int i = 6; i >= 0; --i) {
-        double s = y[i] / d[i];
-ORBX_UNROLL
-        for (int k = i + 1; k < 7; ++k) s = s - L[7 * k + i] * x[k];
-        x[i] = s;
-    }
-    return true;
-}
-
-// SparseOptimizer::optimize(iters) with OptimizationAlgorithmLevenberg::solve over the live edges, as orbx_pose_rounds states
-// it: lambda and nu start anew at iteration 0, at most ten trials per iteration, Terminate, the "Raul" stop, chi' = DBL_MAX on
-// a failed solve.  est carries over; last = where computeActiveErrors ran last (a rejected last trial included).
-template <class Ev>
-ORBX_HD static inline void orbx_sim3opt_optimize(Ev &ev, int iters, bool fix_scale, OrbxSim3 &est, OrbxSim3 &last) {
-    double lambda = 0.0, nu = 2.0;
-    int stall = 0;
-    for (int it = 0; it < iters; ++it) {
-        double acc[ORBX_SIM3OPT_TERMS], x[7];
-        ev.system(est, acc);
-        last = est;
-        double cur = acc[35];
-        const double ini = cur;
-        if (it == 0) {                                         // computeLambdaInit: tau * max |H_jj|, std::max as written
-            double m = 0.0;
-            const int dg[7] = {0, 7, 13, 18, 22, 25, 27};
-ORBX_UNROLL
-            for (int j = 0; j < 7; ++j) { const double a = __builtin_fabs(acc[dg[j]]); m = a < m ? m : a; }
-            lambda = 1e-5 * m;
-            nu = 2.0;
-            stall = 0;
-        }
-        double rho = 0.0;
-        int q = 0;
-        do {
-            const OrbxSim3 backup = est;
-            const bool ok = orbx_sim3opt_solve7(acc, lambda, acc + 28, x);
-            est = orbx_sim3opt_oplus(est, x, fix_scale);       // (zeroes x[6] under fix_scale: computeScale reads it after)
-            double tmp = ev.chi(est);
-            last = est;
-            if (!ok) tmp = ORBX_POSE_DBL_MAX;
-            rho = cur - tmp;
-            double scale = 0.0;
-ORBX_UNROLL
-            for (int j = 0; j < 7; ++j) scale = scale + x[j] * (lambda * x[j] + acc[28 + j]);
-            scale = scale + 1e-3;
-            rho = rho / scale;
-            if (rho > 0 && orbx_pose_finite(tmp)) {
-                const double r2 = 2.0 * rho - 1.0;
-                double alpha = 1.0 - (r2 * r2) * r2;
-                alpha = (2.0 / 3.0) < alpha ? (2.0 / 3.0) : alpha;
-                const double sf = (1.0 / 3.0) < alpha ? alpha : (1.0 / 3.0);
-                lambda = lambda * sf;
-                nu = 2.0;
-                cur = tmp;
-            } else {
-                lambda = lambda * nu;
-                nu = nu * 2.0;
-                est = backup;
-            }
-            ++q;
-        } while (rho < 0 && q < ORBX_SIM3OPT_TRIALS);
-        if (q == ORBX_SIM3OPT_TRIALS || rho == 0) break;       // Terminate
-        if ((ini - cur) * 1e3 < ini) ++stall; else stall = 0;
-        if (stall >= 3) break;                                  // Stop criterium (Raul)
-    }
-}
 
 // g2oS12 and Converter::toCvMat(g2oS12) as the result stores them, with the four counts
 ORBX_HD static inline void orbx_sim3opt_store_result(const OrbxSim3 &est, int nin, int nbad, int n, int written, orbx_sim3opt_result *out) {
@@ -360,23 +243,25 @@ ORBX_UNROLL
     out->ninliers = nin; out->nbad = nbad; out->ncorr = n; out->written = written;
 }
 
-// OptimizeSim3 from optimize(5) on.  Ev supplies the three passes over the live correspondences (edges e12_i, e21_i for i
-// ascending); everything here is uniform over the lanes of a wave that run it side by side:
+// OptimizeSim3 from optimize(5) on (SparseOptimizer::optimize: orbx_lm_optimize).  Ev supplies the three passes over the live
+// correspondences (edges e12_i, e21_i for i ascending) and the vertex; everything here is uniform over the lanes of a wave that
+// run it side by side:
 //   void system(S, acc[36])      the table at S, then computeActiveErrors + activeRobustChi2 + buildSystem, edge order
 //   double chi(S)                computeActiveErrors + activeRobustChi2 at S
+//   OrbxSim3 oplus(S, x[7])      orbx_sim3opt_oplus with the problem's fix_scale (zeroes x[6] under it, before `scale` reads it)
 //   int  classify(Slast)         e12->chi2() > th2 || e21->chi2() > th2 on every live correspondence, errors as they stand at
 //                                Slast; nulls the match; returns how many it nulled
 // n = nCorrespondences.  Fills r, t, s, T12 and the four counts of *out.
 template <class Ev>
-ORBX_HD static inline void orbx_sim3opt_run(Ev &ev, const OrbxSim3 &init, int n, bool fix_scale, orbx_sim3opt_result *out) {
+ORBX_HD static inline void orbx_sim3opt_run(Ev &ev, const OrbxSim3 &init, int n, orbx_sim3opt_result *out) {
     OrbxSim3 est = init, last = init;
     int nbad = 0, nin = 0, written = 0;
     if (n > 0) {                                               // no edge: no active vertex, optimize() returns at once
-        orbx_sim3opt_optimize(ev, 5, fix_scale, est, last);
+        orbx_lm_optimize<7>(ev, 5, est, last);
         nbad = ev.classify(last);
     }
     if (n - nbad >= 10) {
-        orbx_sim3opt_optimize(ev, nbad > 0 ? 10 : 5, fix_scale, est, last);
+        orbx_lm_optimize<7>(ev, nbad > 0 ? 10 : 5, est, last);
         nin = n - nbad - ev.classify(last);
         written = 1;
     } else {

@@ -1,7 +1,7 @@
 """Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:363-607) restated in numpy float64, independent of
 csrc/orbx_pose.h: what g2o executes for one VertexSE3Expmap with unary EdgeSE3ProjectXYZOnlyPose /
-EdgeStereoSE3ProjectXYZOnlyPose edges (SparseOptimizer::optimize, OptimizationAlgorithmLevenberg::solve, BlockSolver::buildSystem,
-BaseUnaryEdge::constructQuadraticForm, RobustKernelHuber, SE3Quat, Converter).  Every operation is an IEEE double operation in
+EdgeStereoSE3ProjectXYZOnlyPose edges (BlockSolver::buildSystem, BaseUnaryEdge::constructQuadraticForm, RobustKernelHuber, SE3Quat, Converter; the dense solve
+and SparseOptimizer::optimize with OptimizationAlgorithmLevenberg::solve are lm_model.py's).  Every operation is an IEEE double operation in
 the written order (numpy elementwise arithmetic over the edges is the same operation per edge); sums over edges run in edge
 order, one addition after the other.  The one primitive taken from the library is sin / cos of SE3Quat::exp
 (orbx_pose_sin_cos), as DESIGN.md section 2 (F11) states.  `trace`, when given, receives what the tests assert branch coverage
@@ -10,13 +10,14 @@ import ctypes as C
 
 import numpy as np
 
+from lm_model import levenberg
+
 F64 = np.float64
 F32 = np.float32
 DELTA_MONO = F64(F32(np.sqrt(F64(5.991))))      # const float deltaMono = sqrt(5.991)
 DELTA_STEREO = F64(F32(np.sqrt(F64(7.815))))
 CHI2_MONO = F32(5.991)
 CHI2_STEREO = F32(7.815)
-DBL_MAX = F64(np.finfo(np.float64).max)
 
 
 def _sincos(theta):
@@ -220,42 +221,6 @@ def _chi(T, K, e, robust):
     return _seq_sum(_huber(_error(T, K, e)[2], e.stereo, robust)[0])
 
 
-def solve6(H, lam, b):
-    """(H + lam I) x = b, unpivoted L D L^T; positive = every pivot > 0 and finite, otherwise (False, 0)"""
-    A = [[(H[(min(i, j), max(i, j))] + lam) if i == j else H[(min(i, j), max(i, j))] for j in range(6)] for i in range(6)]
-    L = [[F64(0)] * 6 for _ in range(6)]
-    d = [F64(0)] * 6
-    ok = True
-    for j in range(6):
-        w = [L[j][k] * d[k] for k in range(j)]
-        s = A[j][j]
-        for k in range(j):
-            s = s - L[j][k] * w[k]
-        d[j] = s
-        if not (s > 0 and s <= DBL_MAX):
-            ok = False
-        for i in range(j + 1, 6):
-            t = A[i][j]
-            for k in range(j):
-                t = t - L[i][k] * w[k]
-            L[i][j] = t / s
-    if not ok:
-        return False, [F64(0)] * 6
-    y = [F64(0)] * 6
-    for i in range(6):
-        s = b[i]
-        for k in range(i):
-            s = s - L[i][k] * y[k]
-        y[i] = s
-    x = [F64(0)] * 6
-    for i in range(5, -1, -1):
-        s = y[i] / d[i]
-        for k in range(i + 1, 6):
-            s = s - L[k][i] * x[k]
-        x[i] = s
-    return True, x
-
-
 def pose_optimization(Tcw, keys_xy, octave, u_right, point, world, camera4, mbf, inv_level_sigma2, outlier_in=None, trace=None):
     """-> (Tcw_out float32 4x4, outlier uint8[n], ninliers).  point[i] = -1 or the pool index of feature i's MapPoint;
     u_right None: all mono.  outlier entries of features without a point keep outlier_in (zeros when not given)."""
@@ -286,7 +251,6 @@ def _pose_optimization(Tcw, keys_xy, octave, u_right, point, world, camera4, mbf
         return Tout, outlier, 0
     init = to_se3quat(Tcw)
     flags = np.zeros(nedges, bool)                      # outlier flag per edge (level 1)
-    third, two_thirds = F64(1) / F64(3), F64(2) / F64(3)
     nbad = 0
     est = init
     for rnd in range(4):
@@ -296,64 +260,13 @@ def _pose_optimization(Tcw, keys_xy, octave, u_right, point, world, camera4, mbf
         act = e.take(~flags)
         tr = {"round": rnd, "nactive": len(act), "iters": [], "flags_before": flags.copy()}
         if len(act) > 0:
-            lam, nu, stall = F64(0), F64(2), 0
-            for it in range(10):
-                H, b, cur, rho1 = _system(est, K, act, robust)
-                last = est
-                ini = cur
-                itr = {"trials": [], "end": "ok"}
-                if it == 0:
-                    m = F64(0)
-                    for j in range(6):
-                        a = np.abs(H[(j, j)])
-                        m = m if a < m else a
-                    lam, nu, stall = F64(1e-5) * m, F64(2), 0
-                    if rnd == 3:      # what the Huber weights of the first three rounds would be here
-                        tr["nonunit_huber"] = int(np.count_nonzero(_huber(_error(est, K, act)[2], act.stereo, True)[1] != 1))
-                rho = F64(0)
-                q = 0
-                while True:
-                    backup = est
-                    ok, x = solve6(H, lam, b)
-                    est = _mul(se3_exp(x, trace), est)
-                    tmp = _chi(est, K, act, robust)
-                    last = est
-                    if not ok:
-                        tmp = DBL_MAX
-                    rho = cur - tmp
-                    scale = F64(0)
-                    for j in range(6):
-                        scale = scale + x[j] * (lam * x[j] + b[j])
-                    scale = scale + F64(1e-3)
-                    rho = rho / scale
-                    accepted = bool(rho > 0 and np.isfinite(tmp))
-                    itr["trials"].append({"ok": ok, "rho": float(rho), "accepted": accepted, "nu": float(nu), "chi": float(tmp)})
-                    if accepted:
-                        r2 = F64(2) * rho - F64(1)
-                        alpha = F64(1) - (r2 * r2) * r2
-                        alpha = two_thirds if two_thirds < alpha else alpha
-                        sf = alpha if third < alpha else third
-                        lam = lam * sf
-                        nu = F64(2)
-                        cur = tmp
-                    else:
-                        lam = lam * nu
-                        nu = nu * F64(2)
-                        est = backup
-                    q += 1
-                    if not (rho < 0 and q < 10):
-                        break
+            def on_iter(it, itr, at, rho1, tr=tr, act=act, rnd=rnd):
                 tr["iters"].append(itr)
-                if q == 10 or rho == 0:
-                    itr["end"] = "trials" if q == 10 else "rho0"
-                    break
-                if (ini - cur) * F64(1e3) < ini:
-                    stall += 1
-                else:
-                    stall = 0
-                if stall >= 3:
-                    itr["end"] = "stall"
-                    break
+                if it == 0 and rnd == 3:      # what the Huber weights of the first three rounds would be here
+                    tr["nonunit_huber"] = int(np.count_nonzero(_huber(_error(at, K, act)[2], act.stereo, True)[1] != 1))
+
+            est, last = levenberg(6, 10, est, lambda T: _system(T, K, act, robust), lambda T: _chi(T, K, act, robust),
+                                  lambda T, x: _mul(se3_exp(x, trace), T), on_iter)
         # the inlier test: an outlier edge is recomputed at the estimate; every other edge keeps the errors of the pose where
         # computeActiveErrors ran last (a rejected trial's, when the last trial was rejected)
         chi_est = _error(est, K, e)[2]

@@ -2,7 +2,7 @@
 csrc/orbx_sim3opt.h: what g2o executes for one free VertexSim3Expmap between fixed points, with EdgeSim3ProjectXYZ /
 EdgeInverseSim3ProjectXYZ edges whose Jacobians BaseBinaryEdge::linearizeOplus takes numerically (central differences,
 delta = 1e-9), BaseBinaryEdge::constructQuadraticForm, RobustKernelHuber, g2o::Sim3, a dense 7x7 and
-OptimizationAlgorithmLevenberg::solve.  Every operation is an IEEE double operation in the written order (numpy elementwise
+OptimizationAlgorithmLevenberg::solve (lm_model.py).  Every operation is an IEEE double operation in the written order (numpy elementwise
 arithmetic over the correspondences is the same operation per correspondence); sums over edges run in edge order -- e12_i, e21_i,
 i ascending -- one addition after the other.  The primitives taken from the library are exp (orbx_sim3opt_exp) and sin / cos
 (orbx_pose_sin_cos), as DESIGN.md section 2 (F16) states.  `trace`, when given, receives what the tests assert branch coverage
@@ -11,11 +11,11 @@ import ctypes as C
 
 import numpy as np
 
+from lm_model import levenberg
 from pose_model import _quat_from_R, _R_from_quat, _rotate, _sincos
 
 F64 = np.float64
 F32 = np.float32
-DBL_MAX = F64(np.finfo(np.float64).max)
 DELTA = F64(1e-9)
 CANON64 = np.uint64(0x7ff8000000000000)
 CANON32 = np.uint32(0x7fc00000)
@@ -217,104 +217,14 @@ def _bad(S, pr, sel):
     return (c12 > pr.th2) | (c21 > pr.th2)
 
 
-def solve7(H, lam, b):
-    """(H + lam I) x = b, unpivoted L D L^T; solved when every pivot is > 0 and finite, otherwise (False, 0)"""
-    N = 7
-    A = [[(H[(min(i, j), max(i, j))] + lam) if i == j else H[(min(i, j), max(i, j))] for j in range(N)] for i in range(N)]
-    L = [[F64(0)] * N for _ in range(N)]
-    d = [F64(0)] * N
-    ok = True
-    for j in range(N):
-        w = [L[j][k] * d[k] for k in range(j)]
-        s = A[j][j]
-        for k in range(j):
-            s = s - L[j][k] * w[k]
-        d[j] = s
-        if not (s > 0 and s <= DBL_MAX):
-            ok = False
-        for i in range(j + 1, N):
-            t = A[i][j]
-            for k in range(j):
-                t = t - L[i][k] * w[k]
-            L[i][j] = t / s
-    if not ok:
-        return False, [F64(0)] * N
-    y = [F64(0)] * N
-    for i in range(N):
-        s = b[i]
-        for k in range(i):
-            s = s - L[i][k] * y[k]
-        y[i] = s
-    x = [F64(0)] * N
-    for i in range(N - 1, -1, -1):
-        s = y[i] / d[i]
-        for k in range(i + 1, N):
-            s = s - L[k][i] * x[k]
-        x[i] = s
-    return True, x
-
-
 def _optimize(pr, sel, iters, est, tr, trace):
     """SparseOptimizer::optimize(iters) -> (est, last)"""
-    last = est
-    third, two_thirds = F64(1) / F64(3), F64(2) / F64(3)
-    lam, nu, stall = F64(0), F64(2), 0
-    for it in range(iters):
-        H, b, cur, J = _system(est, pr, sel, trace)
-        last = est
-        ini = cur
-        itr = {"trials": [], "end": "ok", "col6_zero": all(not np.any(Jk[r][6] != 0) for Jk in J for r in (0, 1))}
-        if it == 0:
-            m = F64(0)
-            for j in range(7):
-                a = np.abs(H[(j, j)])
-                m = m if a < m else a
-            lam, nu, stall = F64(1e-5) * m, F64(2), 0
-        rho = F64(0)
-        q = 0
-        while True:
-            backup = est
-            ok, x = solve7(H, lam, b)
-            est = _oplus(est, x, pr.fix_scale, trace)
-            tmp = _chi(est, pr, sel)
-            last = est
-            if not ok:
-                tmp = DBL_MAX
-            rho = cur - tmp
-            scale = F64(0)
-            for j in range(7):
-                scale = scale + x[j] * (lam * x[j] + b[j])
-            scale = scale + F64(1e-3)
-            rho = rho / scale
-            accepted = bool(rho > 0 and np.isfinite(tmp))
-            itr["trials"].append({"ok": ok, "rho": float(rho), "accepted": accepted})
-            if accepted:
-                r2 = F64(2) * rho - F64(1)
-                alpha = F64(1) - (r2 * r2) * r2
-                alpha = two_thirds if two_thirds < alpha else alpha
-                sf = alpha if third < alpha else third
-                lam = lam * sf
-                nu = F64(2)
-                cur = tmp
-            else:
-                lam = lam * nu
-                nu = nu * F64(2)
-                est = backup
-            q += 1
-            if not (rho < 0 and q < 10):
-                break
+    def on_iter(it, itr, at, J):
+        itr["col6_zero"] = all(not np.any(Jk[r][6] != 0) for Jk in J for r in (0, 1))
         tr["iters"].append(itr)
-        if q == 10 or rho == 0:
-            itr["end"] = "trials" if q == 10 else "rho0"
-            break
-        if (ini - cur) * F64(1e3) < ini:
-            stall += 1
-        else:
-            stall = 0
-        if stall >= 3:
-            itr["end"] = "stall"
-            break
-    return est, last
+
+    return levenberg(7, iters, est, lambda S: _system(S, pr, sel, trace), lambda S: _chi(S, pr, sel),
+                     lambda S, x: _oplus(S, x, pr.fix_scale, trace), on_iter)
 
 
 def _canon64(v):
