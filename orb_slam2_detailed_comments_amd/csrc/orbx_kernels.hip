@@ -787,8 +787,11 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
     uint16_t *s_corn = (uint16_t *)(fast_smem + lds.corn_off);
     const int lane = threadIdx.x;
     const int f = blockIdx.x;   // frame fastest: all groups of one frame share one XCD's L2
-    // FR_GPW groups per wave, one after the other: the next group's tile is fetched into registers while this one
-    // is processed, so the global-load latency is never waited for
+    // One or two groups per wave (gpw; the handle refuses anything else), one after the other, as two PEELED trips of the group
+    // body: the second group's tile is requested into a register set of its own once the first is staged, and nothing reads
+    // those registers before the second group's staging, so its loads stay outstanding during walk, rounds and NMS of the
+    // first.  (As a loop with the tile carried round it, the register allocator split the carried tuples and copied them out
+    // at the loads: the wave waited for the whole tile before the first group's walk, profiles/prefetch_waits.md.)
     const int g0 = blockIdx.y * gpw;
     const int ng = min(gpw, ngroups - g0);
     // staging: a lane loads 12 bytes (one load, a third of the address arithmetic and of the load instructions of a
@@ -797,49 +800,58 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
     // frame's scalar base + that 32-bit offset (global_load saddr form, no 64-bit vector arithmetic).  The lanes of a
     // row's last 12-byte piece read past the tile into the level's next bytes (the pyramid slab has slack at its end).
     const int rq = (lane * 37) >> 8, dq = lane - 7 * rq;   // lane / 7, lane % 7  (lane 63: rq = 9, idle)
-    orbx_uint3_u tv[5];
-    OrbxFastGroup grp_n = groups[g0];
-    OrbxCell c0_n = cells[grp_n.cell0], c1_n = cells[grp_n.cell0 + grp_n.ncell - 1];
+    orbx_uint3_u tv_a[5], tv_b[5];   // the tiles of the wave's first and second group: two register sets, nothing loop-carried
+    // (both groups' records up front -- a wave with one group reads its own twice: the second tile's request then hangs on no
+    // chain of record loads, and no record load is retired behind it)
+    const OrbxFastGroup grp_a = groups[g0], grp_b = groups[g0 + ng - 1];
+    const OrbxCell c0_a = cells[grp_a.cell0], c1_a = cells[grp_a.cell0 + grp_a.ncell - 1];
+    const OrbxCell c0_b = cells[grp_b.cell0], c1_b = cells[grp_b.cell0 + grp_b.ncell - 1];
     const uint8_t *fbase = pyr + (long long)f * g.pyr_bytes;
     const uint8_t *rbase = INPLACE ? raw.img + (long long)f * raw.frame_stride : nullptr;
-#define FR_PREFETCH()                                                                                                     \
-    if (L0ONLY || (INPLACE && c0_n.level == 0)) {                                                                         \
-        int dsh_, shr_;                                                                                                   \
-        const int xb_ = orbx_ip_fast_xb(c0_n.x0, &dsh_);                                                                  \
-        const int col_ = orbx_ip_fast_piece_col(xb_, dq, raw.W, &shr_);                                                   \
-        const int ylast_ = (int)c0_n.y0 + (int)c0_n.ch - 1;                                                               \
-        if ((int)c0_n.y0 >= ORBX_EDGE && ylast_ - ORBX_EDGE < raw.H) {                                                    \
-            /* every cell row but the first and the last: no row is reflected, the offsets are the slab path's adds */    \
-            uint32_t vstride9 = (uint32_t)(9 * raw.stride);                                                               \
-            asm("" : "+v"(vstride9));                                                                                     \
-            const uint32_t olast = orbx_ip_row_off(ylast_ - ORBX_EDGE, raw.stride, col_);                                 \
-            uint32_t o = orbx_ip_row_off((int)c0_n.y0 - ORBX_EDGE + min(rq, 8), raw.stride, col_);                        \
-            _Pragma("unroll") for (int k = 0; k < 5; ++k) {                                                               \
-                tv[k] = *(const orbx_uint3_u *)(rbase + min(o, olast));                                                   \
-                o += vstride9;                                                                                            \
-            }                                                                                                             \
-        } else {                                                                                                          \
-            _Pragma("unroll") for (int k = 0; k < 5; ++k) {                                                               \
-                const int prow_ = min((int)c0_n.y0 + min(rq, 8) + 9 * k, ylast_);                                         \
-                tv[k] = *(const orbx_uint3_u *)(rbase + orbx_ip_row_off(orbx_ip_fast_row(prow_, raw.H), raw.stride, col_)); \
-            }                                                                                                             \
-        }                                                                                                                 \
-    } else {                                                                                                              \
-        const DLevel &Ln = g.lv[c0_n.level];                                                                             \
-        const uint8_t *srcn = fbase + Ln.off;                                                                             \
-        uint32_t vpitch9 = (uint32_t)(9 * Ln.pitch);                                                                      \
-        asm("" : "+v"(vpitch9));   /* in a VGPR: a VOP2 add with an SGPR source issues at the slow rate */                   \
-        const uint32_t olast = (uint32_t)(__mul24((int)c0_n.y0 + (int)c0_n.ch - 1, Ln.pitch) + (c0_n.x0 & ~3) + 12 * dq); \
-        uint32_t o = (uint32_t)(__mul24((int)c0_n.y0 + min(rq, 8), Ln.pitch) + (c0_n.x0 & ~3) + 12 * dq);                \
-        _Pragma("unroll") for (int k = 0; k < 5; ++k) {                                                                   \
-            tv[k] = *(const orbx_uint3_u *)(srcn + min(o, olast));                                                        \
-            o += vpitch9;                                                                                                 \
-        }                                                                                                                 \
+    // the 45 register rows of group cn's tile, requested into tvn
+    auto prefetch = [&](const OrbxCell &cn, orbx_uint3_u (&tvn)[5]) __attribute__((always_inline)) {
+    if (L0ONLY || (INPLACE && cn.level == 0)) {
+        int dsh_, shr_;
+        const int xb_ = orbx_ip_fast_xb(cn.x0, &dsh_);
+        const int col_ = orbx_ip_fast_piece_col(xb_, dq, raw.W, &shr_);
+        const int ylast_ = (int)cn.y0 + (int)cn.ch - 1;
+        if ((int)cn.y0 >= ORBX_EDGE && ylast_ - ORBX_EDGE < raw.H) {
+            /* every cell row but the first and the last: no row is reflected, the offsets are the slab path's adds */
+            uint32_t vstride9 = (uint32_t)(9 * raw.stride);
+            asm("" : "+v"(vstride9));
+            const uint32_t olast = orbx_ip_row_off(ylast_ - ORBX_EDGE, raw.stride, col_);
+            uint32_t o = orbx_ip_row_off((int)cn.y0 - ORBX_EDGE + min(rq, 8), raw.stride, col_);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                tvn[k] = *(const orbx_uint3_u *)(rbase + min(o, olast));
+                o += vstride9;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const int prow_ = min((int)cn.y0 + min(rq, 8) + 9 * k, ylast_);
+                tvn[k] = *(const orbx_uint3_u *)(rbase + orbx_ip_row_off(orbx_ip_fast_row(prow_, raw.H), raw.stride, col_));
+            }
+        }
+    } else {
+        const DLevel &Ln = g.lv[cn.level];
+        const uint8_t *srcn = fbase + Ln.off;
+        uint32_t vpitch9 = (uint32_t)(9 * Ln.pitch);
+        asm("" : "+v"(vpitch9));   /* in a VGPR: a VOP2 add with an SGPR source issues at the slow rate */
+        const uint32_t olast = (uint32_t)(__mul24((int)cn.y0 + (int)cn.ch - 1, Ln.pitch) + (cn.x0 & ~3) + 12 * dq);
+        uint32_t o = (uint32_t)(__mul24((int)cn.y0 + min(rq, 8), Ln.pitch) + (cn.x0 & ~3) + 12 * dq);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            tvn[k] = *(const orbx_uint3_u *)(srcn + min(o, olast));
+            o += vpitch9;
+        }
     }
-    FR_PREFETCH()
-  for (int gi = 0; gi < ng; ++gi) {
-    const OrbxFastGroup grp = grp_n;
-    const OrbxCell c0 = c0_n, c1 = c1_n;
+    };
+    prefetch(c0_a, tv_a);
+  // one group: staged from its register set tv, walked, scored, thinned.  `first` (a std::bool_constant): the trip that requests the
+  // wave's second tile, after its own is staged and before its walk
+  auto group = [&](auto first, const OrbxFastGroup &grp, const OrbxCell &c0, const OrbxCell &c1,
+                   const orbx_uint3_u (&tv)[5]) __attribute__((always_inline)) {
     const int level = L0ONLY ? 0 : (int)c0.level;
     const DLevel &L = g.lv[level];
     const int tw = c1.x0 + c1.cw - c0.x0, th_rows = c0.ch;
@@ -908,10 +920,14 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
     // score map cleared with 16-byte stores (the launcher rounds the row count to a multiple of 4, so the map is
     // 16-byte aligned and a few bytes past the cell's last row still belong to it or to the not-yet-used list)
     for (int i = lane; i < (th_rows * (FR_TP / 4) + 3) / 4; i += 64) ((uint4 *)s_score)[i] = make_uint4(0, 0, 0, 0);
-    if (gi + 1 < ng) {
-        grp_n = groups[g0 + gi + 1];
-        c0_n = cells[grp_n.cell0]; c1_n = cells[grp_n.cell0 + grp_n.ncell - 1];
-        FR_PREFETCH()
+    if constexpr (decltype(first)::value) {
+        // Every load so far is retired HERE, on every path (a wave with one group included: the paths join again below):
+        // s_waitcnt vmcnt(0), gfx9 encoding, expcnt and lgkmcnt left at their maxima.  The wave has consumed its tile, so this
+        // waits for nothing, but the staging stores and the loads of the extra rows sit in divergent branches, and on the paths
+        // around them the compiler's wait bookkeeping keeps those loads outstanding: the first reuse of one of their registers
+        // in the walk would then wait for them -- and for the second tile's loads, which are younger, with them.
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        if (ng > 1) prefetch(c0_b, tv_b);
     }
     FrCtx cx;
     cx.tile = (const uint8_t *)s_tile + (ip0 ? orbx_ip_fast_tile_off(c0.x0) : (c0.x0 & 3));
@@ -929,7 +945,7 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
     gc.cursor = cand_cursor + f * g.nlevels + level;
     gc.out_cap = L.cand_cap;
     orbx_wave_sync();
-    if (dbg_stop == 1) continue;
+    if (dbg_stop == 1) return;
     const bool two_th = g.min_th != g.ini_th;
     const bool colv = lane < niw;
     const bool second = lane >= iw0;
@@ -965,10 +981,6 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
             const uint32_t list0 = (uint32_t)(uintptr_t)(fr_lds_u16 *)s_list;
             uint32_t nb = list0;
             uint32_t code = (uint32_t)((y << 8) | lane);
-            // (unused since the list store is exec-masked: the lane's dummy slot in the stack area.  The compiler schedules the
-            // walk differently without this dead value, and the change that retired the select form kept the code object byte
-            // for byte, profiles/knobs_retired.md: the next change to the walk can drop it.)
-            const uint32_t dummy = list0 + 2u * (uint32_t)lcap + 4u * (uint32_t)lane; (void)dummy;
             // software-pipelined: the three LDS bytes of row y+1 are requested before row y is evaluated (the list
             // store could alias them as far as the compiler knows, so it would not hoist them itself); the row after
             // the last one is read but never used (it is the first row of the score map)
@@ -1073,8 +1085,9 @@ __device__ __forceinline__ void fr_kernel(const DGeom &g, const OrbxCell *__rest
     // more survivors than the cell may report (only when max_cand_per_cell cut the exact worst case): reported, not silent
     if (lane == 0 && (ns0 > gc.cap0 || (grp.ncell == 2 && ns1 > gc.cap1))) atomicMax(&status[f], (int)ORBX_CAPACITY);
     orbx_wave_sync();   // the next group overwrites tile / score / lists
-  }
-#undef FR_PREFETCH
+  };
+    group(std::true_type{}, grp_a, c0_a, c1_a, tv_a);
+    if (ng > 1) group(std::false_type{}, grp_b, c0_b, c1_b, tv_b);
 }
 __global__ __launch_bounds__(64, FR_WPS) void k_fast_rows(DGeom g, const OrbxCell *__restrict__ cells,
                                                           const OrbxFastGroup *__restrict__ groups,
