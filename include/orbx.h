@@ -1091,6 +1091,69 @@ typedef struct orbx_init_camera {
 orbx_status orbx_initialize_batch_create(orbx_handle *h, int nproblems, const orbx_init_problem *problems,
                                          const orbx_init_camera *cameras, orbx_init_batch **ransac, orbx_recon_batch **recon);
 
+/* ---- LocalMapping::CreateNewMapPoints, the per-match geometry of src/LocalMapping.cc:450-651 between SearchForTriangulation
+ * (orbx_triangulation_batch_*) and the refresh of the new points (orbx_distinctive_descriptors_batch,
+ * orbx_update_normal_and_depth_batch): the ray-parallax test, the choice between linear triangulation (the 4 x 4 null vector) and
+ * KeyFrame::UnprojectStereo (src/KeyFrame.cc:937-958) of either keyframe, the two depth tests, the two reprojection tests
+ * (chi2 5.991 monocular, 7.8 stereo) and the scale-consistency test, for any number of keyframe pairs in one device round trip.
+ * A problem is ONE (current keyframe, neighbour) pair with its match list.  Within one keyframe the neighbours are sequential --
+ * a point created for neighbour k sets GetMapPoint(idx1), which SearchForTriangulation of neighbour k + 1 skips -- so a call
+ * holds one problem per stream per round; the batch is across streams and whatever else the caller knows to be independent.
+ * k_new_points: one lane per match, one wave per 64-match chunk of one problem, so the two cameras of a chunk are wave-uniform;
+ * the host gathers the per-match operands by index while it packs; the Jacobi workspace lives in registers.
+ * CONTRACT: status bytes and points of the device equal the library's host path (ORBX_NEWPOINTS=host in the environment, read
+ * per call; host-only handles) and the numpy restatement tests/newpoints_model.py bit for bit, in both fp_modes.  Parity with an
+ * OpenCV build is NOT pinned: DESIGN.md section 2 (F17) lists what follows the reference's source and what this library fixes
+ * where the reference leaves it to OpenCV or libm (cv::SVD::compute, cv::norm, Mat::dot, the products, atan2f, cosf).
+ * ComputeF12, the baseline / median-depth gate, AddObservation and Map::AddMapPoint stay the caller's.
+ * Outputs are ragged in problem order, match order inside: status_out [sum nmatches], points_out [sum nmatches][3] (zeros for
+ * every rejecting status; a stored NaN is the canonical quiet NaN).
+ * DEVIATION: a feature with u_right >= 0 whose depth is not > 0 makes the reference dereference the empty cv::Mat that
+ * UnprojectStereo returns; here a match with such a feature on either side gets ORBX_NEWPOINT_NO_DEPTH before any arithmetic.
+ * Validated before any device work, ORBX_BAD_ARGUMENT: nproblems < 0, a null array whose size is positive, nmatches < 0, a
+ * negative feature or level count, a match index outside its keyframe, an octave of a matched feature outside the scale tables.
+ * nproblems == 0 and problems without a match succeed and launch nothing.
+ * MEASURED on an MI355X (tools/newpoints_rate.py, profiles/newpoints_batch.md; n = 30 / 100 / 300 matches, against the
+ * library's own host path on one core, which is neither the reference nor OpenCV): ONE problem per call takes 29 / 30 / 38 us
+ * against 13 / 37 / 104 us, so a lone problem of 30 matches loses on the device; 16 per call 2.6 / 3.3 / 4.5 us each against
+ * 10 / 34 / 101 us; 256 per call 0.39 / 3.1 / 8.8 us each.  compat/LocalMapping_newpoints.inl, one neighbour per call, runs the
+ * host path below 100 matches. */
+enum { ORBX_NEWPOINT_TRIANGULATED = 1,     /* accepted: x3D from the linear triangulation */
+       ORBX_NEWPOINT_STEREO1 = 2,          /* accepted: mpCurrentKeyFrame->UnprojectStereo(idx1) */
+       ORBX_NEWPOINT_STEREO2 = 3,          /* accepted: pKF2->UnprojectStereo(idx2) */
+       ORBX_NEWPOINT_LOW_PARALLAX = 4,     /* the final else: no stereo and very low parallax */
+       ORBX_NEWPOINT_ZERO_W = 5,           /* x3D.at<float>(3) == 0 */
+       ORBX_NEWPOINT_DEPTH1 = 6,           /* z1 <= 0 */
+       ORBX_NEWPOINT_DEPTH2 = 7,           /* z2 <= 0 */
+       ORBX_NEWPOINT_REPROJ1 = 8,          /* the reprojection test in the current keyframe */
+       ORBX_NEWPOINT_REPROJ2 = 9,          /* the reprojection test in the neighbour */
+       ORBX_NEWPOINT_ZERO_DIST = 10,       /* dist1 == 0 || dist2 == 0 */
+       ORBX_NEWPOINT_SCALE = 11,           /* the scale-consistency test */
+       ORBX_NEWPOINT_NO_DEPTH = 12 };      /* u_right >= 0 without a positive depth (the library's own, see DEVIATION) */
+typedef struct orbx_newpoints_keyframe {
+    float Rcw[9], tcw[3], Ow[3];           /* GetRotation(), GetTranslation(), GetCameraCenter() as the keyframe holds them */
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+    int32_t nlevels;                       /* entries of the two tables */
+    const float *scale_factors;            /* [nlevels] mvScaleFactors */
+    const float *level_sigma2;             /* [nlevels] mvLevelSigma2 */
+    int32_t n;                             /* features */
+    const orbx_keypoint *keys_un;          /* [n] mvKeysUn */
+    const float *keys;                     /* [n][2] mvKeys pt, the distorted positions UnprojectStereo reads */
+    const float *u_right, *depth;          /* [n] mvuRight, mvDepth */
+} orbx_newpoints_keyframe;
+typedef struct orbx_newpoints_problem {
+    orbx_newpoints_keyframe kf1, kf2;      /* mpCurrentKeyFrame, pKF2 */
+    float scale_factor;                    /* mpCurrentKeyFrame->mfScaleFactor */
+    int32_t nmatches;
+    const int32_t *matches;                /* [nmatches][2] vMatchedIndices in order (idx1, idx2) */
+} orbx_newpoints_problem;
+/* One page-locked block up, k_new_points, one block down, the wait.  On a host-only handle the library's host path runs. */
+orbx_status orbx_create_new_map_points_batch(orbx_handle *h, int nproblems, const orbx_newpoints_problem *problems,
+                                             uint8_t *status_out, float *points_out);
+/* cosParallaxStereo = cos(2 * atan2(mb / 2, depth)) as both paths get it for depth > 0 (csrc/orbx_newpoints.h).  Exported for
+ * tests/newpoints_model.py, which takes this primitive from the library, and for the measurement of its distance from libm. */
+float orbx_newpoints_stereo_cos(float mb, float depth);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,23 @@ class InitCamera(C.Structure):   # orbx_init_camera
 
 INIT_NONE, INIT_H, INIT_F = 0, 1, 2
 
+
+class NewPointsKeyFrame(C.Structure):   # orbx_newpoints_keyframe
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float), ("mb", C.c_float),
+                ("mbf", C.c_float), ("nlevels", C.c_int32), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p),
+                ("n", C.c_int32), ("keys_un", C.c_void_p), ("keys", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class NewPointsProblem(C.Structure):   # orbx_newpoints_problem
+    _fields_ = [("kf1", NewPointsKeyFrame), ("kf2", NewPointsKeyFrame), ("scale_factor", C.c_float), ("nmatches", C.c_int32),
+                ("matches", C.c_void_p)]
+
+
+# orbx_create_new_map_points_batch's status bytes (ORBX_NEWPOINT_*); 1..3 accept
+(NEWPOINT_TRIANGULATED, NEWPOINT_STEREO1, NEWPOINT_STEREO2, NEWPOINT_LOW_PARALLAX, NEWPOINT_ZERO_W, NEWPOINT_DEPTH1,
+ NEWPOINT_DEPTH2, NEWPOINT_REPROJ1, NEWPOINT_REPROJ2, NEWPOINT_ZERO_DIST, NEWPOINT_SCALE, NEWPOINT_NO_DEPTH) = range(1, 13)
+
 TRACK_STATE_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),
                               ("level", "<i4")])   # orbx_track_state
 assert TRACK_STATE_DTYPE.itemsize == 20
@@ -186,6 +203,7 @@ SYMBOLS = [
     "orbx_init_batch_normalization", "orbx_init_batch_destroy",
     "orbx_init_reconstruct_batch_create", "orbx_recon_batch_result", "orbx_recon_batch_hypothesis", "orbx_recon_batch_destroy",
     "orbx_initialize_batch_create",
+    "orbx_create_new_map_points_batch", "orbx_newpoints_stereo_cos",
 ]
 
 _lib = None
@@ -278,6 +296,9 @@ def lib():
         L.orbx_recon_batch_destroy.restype = None; L.orbx_recon_batch_destroy.argtypes = [vp]
         L.orbx_initialize_batch_create.restype = i32
         L.orbx_initialize_batch_create.argtypes = [vp, i32, vp, vp, C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(L, "orbx_create_new_map_points_batch"):   # (absent from an ORBX_LIB build older than the symbols: A/B runs against it)
+        L.orbx_create_new_map_points_batch.restype = i32; L.orbx_create_new_map_points_batch.argtypes = [vp, i32, vp, vp, vp]
+        L.orbx_newpoints_stereo_cos.restype = f32; L.orbx_newpoints_stereo_cos.argtypes = [f32, f32]
     L.orbx_get_stream.restype = vp; L.orbx_get_stream.argtypes = [vp]
     L.orbx_set_stream.restype = i32; L.orbx_set_stream.argtypes = [vp, vp]
     L.orbx_synchronize.restype = i32; L.orbx_synchronize.argtypes = [vp]

@@ -4595,6 +4595,30 @@ __global__ __launch_bounds__(64) void k_init_pick(const DReconArgs A) {
     for (int e = lane; e < 3 * n; e += 64) opts[e] = c >= 0 ? pts[e] : 0.0f;
 }
 
+// ---------------------------------------------------------------- LocalMapping::CreateNewMapPoints, the per-match geometry
+#include "orbx_newpoints.h"
+// k_new_points: one workgroup = one wave = one chunk of ORBX_NEWPTS_CHUNK matches of ONE problem (the chunk table of the upload),
+// one lane per match.  The chunk and with it the problem record come from blockIdx alone, so the two cameras are wave-uniform and
+// arrive through scalar loads; the per-match operands are the host's gathered planes, read coalesced.  orbx_newpoints_match keeps
+// the 4 x 4 system and its V in registers.  A lane past the problem's last match does nothing: no barrier, no cross-lane
+// operation follows.  Every match of the call is written exactly once: the status byte and the point (zeros when rejected).
+__global__ __launch_bounds__(ORBX_NEWPTS_CHUNK) void k_new_points(const DNewPtsArgs A) {
+    const int c = blockIdx.x;
+    if (c >= A.nchunks) return;
+    const DNewPtsChunk ch = A.chunk[c];
+    const DNewPtsProb &D = A.prob[ch.prob];
+    const int m = ch.base + (int)threadIdx.x;
+    if (m >= D.n) return;
+    const long long g = (long long)D.m_off + m, total = A.total;
+    float pt[3];
+    const int s = orbx_newpoints_match(D.c1, D.c2, D.ratio_factor, orbx_newpoints_obs(A.planes, total, g, 0),
+                                       orbx_newpoints_obs(A.planes, total, g, 1), pt);
+    A.st[g] = (uint8_t)s;
+    A.pts[3 * g] = pt[0];
+    A.pts[3 * g + 1] = pt[1];
+    A.pts[3 * g + 2] = pt[2];
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from the C ABI units)
 // ------------------------------------------------------------------------------------------------
@@ -5041,4 +5065,8 @@ void orbx_launch_recon(hipStream_t s, const DReconArgs &a) {
 void orbx_launch_init_select(hipStream_t s, const DInitArgs &i, const DReconArgs &a) {
     if (a.nlaunch <= 0) return;
     hipLaunchKernelGGL(k_init_select, dim3(a.nlaunch), dim3(64), 0, s, i, a);
+}
+void orbx_launch_new_points(hipStream_t s, const DNewPtsArgs &a) {
+    if (a.nchunks <= 0) return;
+    hipLaunchKernelGGL(k_new_points, dim3(a.nchunks), dim3(ORBX_NEWPTS_CHUNK), 0, s, a);
 }

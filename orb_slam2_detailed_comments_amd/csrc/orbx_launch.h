@@ -11,6 +11,7 @@
 #include "orbx_pnp.h"
 #include "orbx_init.h"
 #include "orbx_recon.h"
+#include "orbx_newpoints.h"
 
 // ---- launch regimes chosen from the size of a launch alone: ONE definition, used by the launchers (orbx_kernels.hip) and
 // reported by orbx_debug_match_plan / orbx_debug_fast_gpw, so that a test can assert the regime it is running in
@@ -156,6 +157,8 @@ void orbx_launch_init(hipStream_t s, const DInitArgs &a);
 void orbx_launch_recon(hipStream_t s, const DReconArgs &a);
 // the fused call, between orbx_launch_init and orbx_launch_recon: k_init_select, one wave per problem of the RANSAC
 void orbx_launch_init_select(hipStream_t s, const DInitArgs &i, const DReconArgs &a);
+// CreateNewMapPoints, the per-match geometry (orbx_newpoints.h): k_new_points over the chunk table, one wave per chunk
+void orbx_launch_new_points(hipStream_t s, const DNewPtsArgs &a);
 void orbx_launch_hamming_matrix(hipStream_t s, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *dist);
 
 void orbx_launch_stereo_batch(hipStream_t s, const OrbxStereoGeom &sg, int npairs, int cap, const orbx_keypoint *kL,

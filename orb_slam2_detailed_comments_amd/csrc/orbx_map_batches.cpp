@@ -499,3 +499,38 @@ extern "C" orbx_status orbx_initialize_batch_create(orbx_handle *h, int nproblem
     orbx_recon_batch_take(*recon, rp, pin + init_out);
     return ORBX_OK;
 }
+
+// ---------------------------------------------------------------- LocalMapping::CreateNewMapPoints, the per-match geometry,
+// batched (orbx_newpoints.h).  Device path: validation and layout (orbx_newpoints.cpp), the cameras, the chunk table and the
+// operands gathered by index packed into the page-locked block, ONE upload, k_new_points on the handle's stream, ONE download of
+// status | points, the wait, the scatter.  Host path (ORBX_NEWPOINTS=host, read per call; host-only handles): the same header
+// compiled by the host compiler over the same packed block.
+extern "C" orbx_status orbx_create_new_map_points_batch(orbx_handle *h, int nproblems, const orbx_newpoints_problem *problems,
+                                                        uint8_t *status_out, float *points_out) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxNewPtsPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_newpoints_plan(nproblems, problems, status_out, points_out, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (plan.total == 0) return ORBX_OK;                         // no problem, or none with a match: nothing launches
+    if (h->host_only || host_selected("ORBX_NEWPOINTS")) {
+        std::vector<uint8_t> in(plan.in_bytes), out(plan.out_bytes);
+        orbx_newpoints_pack(problems, plan, in.data());
+        orbx_newpoints_host_run(plan, in.data(), out.data());
+        orbx_newpoints_unpack(plan, out.data(), status_out, points_out);
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    const size_t dev_in = pad256(plan.in_bytes);
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + plan.out_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_newpoints_pack(problems, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_new_points(h->stream, orbx_newpoints_args(plan, d, d + dev_in)); }
+    st = stage_download_wait(h, pin, d + dev_in, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    orbx_newpoints_unpack(plan, pin, status_out, points_out);
+    return ORBX_OK;
+}
