@@ -369,6 +369,83 @@ public:
         return n;
     }
 
+    // ---- the SearchBySim3 calls of ONE ROUND of LoopClosing::ComputeSim3 (src/LoopClosing.cc:524-541) as one device round trip:
+    //        for (k : candidates that returned a Sim3) n[k] = matcher.SearchBySim3(mpCurrentKF, vpKF2[k], vvpMatches12[k], vs12[k], vR12[k], vt12[k], 7.5);
+    //   ->   n = matcher.SearchBySim3Batch(mpCurrentKF, vpKF2, vvpMatches12, vs12, vR12, vt12, 7.5);
+    // (orbx_search_by_sim3_batch: pose algebra, PredictScale, windows, selection and the mutual test behind the C ABI; every
+    // keyframe is marshalled, uploaded and gridded once, pKF1 for all candidates.)  vvpMatches12[k] and the counts are left
+    // exactly as the loop of single calls leaves them.  Fewer than ORBX_SIM3SEARCH_BATCH_MIN candidates run that loop; the
+    // value is 1 because the measurement found no break-even (profiles/sim3_search_batch.md: one candidate per call takes
+    // 54 / 58 / 77 us in the batched call against 94 / 136 / 256 us in the single one at 500 / 1000 / 2000 features).  MapPoint keeps mfMinDistance / mfMaxDistance
+    // private; a tree that can hand them over defines ORBX_MAPPOINT_MIN_DISTANCE(p) / ORBX_MAPPOINT_MAX_DISTANCE(p), otherwise
+    // they are recovered from the two invariance getters (RawDistance below).
+#ifndef ORBX_SIM3SEARCH_BATCH_MIN
+#define ORBX_SIM3SEARCH_BATCH_MIN 1
+#endif
+    std::vector<int> SearchBySim3Batch(KeyFrame *pKF1, const std::vector<KeyFrame *> &vpKF2, std::vector<std::vector<MapPoint *> > &vvpMatches12,
+                                       const std::vector<float> &vs12, const std::vector<cv::Mat> &vR12, const std::vector<cv::Mat> &vt12,
+                                       const float th) {
+        const int K = (int)vpKF2.size();
+        if ((int)vvpMatches12.size() != K || (int)vs12.size() != K || (int)vR12.size() != K || (int)vt12.size() != K)
+            throw std::runtime_error("SearchBySim3Batch: one entry per candidate is expected");
+        std::vector<int> found(K, 0);
+        if (K < ORBX_SIM3SEARCH_BATCH_MIN) {
+            for (int k = 0; k < K; ++k) found[k] = SearchBySim3(pKF1, vpKF2[k], vvpMatches12[k], vs12[k], vR12[k], vt12[k], th);
+            return found;
+        }
+        // the pool: pKF1, then every distinct candidate keyframe once
+        std::vector<KeyFrame *> pool(1, pKF1);
+        std::vector<int> kf2(K);
+        for (int k = 0; k < K; ++k) {
+            size_t j = 0;
+            while (j < pool.size() && pool[j] != vpKF2[k]) ++j;
+            if (j == pool.size()) pool.push_back(vpKF2[k]);
+            kf2[k] = (int)j;
+        }
+        std::vector<std::vector<MapPoint *> > vp(pool.size());
+        std::vector<Sim3KeyFrameArrays> arrays;
+        arrays.reserve(pool.size());
+        std::vector<orbx_sim3_search_keyframe> views(pool.size());
+        for (size_t j = 0; j < pool.size(); ++j) {
+            vp[j] = pool[j]->GetMapPointMatches();
+            arrays.push_back(Sim3KeyFrameArrays(pool[j], vp[j]));
+        }
+        for (size_t j = 0; j < pool.size(); ++j) views[j] = arrays[j].View();
+        const int N1 = (int)vp[0].size();
+        std::vector<orbx_sim3_search_problem> probs(K);
+        std::vector<std::vector<uint8_t> > done1(K), done2(K);
+        std::vector<std::vector<int32_t> > m12(K);
+        std::vector<int32_t *> rows(K);
+        for (int k = 0; k < K; ++k) {
+            const int N2 = (int)vp[kf2[k]].size();
+            done1[k].assign(std::max(N1, 1), 0); done2[k].assign(std::max(N2, 1), 0);
+            for (int i = 0; i < N1; ++i) {                            // :1470-1483
+                MapPoint *p = vvpMatches12[k][i];
+                if (!p) continue;
+                done1[k][i] = 1;
+                const int idx2 = p->GetIndexInKeyFrame(vpKF2[k]);
+                if (idx2 >= 0 && idx2 < N2) done2[k][idx2] = 1;
+            }
+            orbx_sim3_search_problem &P = probs[k];
+            P.kf1 = 0; P.kf2 = kf2[k]; P.s12 = vs12[k]; P.th = th;
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) P.R12[3 * r + c] = vR12[k].at<float>(r, c);
+                P.t12[r] = vt12[k].at<float>(r);
+            }
+            P.matched1 = done1[k].data(); P.matched2 = done2[k].data();
+            m12[k].assign(std::max(N1, 1), -1);
+            rows[k] = m12[k].data();
+        }
+        const float camera4[4] = {pKF1->fx, pKF1->fy, pKF1->cx, pKF1->cy};
+        const float bounds4[4] = {(float)pKF1->mnMinX, (float)pKF1->mnMaxX, (float)pKF1->mnMinY, (float)pKF1->mnMaxY};
+        Check(orbx_search_by_sim3_batch(Sim3SearchHandle(), (int)views.size(), views.data(), K, probs.data(), camera4, bounds4, rows.data(),
+                                        found.data(), NULL));
+        for (int k = 0; k < K; ++k)
+            for (int i = 0; i < N1; ++i)
+                if (m12[k][i] >= 0) vvpMatches12[k][i] = vp[kf2[k]][m12[k][i]];
+        return found;
+    }
+
     // ---- include/ORBmatcher.h:197 -- src/ORBmatcher.cc:1100-1280, caller LocalMapping::SearchInNeighbors (src/LocalMapping.cc:750-807)
     int Fuse(KeyFrame *pKF, const std::vector<MapPoint *> &vpMapPoints, const float th = 3.0) {
         const cv::Mat Rcw = pKF->GetRotation(), tcw = pKF->GetTranslation(), Ow = pKF->GetCameraCenter();
@@ -566,6 +643,61 @@ protected:
             v.keys_un = Keys(K->mvKeysUn); v.desc = K->mDescriptors.ptr<uint8_t>(); v.n = K->N; v.has_map_point = has.data();
             v.u_right = K->mvuRight.data(); v.feat_vec = fv.View();
             v.scale_factors = K->mvScaleFactors.data(); v.level_sigma2 = K->mvLevelSigma2.data();
+            return v;
+        }
+    };
+    // the handle of SearchBySim3Batch: Handle(), or the expression ORBX_SIM3SEARCH_HANDLE (a host-only handle runs the library's
+    // host path; so does ORBX_SIM3SEARCH=host in the environment, read per call)
+    static orbx_handle *Sim3SearchHandle() {
+#ifdef ORBX_SIM3SEARCH_HANDLE
+        return (ORBX_SIM3SEARCH_HANDLE);
+#else
+        return Handle();
+#endif
+    }
+    // mfMinDistance / mfMaxDistance from GetMinDistanceInvariance() = 0.8f * min / GetMaxDistanceInvariance() = 1.2f * max: the
+    // smallest float near value / factor whose product with the factor IS the getter's value (the gates read only the product;
+    // the ratio of PredictScale can be one ulp off the private member where two floats share a product)
+    static float RawDistance(float value, float factor) {
+        float x = value / factor;
+        if (!(x == x) || x - x != 0.f) return x;
+        for (int k = 0; k < 4 && factor * x > value; ++k) x = std::nextafterf(x, -INFINITY);
+        for (int k = 0; k < 4 && factor * x < value; ++k) x = std::nextafterf(x, INFINITY);
+        for (int k = 0; k < 4 && factor * std::nextafterf(x, -INFINITY) == value; ++k) x = std::nextafterf(x, -INFINITY);
+        return x;
+    }
+    // one keyframe of the pool of orbx_search_by_sim3_batch
+    struct Sim3KeyFrameArrays {
+        const KeyFrame *K;
+        std::vector<uint8_t> has, pdesc;
+        std::vector<float> pos, dmin, dmax;
+        float Tcw[16];
+        Sim3KeyFrameArrays(KeyFrame *k, const std::vector<MapPoint *> &vp)
+            : K(k), has(std::max(k->N, 1), 0), pdesc((size_t)std::max(k->N, 1) * 32, 0), pos((size_t)std::max(k->N, 1) * 3, 0.f),
+              dmin(std::max(k->N, 1), 0.f), dmax(std::max(k->N, 1), 0.f) {
+            const cv::Mat R = k->GetRotation(), t = k->GetTranslation();
+            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) Tcw[4 * r + c] = r == c ? 1.f : 0.f;
+            for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) Tcw[4 * r + c] = R.at<float>(r, c); Tcw[4 * r + 3] = t.at<float>(r); }
+            for (int i = 0; i < k->N && i < (int)vp.size(); ++i) {
+                MapPoint *p = vp[i];
+                if (!p || p->isBad()) continue;
+                has[i] = 1;
+                const cv::Mat x = p->GetWorldPos();
+                for (int c = 0; c < 3; ++c) pos[3 * (size_t)i + c] = x.at<float>(c);
+#ifdef ORBX_MAPPOINT_MIN_DISTANCE
+                dmin[i] = ORBX_MAPPOINT_MIN_DISTANCE(p); dmax[i] = ORBX_MAPPOINT_MAX_DISTANCE(p);
+#else
+                dmin[i] = RawDistance(p->GetMinDistanceInvariance(), 0.8f); dmax[i] = RawDistance(p->GetMaxDistanceInvariance(), 1.2f);
+#endif
+                CopyDescriptor(p->GetDescriptor(), &pdesc[(size_t)i * 32]);
+            }
+        }
+        orbx_sim3_search_keyframe View() const {
+            orbx_sim3_search_keyframe v = {};
+            v.n = K->N; v.keys_un = Keys(K->mvKeysUn); v.desc = K->mDescriptors.ptr<uint8_t>();
+            for (int i = 0; i < 16; ++i) v.Tcw[i] = Tcw[i];
+            v.has_point = has.data(); v.world_pos = pos.data(); v.min_distance = dmin.data(); v.max_distance = dmax.data();
+            v.point_desc = pdesc.data();
             return v;
         }
     };

@@ -1154,6 +1154,67 @@ orbx_status orbx_create_new_map_points_batch(orbx_handle *h, int nproblems, cons
  * tests/newpoints_model.py, which takes this primitive from the library, and for the measurement of its distance from libm. */
 float orbx_newpoints_stereo_cos(float mb, float depth);
 
+/* ---- ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1433-1684) whole, pose algebra included, for any number of (KF1, KF2, Sim3)
+ * problems in one device round trip: the SearchBySim3 stage of LoopClosing::ComputeSim3 (src/LoopClosing.cc:524-541) for every
+ * candidate of a round.  A call touches nothing outside its own arguments (the reference rebuilds vpMapPointMatches before every
+ * call), so the problems are independent.  The keyframes form a pool: each is uploaded and gridded ONCE, however many problems
+ * name it (KF1 is mpCurrentKF for every candidate).
+ * Arithmetic (csrc/orbx_sim3search.h, shared by host and device; the cv::Mat rule of tests/compat_runtime/opencv2/core/core.hpp):
+ * sR12 = s12 R12 and sR21 = (1.0 / s12) R12^T element by element as (float)((double)elem * scalar); t21 = -sR21 t12, R p and
+ * sR c with a double accumulator over k = 0, 1, 2 rounded once; the + t additions in float; `z < 0.0` rejects (z = +-0 goes on
+ * to invz = +-inf and fails IsInImage); invz = (float)(1.0 / (double)z), x = X invz, y = Y invz; u = fx x + cx, v = fy y + cy
+ * contracted to fmaf under ORBX_FP_GCC_FMA and rounded separately under ORBX_FP_STRICT; IsInImage is u >= minx && u < maxx &&
+ * v >= miny && v < maxy; dist3D = (float)sqrt(double sum of squares in element order) against [0.8f min, 1.2f max]; the level of
+ * orbx_predict_scale(max, dist3D); radius = th * scale[level]; level band [level - 1, level]; the winner is the first strict
+ * minimum of the Hamming distance in GetFeaturesInArea visiting order and must be <= 100; the mutual test of :1667-1681.
+ * Scale factors, level count and the PredictScale table come from the handle.
+ * OUTPUTS: matches12[k][i1] (n of kf1 entries) = the KF2 feature whose MapPoint the reference writes into vpMatches12[i1], -1
+ * where it leaves the entry alone; nfound[k] = the return value.
+ * Debug rows (per problem, one entry per feature of kf1 / kf2; the struct and every field may be NULL): status (see the enum),
+ * best = vnMatch1 / vnMatch2, level = nPredictedLevel where the point reached the search (else -1), uv = (u, v) where computed
+ * (status >= 2; else zeros; a NaN is stored as the canonical quiet NaN).
+ * CONTRACT: device = the library's host path (ORBX_SIM3SEARCH=host in the environment, read per call; host-only handles) =
+ * tests/sim3_search_model.py, every output and debug field, in both fp_modes; matches and counts equal the reference's compiled
+ * src/ORBmatcher.cc behind the stand-in cv::Mat (tests/test_sim3_search_cpu.py, tests/golden/sim3_search_*.json).  Parity with an
+ * OpenCV build is not pinned.
+ * Validated before any device work, ORBX_BAD_ARGUMENT: negative counts, a null field of a non-empty view, a null output row, kf1 /
+ * kf2 outside the pool, an octave outside [0, nlevels), bad image bounds; ORBX_UNSUPPORTED: n > 65535.  nproblems == 0 launches
+ * nothing; a call whose keyframes hold no feature at all has nothing to launch either and fills its (empty) outputs on the host. */
+enum { ORBX_SIM3S_NOT_SEARCHED = 0,        /* no good point, or already matched */
+       ORBX_SIM3S_BEHIND = 1,              /* z < 0 */
+       ORBX_SIM3S_OUTSIDE = 2,             /* outside IsInImage */
+       ORBX_SIM3S_DISTANCE = 3,            /* outside the distance band */
+       ORBX_SIM3S_NO_CANDIDATE = 4,        /* empty window, or nothing in the level band */
+       ORBX_SIM3S_TOO_FAR = 5,             /* best distance > 100 */
+       ORBX_SIM3S_MATCH = 6 };             /* vnMatch set */
+typedef struct orbx_sim3_search_keyframe {     /* host arrays; one entry per keyframe of the pool */
+    int32_t n;
+    const orbx_keypoint *keys_un;              /* mvKeysUn */
+    const uint8_t *desc;                       /* mDescriptors, 32 per feature */
+    float Tcw[16];                             /* row major; GetRotation() / GetTranslation() are read from it */
+    const uint8_t *has_point;                  /* vpMapPoints[i] != NULL && !isBad() */
+    const float *world_pos;                    /* GetWorldPos(), 3 per feature, read where has_point */
+    const float *min_distance, *max_distance;  /* raw mfMinDistance / mfMaxDistance (0.8f / 1.2f applied inside) */
+    const uint8_t *point_desc;                 /* MapPoint::GetDescriptor(), 32 per feature, read where has_point */
+} orbx_sim3_search_keyframe;
+typedef struct orbx_sim3_search_problem {
+    int32_t kf1, kf2;                          /* indices into the pool; many problems may share kf1 */
+    float s12, R12[9], t12[3], th;
+    const uint8_t *matched1;                   /* n of kf1: vpMatches12[i] != NULL (NULL: none) */
+    const uint8_t *matched2;                   /* n of kf2: vbAlreadyMatched2 as :1470-1483 compute it (NULL: none) */
+} orbx_sim3_search_problem;
+typedef struct orbx_sim3_search_debug {        /* one row pointer per problem; every field may be NULL */
+    uint8_t *const *status1, *const *status2;
+    int32_t *const *best1, *const *best2;
+    int32_t *const *level1, *const *level2;
+    float *const *uv1, *const *uv2;            /* 2 per feature */
+} orbx_sim3_search_debug;
+/* One page-locked block up, k_grid_build + k_sim3s_project + k_sim3s_cand + k_sim3s_mutual, one block down, the wait. */
+orbx_status orbx_search_by_sim3_batch(orbx_handle *h, int nkeyframes, const orbx_sim3_search_keyframe *keyframes,
+                                      int nproblems, const orbx_sim3_search_problem *problems, const float *camera4,
+                                      const float *bounds4, int32_t *const *matches12, int *nfound,
+                                      const orbx_sim3_search_debug *dbg);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,24 @@ class NewPointsProblem(C.Structure):   # orbx_newpoints_problem
 (NEWPOINT_TRIANGULATED, NEWPOINT_STEREO1, NEWPOINT_STEREO2, NEWPOINT_LOW_PARALLAX, NEWPOINT_ZERO_W, NEWPOINT_DEPTH1,
  NEWPOINT_DEPTH2, NEWPOINT_REPROJ1, NEWPOINT_REPROJ2, NEWPOINT_ZERO_DIST, NEWPOINT_SCALE, NEWPOINT_NO_DEPTH) = range(1, 13)
 
+class Sim3SearchKeyFrame(C.Structure):   # orbx_sim3_search_keyframe
+    _fields_ = [("n", C.c_int32), ("keys_un", C.c_void_p), ("desc", C.c_void_p), ("Tcw", C.c_float * 16), ("has_point", C.c_void_p),
+                ("world_pos", C.c_void_p), ("min_distance", C.c_void_p), ("max_distance", C.c_void_p), ("point_desc", C.c_void_p)]
+
+
+class Sim3SearchProblem(C.Structure):   # orbx_sim3_search_problem
+    _fields_ = [("kf1", C.c_int32), ("kf2", C.c_int32), ("s12", C.c_float), ("R12", C.c_float * 9), ("t12", C.c_float * 3),
+                ("th", C.c_float), ("matched1", C.c_void_p), ("matched2", C.c_void_p)]
+
+
+class Sim3SearchDebug(C.Structure):   # orbx_sim3_search_debug
+    _fields_ = [("status1", C.c_void_p), ("status2", C.c_void_p), ("best1", C.c_void_p), ("best2", C.c_void_p),
+                ("level1", C.c_void_p), ("level2", C.c_void_p), ("uv1", C.c_void_p), ("uv2", C.c_void_p)]
+
+
+# orbx_search_by_sim3_batch's status bytes (ORBX_SIM3S_*)
+(SIM3S_NOT_SEARCHED, SIM3S_BEHIND, SIM3S_OUTSIDE, SIM3S_DISTANCE, SIM3S_NO_CANDIDATE, SIM3S_TOO_FAR, SIM3S_MATCH) = range(7)
+
 TRACK_STATE_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),
                               ("level", "<i4")])   # orbx_track_state
 assert TRACK_STATE_DTYPE.itemsize == 20
@@ -204,6 +222,7 @@ SYMBOLS = [
     "orbx_init_reconstruct_batch_create", "orbx_recon_batch_result", "orbx_recon_batch_hypothesis", "orbx_recon_batch_destroy",
     "orbx_initialize_batch_create",
     "orbx_create_new_map_points_batch", "orbx_newpoints_stereo_cos",
+    "orbx_search_by_sim3_batch",
 ]
 
 _lib = None
@@ -299,6 +318,9 @@ def lib():
     if hasattr(L, "orbx_create_new_map_points_batch"):   # (absent from an ORBX_LIB build older than the symbols: A/B runs against it)
         L.orbx_create_new_map_points_batch.restype = i32; L.orbx_create_new_map_points_batch.argtypes = [vp, i32, vp, vp, vp]
         L.orbx_newpoints_stereo_cos.restype = f32; L.orbx_newpoints_stereo_cos.argtypes = [f32, f32]
+    if hasattr(L, "orbx_search_by_sim3_batch"):   # (absent from an ORBX_LIB build older than the symbol: A/B runs against it)
+        L.orbx_search_by_sim3_batch.restype = i32
+        L.orbx_search_by_sim3_batch.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
     L.orbx_get_stream.restype = vp; L.orbx_get_stream.argtypes = [vp]
     L.orbx_set_stream.restype = i32; L.orbx_set_stream.argtypes = [vp, vp]
     L.orbx_synchronize.restype = i32; L.orbx_synchronize.argtypes = [vp]

@@ -4619,6 +4619,88 @@ __global__ __launch_bounds__(ORBX_NEWPTS_CHUNK) void k_new_points(const DNewPtsA
     A.pts[3 * g + 2] = pt[2];
 }
 
+// ---------------------------------------------------------------- ORBmatcher::SearchBySim3, batched, pose algebra included
+#include "orbx_sim3search.h"
+// k_sim3s_project: one thread per (problem, direction, feature) -- blockIdx.y = 2 * problem + direction, so the problem record
+// and the direction's pose arrive through scalar loads.  orbx_sim3s_project (the shared header) gives the status, the
+// projection, the level and the window; a point that reaches the search becomes a DTrackQ and its query index is appended to the
+// compacted list of live queries (ballot, one atomic per wave: the list's order is arbitrary, every query's result is its own).
+// Most features of a keyframe are not searched -- no point, or already matched -- and never cost a wave in k_sim3s_cand.
+__global__ __launch_bounds__(256) void k_sim3s_project(const DSim3sArgs A) {
+    const int k = blockIdx.y >> 1, d = blockIdx.y & 1;
+    const DSim3sProb &D = A.prob[k];
+    if (d == 0 && blockIdx.x == 0 && threadIdx.x == 0) A.nfound[k] = 0;   // k_sim3s_mutual adds to it, launches later
+    const int n = D.n[d];
+    if ((int)(blockIdx.x * 256) >= n) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int g = D.q_off + (d ? D.n[0] : 0) + i;
+    bool live = false;
+    if (i < n) {
+        const DSim3sPt T = A.pt[(long long)D.kf[d] * A.fstride + i];
+        OrbxSim3sProj o;
+        o.status = ORBX_SIM3S_NOT_SEARCHED; o.u = 0.0f; o.v = 0.0f; o.r = -1.0f; o.level = -1;
+        if (T.has && !A.flag[g]) o = orbx_sim3s_project(D.dir[d], A.cam, D.th, T);
+        live = o.status == ORBX_SIM3S_NO_CANDIDATE;
+        A.status[g] = (uint8_t)o.status;
+        A.level[g] = o.level;
+        A.best[g] = -1;
+        *(float2 *)(A.uv + 2 * (long long)g) = make_float2(o.u, o.v);
+        if (live) {
+            DTrackQ Q;
+            Q.x = o.u; Q.y = o.v; Q.ur = 0.0f; Q.r = o.r;
+            Q.min_level = o.level - 1; Q.max_level = o.level;      // max_level >= 0: track_scan applies the band [level - 1, level]
+            Q.obs = 0; Q.angle = 0.0f; Q.prob = k; Q.pad = d;
+            A.q[g] = Q;
+        }
+    }
+    const unsigned long long m = orbx_ballot(live);
+    int base = 0;
+    if ((threadIdx.x & 63) == 0 && m) base = atomicAdd(A.ctr, (int)__popcll(m));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (live) A.live[base + orbx_wave_rank(m)] = g;
+}
+// k_sim3s_cand: a bounded grid of waves strides over the live queries; each runs track_scan<false> (GetFeaturesInArea's bucket
+// walk with the level band, the smallest key dist << 16 | visiting position = the first strict minimum) against the target
+// keyframe's grid, with the MapPoint's descriptor read where the pool holds it, and writes vnMatch and the final status.
+__global__ __launch_bounds__(256) void k_sim3s_cand(const DSim3sArgs A, const DGrid gp) {
+    const int lane = threadIdx.x & 63;
+    const int nlive = min(A.ctr[0], A.nq), nw = gridDim.x * 4;
+    for (int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); w < nlive; w += nw) {
+        const int g = __builtin_amdgcn_readfirstlane(A.live[w]);
+        const DTrackQ Q = A.q[g];
+        const int k = __builtin_amdgcn_readfirstlane(Q.prob), d = __builtin_amdgcn_readfirstlane(Q.pad) & 1;
+        const DSim3sProb &D = A.prob[k];
+        const long long src = D.kf[d], tgt = D.kf[1 - d];
+        const int i = g - D.q_off - (d ? D.n[0] : 0);
+        const uint4 *qp = (const uint4 *)(A.pdesc + (src * A.fstride + i) * 32);
+        const TrackBest B = track_scan<false>(gp, Q, qp[0], qp[1], A.keys + tgt * A.fstride, A.desc + tgt * A.fstride * 32, nullptr,
+                                              A.cb + tgt * (GR_CELLS + 1), A.items + tgt * A.fstride, min(A.cnt[tgt], A.fstride),
+                                              nullptr, lane);
+        if (lane == 0) {
+            int32_t best;
+            A.status[g] = (uint8_t)orbx_sim3s_outcome(B.k1, (int)(B.p1 & 0xffffu), &best);
+            A.best[g] = best;
+        }
+    }
+}
+// k_sim3s_mutual: one thread per KF1 feature (blockIdx.y = problem): the agreement test of :1667-1681, the count by ballot and
+// one atomic per wave.
+__global__ __launch_bounds__(256) void k_sim3s_mutual(const DSim3sArgs A) {
+    const int k = blockIdx.y;
+    const DSim3sProb &D = A.prob[k];
+    const int n1 = D.n[0];
+    if ((int)(blockIdx.x * 256) >= n1) return;
+    const int i1 = blockIdx.x * 256 + threadIdx.x;
+    bool both = false;
+    if (i1 < n1) {
+        const int idx2 = A.best[D.q_off + i1];
+        both = idx2 >= 0 && idx2 < D.n[1] && A.best[D.q_off + n1 + idx2] == i1;
+        A.matches[D.m_off + i1] = both ? idx2 : -1;
+    }
+    const unsigned long long m = orbx_ballot(both);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(A.nfound + k, (int)__popcll(m));
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from the C ABI units)
 // ------------------------------------------------------------------------------------------------
@@ -5069,4 +5151,14 @@ void orbx_launch_init_select(hipStream_t s, const DInitArgs &i, const DReconArgs
 void orbx_launch_new_points(hipStream_t s, const DNewPtsArgs &a) {
     if (a.nchunks <= 0) return;
     hipLaunchKernelGGL(k_new_points, dim3(a.nchunks), dim3(ORBX_NEWPTS_CHUNK), 0, s, a);
+}
+void orbx_launch_sim3_search(hipStream_t s, const DSim3sArgs &a, const OrbxSim3sGrid &g) {
+    if (a.nq <= 0 || a.nproblems <= 0) return;
+    const DGrid gp = {g.minx, g.miny, g.winv, g.hinv};
+    const int bx = (a.max_n + 255) / 256;
+    hipLaunchKernelGGL(k_grid_build, dim3(a.nkf), dim3(1024), 0, s, gp, a.keys, a.cnt, 0, a.fstride, a.cb, a.items);
+    hipLaunchKernelGGL(k_sim3s_project, dim3(bx, 2 * a.nproblems), dim3(256), 0, s, a);
+    // one wave per live query up to 2048 workgroups; the waves stride over the rest
+    hipLaunchKernelGGL(k_sim3s_cand, dim3(std::min((a.nq + 3) / 4, 2048)), dim3(256), 0, s, a, gp);
+    hipLaunchKernelGGL(k_sim3s_mutual, dim3(bx, a.nproblems), dim3(256), 0, s, a);
 }

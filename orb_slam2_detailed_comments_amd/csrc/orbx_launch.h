@@ -12,6 +12,7 @@
 #include "orbx_init.h"
 #include "orbx_recon.h"
 #include "orbx_newpoints.h"
+#include "orbx_sim3search.h"
 
 // ---- launch regimes chosen from the size of a launch alone: ONE definition, used by the launchers (orbx_kernels.hip) and
 // reported by orbx_debug_match_plan / orbx_debug_fast_gpw, so that a test can assert the regime it is running in
@@ -159,6 +160,8 @@ void orbx_launch_recon(hipStream_t s, const DReconArgs &a);
 void orbx_launch_init_select(hipStream_t s, const DInitArgs &i, const DReconArgs &a);
 // CreateNewMapPoints, the per-match geometry (orbx_newpoints.h): k_new_points over the chunk table, one wave per chunk
 void orbx_launch_new_points(hipStream_t s, const DNewPtsArgs &a);
+// SearchBySim3 batched (orbx_sim3search.h): k_grid_build over the pool, k_sim3s_project, k_sim3s_cand over the live queries, k_sim3s_mutual
+void orbx_launch_sim3_search(hipStream_t s, const DSim3sArgs &a, const OrbxSim3sGrid &g);
 void orbx_launch_hamming_matrix(hipStream_t s, const uint8_t *q, int nq, const uint8_t *t, int nt, uint16_t *dist);
 
 void orbx_launch_stereo_batch(hipStream_t s, const OrbxStereoGeom &sg, int npairs, int cap, const orbx_keypoint *kL,

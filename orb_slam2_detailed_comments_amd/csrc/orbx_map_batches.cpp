@@ -534,3 +534,45 @@ extern "C" orbx_status orbx_create_new_map_points_batch(orbx_handle *h, int npro
     orbx_newpoints_unpack(plan, pin, status_out, points_out);
     return ORBX_OK;
 }
+
+// ---------------------------------------------------------------- ORBmatcher::SearchBySim3, batched, pose algebra included
+// (orbx_sim3search.h).  Device path: validation and layout (orbx_sim3search.cpp), the keyframe pool -- each keyframe once -- and
+// the problems packed into the page-locked block, ONE upload, k_grid_build over the pool + k_sim3s_project + k_sim3s_cand +
+// k_sim3s_mutual on the handle's stream, ONE download (counts | matches, and the debug rows where asked for), the wait, the
+// scatter.  Host path (ORBX_SIM3SEARCH=host, read per call; host-only handles): the same header over the same packed block.
+extern "C" orbx_status orbx_search_by_sim3_batch(orbx_handle *h, int nkeyframes, const orbx_sim3_search_keyframe *keyframes,
+                                                 int nproblems, const orbx_sim3_search_problem *problems, const float *camera4,
+                                                 const float *bounds4, int32_t *const *matches12, int *nfound,
+                                                 const orbx_sim3_search_debug *dbg) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxSim3sPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_sim3s_plan(nkeyframes, keyframes, nproblems, problems, camera4, bounds4, h->p.nlevels, matches12, nfound,
+                                     plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (nproblems == 0) return ORBX_OK;
+    OrbxSim3sCam cam;
+    OrbxSim3sGrid grid;
+    orbx_sim3s_camera(camera4, bounds4, h->p.fp_mode == ORBX_FP_GCC_FMA ? 1 : 0, h->p.nlevels, h->ps_thr, h->tab.scale, cam, grid);
+    if (plan.nq == 0 || h->host_only || host_selected("ORBX_SIM3SEARCH")) {   // (no feature anywhere: nothing to launch)
+        std::vector<uint8_t> in(plan.in_bytes), out(plan.out_bytes);
+        orbx_sim3s_pack(keyframes, problems, plan, in.data());
+        orbx_sim3s_host_run(plan, cam, grid, in.data(), out.data());
+        orbx_sim3s_unpack(plan, in.data(), out.data(), matches12, nfound, dbg);
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    const size_t down = dbg ? plan.out_bytes : plan.out_small;
+    st = stage_begin(h, plan.in_bytes + down, plan.in_bytes + plan.dev_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_sim3s_pack(keyframes, problems, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    uint8_t *dev = d + plan.in_bytes;
+    { ProfScope ps(h, ORBX_K_MATCH);
+      orbx_launch_sim3_search(h->stream, orbx_sim3s_args(plan, cam, d, dev), grid); }
+    st = stage_download_wait(h, pin + plan.in_bytes, dev + plan.o_out, down);
+    if (st != ORBX_OK) return st;
+    orbx_sim3s_unpack(plan, pin, pin + plan.in_bytes, matches12, nfound, dbg);
+    return ORBX_OK;
+}

@@ -412,6 +412,17 @@ class ORBmatcher:
                                           ptr(out), C.byref(n)))
         return n.value, out[:t1.n].copy()
 
+    def SearchBySim3Batch(self, keyframes, problems, camera4, bounds4, debug=False):
+        """SearchBySim3 (src/ORBmatcher.cc:1433-1684) whole, pose algebra included, for many (KF1, KF2, Sim3) problems in ONE
+        device round trip (orbx_search_by_sim3_batch); each keyframe of the pool is uploaded and gridded once.
+        keyframes: dicts keys_un, desc [n, 32], Tcw [4, 4], has_point [n], world_pos [n, 3], min_distance, max_distance [n] (raw
+        mfMinDistance / mfMaxDistance), point_desc [n, 32].  problems: dicts kf1, kf2 (pool indices), s12, R12 [3, 3], t12 [3], th
+        and optionally matched1 [n1], matched2 [n2].  camera4 = (fx, fy, cx, cy) of KF1, bounds4 = (minx, maxx, miny, maxy).
+        Returns ([nFound_k], [matches12_k]) -- matches12_k[i1] = the KF2 feature whose MapPoint vpMatches12[i1] receives, else -1 --
+        and with debug=True a third list of dicts status1/2, best1/2, level1/2, uv1/2 per problem."""
+        call = Sim3SearchCall(keyframes, problems, camera4, bounds4, debug)
+        return call.run(self._ex)
+
     def SearchByProjectionKeyFrame(self, cur, pts, cur_has_map_point, th, ORBdist):
         """SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist); cur_has_map_point updated in place."""
         import ctypes as C
@@ -473,3 +484,85 @@ class _TriangulationBatch:
     def __enter__(self): return self
     def __exit__(self, *a): self.close()
     def __del__(self): self.close()
+
+
+class Sim3SearchCall:
+    """The marshalled arguments of one orbx_search_by_sim3_batch call (ORBmatcher.SearchBySim3Batch): built once, run on any
+    extractor's handle any number of times (tools/sim3_search_rate.py times run_raw alone)."""
+    DEBUG_ROWS = (("status", np.uint8, 1, 0), ("best", np.int32, 1, -1), ("level", np.int32, 1, -1), ("uv", np.float32, 2, 0))
+
+    def __init__(self, keyframes, problems, camera4, bounds4, debug=False):
+        import ctypes as C
+        self._C, self._keep = C, []
+        self.nkf, self.K = len(keyframes), len(problems)
+        self.kv = (_capi.Sim3SearchKeyFrame * max(self.nkf, 1))()
+        self.ns = [self._keyframe(self.kv[f], kf) for f, kf in enumerate(keyframes)]
+        self.pv = (_capi.Sim3SearchProblem * max(self.K, 1))()
+        for k, p in enumerate(problems):
+            self._problem(self.pv[k], p)
+        self.matches = self._rows(1, np.int32, 1, -1)
+        self._match_table = self._table(self.matches)
+        self.nfound = (C.c_int * max(self.K, 1))()
+        self.debug, self._dv = None, None
+        if debug:
+            self.debug, self._dv = {}, _capi.Sim3SearchDebug()
+            for name, ty, width, fill in self.DEBUG_ROWS:
+                for side in (1, 2):
+                    rows = self._rows(side, ty, width, fill)
+                    table = self._table(rows)
+                    self._keep.append(table)
+                    self.debug["%s%d" % (name, side)] = rows
+                    setattr(self._dv, "%s%d" % (name, side), C.cast(table, C.c_void_p))
+        self.cam, self.bnd = np.ascontiguousarray(camera4, np.float32), np.ascontiguousarray(bounds4, np.float32)
+
+    def _keyframe(self, v, kf):
+        keys = np.ascontiguousarray(kf["keys_un"], _capi.KP_DTYPE)
+        n = len(keys)
+        arrs = [keys] + [np.ascontiguousarray(kf[name], ty) for name, ty in (("desc", np.uint8), ("has_point", np.uint8), ("world_pos", np.float32),
+                                                                          ("min_distance", np.float32), ("max_distance", np.float32),
+                                                                          ("point_desc", np.uint8))]
+        assert [a.size for a in arrs[1:]] == [n * 32, n, n * 3, n, n, n * 32]
+        self._keep += arrs
+        v.n = n
+        v.Tcw[:] = [float(x) for x in np.asarray(kf["Tcw"], np.float32).reshape(16)]
+        if n:
+            v.keys_un, v.desc, v.has_point, v.world_pos, v.min_distance, v.max_distance, v.point_desc = [a.ctypes.data for a in arrs]
+        return n
+
+    def _problem(self, v, p):
+        v.kf1, v.kf2, v.s12, v.th = int(p["kf1"]), int(p["kf2"]), float(p["s12"]), float(p["th"])
+        v.R12[:] = [float(x) for x in np.asarray(p["R12"], np.float32).reshape(9)]
+        v.t12[:] = [float(x) for x in np.asarray(p["t12"], np.float32).reshape(3)]
+        for name, kf in (("matched1", v.kf1), ("matched2", v.kf2)):
+            if p.get(name) is not None and self._n_of_keyframe(kf):
+                m = np.ascontiguousarray(p[name], np.uint8)
+                assert m.size == self.ns[kf]
+                self._keep.append(m)
+                setattr(v, name, m.ctypes.data)
+
+    def _n_of_keyframe(self, kf):
+        return self.ns[kf] if 0 <= kf < self.nkf else 0          # (an index outside the pool is the library's to refuse)
+
+    def n_of(self, k, side):
+        return self._n_of_keyframe(self.pv[k].kf1 if side == 1 else self.pv[k].kf2)
+
+    def _rows(self, side, ty, width, fill):
+        return [np.full((max(self.n_of(k, side), 1),) + ((width,) if width > 1 else ()), fill, ty) for k in range(self.K)]
+
+    def _table(self, rows):
+        return (self._C.c_void_p * max(self.K, 1))(*[r.ctypes.data for r in rows])
+
+    def run_raw(self, extractor):
+        C = self._C
+        check(lib().orbx_search_by_sim3_batch(extractor.handle, self.nkf, C.cast(self.kv, C.c_void_p), self.K, C.cast(self.pv, C.c_void_p),
+                                              ptr(self.cam), ptr(self.bnd), C.cast(self._match_table, C.c_void_p),
+                                              C.cast(self.nfound, C.c_void_p), C.byref(self._dv) if self._dv is not None else None))
+
+    def run(self, extractor):
+        self.run_raw(extractor)
+        counts = [int(self.nfound[k]) for k in range(self.K)]
+        matches = [self.matches[k][:self.n_of(k, 1)].copy() for k in range(self.K)]
+        if self.debug is None:
+            return counts, matches
+        per = [{name: rows[k][:self.n_of(k, int(name[-1]))].copy() for name, rows in self.debug.items()} for k in range(self.K)]
+        return counts, matches, per

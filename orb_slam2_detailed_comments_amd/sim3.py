@@ -129,3 +129,49 @@ def compute_sim3_rounds_batched(ransac, prepare, n_iterations=5, min_inliers=20,
                 if results[j]["ninliers"] >= min_inliers:
                     return k, calls, results[j].copy(), keeps[j]
     return -1, calls, None, None
+
+
+def compute_sim3_rounds_device(ransac, matcher, keyframes, search, optimize, camera4, bounds4, n_iterations=5, min_inliers=20,
+                               extractor=None):
+    """compute_sim3_rounds_batched with SearchBySim3 batched as well: every stage of a round is one device round trip.  Every
+    live solver gets iterate(n_iterations); search(k, T12, inliers) gives the ORBmatcher.SearchBySim3Batch problem of each solver
+    that returned a Sim3 (kf1, kf2 as indices into `keyframes`, s12, R12, t12, th, matched1, matched2 -- or None); ONE
+    matcher.SearchBySim3Batch call serves the round; optimize(k, T12, inliers, matches12, nfound) turns a solver's matches into its
+    optimize_sim3_batch problem (or None); ONE optimize_sim3_batch call follows, and the lowest k with ninliers >= min_inliers is
+    accepted.  Returns what compute_sim3_rounds_batched returns when its prepare runs the single SearchBySim3 between the same
+    two callbacks."""
+    from .optimizer import optimize_sim3_batch
+    ex = extractor if extractor is not None else ransac.extractor
+    K = len(ransac)
+    discarded = [False] * K
+    live = K
+    calls = []
+    while live > 0:
+        found = []
+        for k in range(K):
+            if discarded[k]:
+                continue
+            T, no_more, inl, nin = ransac.iterate(k, n_iterations)
+            calls.append((k, T is not None, no_more, nin))
+            if no_more:
+                discarded[k] = True
+                live -= 1
+            if T is not None:
+                sp = search(k, T, inl)
+                if sp is not None:
+                    found.append((k, T, inl, sp))
+        if not found:
+            continue
+        counts, matches = matcher.SearchBySim3Batch(keyframes, [f[3] for f in found], camera4, bounds4)
+        ks, problems = [], []
+        for j, (k, T, inl, _) in enumerate(found):
+            p = optimize(k, T, inl, matches[j], counts[j])
+            if p is not None:
+                ks.append(k)
+                problems.append(p)
+        if problems:
+            results, keeps = optimize_sim3_batch(ex, problems)
+            for j, k in enumerate(ks):
+                if results[j]["ninliers"] >= min_inliers:
+                    return k, calls, results[j].copy(), keeps[j]
+    return -1, calls, None, None
