@@ -907,6 +907,65 @@ orbx_status orbx_debug_sim3opt_inlier_test(orbx_handle *h, int nproblems, const 
  * which takes this primitive and orbx_pose_sin_cos from the library. */
 double orbx_sim3opt_exp(double sigma);
 
+/* ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:631-1030), the last heavy stage of LocalMapping::Run, from the point
+ * where the reference holds lLocalKeyFrames, lFixedCameras and lLocalMapPoints with their observations (:710) to the optimised
+ * poses, the optimised points and vToErase (:991), for many problems in one call.  Every edge joins one keyframe and one
+ * point and all points are marginalised, so H_pp is 6x6 block diagonal, H_ll 3x3 block diagonal, and the only coupled system is
+ * the Schur complement over the free keyframes: dense, 6 per free keyframe wide (k_local_ba: one workgroup per problem).
+ * optimize(5) with Huber on every edge, the classification (chi2 > 5.991 / 7.815 || !isDepthPositive; flagged edges leave the
+ * system, the kernel comes off every edge), optimize(10) when second_round, the final classification into erase.
+ * A problem is flat host arrays.  Keyframes: the nlocal local ones in list order, then the nfixed fixed ones; local_fixed[k]
+ * carries mnId == 0 (:738).  camera (fx, fy, cx, cy) and bf are per problem.  Observations are CSR by point (obs_begin); within a
+ * point the caller's order stands (the reference walks a std::map<KeyFrame*, size_t>: pointer order); obs = kpUn.pt.x, kpUn.pt.y,
+ * mvuRight (< 0: a monocular edge); bad keyframes are left out by the caller (:813).  second_round is what bDoMore would be: the
+ * reference samples *pbStopFlag between the rounds, a batch call cannot, so the caller decides before the call (and does not
+ * call at all with the flag set on entry, :886-888).  The library classifies every edge: pMP->isBad() inside the two
+ * classification loops cannot be seen from a snapshot; the caller drops an erase entry whose point has gone bad.
+ * Results: Tcw_out[k] = Converter::toCvMat(vSE3->estimate()) for EVERY local keyframe (a locally fixed one gets the quaternion
+ * round trip of its input, as SetPose does in the reference); world_out; erase[e] = 1 where the pair goes into vToErase.
+ * CONTRACT: the device equals the library's host path (ORBX_LOCALBA=host in the environment, read per call; host-only handles)
+ * and the numpy restatement tests/localba_model.py bit for bit, in both fp_modes.  Parity with a g2o + Eigen build is NOT
+ * pinned: DESIGN.md section 2 (F19) lists what follows the reference's source and what this library fixes where the reference
+ * leaves it to Eigen and to a sparse Cholesky with a fill-reducing ordering.
+ * Validated before any device work, ORBX_BAD_ARGUMENT: nproblems < 0, a null array whose size is positive, a negative count, an
+ * obs_begin that does not start at 0 or decreases, an obs_kf outside the keyframe list, a point that lists one keyframe twice;
+ * ORBX_UNSUPPORTED: nlocal > 128 (the reduced system's workspace), more than 4000000 observations in a problem.  Outputs of a
+ * rejected call are not written.  nproblems == 0 launches nothing.
+ * OUTSIDE the contract (z == 0 in a keyframe, non-finite input, a keyframe without edges): the same bounded loops run
+ * ((5 + 10) iterations x 10 trials), a failed reduced solve gives chi2 = DBL_MAX, and every stored NaN is the canonical one.
+ * MEASURED: profiles/localba_batch.md. */
+typedef struct orbx_localba_problem {
+    int32_t nlocal, nfixed, npoints;
+    int32_t second_round;              /* 0 / 1: what bDoMore would be */
+    const float *Tcw;                  /* [nlocal + nfixed][16] */
+    const uint8_t *local_fixed;        /* [nlocal] mnId == 0 */
+    float camera[4], bf;
+    const float *world;                /* [npoints][3] */
+    const int32_t *obs_begin;          /* [npoints + 1] */
+    const int32_t *obs_kf;             /* [nobs] index into the keyframe list */
+    const float *obs;                  /* [nobs][3] */
+    const float *inv_sigma2;           /* [nobs] */
+    float *Tcw_out;                    /* [nlocal][16] out */
+    float *world_out;                  /* [npoints][3] out */
+    uint8_t *erase;                    /* [nobs] out */
+} orbx_localba_problem;
+typedef struct orbx_localba_result {
+    int32_t iters[2];                  /* iterations run by optimize(5), optimize(10) */
+    int32_t nflagged, nerase;          /* edges at level 1 after the first classification; entries of vToErase */
+    double chi2[4];                    /* activeRobustChi2 at the first linearisation and at the end of round 1, of round 2 */
+} orbx_localba_result;
+/* One page-locked block up, k_local_ba, one block down, the wait.  Synchronous: the results go straight back into the map. */
+orbx_status orbx_local_bundle_adjustment_batch(orbx_handle *h, int nproblems, const orbx_localba_problem *problems,
+                                               orbx_localba_result *results);
+/* parity tests only: the classification alone on every edge, chi2 at the estimates where computeActiveErrors ran last
+ * (Tcw_last, world_last) and isDepthPositive at the current estimates (Tcw_est, world_est); arrays as in the problem.  Writes
+ * erase and nerase; Tcw_out and world_out are not written. */
+typedef struct orbx_localba_debug {
+    const float *Tcw_est, *world_est, *Tcw_last, *world_last;
+} orbx_localba_debug;
+orbx_status orbx_debug_localba_classify(orbx_handle *h, int nproblems, const orbx_localba_problem *problems,
+                                        const orbx_localba_debug *states, orbx_localba_result *results);
+
 /* ---- PnPsolver (src/PnPsolver.cc), the EPnP RANSAC between SearchByBoW and PoseOptimization in Tracking::Relocalization
  * (src/Tracking.cc:2336-2366), for all candidate keyframes in one device round trip.  An iteration is an independent 4-point
  * EPnP followed by one projection of every correspondence, so every iteration of every candidate is evaluated ahead of time --

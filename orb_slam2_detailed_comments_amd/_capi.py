@@ -89,6 +89,21 @@ SIM3OPT_RESULT_DTYPE = np.dtype([("r", "<f8", 4), ("t", "<f8", 3), ("s", "<f8"),
 assert SIM3OPT_RESULT_DTYPE.itemsize == 144
 
 
+class LocalBAProblem(C.Structure):   # orbx_localba_problem
+    _fields_ = [("nlocal", C.c_int32), ("nfixed", C.c_int32), ("npoints", C.c_int32), ("second_round", C.c_int32),
+                ("Tcw", C.c_void_p), ("local_fixed", C.c_void_p), ("camera", C.c_float * 4), ("bf", C.c_float),
+                ("world", C.c_void_p), ("obs_begin", C.c_void_p), ("obs_kf", C.c_void_p), ("obs", C.c_void_p),
+                ("inv_sigma2", C.c_void_p), ("Tcw_out", C.c_void_p), ("world_out", C.c_void_p), ("erase", C.c_void_p)]
+
+
+class LocalBADebug(C.Structure):   # orbx_localba_debug
+    _fields_ = [("Tcw_est", C.c_void_p), ("world_est", C.c_void_p), ("Tcw_last", C.c_void_p), ("world_last", C.c_void_p)]
+
+
+LOCALBA_RESULT_DTYPE = np.dtype([("iters", "<i4", 2), ("nflagged", "<i4"), ("nerase", "<i4"), ("chi2", "<f8", 4)])   # orbx_localba_result
+assert LOCALBA_RESULT_DTYPE.itemsize == 48
+
+
 class PnpProblem(C.Structure):   # orbx_pnp_problem
     _fields_ = [("n", C.c_int32), ("p3dw", C.c_void_p), ("p2d", C.c_void_p), ("max_err", C.c_void_p), ("camera", C.c_double * 4),
                 ("min_inliers", C.c_int32), ("iterations", C.c_int32), ("sets", C.c_void_p)]
@@ -215,6 +230,7 @@ SYMBOLS = [
     "orbx_sim3_ransac_iterations", "orbx_sim3_ransac_batch_create", "orbx_sim3_batch_iterate", "orbx_sim3_batch_best",
     "orbx_sim3_batch_counts", "orbx_sim3_batch_hypothesis", "orbx_sim3_batch_destroy", "orbx_sim3_atan2",
     "orbx_optimize_sim3_batch", "orbx_debug_sim3opt_inlier_test", "orbx_sim3opt_exp",
+    "orbx_local_bundle_adjustment_batch", "orbx_debug_localba_classify",
     "orbx_pnp_ransac_parameters", "orbx_pnp_ransac_batch_create", "orbx_pnp_batch_iterate", "orbx_pnp_batch_append",
     "orbx_pnp_batch_best", "orbx_pnp_batch_counts", "orbx_pnp_batch_hypothesis", "orbx_pnp_batch_destroy",
     "orbx_init_ransac_batch_create", "orbx_init_batch_result", "orbx_init_batch_scores", "orbx_init_batch_hypothesis",
@@ -289,6 +305,9 @@ def lib():
         L.orbx_optimize_sim3_batch.restype = i32; L.orbx_optimize_sim3_batch.argtypes = [vp, i32, vp, vp]
         L.orbx_debug_sim3opt_inlier_test.restype = i32; L.orbx_debug_sim3opt_inlier_test.argtypes = [vp, i32, vp, vp, vp]
         L.orbx_sim3opt_exp.restype = C.c_double; L.orbx_sim3opt_exp.argtypes = [C.c_double]
+    if hasattr(L, "orbx_local_bundle_adjustment_batch"):
+        L.orbx_local_bundle_adjustment_batch.restype = i32; L.orbx_local_bundle_adjustment_batch.argtypes = [vp, i32, vp, vp]
+        L.orbx_debug_localba_classify.restype = i32; L.orbx_debug_localba_classify.argtypes = [vp, i32, vp, vp, vp]
     L.orbx_pnp_ransac_parameters.restype = None
     L.orbx_pnp_ransac_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
     L.orbx_pnp_ransac_batch_create.restype = i32; L.orbx_pnp_ransac_batch_create.argtypes = [vp, i32, vp, C.POINTER(vp)]

@@ -4242,6 +4242,36 @@ __global__ __launch_bounds__(64) void k_sim3_opt(const DSim3OptArgs A) {
     if (ev.lane == 0) A.res[p] = out;
 }
 
+#include "orbx_localba.h"
+// Optimizer::LocalBundleAdjustment, batched (orbx_localba.h): one workgroup of 256 threads per problem, several problems per
+// launch, all arithmetic in double.  The header cuts the work into phases over independent items -- one lane per point walks
+// its observations; (keyframe, chain) pairs add the keyframe's edges in 64 interleaved chains; one lane per row of a Schur
+// block walks the block's pair list; one lane per row of the reduced system runs its left-looking L D L^T chain, one barrier
+// per column -- and the lanes stride over a phase's items with a barrier behind it, so every sum has the order the host path
+// gives it.  The Levenberg-Marquardt bookkeeping runs redundantly in every lane on values every lane reads from the same
+// places, so every branch around a barrier is uniform.  Everything a phase hands to the next lives in the problem's global
+// workspace (L2-resident at the sizes of a local map; the reduced system is not moved into LDS: profiles/localba_batch.md).
+// Every loop is bounded ((5 + 10) iterations x 10 trials) and nothing waits on another workgroup.
+struct LbaExDev {
+    int tid;
+    template <class F> __device__ __forceinline__ void each(int n, F f) {
+        for (int i = tid; i < n; i += ORBX_LBA_THREADS) f(i);
+        __syncthreads();
+    }
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+    __device__ __forceinline__ bool lead() const { return tid == 0; }
+};
+__global__ __launch_bounds__(ORBX_LBA_THREADS) void k_local_ba(const DLbaArgs A) {
+    const int p = blockIdx.x;
+    if (p >= A.nproblems) return;
+    const DLbaProb P = A.prob[p];
+    OrbxLbaCtx c;
+    orbx_localba_bind(P, A.in + P.o_in, A.work + P.o_work, A.out + P.o_out, c);
+    LbaExDev ex;
+    ex.tid = threadIdx.x;
+    orbx_localba_run(ex, c, (orbx_localba_result *)A.out + p);
+}
+
 #include "orbx_sim3.h"
 // CheckInliers of the batched RANSACs (k_sim3_inliers, k_pnp_inliers): one workgroup = WAVES consecutive hypotheses of ONE
 // problem, one wave each.  The problem's points are staged in LDS once per workgroup, CHUNK at a time as PLANES planes (lane i
@@ -5116,6 +5146,10 @@ void orbx_launch_mp_normal_depth(hipStream_t s, const int32_t *obs_begin, const 
 void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a) {
     if (a.nproblems <= 0) return;
     hipLaunchKernelGGL(k_pose_opt, dim3(a.nproblems), dim3(64), 0, s, a);
+}
+void orbx_launch_local_ba(hipStream_t s, const DLbaArgs &a) {
+    if (a.nproblems <= 0) return;
+    hipLaunchKernelGGL(k_local_ba, dim3(a.nproblems), dim3(ORBX_LBA_THREADS), 0, s, a);
 }
 void orbx_launch_sim3_opt(hipStream_t s, const DSim3OptArgs &a) {
     if (a.nproblems <= 0) return;

@@ -84,7 +84,7 @@ extern "C" orbx_status orbx_update_normal_and_depth_batch(orbx_handle *h, int np
 // (ORBX_POSE=host, read per call; host-only handles, where the "d_" arguments are host arrays): the same header compiled by
 // the host compiler.  On a device handle it downloads the rows it needs, runs, and uploads the results -- a cross-check, not a
 // fast path.
-static bool host_selected(const char *var) {                  // ORBX_POSE / ORBX_SIM3 / ORBX_PNP / ORBX_INIT / ORBX_RECON = host, read per call
+static bool host_selected(const char *var) {                  // ORBX_POSE / ORBX_SIM3 / ORBX_PNP / ORBX_INIT / ORBX_RECON / ORBX_LOCALBA = host, read per call
     const char *e = getenv(var);
     return e && strcmp(e, "host") == 0;
 }
@@ -244,6 +244,54 @@ extern "C" orbx_status orbx_optimize_sim3_batch(orbx_handle *h, int nproblems, c
 extern "C" orbx_status orbx_debug_sim3opt_inlier_test(orbx_handle *h, int nproblems, const orbx_sim3opt_problem *problems,
                                                       const double *S_last, orbx_sim3opt_result *results) {
     return sim3opt_batch(h, nproblems, problems, S_last, true, results);
+}
+
+// ---------------------------------------------------------------- Optimizer::LocalBundleAdjustment, batched (orbx_localba.h).
+// Device path: validation, layout and the derived index lists (orbx_localba.cpp), all problems packed into the page-locked block,
+// ONE upload, k_local_ba on the handle's stream, ONE download of results | poses | points | erase, the wait, the scatter.  The
+// device block is input | workspace | output.  Host path (ORBX_LOCALBA=host, read per call; host-only handles): the same header
+// compiled by the host compiler over the same packed block.
+static orbx_status localba_batch(orbx_handle *h, int nproblems, const orbx_localba_problem *problems, const orbx_localba_debug *dbg,
+                                 bool debug, orbx_localba_result *results) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    OrbxLbaPlan plan;
+    std::vector<DLbaProb> probs;
+    const char *why = "";
+    orbx_status st = orbx_localba_plan(nproblems, problems, results, dbg, debug, plan, probs, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (nproblems == 0) return ORBX_OK;
+    if (h->host_only || host_selected("ORBX_LOCALBA")) {
+        std::vector<uint8_t> in(plan.in_bytes), work(plan.work_bytes), out(plan.out_bytes);
+        orbx_localba_pack(problems, dbg, plan, probs, in.data());
+        orbx_localba_host_run(plan, in.data(), work.data(), out.data());
+        orbx_localba_unpack(problems, probs, out.data(), debug, results);
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    const size_t dev_in = pad256(plan.in_bytes), dev_work = pad256(plan.work_bytes);
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + dev_work + plan.out_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_localba_pack(problems, dbg, plan, probs, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    DLbaArgs a;
+    a.prob = (const DLbaProb *)(d + plan.o_prob);
+    a.in = d; a.work = d + dev_in; a.out = d + dev_in + dev_work;
+    a.nproblems = nproblems;
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_local_ba(h->stream, a); }
+    st = stage_download_wait(h, pin, a.out, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    orbx_localba_unpack(problems, probs, pin, debug, results);
+    return ORBX_OK;
+}
+extern "C" orbx_status orbx_local_bundle_adjustment_batch(orbx_handle *h, int nproblems, const orbx_localba_problem *problems,
+                                                          orbx_localba_result *results) {
+    return localba_batch(h, nproblems, problems, nullptr, false, results);
+}
+extern "C" orbx_status orbx_debug_localba_classify(orbx_handle *h, int nproblems, const orbx_localba_problem *problems,
+                                                   const orbx_localba_debug *states, orbx_localba_result *results) {
+    return localba_batch(h, nproblems, problems, states, true, results);
 }
 
 // ---------------------------------------------------------------- the batched RANSACs (orbx_ransac.h): one sequence for all.

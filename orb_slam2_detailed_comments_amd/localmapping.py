@@ -139,3 +139,51 @@ def create_new_map_points_rounds(ex, streams):
     finally:
         for tb in closers:
             tb.close()
+
+
+def local_bundle_adjustment_rounds(ex, streams, refresh=None):
+    """Optimizer::LocalBundleAdjustment for the keyframe each of B streams has just processed: ONE
+    optimizer.local_bundle_adjustment_batch call for all streams, then -- as src/Optimizer.cc:1028 does per point -- ONE
+    mappoint.update_normal_and_depth_batch call over the moved points of all streams.
+
+    streams: dicts with the problem keys of optimizer.local_bundle_adjustment_batch (nlocal, Tcw, local_fixed, camera, bf, world,
+    obs_begin, obs_kf, obs, inv_sigma2, second_round) and, for the refresh, ref_kf [npoints] (index of each point's reference
+    keyframe in the keyframe list) and ref_level [npoints] (the octave of the point's keypoint in it).  A stream whose stop flag
+    is set on entry is passed as None and is skipped (src/Optimizer.cc:886-888).  refresh=False skips the second call (it needs
+    a device handle).  Returns per stream None or a dict: Tcw [nlocal, 16], world [npoints, 3], erase [nobs], info, and with the
+    refresh normal [npoints, 3], min_distance, max_distance.  The refresh reads the optimised poses and points and leaves the
+    erased observations out, as the map would hold them after the erase list is applied."""
+    from . import mappoint, optimizer
+    who = [j for j, s in enumerate(streams) if s is not None]
+    out = [None] * len(streams)
+    got = optimizer.local_bundle_adjustment_batch(ex, [streams[j] for j in who])
+    for j, (T, w, e, info) in zip(who, got):
+        out[j] = {"Tcw": T, "world": w, "erase": e, "info": info}
+    if refresh is None:
+        refresh = all("ref_kf" in streams[j] for j in who) and bool(who)
+    if not refresh:
+        return out
+    begin, pos, centers, refc, level, counts = [0], [], [], [], [], []
+    for j in who:
+        s, r = streams[j], out[j]
+        T = np.array(np.asarray(s["Tcw"], np.float32).reshape(-1, 4, 4))
+        T[:s["nlocal"]] = r["Tcw"].reshape(-1, 4, 4)
+        Ow = -np.einsum("kji,kj->ki", T[:, :3, :3], T[:, :3, 3])        # GetCameraCenter: -R^T t, in float as SetPose computes it
+        ob = np.asarray(s["obs_begin"], np.int64)
+        kf = np.asarray(s["obs_kf"], np.int64)
+        for p in range(len(ob) - 1):
+            live = np.arange(ob[p], ob[p + 1])[r["erase"][ob[p]:ob[p + 1]] == 0]
+            centers.append(Ow[kf[live]])
+            begin.append(begin[-1] + len(live))
+        pos.append(r["world"]); refc.append(Ow[np.asarray(s["ref_kf"], np.int64)]); level.append(np.asarray(s["ref_level"], np.int32))
+        counts.append(len(ob) - 1)
+    if begin[-1] == 0 and not sum(counts):
+        return out
+    normal, dmin, dmax = mappoint.update_normal_and_depth_batch(
+        ex, np.array(begin, np.int32), np.concatenate(pos).reshape(-1, 3), np.concatenate(centers).reshape(-1, 3) if centers else np.zeros((0, 3)),
+        np.concatenate(refc).reshape(-1, 3), np.concatenate(level))
+    at = 0
+    for j, n in zip(who, counts):
+        out[j].update(normal=normal[at:at + n], min_distance=dmin[at:at + n], max_distance=dmax[at:at + n])
+        at += n
+    return out

@@ -1,5 +1,5 @@
 """Optimizer::PoseOptimization(Frame*) for tracked frames (include/orbx.h: orbx_pose_optimization_batch_device,
-orbx_pose_optimization) and Optimizer::OptimizeSim3 for loop-closure candidates (orbx_optimize_sim3_batch).  ctypes marshalling only; `extractor` is the ORBextractor whose handle (stream, staging block) the
+orbx_pose_optimization), Optimizer::OptimizeSim3 for loop-closure candidates (orbx_optimize_sim3_batch) and Optimizer::LocalBundleAdjustment for local mapping (orbx_local_bundle_adjustment_batch).  ctypes marshalling only; `extractor` is the ORBextractor whose handle (stream, staging block) the
 calls run on.  The batch reads the frames where the device batch left them and writes poses, outlier rows and inlier counts on
 the device; nothing is downloaded.  On a host-only extractor (device=-2) every device argument is a numpy array and the
 library's host path runs."""
@@ -118,3 +118,74 @@ def debug_sim3opt_inlier_test(extractor, problems, S_last):
     check(_capi.lib().orbx_debug_sim3opt_inlier_test(extractor.handle, len(problems), C.cast(arr, C.c_void_p), ptr(last),
                                                      ptr(results)))
     return results, keeps
+
+
+def _localba_marshal(problems, debug=False):
+    arr = (_capi.LocalBAProblem * max(len(problems), 1))()
+    hold, outs = [], []
+    for k, p in enumerate(problems):
+        T = np.ascontiguousarray(p["Tcw"], np.float32).reshape(-1, 16)
+        nlocal = int(p["nlocal"])
+        lf = np.ascontiguousarray(p.get("local_fixed", np.zeros(nlocal, np.uint8)), np.uint8).reshape(-1)
+        world = np.ascontiguousarray(p["world"], np.float32).reshape(-1, 3)
+        begin = np.ascontiguousarray(p["obs_begin"], np.int32).reshape(-1)
+        kf = np.ascontiguousarray(p["obs_kf"], np.int32).reshape(-1)
+        obs = np.ascontiguousarray(p["obs"], np.float32).reshape(-1, 3)
+        w = np.ascontiguousarray(p["inv_sigma2"], np.float32).reshape(-1)
+        nobs = len(kf)
+        assert len(lf) == nlocal and len(T) >= nlocal and len(begin) == len(world) + 1 and len(obs) == nobs and len(w) == nobs
+        Tout = p.get("Tcw_out")
+        Tout = np.zeros((nlocal, 16), np.float32) if Tout is None else Tout
+        wout = p.get("world_out")
+        wout = np.zeros((len(world), 3), np.float32) if wout is None else wout
+        erase = p.get("erase")
+        erase = np.zeros(nobs, np.uint8) if erase is None else erase
+        assert Tout.dtype == np.float32 and Tout.flags.c_contiguous and Tout.size == 16 * nlocal
+        assert wout.dtype == np.float32 and wout.flags.c_contiguous and wout.size == 3 * len(world)
+        assert erase.dtype == np.uint8 and erase.flags.c_contiguous and erase.size == nobs
+        hold += [T, lf, world, begin, kf, obs, w]
+        outs.append((Tout, wout, erase))
+        a = arr[k]
+        a.nlocal, a.nfixed, a.npoints = nlocal, len(T) - nlocal, len(world)
+        a.second_round = int(bool(p.get("second_round", True)))
+        a.Tcw = T.ctypes.data if len(T) else None
+        a.local_fixed = lf.ctypes.data if nlocal else None
+        a.camera[:] = np.asarray(p["camera"], np.float32).tolist()
+        a.bf = float(np.float32(p["bf"]))
+        a.world = world.ctypes.data if len(world) else None
+        a.obs_begin = begin.ctypes.data
+        a.obs_kf, a.obs, a.inv_sigma2 = (v.ctypes.data if nobs else None for v in (kf, obs, w))
+        a.Tcw_out = Tout.ctypes.data if nlocal else None
+        a.world_out = wout.ctypes.data if len(world) else None
+        a.erase = erase.ctypes.data if nobs else None
+    return arr, hold, outs
+
+
+def local_bundle_adjustment_batch(extractor, problems):
+    """Optimizer::LocalBundleAdjustment for many local maps in one call (orbx_local_bundle_adjustment_batch).  problems: dicts
+    with nlocal, Tcw [nlocal + nfixed, 16] (the local keyframes in list order, then the fixed ones), optionally local_fixed
+    [nlocal] uint8 (mnId == 0), camera (fx, fy, cx, cy), bf, world [npoints, 3], obs_begin [npoints + 1] (CSR by point), obs_kf
+    [nobs], obs [nobs, 3] (x, y, mvuRight; < 0: monocular), inv_sigma2 [nobs], second_round (default True: what bDoMore would be)
+    and optionally Tcw_out / world_out / erase to be written in place.  Returns per problem (Tcw [nlocal, 16] float32, world
+    [npoints, 3] float32, erase [nobs] uint8, info), info a record of _capi.LOCALBA_RESULT_DTYPE (iters, nflagged, nerase, chi2).
+    On a host-only extractor the library's host path runs."""
+    arr, hold, outs = _localba_marshal(problems)
+    results = np.zeros(len(problems), _capi.LOCALBA_RESULT_DTYPE)
+    check(_capi.lib().orbx_local_bundle_adjustment_batch(extractor.handle, len(problems), C.cast(arr, C.c_void_p),
+                                                         ptr(results) if len(problems) else None))
+    return [(T, w, e, results[k]) for k, (T, w, e) in enumerate(outs)]
+
+
+def debug_localba_classify(extractor, problems, states):
+    """parity tests only (orbx_debug_localba_classify): states[k] = (Tcw_est, world_est, Tcw_last, world_last), float32 arrays
+    shaped like the problem's Tcw and world.  Returns per problem (erase, info)."""
+    arr, hold, outs = _localba_marshal(problems)
+    st = (_capi.LocalBADebug * max(len(problems), 1))()
+    for k, s in enumerate(states):
+        a = [np.ascontiguousarray(v, np.float32) for v in s]
+        hold += a
+        st[k].Tcw_est, st[k].world_est, st[k].Tcw_last, st[k].world_last = (v.ctypes.data if v.size else None for v in a)
+    results = np.zeros(len(problems), _capi.LOCALBA_RESULT_DTYPE)
+    check(_capi.lib().orbx_debug_localba_classify(extractor.handle, len(problems), C.cast(arr, C.c_void_p), C.cast(st, C.c_void_p),
+                                                  ptr(results) if len(problems) else None))
+    return [(e, results[k]) for k, (T, w, e) in enumerate(outs)]
