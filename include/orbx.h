@@ -134,8 +134,14 @@ orbx_status orbx_set_input_format(orbx_handle *h, int pixel_format);
  * with the CV_32F maps of cv::initUndistortRectifyMap is fused into level 0; the extract entry points then take the RAW
  * image.  map_x / map_y: width x height floats, row major (M1l / M2l); raw and rectified images have the same size, as in
  * the reference's EuRoC driver.  OpenCV 3.2 fixed-point arithmetic (5-bit fractions, 2^15 weights, border value 0): parity
- * unpinned.  NULL, NULL switches it off.  8-bit gray input only. */
+ * unpinned.  NULL, NULL switches it off.  8-bit gray input only.
+ * Map entries: s = cvRound(map * 32) as OpenCV's 32-bit conversion does it -- half to even; NaN, +-inf and every product
+ * outside [-2^31, 2^31) give INT_MIN -- then i = saturate_cast<short>(s >> 5), f = s & 31 (include/orbx_rect_digest.h).  An
+ * entry that marks an invalid pixel with NaN or inf therefore reads i = -32768: all four taps outside, border value 0. */
 orbx_status orbx_set_rectification(orbx_handle *h, const float *map_x, const float *map_y, int width, int height);
+/* The digest orbx_set_rectification uploads, for n map entries: out_xy[i] = ix | iy << 16 (int16 each), out_frac[i] =
+ * fy << 5 | fx.  Pure host arithmetic: needs no handle and no device; n == 0 writes nothing. */
+orbx_status orbx_debug_rect_digest(const float *map_x, const float *map_y, int64_t n, uint32_t *out_xy, uint32_t *out_frac);
 
 /* ---- pyramid access: replaces the public member `mvImagePyramid` (include/ORBextractor.h:185),
  *      read by Frame::ComputeStereoMatches (src/Frame.cc:910,1040,1072,1079).  Valid until the next
@@ -621,7 +627,10 @@ orbx_status orbx_kfdb_state(orbx_kfdb *db, int64_t id, int loop_form, int64_t *m
 
 /* ---- Frame glue: Frame::UndistortKeyPoints / ComputeImageBounds (src/Frame.cc:770-865) =
  * cv::undistortPoints(mat, mat, mK, mDistCoef, cv::Mat(), mK) on the keypoint coordinates.  camera4 = fx, fy, cx, cy of mK;
- * dist = mDistCoef (k1, k2, p1, p2[, k3], at most 14); dist[0] == 0 copies the keypoints unchanged (:772-776).  OpenCV 3.2
+ * dist = mDistCoef (k1, k2, p1, p2[, k3[, k4, k5, k6[, s1, s2, s3, s4[, tauX, tauY]]]], ndist <= 14); the first 12 are
+ * evaluated.  The tilted-sensor terms are not implemented: ndist 13 or 14 is accepted only with dist[12] == dist[13] == 0, a
+ * non-zero tilt term is ORBX_UNSUPPORTED before any work (here, in orbx_image_bounds, orbx_rgbd_depth_device and
+ * orbx_extract_rgbd_batch; outputs untouched).  dist[0] == 0 copies the keypoints unchanged (:772-776).  OpenCV 3.2
  * arithmetic (double precision, five fixed iterations): parity unpinned, like every OpenCV-owned stage.  The device form
  * works on the buffers orbx_extract_batch_device filled (records `cap` apart, counts per frame) so that the keypoints need
  * not leave the GPU; AssignFeaturesToGrid on those buffers is orbx_grid_build_device (below), so a gated match reads them

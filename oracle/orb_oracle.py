@@ -19,7 +19,8 @@ def build(force=False):
     if os.environ.get("ORB_ORACLE_LIB"):   # another build of the same sources (sanitizer run, tests/test_sanitizers.py)
         return os.environ["ORB_ORACLE_LIB"]
     so = os.path.join(_HERE, "liborb_oracle.so")
-    srcs = [os.path.join(_HERE, f) for f in ("orb_oracle.c", "orb_oracle_match.c", "orb_oracle.h")]
+    srcs = [os.path.join(_HERE, f) for f in ("orb_oracle.c", "orb_oracle_match.c", "orb_oracle.h",
+                                             os.path.join("..", "include", "orbx_rect_digest.h"))]
     if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-B", "liborb_oracle.so"], stdout=subprocess.DEVNULL)
     return so

@@ -11,6 +11,7 @@
  */
 #define _GNU_SOURCE
 #include "orb_oracle.h"
+#include "../include/orbx_rect_digest.h" /* orbx_cv_round32: the 32-bit cvRound of cv::remap's map digest */
 #include <limits.h>
 #include <math.h>
 #include <stdlib.h>
@@ -975,7 +976,8 @@ void orc_image_bounds(int cols, int rows, float fx, float fy, float cx, float cy
  * cv::remap(src, dst, map1 CV_32FC1, map2 CV_32FC1, INTER_LINEAR, BORDER_CONSTANT 0) for 8-bit single-channel images
  * (reference Examples/Stereo/stereo_euroc.cc:183-194: rectification of both EuRoC images before the extractor).
  * OpenCV boundary, PARITY UNPINNED: restated from OpenCV 3.2 imgproc/imgwarp.cpp:
- *   sx = cvRound(map1 * 32), sy = cvRound(map2 * 32)            (INTER_TAB_SIZE = 32; round half to even)
+ *   sx = cvRound(map1 * 32), sy = cvRound(map2 * 32)            (INTER_TAB_SIZE = 32; round half to even; a 32-bit conversion:
+ *                                                                INT_MIN for NaN, +-inf and anything outside the int range)
  *   ix = saturate_cast<short>(sx >> 5), iy likewise, fx = sx & 31, fy = sy & 31
  *   weights = BilinearTab_i[fy * 32 + fx] : saturate_cast<short>((1 - fy/32)(1 - fx/32) * 32768) etc. -- exact integers
  *             (32 - fx)(32 - fy) * 32 ..., except the entry fx = fy = 0: 32768 saturates to 32767 and initInterTab2D's
@@ -1006,7 +1008,8 @@ void orc_remap_linear_u8(const uint8_t *src, int sw, int sh, int sstride, const 
     }
     for (int y = 0; y < dh; ++y)
         for (int x = 0; x < dw; ++x) {
-            const int sx = (int)lrintf(mapx[(size_t)y * dw + x] * 32.f), sy = (int)lrintf(mapy[(size_t)y * dw + x] * 32.f);
+            /* cvRound is a 32-bit conversion: NaN, +-inf and values outside the int range give INT_MIN (orbx_rect_digest.h) */
+            const int sx = orbx_cv_round32(mapx[(size_t)y * dw + x] * 32.f), sy = orbx_cv_round32(mapy[(size_t)y * dw + x] * 32.f);
             const int ix = orc_sat_short(sx >> 5), iy = orc_sat_short(sy >> 5);
             const short *w = tab[(sy & 31) * 32 + (sx & 31)];
             int acc = 0;

@@ -133,9 +133,9 @@ def build(force=False):
     oracle = os.path.dirname(HERE)
     mdeps = ([os.path.join(MATCHER, f) for f in MATCHER_STANDINS + ["harness.cpp"]] + [os.path.join(HERE, "build_ref.py")] +
              [os.path.join(ROOT, "tests", "compat_runtime", "opencv2", "core", "core.hpp")] +
-             [os.path.join(oracle, f) for f in ORACLE_C + ["orb_oracle.h"]] + [os.path.join(reference_dir(), s) for s in MATCHER_SOURCES])
+             [os.path.join(oracle, f) for f in ORACLE_C + ["orb_oracle.h", os.path.join("..", "include", "orbx_rect_digest.h")]] + [os.path.join(reference_dir(), s) for s in MATCHER_SOURCES])
     xdeps = ([os.path.join(EXTRACTOR, f) for f in EXTRACTOR_STANDINS + ["harness.cpp", "exports.map"]] + [os.path.join(HERE, "build_ref.py")] +
-             [os.path.join(oracle, f) for f in ORACLE_C + ["orb_oracle.h"]] + [os.path.join(reference_dir(), s) for s in EXTRACTOR_SOURCES])
+             [os.path.join(oracle, f) for f in ORACLE_C + ["orb_oracle.h", os.path.join("..", "include", "orbx_rect_digest.h")]] + [os.path.join(reference_dir(), s) for s in EXTRACTOR_SOURCES])
     t0 = time.time()
     jobs = []
     for path, cmd, dd, names in ((lib_path, command, deps, VARIANTS), (matcher_lib_path, matcher_command, mdeps, VARIANTS),

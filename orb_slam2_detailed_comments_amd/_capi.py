@@ -239,6 +239,7 @@ SYMBOLS = [
     "orbx_initialize_batch_create",
     "orbx_create_new_map_points_batch", "orbx_newpoints_stereo_cos",
     "orbx_search_by_sim3_batch",
+    "orbx_debug_rect_digest",
 ]
 
 _lib = None
@@ -428,6 +429,8 @@ def lib():
     L.orbx_undistort_keypoints.restype = i32; L.orbx_undistort_keypoints.argtypes = [vp, vp, i32, vp, vp, i32, vp]
     L.orbx_image_bounds.restype = i32; L.orbx_image_bounds.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     L.orbx_set_rectification.restype = i32; L.orbx_set_rectification.argtypes = [vp, vp, vp, i32, i32]
+    if hasattr(L, "orbx_debug_rect_digest"):   # (absent from an ORBX_LIB build older than the symbol: A/B runs against it)
+        L.orbx_debug_rect_digest.restype = i32; L.orbx_debug_rect_digest.argtypes = [vp, vp, i64, vp, vp]
     L.orbx_rgbd_depth_device.restype = i32
     L.orbx_rgbd_depth_device.argtypes = [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i64, f32, f32, vp, vp, vp]
     L.orbx_rgbd_depth.restype = i32

@@ -20,7 +20,7 @@ SOURCES = ["orbx_kernels.hip", "orbx_api.cpp", "orbx_extract.cpp", "orbx_pyramid
            "orbx_newpoints.cpp", "orbx_sim3search.cpp", "orbx_localba.cpp"]
 HEADERS = ["orbx_device.h", "orbx_inplace.h", "orbx_fast_net.h", "orbx_internal.h", "orbx_launch.h", "orbx_sincos.h", "orbx_track.h",
            "orbx_mappoint.h", "orbx_lm.h", "orbx_pose.h", "orbx_sim3opt.h", "orbx_localba.h", "orbx_ransac.h", "orbx_sim3.h", "orbx_pnp.h", "orbx_init.h", "orbx_recon.h", "orbx_newpoints.h", "orbx_sim3search.h", "orbx_handle.h", "orbx_gate.h", os.path.join("..", "..", "include", "orbx.h"),
-           os.path.join("..", "..", "include", "orbx_pattern_data.h")]
+           os.path.join("..", "..", "include", "orbx_pattern_data.h"), os.path.join("..", "..", "include", "orbx_rect_digest.h")]
 
 
 def kernels_hash():

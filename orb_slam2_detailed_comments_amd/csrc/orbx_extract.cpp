@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <vector>
 #include "orbx_handle.h"
+#include "../../include/orbx_rect_digest.h"
 
 // orbx_extract_rgbd_batch with page-locked, device-mapped depth: read it in place (true) or upload it (false) by default;
 // ORBX_RGBD_DEPTH=upload|inplace overrides per call.  Measured at 640x480, chunks of 64: 46.8 k / 49.2 k frames/s per 256 /
@@ -19,8 +20,9 @@
 // ---------------------------------------------------------------- extraction
 static inline int orbx_fmt_channels(int fmt) { return fmt == ORBX_FMT_GRAY8 ? 1 : (fmt == ORBX_FMT_RGB8 || fmt == ORBX_FMT_BGR8) ? 3 : 4; }
 // cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) of Examples/Stereo/stereo_euroc.cc:183-194 in front of the extractor:
-// the float maps are digested once (cvRound(map * 32), split into integer part and 5-bit fractions, as remap() does per
-// block) and level 0 samples the raw image through them.  NULL maps switch the rectification off.
+// the float maps are digested once (include/orbx_rect_digest.h: the 32-bit cvRound(map * 32), split into integer part and
+// 5-bit fractions, as remap() does per block) and level 0 samples the raw image through them.  NULL maps switch the
+// rectification off.
 extern "C" orbx_status orbx_set_rectification(orbx_handle *h, const float *map_x, const float *map_y, int width, int height) {
     if (!h || h->host_only) return orbx_fail(h ? ORBX_NO_DEVICE : ORBX_BAD_ARGUMENT, "no device handle");
     HIPCHK(hipSetDevice(h->dev));
@@ -30,17 +32,19 @@ extern "C" orbx_status orbx_set_rectification(orbx_handle *h, const float *map_x
     if (!map_x || !map_y || width <= 0 || height <= 0) return orbx_fail(ORBX_BAD_ARGUMENT, "bad rectification maps");
     if (h->input_format != ORBX_FMT_GRAY8) return orbx_fail(ORBX_BAD_ARGUMENT, "rectification needs 8-bit gray input");
     std::vector<uint2> t((size_t)width * height);
-    for (size_t i = 0; i < t.size(); ++i) {
-        const int sx = (int)lrintf(map_x[i] * 32.f), sy = (int)lrintf(map_y[i] * 32.f);   // cvRound: half to even
-        const int ix = std::min(std::max(sx >> 5, -32768), 32767), iy = std::min(std::max(sy >> 5, -32768), 32767);
-        t[i].x = (uint32_t)(uint16_t)(int16_t)ix | ((uint32_t)(uint16_t)(int16_t)iy << 16);
-        t[i].y = (uint32_t)(((sy & 31) << 5) | (sx & 31));
-    }
+    static_assert(sizeof(uint2) == 2 * sizeof(uint32_t), "interleaved digest");
+    orbx_rect_digest(map_x, map_y, t.size(), &t[0].x, &t[0].y, 2);
     HIPCHK(hipMalloc(&h->d_rect, t.size() * sizeof(uint2)));
     // on the handle's stream (ordered with the kernels that read the maps); `t` is a local: wait for the copy, on this stream only
     HIPCHK(hipMemcpyAsync(h->d_rect, t.data(), t.size() * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->rect_w = width; h->rect_h = height;
+    return ORBX_OK;
+}
+// the digest alone, as orbx_set_rectification uploads it: pure host arithmetic, no handle, no device
+extern "C" orbx_status orbx_debug_rect_digest(const float *map_x, const float *map_y, int64_t n, uint32_t *out_xy, uint32_t *out_frac) {
+    if (n < 0 || (n > 0 && (!map_x || !map_y || !out_xy || !out_frac))) return orbx_fail(ORBX_BAD_ARGUMENT, "bad rectification maps");
+    orbx_rect_digest(map_x, map_y, (size_t)n, out_xy, out_frac, 1);
     return ORBX_OK;
 }
 extern "C" orbx_status orbx_set_input_format(orbx_handle *h, int pixel_format) {
@@ -565,11 +569,18 @@ extern "C" orbx_status orbx_extract_batch(orbx_handle *h, int nframes, const uin
 }
 
 // ---------------------------------------------------------------- RGB-D Frame: Frame::ComputeStereoFromRGBD (k_rgbd)
-// camera4 / dist as the doubles k_undistort and k_rgbd take (section (f)2 below); dist[0] == 0: identity
-static void undistort_args(const float *camera4, const float *dist, int ndist, double *K4, double *k14, int *identity) {
+// camera4 / dist as the doubles k_undistort and k_rgbd take (section (f)2 below); dist[0] == 0: identity.  The ONE copy of the
+// coefficient rule: k_undistort evaluates k[0..11] (radial, tangential, rational, thin prism); the tilted-sensor terms tauX,
+// tauY (dist[12], dist[13]) are not implemented, so a model that sets either is refused instead of being answered without them.
+static orbx_status undistort_args(const float *camera4, const float *dist, int ndist, double *K4, double *k14, int *identity) {
+    for (int i = 12; i < ndist && i < 14; ++i)
+        if (dist[i] != 0.0f)   // (NaN included)
+            return orbx_fail(ORBX_UNSUPPORTED, "the tilt terms of the distortion model (dist[12], dist[13]: tauX, tauY) are not supported; at most 12 coefficients are evaluated");
+    if (!camera4) { *identity = 1; return ORBX_OK; }   // (orbx_image_bounds asking for the rule alone)
     for (int i = 0; i < 4; ++i) K4[i] = (double)camera4[i];
     for (int i = 0; i < 14; ++i) k14[i] = i < ndist ? (double)dist[i] : 0.0;
     *identity = (ndist < 1 || dist[0] == 0.0f) ? 1 : 0;
+    return ORBX_OK;
 }
 // argument rules shared by the three RGB-D entry points (checked before any device work)
 static orbx_status rgbd_check(int nframes, const void *depth, int format, int width, int height, int stride, int64_t frame_stride) {
@@ -595,10 +606,11 @@ extern "C" orbx_status orbx_rgbd_depth_device(orbx_handle *h, int nframes, const
         return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
     orbx_status st = rgbd_check(nframes, d_depth, depth_format, width, height, stride, frame_stride);
     if (st != ORBX_OK) return st;
+    double K4[4], k14[14]; int identity;
+    st = undistort_args(camera4, dist, ndist, K4, k14, &identity);
+    if (st != ORBX_OK) return st;
     if (h->host_only) return orbx_fail(ORBX_NO_DEVICE, "no device handle");
     HIPCHK(hipSetDevice(h->dev));
-    double K4[4], k14[14]; int identity;
-    undistort_args(camera4, dist, ndist, K4, k14, &identity);
     OrbxRgbdArgs a;
     a.depth = (const uint8_t *)d_depth; a.frame_stride = frame_stride; a.stride = stride; a.format = depth_format;
     a.width = width; a.height = height; a.scale_f32 = rgbd_scale_f32(depth_format, depth_scale); a.scale = depth_scale; a.mbf = mbf;
@@ -659,12 +671,13 @@ extern "C" orbx_status orbx_extract_rgbd_batch(orbx_handle *h, int nframes, cons
         return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
     orbx_status st = rgbd_check(nframes, depth, depth_format, width, height, depth_stride, depth_frame_stride);
     if (st != ORBX_OK) return st;
-    if (h->host_only) return orbx_fail(ORBX_NO_DEVICE, "no device handle");
     RgbdHost rg;
+    st = undistort_args(camera4, dist, ndist, rg.K4, rg.k14, &rg.identity);
+    if (st != ORBX_OK) return st;
+    if (h->host_only) return orbx_fail(ORBX_NO_DEVICE, "no device handle");
     rg.depth = (const uint8_t *)depth; rg.format = depth_format; rg.stride = depth_stride;
     rg.frame_stride = nframes > 1 ? depth_frame_stride : depth_span(depth_format, width, height, depth_stride);
     rg.scale = depth_scale; rg.mbf = mbf; rg.scale_f32 = rgbd_scale_f32(depth_format, depth_scale);
-    undistort_args(camera4, dist, ndist, rg.K4, rg.k14, &rg.identity);
     rg.kps_un = kps_un; rg.u_right = u_right; rg.depth_out = depth_out;
     return extract_host(h, nframes, imgs, width, height, stride, frame_stride, kps, desc, counts, cap, &rg);
 }
@@ -684,12 +697,14 @@ extern "C" orbx_status orbx_extract(orbx_handle *h, const uint8_t *img, int widt
 extern "C" orbx_status orbx_undistort_keypoints_device(orbx_handle *h, int nframes, const orbx_keypoint *d_kps,
                                                        const int32_t *d_counts, int cap, const float *camera4, const float *dist,
                                                        int ndist, orbx_keypoint *d_kps_un) {
-    if (!h || h->host_only) return orbx_fail(h ? ORBX_NO_DEVICE : ORBX_BAD_ARGUMENT, "no device handle");
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no device handle");
     if (nframes <= 0 || cap <= 0 || !d_kps || !d_counts || !d_kps_un || !camera4 || ndist < 0 || ndist > 14 || (ndist > 0 && !dist))
         return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
-    HIPCHK(hipSetDevice(h->dev));
     double K4[4], k14[14]; int identity;
-    undistort_args(camera4, dist, ndist, K4, k14, &identity);
+    orbx_status st = undistort_args(camera4, dist, ndist, K4, k14, &identity);
+    if (st != ORBX_OK) return st;
+    if (h->host_only) return orbx_fail(ORBX_NO_DEVICE, "no device handle");
+    HIPCHK(hipSetDevice(h->dev));
     { ProfScope ps(h, ORBX_K_MISC);
       orbx_launch_undistort(h->stream, nframes, cap, cap, K4, k14, identity, d_kps, d_counts, d_kps_un); }
     hipError_t e = hipGetLastError();
@@ -698,16 +713,18 @@ extern "C" orbx_status orbx_undistort_keypoints_device(orbx_handle *h, int nfram
 }
 extern "C" orbx_status orbx_undistort_keypoints(orbx_handle *h, const orbx_keypoint *kps, int n, const float *camera4,
                                                 const float *dist, int ndist, orbx_keypoint *kps_un) {
-    if (!h || h->host_only) return orbx_fail(h ? ORBX_NO_DEVICE : ORBX_BAD_ARGUMENT, "no device handle");
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no device handle");
     if (n < 0 || (n > 0 && (!kps || !kps_un)) || !camera4 || ndist < 0 || ndist > 14 || (ndist > 0 && !dist))
         return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
+    double K4[4], k14[14]; int identity;
+    orbx_status st = undistort_args(camera4, dist, ndist, K4, k14, &identity);
+    if (st != ORBX_OK) return st;
+    if (h->host_only) return orbx_fail(ORBX_NO_DEVICE, "no device handle");
     if (n == 0) return ORBX_OK;
     HIPCHK(hipSetDevice(h->dev));
-    orbx_status st = scratch_reserve(h, 2 * pad256((size_t)n * sizeof(orbx_keypoint)));
+    st = scratch_reserve(h, 2 * pad256((size_t)n * sizeof(orbx_keypoint)));
     if (st != ORBX_OK) return st;
     orbx_keypoint *din = scratch_take<orbx_keypoint>(h, n), *dout = scratch_take<orbx_keypoint>(h, n);
-    double K4[4], k14[14]; int identity;
-    undistort_args(camera4, dist, ndist, K4, k14, &identity);
     HIPCHK(hipMemcpyAsync(din, kps, (size_t)n * sizeof(orbx_keypoint), hipMemcpyHostToDevice, h->stream));
     orbx_launch_undistort(h->stream, 1, n, n, K4, k14, identity, din, nullptr, dout);
     HIPCHK(hipMemcpyAsync(kps_un, dout, (size_t)n * sizeof(orbx_keypoint), hipMemcpyDeviceToHost, h->stream));
@@ -718,6 +735,11 @@ extern "C" orbx_status orbx_undistort_keypoints(orbx_handle *h, const orbx_keypo
 extern "C" orbx_status orbx_image_bounds(orbx_handle *h, int cols, int rows, const float *camera4, const float *dist, int ndist,
                                          float *bounds4) {
     if (!bounds4 || cols <= 0 || rows <= 0) return orbx_fail(ORBX_BAD_ARGUMENT, "bad argument");
+    if (dist) {   // the tilt rule holds for the identity answer too: one rule for every entry point
+        double K4[4], k14[14]; int identity;
+        const orbx_status st = undistort_args(nullptr, dist, ndist, K4, k14, &identity);
+        if (st != ORBX_OK) return st;
+    }
     if (ndist < 1 || !dist || dist[0] == 0.0f) {
         bounds4[0] = 0.0f; bounds4[1] = (float)cols; bounds4[2] = 0.0f; bounds4[3] = (float)rows;
         return ORBX_OK;
