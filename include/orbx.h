@@ -975,6 +975,71 @@ typedef struct orbx_localba_debug {
 orbx_status orbx_debug_localba_classify(orbx_handle *h, int nproblems, const orbx_localba_problem *problems,
                                         const orbx_localba_debug *states, orbx_localba_result *results);
 
+/* ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1050-1358), the pose graph over all keyframes that
+ * LoopClosing::CorrectLoop runs after SearchAndFuse, for many problems in one call.  Every vertex is a VertexSim3Expmap, nothing is
+ * marginalised, every edge is an EdgeSim3 with identity information and no robust kernel, and g2o takes its Jacobians
+ * numerically (central differences, delta = 1e-9).  The normal equations are 7 x 7 block-sparse over the free keyframes; the
+ * library factors them by a block L D L^T in an elimination order it fixes itself (rounds of independent low-degree vertices,
+ * k_essential_graph: one workgroup per problem), runs Levenberg-Marquardt with setUserLambdaInit(1e-16) for at most 20
+ * iterations, recovers Tiw = [R, t / s] (:1304-1321) and maps every map point through Srw and correctedSwr (:1326-1357,
+ * k_eg_correct_points: one lane per point).
+ * A problem is flat host arrays.  Vertices: Scw[v] = vScw (CorrectedSim3 where the keyframe has one, else (Rcw, tcw, 1)) as the
+ * quaternion x y z w, t and s, 8 doubles; fixed[v] (pKF == pLoopKF); optionally non_corrected[v] with has_non_corrected[v]
+ * (NonCorrectedSim3).  Only keyframes that are not bad are passed (the reference dereferences optimizer.vertex(id) of a bad one
+ * at :1166 and :1308).  Edges: (i, j, kind) with vertex 0 = i and vertex 1 = j of the EdgeSim3; kind 1 is a loop-connection edge
+ * of step 3, whose measurement Sji = Sjw * Swi takes both poses from Scw; kind 0 is an edge of step 4 (spanning tree, loop
+ * edge, covisibility), which prefers non_corrected where present.  The library computes the measurements.  Parallel edges on
+ * one pair are allowed, as in the reference.  A fixed vertex, or a vertex without an edge, leaves the system; an edge between
+ * two fixed vertices is not active.  Points: world[p] and ref[p], the index of the vertex the point is corrected by
+ * (mnCorrectedReference or the reference keyframe), -1 for a bad point, which is copied through.
+ * Results: Siw_out[v] = the corrected Siw, 8 doubles; Tiw_out[v] = [R, t / s] narrowed to float, for EVERY vertex (a vertex
+ * outside the system gets the round trip of its input); world_out; the record below.
+ * CONTRACT: the device equals the library's host path (ORBX_ESSGRAPH=host in the environment, read per call; host-only handles)
+ * and the numpy restatement tests/essgraph_model.py bit for bit, in both fp_modes.  Parity with a g2o + Eigen build is NOT
+ * pinned: DESIGN.md section 2 (F20) lists what follows the reference's source and what this library fixes where the reference
+ * leaves it to libm, to Eigen and to a sparse Cholesky with a fill-reducing ordering.
+ * Validated before any device work, ORBX_BAD_ARGUMENT: nproblems < 0, a null array whose size is positive, a negative count, an
+ * edge index outside the vertices, i == j, a kind other than 0 / 1, a non-finite pose, s <= 0, a ref outside [-1, nvertices);
+ * ORBX_UNSUPPORTED: more than 2^20 vertices or 2^22 edges in a problem; ORBX_CAPACITY: on the device path, a problem whose L has
+ * more than ORBX_ESSGRAPH_MAX_LBLOCKS blocks (the host path has no such cap).  Outputs of a rejected call are not written.
+ * nproblems == 0 launches nothing.
+ * OUTSIDE the contract (estimates that leave s > 0, a component without a fixed vertex): the same bounded loops run (20
+ * iterations x 10 trials), a failed factorisation gives x = 0 and chi2 = DBL_MAX, and every stored NaN is the canonical one.
+ * MEASURED: profiles/essgraph_batch.md. */
+#define ORBX_ESSGRAPH_MAX_LBLOCKS 32768
+typedef struct orbx_essgraph_problem {
+    int32_t nvertices, nedges, npoints;
+    int32_t fix_scale;                 /* 0 / 1: bFixScale */
+    const double *Scw;                 /* [nvertices][8] */
+    const uint8_t *fixed;              /* [nvertices] */
+    const double *non_corrected;       /* [nvertices][8], or NULL: none */
+    const uint8_t *has_non_corrected;  /* [nvertices], or NULL: none */
+    const int32_t *edges;              /* [nedges][3] i, j, kind */
+    const float *world;                /* [npoints][3] */
+    const int32_t *ref;                /* [npoints] */
+    double *Siw_out;                   /* [nvertices][8] out */
+    float *Tiw_out;                    /* [nvertices][16] out */
+    float *world_out;                  /* [npoints][3] out */
+} orbx_essgraph_problem;
+typedef struct orbx_essgraph_result {
+    int32_t iters;                     /* iterations run by optimize(20) */
+    int32_t nactive;                   /* vertices in the system */
+    int32_t nfailed;                   /* solves whose factorisation was not positive */
+    int32_t nrounds, nlblocks;         /* elimination rounds; 7 x 7 blocks of L, the diagonal ones included */
+    int32_t pad;
+    double chi2[2];                    /* activeChi2 at the first linearisation and at the end */
+    double lambda;                     /* at the end */
+} orbx_essgraph_result;
+/* One page-locked block up, k_essential_graph and k_eg_correct_points, one block down, the wait.  Synchronous. */
+orbx_status orbx_optimize_essential_graph_batch(orbx_handle *h, int nproblems, const orbx_essgraph_problem *problems,
+                                                orbx_essgraph_result *results);
+/* tests and tools: the library's log (Sim3::log's std::log), x > 0; and Sim3::log of (r x y z w, t, s) into out[7] */
+double orbx_essgraph_log(double x);
+void orbx_essgraph_sim3_log(const double *S8, double *out7);
+/* g2o::Sim3(toMatrix3d(Rcw), toVector3d(tcw), 1.0) (:1109-1111) of a keyframe pose Tcw [16] as the 8 doubles of an Scw row: the
+ * floats widened, Eigen's Quaterniond(Matrix3d), nothing normalised */
+void orbx_essgraph_sim3_from_tcw(const float *Tcw, double *S8);
+
 /* ---- PnPsolver (src/PnPsolver.cc), the EPnP RANSAC between SearchByBoW and PoseOptimization in Tracking::Relocalization
  * (src/Tracking.cc:2336-2366), for all candidate keyframes in one device round trip.  An iteration is an independent 4-point
  * EPnP followed by one projection of every correspondence, so every iteration of every candidate is evaluated ahead of time --

@@ -104,6 +104,19 @@ LOCALBA_RESULT_DTYPE = np.dtype([("iters", "<i4", 2), ("nflagged", "<i4"), ("ner
 assert LOCALBA_RESULT_DTYPE.itemsize == 48
 
 
+class EssGraphProblem(C.Structure):   # orbx_essgraph_problem
+    _fields_ = [("nvertices", C.c_int32), ("nedges", C.c_int32), ("npoints", C.c_int32), ("fix_scale", C.c_int32),
+                ("Scw", C.c_void_p), ("fixed", C.c_void_p), ("non_corrected", C.c_void_p), ("has_non_corrected", C.c_void_p),
+                ("edges", C.c_void_p), ("world", C.c_void_p), ("ref", C.c_void_p), ("Siw_out", C.c_void_p),
+                ("Tiw_out", C.c_void_p), ("world_out", C.c_void_p)]
+
+
+ESSGRAPH_RESULT_DTYPE = np.dtype([("iters", "<i4"), ("nactive", "<i4"), ("nfailed", "<i4"), ("nrounds", "<i4"), ("nlblocks", "<i4"),
+                                  ("pad", "<i4"), ("chi2", "<f8", 2), ("lambda", "<f8")])   # orbx_essgraph_result
+assert ESSGRAPH_RESULT_DTYPE.itemsize == 48
+ESSGRAPH_MAX_LBLOCKS = 32768   # ORBX_ESSGRAPH_MAX_LBLOCKS
+
+
 class PnpProblem(C.Structure):   # orbx_pnp_problem
     _fields_ = [("n", C.c_int32), ("p3dw", C.c_void_p), ("p2d", C.c_void_p), ("max_err", C.c_void_p), ("camera", C.c_double * 4),
                 ("min_inliers", C.c_int32), ("iterations", C.c_int32), ("sets", C.c_void_p)]
@@ -231,6 +244,7 @@ SYMBOLS = [
     "orbx_sim3_batch_counts", "orbx_sim3_batch_hypothesis", "orbx_sim3_batch_destroy", "orbx_sim3_atan2",
     "orbx_optimize_sim3_batch", "orbx_debug_sim3opt_inlier_test", "orbx_sim3opt_exp",
     "orbx_local_bundle_adjustment_batch", "orbx_debug_localba_classify",
+    "orbx_optimize_essential_graph_batch", "orbx_essgraph_log", "orbx_essgraph_sim3_log", "orbx_essgraph_sim3_from_tcw",
     "orbx_pnp_ransac_parameters", "orbx_pnp_ransac_batch_create", "orbx_pnp_batch_iterate", "orbx_pnp_batch_append",
     "orbx_pnp_batch_best", "orbx_pnp_batch_counts", "orbx_pnp_batch_hypothesis", "orbx_pnp_batch_destroy",
     "orbx_init_ransac_batch_create", "orbx_init_batch_result", "orbx_init_batch_scores", "orbx_init_batch_hypothesis",
@@ -309,6 +323,11 @@ def lib():
     if hasattr(L, "orbx_local_bundle_adjustment_batch"):
         L.orbx_local_bundle_adjustment_batch.restype = i32; L.orbx_local_bundle_adjustment_batch.argtypes = [vp, i32, vp, vp]
         L.orbx_debug_localba_classify.restype = i32; L.orbx_debug_localba_classify.argtypes = [vp, i32, vp, vp, vp]
+    if hasattr(L, "orbx_optimize_essential_graph_batch"):
+        L.orbx_optimize_essential_graph_batch.restype = i32; L.orbx_optimize_essential_graph_batch.argtypes = [vp, i32, vp, vp]
+        L.orbx_essgraph_log.restype = C.c_double; L.orbx_essgraph_log.argtypes = [C.c_double]
+        L.orbx_essgraph_sim3_log.restype = None; L.orbx_essgraph_sim3_log.argtypes = [vp, vp]
+        L.orbx_essgraph_sim3_from_tcw.restype = None; L.orbx_essgraph_sim3_from_tcw.argtypes = [vp, vp]
     L.orbx_pnp_ransac_parameters.restype = None
     L.orbx_pnp_ransac_parameters.argtypes = [i32, C.c_double, i32, i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]
     L.orbx_pnp_ransac_batch_create.restype = i32; L.orbx_pnp_ransac_batch_create.argtypes = [vp, i32, vp, C.POINTER(vp)]

@@ -17,9 +17,9 @@ LIB = os.path.join(LIBDIR, "liborbx.so")
 SOURCES = ["orbx_kernels.hip", "orbx_api.cpp", "orbx_extract.cpp", "orbx_pyramid.cpp", "orbx_match.cpp", "orbx_tracking.cpp",
            "orbx_map_batches.cpp", "orbx_bow.cpp", "orbx_geometry.cpp", "orbx_policies.cpp", "orbx_kfdb.cpp", "orbx_track_pack.cpp",
            "orbx_mappoint.cpp", "orbx_pose.cpp", "orbx_sim3opt.cpp", "orbx_sim3.cpp", "orbx_pnp.cpp", "orbx_init.cpp", "orbx_recon.cpp",
-           "orbx_newpoints.cpp", "orbx_sim3search.cpp", "orbx_localba.cpp"]
+           "orbx_newpoints.cpp", "orbx_sim3search.cpp", "orbx_localba.cpp", "orbx_essgraph.cpp"]
 HEADERS = ["orbx_device.h", "orbx_inplace.h", "orbx_fast_net.h", "orbx_internal.h", "orbx_launch.h", "orbx_sincos.h", "orbx_track.h",
-           "orbx_mappoint.h", "orbx_lm.h", "orbx_pose.h", "orbx_sim3opt.h", "orbx_localba.h", "orbx_ransac.h", "orbx_sim3.h", "orbx_pnp.h", "orbx_init.h", "orbx_recon.h", "orbx_newpoints.h", "orbx_sim3search.h", "orbx_handle.h", "orbx_gate.h", os.path.join("..", "..", "include", "orbx.h"),
+           "orbx_mappoint.h", "orbx_lm.h", "orbx_pose.h", "orbx_sim3opt.h", "orbx_localba.h", "orbx_essgraph.h", "orbx_ransac.h", "orbx_sim3.h", "orbx_pnp.h", "orbx_init.h", "orbx_recon.h", "orbx_newpoints.h", "orbx_sim3search.h", "orbx_handle.h", "orbx_gate.h", os.path.join("..", "..", "include", "orbx.h"),
            os.path.join("..", "..", "include", "orbx_pattern_data.h"), os.path.join("..", "..", "include", "orbx_rect_digest.h")]
 
 

@@ -4272,6 +4272,44 @@ __global__ __launch_bounds__(ORBX_LBA_THREADS) void k_local_ba(const DLbaArgs A)
     orbx_localba_run(ex, c, (orbx_localba_result *)A.out + p);
 }
 
+#include "orbx_essgraph.h"
+// Optimizer::OptimizeEssentialGraph, batched (orbx_essgraph.h): one workgroup of 256 threads per problem, several problems per
+// launch, all arithmetic in double.  The header cuts the work into phases over independent items -- one lane per (edge, side,
+// column) takes a central difference and writes one 7-vector of a Jacobian; one lane per (block, row) of the 7 x 7 block-sparse
+// system adds its edges; per elimination round one lane per (block, row) forms T, one lane per column factors its 7 x 7
+// diagonal block in place, one lane per (block, row) forms L; one lane per column of a round runs the forward and the backward
+// solve -- and the lanes stride over a phase's items with a barrier behind it, so every sum has the order the host path gives
+// it.  The Levenberg-Marquardt bookkeeping runs redundantly in every lane on values every lane reads from the same places, so
+// every branch around a barrier is uniform.  Everything a phase hands to the next lives in the problem's global workspace; no
+// lane holds a 7 x 7 block.  Every loop is bounded (20 iterations x 10 trials) and nothing waits on another workgroup.
+struct EgExDev {
+    int tid;
+    template <class F> __device__ __forceinline__ void each(int n, F f) {
+        for (int i = tid; i < n; i += ORBX_EG_THREADS) f(i);
+        __syncthreads();
+    }
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+    __device__ __forceinline__ bool lead() const { return tid == 0; }
+};
+__global__ __launch_bounds__(ORBX_EG_THREADS) void k_essential_graph(const DEgArgs A) {
+    const int p = blockIdx.x;
+    if (p >= A.nproblems) return;
+    const DEgProb P = A.prob[p];
+    OrbxEgCtx c;
+    orbx_eg_bind(P, A.in + P.o_in, A.work + P.o_work, A.out + P.o_out, c);
+    EgExDev ex;
+    ex.tid = threadIdx.x;
+    orbx_eg_run(ex, c, (orbx_essgraph_result *)A.out + p);
+}
+// Step 7 of OptimizeEssentialGraph: one lane per map point over all problems of the call, after k_essential_graph on the stream
+__global__ __launch_bounds__(256) void k_eg_correct_points(const DEgArgs A) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.npoints) return;
+    const float *world = (const float *)(A.in + A.o_pts_in);
+    const int32_t *ref = (const int32_t *)(world + 3 * A.npoints), *pprob = ref + A.npoints;
+    orbx_eg_correct_point(A.prob, A.in, A.out, world, ref, pprob, (float *)(A.out + A.o_pts_out), i);
+}
+
 #include "orbx_sim3.h"
 // CheckInliers of the batched RANSACs (k_sim3_inliers, k_pnp_inliers): one workgroup = WAVES consecutive hypotheses of ONE
 // problem, one wave each.  The problem's points are staged in LDS once per workgroup, CHUNK at a time as PLANES planes (lane i
@@ -5150,6 +5188,11 @@ void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a) {
 void orbx_launch_local_ba(hipStream_t s, const DLbaArgs &a) {
     if (a.nproblems <= 0) return;
     hipLaunchKernelGGL(k_local_ba, dim3(a.nproblems), dim3(ORBX_LBA_THREADS), 0, s, a);
+}
+void orbx_launch_essential_graph(hipStream_t s, const DEgArgs &a) {
+    if (a.nproblems <= 0) return;
+    hipLaunchKernelGGL(k_essential_graph, dim3(a.nproblems), dim3(ORBX_EG_THREADS), 0, s, a);
+    if (a.npoints > 0) hipLaunchKernelGGL(k_eg_correct_points, dim3((unsigned)((a.npoints + 255) / 256)), dim3(256), 0, s, a);
 }
 void orbx_launch_sim3_opt(hipStream_t s, const DSim3OptArgs &a) {
     if (a.nproblems <= 0) return;

@@ -8,6 +8,7 @@
 #include "orbx_pose.h"
 #include "orbx_sim3opt.h"
 #include "orbx_localba.h"
+#include "orbx_essgraph.h"
 #include "orbx_sim3.h"
 #include "orbx_pnp.h"
 #include "orbx_init.h"
@@ -151,6 +152,8 @@ void orbx_launch_pose_opt(hipStream_t s, const DPoseArgs &a);
 void orbx_launch_sim3_opt(hipStream_t s, const DSim3OptArgs &a);
 // Optimizer::LocalBundleAdjustment (orbx_localba.h): k_local_ba, one workgroup per problem
 void orbx_launch_local_ba(hipStream_t s, const DLbaArgs &a);
+// Optimizer::OptimizeEssentialGraph (orbx_essgraph.h): k_essential_graph, one workgroup per problem, then k_eg_correct_points
+void orbx_launch_essential_graph(hipStream_t s, const DEgArgs &a);
 // Sim3Solver RANSAC (orbx_sim3.h): k_sim3_hypotheses over all iterations, then k_sim3_inliers over the workgroup table
 void orbx_launch_sim3(hipStream_t s, const DSim3Args &a);
 // PnPsolver RANSAC (orbx_pnp.h): k_pnp_hypotheses over all iterations, then k_pnp_inliers over the workgroup table

@@ -294,6 +294,48 @@ extern "C" orbx_status orbx_debug_localba_classify(orbx_handle *h, int nproblems
     return localba_batch(h, nproblems, problems, states, true, results);
 }
 
+// ---------------------------------------------------------------- Optimizer::OptimizeEssentialGraph, batched (orbx_essgraph.h).
+// Device path: validation, the elimination order and the symbolic factorisation (orbx_essgraph.cpp; a problem above
+// ORBX_EG_MAX_LBLOCKS is ORBX_CAPACITY here), all problems packed into the page-locked block, ONE upload, k_essential_graph and
+// k_eg_correct_points on the handle's stream, ONE download of results | Siw | Tiw | points, the wait, the scatter.  The device
+// block is input | workspace | output.  Host path (ORBX_ESSGRAPH=host, read per call; host-only handles): the same header
+// compiled by the host compiler over the same packed block, without the cap.
+extern "C" orbx_status orbx_optimize_essential_graph_batch(orbx_handle *h, int nproblems, const orbx_essgraph_problem *problems,
+                                                           orbx_essgraph_result *results) {
+    if (!h) return orbx_fail(ORBX_BAD_ARGUMENT, "no handle");
+    const bool host = h->host_only || host_selected("ORBX_ESSGRAPH");
+    OrbxEgPlan plan;
+    const char *why = "";
+    orbx_status st = orbx_eg_plan(nproblems, problems, results, !host, plan, &why);
+    if (st != ORBX_OK) return orbx_fail(st, why);
+    if (nproblems == 0) return ORBX_OK;
+    if (host) {
+        std::vector<uint8_t> in(plan.in_bytes), work(plan.work_bytes), out(plan.out_bytes);
+        orbx_eg_pack(problems, plan, in.data());
+        orbx_eg_host_run(plan, in.data(), work.data(), out.data());
+        orbx_eg_unpack(problems, plan, out.data(), results);
+        return ORBX_OK;
+    }
+    uint8_t *pin = nullptr, *d = nullptr;
+    const size_t dev_in = pad256(plan.in_bytes), dev_work = pad256(plan.work_bytes);
+    st = stage_begin(h, std::max(plan.in_bytes, plan.out_bytes), dev_in + dev_work + plan.out_bytes, &pin, &d, false);
+    if (st != ORBX_OK) return st;
+    orbx_eg_pack(problems, plan, pin);
+    st = stage_upload(h, pin, d, plan.in_bytes);
+    if (st != ORBX_OK) return st;
+    DEgArgs a;
+    a.prob = (const DEgProb *)(d + plan.o_prob);
+    a.in = d; a.work = d + dev_in; a.out = d + dev_in + dev_work;
+    a.nproblems = nproblems;
+    a.npoints = plan.npoints; a.o_pts_in = (int64_t)plan.o_pts_in; a.o_pts_out = (int64_t)plan.o_pts_out;
+    { ProfScope ps(h, ORBX_K_MISC);
+      orbx_launch_essential_graph(h->stream, a); }
+    st = stage_download_wait(h, pin, a.out, plan.out_bytes);
+    if (st != ORBX_OK) return st;
+    orbx_eg_unpack(problems, plan, pin, results);
+    return ORBX_OK;
+}
+
 // ---------------------------------------------------------------- the batched RANSACs (orbx_ransac.h): one sequence for all.
 // Device path: validation and layout (S::plan), all problems packed into the page-locked block, ONE upload, the solver's two
 // kernels on the handle's stream (S::launch), ONE download of hypotheses | masks | tally, the wait; the batch keeps a host copy

@@ -1,5 +1,5 @@
 """Optimizer::PoseOptimization(Frame*) for tracked frames (include/orbx.h: orbx_pose_optimization_batch_device,
-orbx_pose_optimization), Optimizer::OptimizeSim3 for loop-closure candidates (orbx_optimize_sim3_batch) and Optimizer::LocalBundleAdjustment for local mapping (orbx_local_bundle_adjustment_batch).  ctypes marshalling only; `extractor` is the ORBextractor whose handle (stream, staging block) the
+orbx_pose_optimization), Optimizer::OptimizeSim3 for loop-closure candidates (orbx_optimize_sim3_batch) Optimizer::LocalBundleAdjustment for local mapping (orbx_local_bundle_adjustment_batch) and Optimizer::OptimizeEssentialGraph for loop closing (orbx_optimize_essential_graph_batch).  ctypes marshalling only; `extractor` is the ORBextractor whose handle (stream, staging block) the
 calls run on.  The batch reads the frames where the device batch left them and writes poses, outlier rows and inlier counts on
 the device; nothing is downloaded.  On a host-only extractor (device=-2) every device argument is a numpy array and the
 library's host path runs."""
@@ -189,3 +189,57 @@ def debug_localba_classify(extractor, problems, states):
     check(_capi.lib().orbx_debug_localba_classify(extractor.handle, len(problems), C.cast(arr, C.c_void_p), C.cast(st, C.c_void_p),
                                                   ptr(results) if len(problems) else None))
     return [(e, results[k]) for k, (T, w, e) in enumerate(outs)]
+
+
+def _essgraph_marshal(problems):
+    arr = (_capi.EssGraphProblem * max(len(problems), 1))()
+    hold, outs = [], []
+    for k, p in enumerate(problems):
+        S = np.ascontiguousarray(p["Scw"], np.float64).reshape(-1, 8)
+        nv = len(S)
+        fixed = np.ascontiguousarray(p.get("fixed", np.zeros(nv, np.uint8)), np.uint8).reshape(-1)
+        nc, has = p.get("non_corrected"), p.get("has_non_corrected")
+        if nc is not None:
+            nc = np.ascontiguousarray(nc, np.float64).reshape(-1, 8)
+            has = np.ascontiguousarray(has, np.uint8).reshape(-1)
+            assert len(nc) == nv and len(has) == nv
+        edges = np.ascontiguousarray(p.get("edges", np.zeros((0, 3), np.int32)), np.int32).reshape(-1, 3)
+        world = np.ascontiguousarray(p.get("world", np.zeros((0, 3), np.float32)), np.float32).reshape(-1, 3)
+        ref = np.ascontiguousarray(p.get("ref", np.zeros(0, np.int32)), np.int32).reshape(-1)
+        assert len(fixed) == nv and len(ref) == len(world)
+        Sout, Tout, wout = p.get("Siw_out"), p.get("Tiw_out"), p.get("world_out")
+        Sout = np.zeros((nv, 8), np.float64) if Sout is None else Sout
+        Tout = np.zeros((nv, 16), np.float32) if Tout is None else Tout
+        wout = np.zeros((len(world), 3), np.float32) if wout is None else wout
+        assert Sout.dtype == np.float64 and Sout.flags.c_contiguous and Sout.size == 8 * nv
+        assert Tout.dtype == np.float32 and Tout.flags.c_contiguous and Tout.size == 16 * nv
+        assert wout.dtype == np.float32 and wout.flags.c_contiguous and wout.size == 3 * len(world)
+        hold += [S, fixed, nc, has, edges, world, ref]
+        outs.append((Sout, Tout, wout))
+        a = arr[k]
+        a.nvertices, a.nedges, a.npoints, a.fix_scale = nv, len(edges), len(world), int(bool(p.get("fix_scale", False)))
+        a.Scw, a.fixed = (v.ctypes.data if nv else None for v in (S, fixed))
+        a.non_corrected = nc.ctypes.data if nc is not None and nv else None
+        a.has_non_corrected = has.ctypes.data if nc is not None and nv else None
+        a.edges = edges.ctypes.data if len(edges) else None
+        a.world, a.ref = (v.ctypes.data if len(world) else None for v in (world, ref))
+        a.Siw_out, a.Tiw_out = (v.ctypes.data if nv else None for v in (Sout, Tout))
+        a.world_out = wout.ctypes.data if len(world) else None
+    return arr, hold, outs
+
+
+def optimize_essential_graph_batch(extractor, problems):
+    """Optimizer::OptimizeEssentialGraph for many pose graphs in one call (orbx_optimize_essential_graph_batch).  problems: dicts
+    with Scw [nv, 8] float64 (vScw: quaternion x y z w, t, s; loopclosing.sim3_from_Tcw for a keyframe without a CorrectedSim3),
+    optionally fixed [nv] uint8 (pKF == pLoopKF), non_corrected [nv, 8] with has_non_corrected [nv] (NonCorrectedSim3), edges
+    [ne, 3] int32 (i, j, kind; loopclosing.essential_graph_edges), fix_scale, world [npoints, 3] float32 and ref [npoints] int32
+    (the vertex a point is corrected by, -1: a bad point, copied through), and optionally Siw_out / Tiw_out / world_out to be
+    written in place.  Returns per problem (Siw [nv, 8] float64, Tiw [nv, 16] float32, world [npoints, 3] float32, info), info a
+    record of _capi.ESSGRAPH_RESULT_DTYPE (iters, nactive, nfailed, nrounds, nlblocks, chi2, lambda).  On a host-only extractor
+    the library's host path runs; on the device a problem whose L has more than _capi.ESSGRAPH_MAX_LBLOCKS blocks raises
+    OrbxError with status CAPACITY."""
+    arr, hold, outs = _essgraph_marshal(problems)
+    results = np.zeros(len(problems), _capi.ESSGRAPH_RESULT_DTYPE)
+    check(_capi.lib().orbx_optimize_essential_graph_batch(extractor.handle, len(problems), C.cast(arr, C.c_void_p),
+                                                          ptr(results) if len(problems) else None))
+    return [(S, T, w, results[k]) for k, (S, T, w) in enumerate(outs)]
